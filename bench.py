@@ -18,6 +18,19 @@ LOCAL_RANK / WORLD_SIZE in the environment), or plain `python bench.py --gpus N`
 rank processes itself -- before anything in this process touches the GPU -- and fails loudly when the
 node has fewer than N devices.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more:
+set-up, W warm-up steps, N timed steps, the outputs of the last step if `--dump-outputs DIR` is given,
+and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+workload and the splat schedule).  `--full` adds everything measured or checked beside it: the oracle
+check of one frame, the single-frame latency, per-stage times and the roofline position, the extras of
+rovinasemanticsegmentation_amd/bench_extras.py and the CPU baseline.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller as
+float32 / float64 .npy files: the CRF marginals and labels at a fixed, seeded sample of pixels of the
+batch (marginals.npy: K x 9, labels.npy: K, pixel_index.npy: the flat frame * H * W + pixel index of
+each row), and with `--config 3` on one GPU the gathered labels at the same pixels (fused_labels.npy).
+The inputs depend on the arguments only, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -39,6 +52,8 @@ C_CLASSES = 9
 D_FEAT = 6
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 MARGINAL_TOL = 1e-4    # BASELINE.json north_star
+DUMP_PIXELS = 1 << 19  # --dump-outputs: sampled pixels (marginals + labels + index: ~25 MB)
+DUMP_SEED = 20240611
 
 # Algorithmic HBM bytes per full-resolution pixel and LAUNCH GROUP (SURVEY.md 8d, C = 9, d = 6).
 # `launches` = how many times the stage runs per step.
@@ -125,13 +140,20 @@ def parse():
                          "256 key frames sharded over 8 GPUs (32 per rank) + label gather to the fusion rank every step")
     ap.add_argument("--no-overlap", action="store_true", help="every kernel alone on the GPU (profiling: no side streams)")
     ap.add_argument("--no-holes", action="store_true", help="frames without invalid-depth holes (round 1/2 inputs)")
-    ap.add_argument("--cpu-frames", type=int, default=2, help="frames timed on the CPU oracle (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-frame latency probe (profiling runs)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run oracle check of one batch frame")
+    ap.add_argument("--cpu-frames", type=int, default=2, help="frames timed on the CPU oracle (--full; rank 0, N=1 only)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the single-frame latency probe")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the post-run oracle check of one batch frame")
     ap.add_argument("--extras", default="default",
-                    help="comma list of extra measurements outside the timed region (N=1 only): host,localmap,config5,train,deep; "
+                    help="comma list of extra measurements outside the timed region (--full, N=1 only): host,localmap,config5,train,deep; "
                          "'default' = all that the build supports, 'none' = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured or checked beside the headline figure: oracle check, single-frame "
+                         "latency, per-stage times + roofline, extras and the CPU baseline (the --no-* / --extras options "
+                         "trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's marginals and labels (seeded pixel sample) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--rehearsal", action="store_true",
                     help="CPU rehearsal of the multi-rank protocol (gloo, no GPU, no hot path): launcher, sharding, "
                          "gather, barriers, max-over-ranks timing")
@@ -245,6 +267,28 @@ def verify_frame(blob, rgb, depth, calib, marg, labels, frame):
     lab_ok = bool(np.array_equal(labels.ravel(), wl))
     return {"ok": lab_ok and diff <= MARGINAL_TOL, "frame": int(frame), "labels_bit_exact": lab_ok,
             "marginals_max_abs_diff": diff, "marginals_bit_exact": bool(np.array_equal(marg, wm)), "tolerance": MARGINAL_TOL}
+
+
+def dump_outputs(dirname, n, d_marg, d_labels, d_fused):
+    """The last timed step's outputs at a fixed, seeded sample of pixels (the whole batch does not fit the
+    64 MB budget): the sample is gathered on the device, only the sample is copied to the host."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    N = W * H
+    k = min(DUMP_PIXELS, n * N)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n * N, size=k, replace=False))
+    t = torch.from_numpy(idx).to(d_marg.device)
+    f, p = t // N, t % N
+    arrays = {"pixel_index": idx.astype(np.float64),
+              "marginals": d_marg.view(n, N, C_CLASSES)[f, p, :],   # k x C: per frame [y][x][class] (include/rvseg.h)
+              "labels": d_labels.view(n, N)[f, p]}
+    if d_fused is not None:
+        arrays["fused_labels"] = d_fused.view(n, N)[f, p]
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def rehearsal(args):
@@ -385,9 +429,11 @@ def main():
     async_status = ctx.poll_status(wait=True)   # hash overflow of the last step would show here
     schedule = ctx.last_schedule()
     last_set = (steps_done[0] - 1) % N_SETS
+    if rank == 0 and args.dump_outputs:   # before anything below reuses d_marg / d_labels
+        dump_outputs(args.dump_outputs, n, d_marg, d_labels, d_fused)
 
     # per-stage durations of the LAST step, from HIP events recorded on the launch stream
-    stages = ctx.last_timing()
+    stages = ctx.last_timing() if args.full else {}
     devices_seen = None
     if world > 1:
         devices_seen = [None] * world
@@ -395,7 +441,7 @@ def main():
                                               "name": torch.cuda.get_device_name(dev)})
 
     verified = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         vf = 9 % n
         verified = verify_frame(blob, sets_h[last_set][0], sets_h[last_set][1], calib, d_marg[vf].cpu().numpy(),
                                 d_labels[vf].cpu().numpy(), vf)
@@ -407,7 +453,7 @@ def main():
     # single-frame latency (configs[1]) -- outside the timed region
     lat = None
     stages_single = {}
-    if rank == 0 and not args.no_latency:
+    if rank == 0 and args.full and not args.no_latency:
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         reps = 5
@@ -420,7 +466,7 @@ def main():
         ctx.poll_status(wait=True)
 
     extras = {}
-    if rank == 0 and n_gpus == 1 and args.extras != "none":
+    if rank == 0 and args.full and n_gpus == 1 and args.extras != "none":
         try:
             from rovinasemanticsegmentation_amd import bench_extras
             want = None if args.extras == "default" else set(args.extras.split(","))
@@ -431,22 +477,6 @@ def main():
     if rank == 0:
         px_per_step = n * N
         value = n_gpus * px_per_step * args.steps / dt / 1e6
-        # dominant stage and its roofline position
-        launches = {"softmax": 1, "splat": CRF_ITERS, "blur": CRF_ITERS, "slice": CRF_ITERS, "mf_update": CRF_ITERS}
-        cand = {k: v for k, v in stages.items() if k in SINGLE_KERNEL_STAGES}
-        dom = max(cand, key=cand.get) if cand else None
-        roof = None
-        if dom:
-            k = launches.get(dom, 1)
-            bytes_per_launch = STAGE_BYTES_PER_PX.get(dom, 0.0) * px_per_step
-            avg_ms = stages[dom] / k
-            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-            roof = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                    # PMC counters of this very command (profiles/scripts/pmc.sh); only the headline shape has them
-                    "traffic": pmc_traffic(dom) if (n == FRAMES_PER_STEP and args.config == 2 and not args.no_overlap) else None,
-                    "avg_launch_ms": round(avg_ms, 4), "launches_per_step": k,
-                    "algorithmic_bytes_per_launch": bytes_per_launch}
         out = {
             "metric": "Mpix/s RF+5-iter DenseCRF @640x480 RGB-D", "value": round(value, 3), "unit": "Mpix/s",
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -462,22 +492,44 @@ def main():
                        "frames_per_step_per_gpu": n,
                        "label_gather": ("%s gather to rank 0" % ("rccl" if backend == "nccl" else backend)) if world > 1
                                        else ("rccl gather, world size 1 (C ABI)" if d_fused is not None else "none")},
+            "full": bool(args.full),
             "schedule": schedule,
-            "roofline": roof,
-            "verified": (verified["ok"] if verified else None), "verification": verified,
             "async_status": "ok" if async_status == rv.capi.OK else str(async_status),
             "world_size_seen": dist.get_world_size() if world > 1 else 1, "device_count": device_count,
             "devices_seen": devices_seen,
-            "pipeline_hbm_frac": round(PIPELINE_BYTES_PER_PX * value * 1e6 / n_gpus / (HBM_PEAK_GBS * 1e9), 5),
-            "stage_ms_last_step": {k: round(v, 3) for k, v in stages.items()},
-            "latency_ms_single_frame": round(lat, 3) if lat else None,
-            "stage_ms_single_frame": {k: round(v, 3) for k, v in stages_single.items()},
         }
-        out.update(extras)
-        if n_gpus == 1 and not args.no_cpu and args.cpu_frames > 0:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_frames, blob, rgb_h, depth_h, calib)
-        else:
-            out["cpu_baseline"] = None
+        if args.dump_outputs:
+            out["dump_outputs"] = os.path.abspath(args.dump_outputs)
+        if args.full:
+            # dominant stage and its roofline position
+            launches = {"softmax": 1, "splat": CRF_ITERS, "blur": CRF_ITERS, "slice": CRF_ITERS, "mf_update": CRF_ITERS}
+            cand = {k: v for k, v in stages.items() if k in SINGLE_KERNEL_STAGES}
+            dom = max(cand, key=cand.get) if cand else None
+            roof = None
+            if dom:
+                k = launches.get(dom, 1)
+                bytes_per_launch = STAGE_BYTES_PER_PX.get(dom, 0.0) * px_per_step
+                avg_ms = stages[dom] / k
+                achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+                roof = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                        # PMC counters of this very command (profiles/scripts/pmc.sh); only the headline shape has them
+                        "traffic": pmc_traffic(dom) if (n == FRAMES_PER_STEP and args.config == 2 and not args.no_overlap) else None,
+                        "avg_launch_ms": round(avg_ms, 4), "launches_per_step": k,
+                        "algorithmic_bytes_per_launch": bytes_per_launch}
+            out.update({
+                "roofline": roof,
+                "verified": (verified["ok"] if verified else None), "verification": verified,
+                "pipeline_hbm_frac": round(PIPELINE_BYTES_PER_PX * value * 1e6 / n_gpus / (HBM_PEAK_GBS * 1e9), 5),
+                "stage_ms_last_step": {k: round(v, 3) for k, v in stages.items()},
+                "latency_ms_single_frame": round(lat, 3) if lat else None,
+                "stage_ms_single_frame": {k: round(v, 3) for k, v in stages_single.items()},
+            })
+            out.update(extras)
+            if n_gpus == 1 and not args.no_cpu and args.cpu_frames > 0:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_frames, blob, rgb_h, depth_h, calib)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out))
     ctx.close()
     if world > 1:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""TEST INFRASTRUCTURE ONLY -- regenerates tests/golden/forest_* with the REFERENCE's own code.
+"""TEST INFRASTRUCTURE ONLY -- regenerates tests/golden/forest_* with the REFERENCE's own code
+(`--bench`: only tests/golden/forest_bench_ref.json).
 
 Runs only in the build container (it needs oracle/_ref/libforest_ref, i.e. the reference's
 third-party/libforest/src/classifier.cpp compiled in place by `make -C oracle ref`).  The forests
@@ -7,9 +8,12 @@ are serialised by the reference's RandomForest::write and the expected outputs a
 the reference's classLogPosterior / multiClassLogPosterior (classifier.cpp:166-235).  The vectors
 pin the model format, the strict '<' split rule and the tree-order fp32 accumulation bit-exactly.
 """
+import hashlib
+import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -66,5 +70,50 @@ def main():
     print("wrote", sorted(out.keys()))
 
 
+def bench_digests():
+    """`--bench`: tests/golden/forest_bench_ref.json, the reference's outputs on bench-sized forests, pinned as SHA-256
+    of their float32 bytes (the arrays themselves are megabytes).  Inputs are the tests' own seeded ones: the forest
+    bench.py uses (4 trees x 2^14 leaves, depth <= 30) on 5 000 points (tests/test_oracle_forest.py) and on 20 000
+    points (tests/test_gpu_forest.py), and a 3-tree two-layer forest trained on those 20 000 points by the oracle's
+    learner, which writes the GPU trainer's file byte for byte (tests/test_gpu_train.py)."""
+    import importlib.util
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    from rovinasemanticsegmentation_amd import synthetic
+    spec = importlib.util.spec_from_file_location("rvseg_oracle_py", os.path.join(HERE, "oracle.py"))
+    O = importlib.util.module_from_spec(spec)   # (this directory also holds a module named oracle)
+    spec.loader.exec_module(O)
+    if not os.path.exists(REF):
+        sys.exit("oracle/_ref/libforest_ref missing: run `make -C oracle ref` in the build container")
+    sha = lambda b: hashlib.sha256(b).hexdigest()
+    out = {}
+
+    def ref_eval(tmp, name, blob, X, mode):
+        dat, xs, o = (os.path.join(tmp, n) for n in ("f.dat", "x.f32", "o.f32"))
+        with open(dat, "wb") as fh:
+            fh.write(blob)
+        X.tofile(xs)
+        subprocess.check_call([REF, "eval", dat, xs, "366", mode, o])
+        y = np.fromfile(o, np.float32)
+        out[name + "_" + mode] = {"size": int(y.size), "sha256": sha(y.astype("<f4").tobytes())}
+
+    big = synthetic.make_forest_bytes(seed=7, n_trees=4, leaves_per_tree=1 << 14, max_depth=30, single_classes=9,
+                                      layer_classes=(8, 9))
+    X5k = synthetic.random_points(78, 5000)       # tests/test_oracle_forest.py
+    X20k = synthetic.random_points(77, 20000)     # tests/test_gpu_forest.py
+    lab = np.stack([(X20k[:, 3] // 32).astype(np.int32),
+                    (X20k[:, 363] > 7).astype(np.int32) + 2 * (X20k[:, 100] > 128).astype(np.int32)], 1)
+    trained = O.forest_train(X20k, lab, [8, 4], num_trees=3, max_depth=12, min_split_examples=20, seed=3)
+    out["trained_x77_20000_forest"] = {"size": len(trained), "sha256": sha(trained)}
+    with tempfile.TemporaryDirectory() as tmp:
+        for mode in ("single", "multi"):
+            ref_eval(tmp, "bench_x78_5000", big, X5k, mode)
+            ref_eval(tmp, "bench_x77_20000", big, X20k, mode)
+        ref_eval(tmp, "trained_x77_20000", trained, X20k, "multi")
+    with open(os.path.join(GOLD, "forest_bench_ref.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote", sorted(out))
+
+
 if __name__ == "__main__":
-    main()
+    bench_digests() if sys.argv[1:] == ["--bench"] else main()

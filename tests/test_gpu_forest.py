@@ -79,18 +79,23 @@ def test_loader_errors(gpu_ctx_factory, golden_dir):
     assert e.value.status == rv.capi.ERR_FORMAT and "mismatch" in str(e.value)
 
 
-def test_forest_eval_equals_the_reference_evaluator_run_on_this_box(gpu_ctx_factory, tmp_path):
-    """oracle/_ref/libforest_ref is the REFERENCE's own classifier.cpp compiled in the build container (make -C oracle
-    ref; nothing of the reference is in the repository, the binary travels with the snapshot).  It is run here, on the GPU
-    box, on a bench-sized forest (4 trees x 2^14 leaves, depth <= 30, D = 366) and on a forest written by the GPU trainer:
-    RandomForest::read parses both files, multiClassLogPosterior / classLogPosterior evaluate 20 000 points, and the HIP
-    evaluator must return the same floats bit for bit -- reference-pinned parity at a size the committed vectors
-    (1 024 points, 96 leaves per tree) do not reach."""
+def test_forest_eval_equals_the_reference_evaluator_run_on_this_box(gpu_ctx_factory, golden_dir, tmp_path):
+    """The REFERENCE's own classifier.cpp on a bench-sized forest (4 trees x 2^14 leaves, depth <= 30, D = 366) and on a
+    forest written by the GPU trainer: RandomForest::read parses both files, multiClassLogPosterior / classLogPosterior
+    evaluate 20 000 points, and the HIP evaluator must return the same floats bit for bit -- reference-pinned parity at a
+    size the committed vectors (1 024 points, 96 leaves per tree) do not reach.  The reference's outputs are pinned in
+    tests/golden/forest_bench_ref.json (SHA-256 of the float32 bytes, `oracle/gen_golden.py --bench`; the trained file
+    there is the oracle learner's, which the GPU trainer must write byte for byte).  Where oracle/_ref/libforest_ref
+    (`make -C oracle ref`, needs the reference tree; nothing of the reference is in the repository) is present, it is
+    run here as well."""
+    import hashlib
+    import json
     import os
     import subprocess
     ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libforest_ref")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/libforest_ref not built (needs /root/reference in the build container)")
+    with open(os.path.join(golden_dir, "forest_bench_ref.json")) as fh:
+        pinned = json.load(fh)
+    sha = lambda b: hashlib.sha256(b).hexdigest()
     X = synthetic.random_points(77, 20000)
     (tmp_path / "x.f32").write_bytes(X.tobytes())
     big = synthetic.make_forest_bytes(seed=7, n_trees=4, leaves_per_tree=1 << 14, max_depth=30, single_classes=9, layer_classes=(8, 9))
@@ -98,15 +103,20 @@ def test_forest_eval_equals_the_reference_evaluator_run_on_this_box(gpu_ctx_fact
     tctx = gpu_ctx_factory()
     lab = np.stack([(X[:, 3] // 32).astype(np.int32), (X[:, 363] > 7).astype(np.int32) + 2 * (X[:, 100] > 128).astype(np.int32)], 1)
     trained = tctx.forest_train(X, lab, [8, 4], num_trees=3, max_depth=12, min_split_examples=20, seed=3)
+    assert sha(trained) == pinned["trained_x77_20000_forest"]["sha256"], "the trained file is not the one the pinned outputs belong to"
     for name, blob, modes in (("bench", big, ("single", "multi")), ("trained", trained, ("multi",))):
         path = tmp_path / (name + ".dat")
         path.write_bytes(blob)
         for mode in modes:
-            out = tmp_path / (name + "_" + mode + ".f32")
-            subprocess.check_call([ref, "eval", str(path), str(tmp_path / "x.f32"), "366", mode, str(out)], timeout=300)
-            want = np.fromfile(out, np.float32)
             ctx = gpu_ctx_factory(multi_layer=1 if mode == "multi" else 0)
             ctx.forest_load(blob)
             got = ctx.forest_eval(X)
-            assert got.size == want.size, (name, mode)
-            assert np.array_equal(got.ravel(), want), (name, mode)
+            if os.path.exists(ref):
+                out = tmp_path / (name + "_" + mode + ".f32")
+                subprocess.check_call([ref, "eval", str(path), str(tmp_path / "x.f32"), "366", mode, str(out)], timeout=300)
+                want = np.fromfile(out, np.float32)
+                assert got.size == want.size, (name, mode)
+                assert np.array_equal(got.ravel(), want), (name, mode)
+            want = pinned["%s_x77_20000_%s" % (name, mode)]
+            assert got.dtype == np.float32 and got.size == want["size"], (name, mode)
+            assert sha(np.ascontiguousarray(got).astype("<f4").tobytes()) == want["sha256"], (name, mode)

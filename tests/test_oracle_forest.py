@@ -76,21 +76,29 @@ def test_python_writer_round_trips_through_oracle(oracle):
     assert out.shape == (50, 17) and np.isfinite(out).all() and (out < 0).all()
 
 
-def test_oracle_equals_the_compiled_reference_on_a_bench_sized_forest(oracle, tmp_path):
-    """The reference's own classifier.cpp (oracle/_ref/libforest_ref, built by `make -C oracle ref` where /root/reference
-    exists) against the C restatement on the forest bench.py uses (4 trees x 2^14 leaves, depth <= 30) and 5 000 points:
-    single- and multi-layer outputs bit for bit."""
+def test_oracle_equals_the_compiled_reference_on_a_bench_sized_forest(oracle, golden_dir, tmp_path):
+    """The reference's own classifier.cpp against the C restatement on the forest bench.py uses (4 trees x 2^14 leaves,
+    depth <= 30) and 5 000 points: single- and multi-layer outputs bit for bit.  The reference's outputs are pinned in
+    tests/golden/forest_bench_ref.json (SHA-256 of the float32 bytes, `oracle/gen_golden.py --bench`); where
+    oracle/_ref/libforest_ref is built (`make -C oracle ref`, needs the reference tree) it is run here as well."""
+    import hashlib
+    import json
     import subprocess
     from rovinasemanticsegmentation_amd import synthetic
     ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libforest_ref")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/libforest_ref not built")
+    with open(os.path.join(golden_dir, "forest_bench_ref.json")) as fh:
+        pinned = json.load(fh)
     X = synthetic.random_points(78, 5000)
     (tmp_path / "x.f32").write_bytes(X.tobytes())
     blob = synthetic.make_forest_bytes(seed=7, n_trees=4, leaves_per_tree=1 << 14, max_depth=30, single_classes=9, layer_classes=(8, 9))
     (tmp_path / "f.dat").write_bytes(blob)
     forest = oracle.Forest(blob)
     for mode, multi in (("single", 0), ("multi", 1)):
-        out = tmp_path / (mode + ".f32")
-        subprocess.check_call([ref, "eval", str(tmp_path / "f.dat"), str(tmp_path / "x.f32"), "366", mode, str(out)], timeout=300)
-        assert np.array_equal(forest.eval(X, multi).ravel(), np.fromfile(out, np.float32)), mode
+        got = forest.eval(X, multi).ravel()
+        if os.path.exists(ref):
+            out = tmp_path / (mode + ".f32")
+            subprocess.check_call([ref, "eval", str(tmp_path / "f.dat"), str(tmp_path / "x.f32"), "366", mode, str(out)], timeout=300)
+            assert np.array_equal(got, np.fromfile(out, np.float32)), mode
+        want = pinned["bench_x78_5000_" + mode]
+        assert got.dtype == np.float32 and got.size == want["size"], mode
+        assert hashlib.sha256(got.astype("<f4").tobytes()).hexdigest() == want["sha256"], mode
