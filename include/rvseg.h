@@ -330,6 +330,65 @@ void rvseg_comm_destroy(rvseg_ctx *ctx);
 rvseg_status rvseg_gather_frames(rvseg_ctx *ctx, const void *d_local, size_t bytes_per_rank, void *d_recv,
                                  int32_t root, void *hip_stream);
 
+/* ---- scoring: replaces RgbLabelConversion (include/rgb_label_conversion.h) and the confusion / score block of
+ *      src/test.cpp:182-228 and src/test_multi.cpp:222-268.  L and C_l are the loaded model's (rvseg_forest_info);
+ *      every call below except rvseg_eval_scores_from_counts needs a loaded model (else RVSEG_ERR_INVALID_ARG), and
+ *      rvseg_forest_load discards colour codings and counters.  Label images are the layout of labels_out above:
+ *      n x L x H x W int8 (layer < 0), or n x H x W of one layer (layer >= 0); RGB8 images add a trailing R, G, B byte
+ *      triple per pixel -- the bytes of the PNG the reference reads or writes (it swaps to BGR and back,
+ *      rgb_label_conversion.h:47-49,67-69,80-88, test.cpp:199).
+ *
+ * Colour coding of one layer: n entries (n <= 256, else RVSEG_ERR_CAPACITY) in config.json's color_codings[l].coding
+ * order, rgb n x 3 and labels n, negative labels included (Void = -1, Other = -2).  Replaces the RgbLabelConversion
+ * constructor (rgb_label_conversion.h:20-39):
+ *   decode  a colour maps to the label of the LAST entry with that colour; a colour not in the table maps to
+ *           missing_label.  The reference's std::map::operator[] gives 0 there (:86-88): pass 0 for its behaviour,
+ *           -1 to leave unknown colours unscored.
+ *   encode  a label maps to the colour of the LAST entry with that label; a label not in the table to (0, 0, 0) (:80-84). */
+rvseg_status rvseg_color_coding_set(rvseg_ctx *ctx, int32_t layer, int32_t n, const uint8_t *rgb, const int8_t *labels,
+                                    int8_t missing_label);
+/* RgbLabelConversion::rgbToLabel / labelToRgb (rgb_label_conversion.h:42-78) over n_images label images.  _device:
+ * device buffers, enqueued on hip_stream, not waited for.  Host variants stage through the context's stream. */
+rvseg_status rvseg_labels_from_rgb_device(rvseg_ctx *ctx, int32_t layer, int32_t n_images, const uint8_t *d_rgb,
+                                          int8_t *d_labels, void *hip_stream);
+rvseg_status rvseg_labels_to_rgb_device(rvseg_ctx *ctx, int32_t layer, int32_t n_images, const int8_t *d_labels,
+                                        uint8_t *d_rgb, void *hip_stream);
+rvseg_status rvseg_labels_from_rgb(rvseg_ctx *ctx, int32_t layer, int32_t n_images, const uint8_t *rgb, int8_t *labels);
+rvseg_status rvseg_labels_to_rgb(rvseg_ctx *ctx, int32_t layer, int32_t n_images, const int8_t *labels, uint8_t *rgb);
+
+/* Confusion matrix per layer, uint64 counts on the device (the reference's int counters overflow after ~7 000 VGA
+ * frames).  The accumulate calls replace the counting loop of test.cpp:186-195 (test_multi.cpp:222-233) over every
+ * full-resolution pixel of every layer: count[gt][pred] += 1 where pred >= 0 and gt >= 0.  A pair with pred >= C_l or
+ * gt >= C_l (the reference indexes past its arrays) goes to the layer's out-of-range counter instead.
+ *   d_pred   n_frames x L x H x W int8: labels_out of rvseg_segment_frames[_device] as it is.  test.cpp scores
+ *            multi_layer = 0, fill_value = -1000, RVSEG_LABEL_EVAL, no CRF, stride 2 (its "/2" is hard-coded,
+ *            :141,152); test_multi.cpp the same with multi_layer = 1 at the configured stride
+ *   d_gt     RVSEG_GT_LABELS: n_frames x L x H x W int8; RVSEG_GT_RGB: the colour-coded images (x 3 bytes), decoded on
+ *            the fly through each layer's colour coding (no int8 image is written)
+ * _device: enqueued on hip_stream (NULL = the context's stream, as for rvseg_segment_frames_device) without
+ * synchronising; the context records an event there, and
+ * rvseg_eval_confusion waits for it, so segment_frames_device -> eval_accumulate_device can share one stream with no
+ * host synchronisation in between.  Counts are integers: the result does not depend on the order of the work. */
+typedef enum rvseg_gt_format {
+    RVSEG_GT_LABELS = 0,
+    RVSEG_GT_RGB = 1
+} rvseg_gt_format;
+rvseg_status rvseg_eval_reset(rvseg_ctx *ctx);
+rvseg_status rvseg_eval_accumulate_device(rvseg_ctx *ctx, int32_t n_frames, const int8_t *d_pred, const void *d_gt,
+                                          int32_t gt_format, void *hip_stream);
+rvseg_status rvseg_eval_accumulate(rvseg_ctx *ctx, int32_t n_frames, const int8_t *pred, const void *gt,
+                                   int32_t gt_format);
+/* Counts of one layer since the last reset: counts_out C_l x C_l, row = ground truth, column = prediction
+ * (label_count of test.cpp:186-195).  Either output may be NULL. */
+rvseg_status rvseg_eval_confusion(rvseg_ctx *ctx, int32_t layer, uint64_t *counts_out, uint64_t *out_of_range);
+/* The scores of test.cpp:203-228 from a C x C count matrix, in the reference's types and order: float accumulators
+ * of double expressions over static_cast<float>(count), divisors converted to double, C counting every class (empty
+ * ones included).  global_acc = 100.0 * (float)sum(diag) / total (NaN when total == 0, as in the reference);
+ * class_avg_acc and iou as printed at :226-227; row_pct_out (optional, C x C) = the printed table,
+ * 100.0 * (float)count / row total (row total 0 -> 1).  Host only: no context, no GPU. */
+rvseg_status rvseg_eval_scores_from_counts(const uint64_t *counts, int32_t C, double *global_acc, float *class_avg_acc,
+                                           float *iou, double *row_pct_out);
+
 /* ---- launch schedules.  The library picks the schedule of the ordered splat (the dominant kernel) and the stream
  *      overlaps from the shape of the work; this block overrides those choices for tests, profiling and tuning.
  *      Nothing on the call path reads the environment.  The reference has no counterpart (single thread). */

@@ -32,6 +32,8 @@
 //                                                                 layer name or map id, layers concatenated
 //   /tmp/cloud<ID>_rgb.cld, _layer_<l>.cld dumps  :684-706    dumpClouds()
 //   DenseCRF2D::addPairwiseGaussian/Bilateral     densecrf.cpp:61-81   DenseCRF2D (rvseg_crf_features_*)
+//   RgbLabelConversion (rgb_label_conversion.h)                RgbLabelConversion: full coding, negative labels included
+//   test.cpp / test_multi.cpp confusion + scores  :182-228    Evaluator: counts on the GPU, scores(), report()
 //
 // Thread rule as in the reference: one thread drives one Segmenter (the RF worker owns the frame
 // context, the fusion thread the cloud context); create one object per thread and GPU.
@@ -46,6 +48,8 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <stdexcept>
@@ -640,6 +644,134 @@ private:
     std::vector<std::vector<float>> feats_;
     std::vector<int32_t> ds_;
     std::vector<float> ws_;
+};
+
+// ---- scoring: RgbLabelConversion (include/rgb_label_conversion.h) and the score block of src/test.cpp:182-228 --------
+// One entry of config.json color_codings[l].coding, negative labels included (LabelClass above keeps only classes >= 0).
+struct ColorCodingEntry {
+    std::string name;
+    std::array<uint8_t, 3> color;   // r, g, b
+    int label;                      // stored as label_type = char (include/defines.h)
+};
+
+// Binds one layer's coding to a context (rvseg_color_coding_set; a later rvseg_forest_load discards it).  Images are
+// the context's H x W in R, G, B byte order; conversions run on the GPU (host buffers, staged by the library).
+class RgbLabelConversion {
+public:
+    RgbLabelConversion(rvseg_ctx* ctx, const std::vector<ColorCodingEntry>& coding, int layer = 0, int8_t missing_label = 0)
+        : ctx_(ctx), layer_(layer) {
+        std::vector<uint8_t> rgb;
+        std::vector<int8_t> labels;
+        for (const ColorCodingEntry& e : coding) {   // std::map assignments in entry order (:29-38)
+            const int8_t l = (int8_t)e.label;
+            rgb.insert(rgb.end(), e.color.begin(), e.color.end());
+            labels.push_back(l);
+            name_to_label_[e.name] = l;
+            label_to_name_[l] = e.name;
+        }
+        check(rvseg_color_coding_set(ctx_, layer_, (int32_t)labels.size(), rgb.data(), labels.data(), missing_label));
+    }
+    void rgbToLabel(const uint8_t* rgb, int8_t* labels, int n_images = 1) { check(rvseg_labels_from_rgb(ctx_, layer_, n_images, rgb, labels)); }   // :59-78
+    void labelToRgb(const int8_t* labels, uint8_t* rgb, int n_images = 1) { check(rvseg_labels_to_rgb(ctx_, layer_, n_images, labels, rgb)); }     // :42-57
+    std::string getLabelName(int8_t label) const {                  // :91-93
+        auto it = label_to_name_.find(label);
+        return it == label_to_name_.end() ? std::string() : it->second;
+    }
+    int8_t getLabelNumber(const std::string& name) const {          // :95-97
+        auto it = name_to_label_.find(name);
+        return it == name_to_label_.end() ? 0 : it->second;
+    }
+    int getValidLabelCount() const {                                // :103-110
+        int n = 0;
+        for (const auto& kv : label_to_name_) n += kv.first >= 0;
+        return n;
+    }
+private:
+    void check(rvseg_status st) const {
+        if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
+    }
+    rvseg_ctx* ctx_;
+    int layer_;
+    std::map<std::string, int8_t> name_to_label_;
+    std::map<int8_t, std::string> label_to_name_;
+};
+
+// The confusion matrices of every label layer of a context, accumulated on the GPU (uint64), and the reference's scores.
+struct EvalScores {
+    double global_acc;      // NaN before anything was counted, as the reference prints it
+    float class_avg_acc;
+    float iou;
+    std::vector<double> row_pct;   // C x C, the printed table
+};
+
+class Evaluator {
+public:
+    // codings: one per label layer of the loaded model; an empty coding leaves that layer to int8 ground truth
+    Evaluator(rvseg_ctx* ctx, const std::vector<std::vector<ColorCodingEntry>>& codings, int8_t missing_label = 0) : ctx_(ctx) {
+        int32_t n_layers = 0, cc[RVSEG_MAX_LAYERS];
+        check(rvseg_forest_info(ctx_, nullptr, nullptr, nullptr, &n_layers, cc));
+        if ((size_t)n_layers != codings.size()) throw std::runtime_error("one colour coding per label layer");
+        class_counts_.assign(cc, cc + n_layers);
+        for (int l = 0; l < n_layers; l++)
+            conv_.emplace_back(codings[l].empty() ? nullptr : new RgbLabelConversion(ctx_, codings[l], l, missing_label));
+        reset();
+    }
+    void reset() { check(rvseg_eval_reset(ctx_)); }
+    // pred: n x L x H x W int8 (labels_out); gt: the same int8 layout (RVSEG_GT_LABELS) or x 3 bytes (RVSEG_GT_RGB)
+    void add(int n_frames, const int8_t* pred, const void* gt, int gt_format = RVSEG_GT_LABELS) {
+        check(rvseg_eval_accumulate(ctx_, n_frames, pred, gt, gt_format));
+    }
+    void addDevice(int n_frames, const int8_t* d_pred, const void* d_gt, int gt_format, void* hip_stream) {
+        check(rvseg_eval_accumulate_device(ctx_, n_frames, d_pred, d_gt, gt_format, hip_stream));
+    }
+    std::vector<uint64_t> confusion(int layer, uint64_t* out_of_range = nullptr) {
+        std::vector<uint64_t> c((size_t)class_counts_.at(layer) * class_counts_.at(layer));
+        check(rvseg_eval_confusion(ctx_, layer, c.data(), out_of_range));
+        return c;
+    }
+    EvalScores scores(int layer) {
+        const std::vector<uint64_t> c = confusion(layer);
+        const int C = class_counts_.at(layer);
+        EvalScores s;
+        s.row_pct.resize((size_t)C * C);
+        check(rvseg_eval_scores_from_counts(c.data(), C, &s.global_acc, &s.class_avg_acc, &s.iou, s.row_pct.data()));
+        return s;
+    }
+    // the text test.cpp:206-228 prints
+    std::string report(int layer) {
+        const std::vector<uint64_t> c = confusion(layer);
+        const EvalScores s = scores(layer);
+        const int C = class_counts_.at(layer);
+        std::string out = "confusion:\n";
+        char buf[64];
+        for (int i = 0; i < C; i++) {
+            std::string n = conv_[layer] ? conv_[layer]->getLabelName((int8_t)i) : std::string();
+            for (int p = (int)n.length(); p < 15; p++) n += " ";
+            out += n;
+            uint64_t row = 0;
+            for (int j = 0; j < C; j++) {
+                std::snprintf(buf, sizeof(buf), " %6.2f", s.row_pct[(size_t)i * C + j]);
+                out += buf;
+                row += c[(size_t)i * C + j];
+            }
+            out += "   out of " + std::to_string(row) + " pixels\n";
+        }
+        std::snprintf(buf, sizeof(buf), "Global accuracy:         %6.2f \n", s.global_acc);
+        out += buf;
+        std::snprintf(buf, sizeof(buf), "Class averge accuracy:   %6.2f \n", s.class_avg_acc);
+        out += buf;
+        std::snprintf(buf, sizeof(buf), "Intersection over union: %6.2f \n", s.iou);
+        out += buf;
+        return out;
+    }
+    RgbLabelConversion* conversion(int layer) { return conv_.at(layer).get(); }
+private:
+    void check(rvseg_status st) const {
+        if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
+    }
+    rvseg_ctx* ctx_;
+    std::vector<int> class_counts_;
+    std::vector<std::unique_ptr<RgbLabelConversion>> conv_;
 };
 
 }  // namespace rvseg

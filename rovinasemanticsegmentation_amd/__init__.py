@@ -6,7 +6,9 @@ runtime.  There is no CPU fallback: without the built library the import of `_ca
 without a GPU `Context()` raises.
 """
 from . import _capi as capi  # noqa: F401
-from .segmenter import Context, DenseCRF, FeatureExtractor, LocalMapStore, RandomForest, Segmenter  # noqa: F401
+from .segmenter import (Context, DenseCRF, Evaluator, FeatureExtractor, LocalMapStore, RandomForest,  # noqa: F401
+                        RgbLabelConversion, Segmenter)
 from . import synthetic  # noqa: F401
 
-__all__ = ["capi", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic"]
+__all__ = ["capi", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
+           "RgbLabelConversion", "Evaluator"]

@@ -15,6 +15,7 @@ RVSEG_MAX_LAYERS = 8
 
 OK, ERR_INVALID_ARG, ERR_IO, ERR_FORMAT, ERR_NO_FOREST, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY, NOT_READY = range(9)
 LABEL_EVAL, LABEL_CRF, LABEL_NOCRF, LABEL_ARGMAX = range(4)
+GT_LABELS, GT_RGB = range(2)
 
 # every symbol include/rvseg.h declares
 SYMBOLS = [
@@ -34,6 +35,9 @@ SYMBOLS = [
     "rvseg_schedule_default", "rvseg_set_schedule", "rvseg_last_schedule",
     "rvseg_forest_train_result", "rvseg_forest_train_frames",
     "rvseg_host_register", "rvseg_host_unregister",
+    "rvseg_color_coding_set", "rvseg_labels_from_rgb_device", "rvseg_labels_to_rgb_device",
+    "rvseg_labels_from_rgb", "rvseg_labels_to_rgb", "rvseg_eval_reset", "rvseg_eval_accumulate_device",
+    "rvseg_eval_accumulate", "rvseg_eval_confusion", "rvseg_eval_scores_from_counts",
 ]
 
 
@@ -154,6 +158,16 @@ def lib():
     L.rvseg_schedule_default.restype = None
     L.rvseg_set_schedule.argtypes = [vp, C.POINTER(RvsegSchedule)]
     L.rvseg_last_schedule.argtypes = [vp, C.POINTER(RvsegScheduleInfo)]
+    L.rvseg_color_coding_set.argtypes = [vp, i32, i32, vp, vp, C.c_int8]
+    L.rvseg_labels_from_rgb_device.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.rvseg_labels_to_rgb_device.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.rvseg_labels_from_rgb.argtypes = [vp, i32, i32, vp, vp]
+    L.rvseg_labels_to_rgb.argtypes = [vp, i32, i32, vp, vp]
+    L.rvseg_eval_reset.argtypes = [vp]
+    L.rvseg_eval_accumulate_device.argtypes = [vp, i32, vp, vp, i32, vp]
+    L.rvseg_eval_accumulate.argtypes = [vp, i32, vp, vp, i32]
+    L.rvseg_eval_confusion.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64)]
+    L.rvseg_eval_scores_from_counts.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(f32), C.POINTER(f32), vp]
     for name in SYMBOLS:
         getattr(L, name)  # raises AttributeError if the library does not export it
     _lib = L
@@ -222,3 +236,19 @@ def crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im):
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return out
+
+
+def eval_scores_from_counts(counts):
+    """Host-only (no GPU): the scores of src/test.cpp:203-228 from a C x C uint64 count matrix (row = ground truth).
+    Returns dict(global_acc, class_avg_acc, iou, row_pct) -- global_acc is NaN when the matrix is empty."""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, np.uint64)
+    Cn = counts.shape[0]
+    assert counts.shape == (Cn, Cn)
+    g, a, u = C.c_double(), C.c_float(), C.c_float()
+    row = np.empty((Cn, Cn), np.float64)
+    st = lib().rvseg_eval_scores_from_counts(counts.ctypes.data_as(C.c_void_p), Cn, C.byref(g), C.byref(a), C.byref(u),
+                                             row.ctypes.data_as(C.c_void_p))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    return {"global_acc": g.value, "class_avg_acc": a.value, "iou": u.value, "row_pct": row}

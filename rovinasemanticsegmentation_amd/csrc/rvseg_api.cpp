@@ -327,6 +327,7 @@ void rvseg_destroy(rvseg_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     rvseg_comm_destroy(ctx);
     rvseg_pipeline_destroy(ctx);
+    eval_destroy(ctx);
     dev_free(ctx->forest.nodes);
     dev_free(ctx->forest.nodes8);
     dev_free(ctx->forest.roots);
@@ -356,6 +357,7 @@ rvseg_status rvseg_forest_load_mem(rvseg_ctx* ctx, const void* buf, size_t size)
     // the device copy of the previous model may still be read by work the caller enqueued on its own
     // stream (rvseg_segment_frames_device returns without synchronising)
     RV_HIP(ctx, hipDeviceSynchronize());
+    eval_destroy(ctx);   // layer and class counts may change: colour codings and counters start again
     ctx->host_forest = std::move(m);
     ctx->forest_loaded = false;
     return upload_forest(ctx);

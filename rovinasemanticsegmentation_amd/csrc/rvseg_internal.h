@@ -56,6 +56,8 @@ struct StageTimer {
     bool side_used = false;
 };
 
+struct EvalState;   // colour codings + confusion counters of the scoring calls (kernels_eval.hip)
+
 }  // namespace rvseg
 
 struct rvseg_ctx {
@@ -76,6 +78,7 @@ struct rvseg_ctx {
     std::vector<uint8_t> trained_model;   // forest.dat image of the last rvseg_forest_train* call (rvseg_forest_train_result)
     void* comm = nullptr;  // RCCL communicator of the local-map gather (rvseg_comm.cpp), or null
     int comm_rank = 0, comm_world = 0;
+    rvseg::EvalState* eval = nullptr;     // allocated by the first scoring call; discarded by rvseg_forest_load
 };
 
 namespace rvseg {
@@ -103,6 +106,9 @@ rvseg_status dev_alloc(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 void dev_free(DevBuf& b);
 // grow-only allocation: reallocates when the buffer is too small
 rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
+
+// ---- kernels_eval.hip: frees the scoring state (waits for its pending work first) -----------------------------
+void eval_destroy(rvseg_ctx* ctx);
 
 // ---- kernels_rf.hip --------------------------------------------------------------------------
 // P points with materialised D-dimensional features -> P x S log-posteriors

@@ -6,6 +6,8 @@ Names follow the reference so that the parity tests read like its call sites:
   FeatureExtractor.extract                                         (include/feature_extractor.h:41)
   DenseCRF(N, C).setUnaryEnergy / addPairwiseEnergy / inference / map  (densecrf.h:36-121)
   Segmenter.processFrames                                          (src/segmenter.cpp:323-443)
+  RgbLabelConversion.rgbToLabel / labelToRgb / getLabelName / ...  (include/rgb_label_conversion.h)
+  Evaluator: the confusion matrix and scores of src/test.cpp:182-228 (test_multi.cpp:222-268)
 
 All compute happens in librvseg.so (HIP, gfx950).  Nothing here falls back to the CPU.
 """
@@ -345,6 +347,72 @@ class Context:
         capi.check(self.h, self.L.rvseg_lattice_filter(self.h, _ptr(V), V.shape[1], _ptr(out)))
         return out
 
+    # ---- scoring (colour-coded labels, confusion matrix; include/rvseg.h "scoring") -------------------------------
+    def color_coding_set(self, layer, coding, missing_label=0):
+        """rvseg_color_coding_set: `coding` is one config.json color_codings[*].coding list of {name, color, label}."""
+        n = len(coding)
+        rgb = np.array([[int(c) & 255 for c in e["color"]] for e in coding], np.uint8).reshape(n, 3)
+        lab = np.array([int(e["label"]) for e in coding], np.int64).astype(np.int8)   # label_type = char (defines.h)
+        capi.check(self.h, self.L.rvseg_color_coding_set(self.h, layer, n, _ptr(rgb), _ptr(lab), missing_label))
+
+    def _label_image_shape(self, layer):
+        p = self.params
+        return (p.height, p.width) if layer >= 0 else (len(self.forest_info()["class_counts"]), p.height, p.width)
+
+    def labels_from_rgb(self, rgb, layer=-1):
+        """rvseg_labels_from_rgb: rgb (n, [L,] H, W, 3) uint8 -> (n, [L,] H, W) int8; layer < 0: every layer."""
+        shp = self._label_image_shape(layer)
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.shape[1:] == shp + (3,), rgb.shape
+        out = np.empty(rgb.shape[:-1], np.int8)
+        capi.check(self.h, self.L.rvseg_labels_from_rgb(self.h, layer, rgb.shape[0], _ptr(rgb), _ptr(out)))
+        return out
+
+    def labels_to_rgb(self, labels, layer=-1):
+        """rvseg_labels_to_rgb: (n, [L,] H, W) int8 -> (n, [L,] H, W, 3) uint8 (R, G, B bytes)."""
+        shp = self._label_image_shape(layer)
+        labels = np.ascontiguousarray(labels, np.int8)
+        assert labels.shape[1:] == shp, labels.shape
+        out = np.empty(labels.shape + (3,), np.uint8)
+        capi.check(self.h, self.L.rvseg_labels_to_rgb(self.h, layer, labels.shape[0], _ptr(labels), _ptr(out)))
+        return out
+
+    def labels_from_rgb_device(self, n, d_rgb, d_labels, layer=-1, stream=0):
+        capi.check(self.h, self.L.rvseg_labels_from_rgb_device(self.h, layer, n, C.c_void_p(d_rgb), C.c_void_p(d_labels),
+                                                               C.c_void_p(stream or None)))
+
+    def labels_to_rgb_device(self, n, d_labels, d_rgb, layer=-1, stream=0):
+        capi.check(self.h, self.L.rvseg_labels_to_rgb_device(self.h, layer, n, C.c_void_p(d_labels), C.c_void_p(d_rgb),
+                                                             C.c_void_p(stream or None)))
+
+    def eval_reset(self):
+        capi.check(self.h, self.L.rvseg_eval_reset(self.h))
+
+    def eval_accumulate(self, pred, gt, gt_format=None):
+        """rvseg_eval_accumulate: pred (n, L, H, W) int8; gt (n, L, H, W) int8 or (n, L, H, W, 3) uint8 colour codes.
+        gt_format defaults by shape (capi.GT_RGB for the trailing 3)."""
+        pred = np.ascontiguousarray(pred, np.int8)
+        n = pred.shape[0]
+        if gt_format is None:
+            gt_format = capi.GT_RGB if np.ndim(gt) == pred.ndim + 1 else capi.GT_LABELS
+        gt = np.ascontiguousarray(gt, np.uint8 if gt_format == capi.GT_RGB else np.int8)
+        assert pred.shape == (n,) + self._label_image_shape(-1), pred.shape
+        assert gt.shape == pred.shape + ((3,) if gt_format == capi.GT_RGB else ()), gt.shape
+        capi.check(self.h, self.L.rvseg_eval_accumulate(self.h, n, _ptr(pred), _ptr(gt), gt_format))
+
+    def eval_accumulate_device(self, n, d_pred, d_gt, gt_format=capi.GT_LABELS, stream=0):
+        """rvseg_eval_accumulate_device: integer device addresses, enqueues only."""
+        capi.check(self.h, self.L.rvseg_eval_accumulate_device(self.h, n, C.c_void_p(d_pred), C.c_void_p(d_gt), gt_format,
+                                                               C.c_void_p(stream or None)))
+
+    def eval_confusion(self, layer):
+        """(C x C uint64 counts, out-of-range count) of one layer; waits for the pending accumulates."""
+        Cn = self.forest_info()["class_counts"][layer]
+        counts = np.empty((Cn, Cn), np.uint64)
+        oor = C.c_uint64()
+        capi.check(self.h, self.L.rvseg_eval_confusion(self.h, layer, _ptr(counts), C.byref(oor)))
+        return counts, oor.value
+
     def last_timing(self):
         names = C.create_string_buffer(4096)
         ms = (C.c_float * 64)()
@@ -528,3 +596,91 @@ class Segmenter:
 
     def close(self):
         self.ctx.close()
+
+
+class RgbLabelConversion:
+    """RgbLabelConversion (include/rgb_label_conversion.h) for one layer of a context: `coding` is one config.json
+    color_codings[*].coding list ({name, color: [r, g, b], label}).  Images convert on the GPU; images are RGB byte
+    order (the PNG's), the reference's BGR swaps cancel out.  missing_label: label of colours not in the table -- 0 as
+    the reference's std::map gives (rgb_label_conversion.h:86-88), -1 to leave them unscored."""
+
+    def __init__(self, ctx, coding, layer=0, missing_label=0):
+        self.ctx, self.layer, self.coding = ctx, layer, list(coding)
+        self._name_to_label, self._label_to_name = {}, {}
+        for e in self.coding:                      # std::map assignments in entry order (:29-38)
+            lab = int(np.int64(e["label"]).astype(np.int8))
+            self._name_to_label[e["name"]] = lab
+            self._label_to_name[lab] = e["name"]
+        ctx.color_coding_set(layer, self.coding, missing_label)
+
+    def rgbToLabel(self, image):                   # :59-78; (H, W, 3) or (n, H, W, 3)
+        im = np.asarray(image, np.uint8)
+        one = im.ndim == 3
+        out = self.ctx.labels_from_rgb(im[None] if one else im, self.layer)
+        return out[0] if one else out
+
+    def labelToRgb(self, labels):                  # :42-57; (H, W) or (n, H, W)
+        lab = np.asarray(labels, np.int8)
+        one = lab.ndim == 2
+        out = self.ctx.labels_to_rgb(lab[None] if one else lab, self.layer)
+        return out[0] if one else out
+
+    def getLabelName(self, label):                 # :91-93 ("" for an unknown label, as operator[] gives)
+        return self._label_to_name.get(int(label), "")
+
+    def getLabelNumber(self, name):                # :95-97 (0 for an unknown name)
+        return self._name_to_label.get(name, 0)
+
+    def getValidLabelCount(self):                  # :103-110
+        return sum(1 for l in self._label_to_name if l >= 0)
+
+
+class Evaluator:
+    """The scoring of src/test.cpp:182-228 / src/test_multi.cpp:222-268 on the GPU for every label layer of a context:
+    `codings` holds one config.json coding list per layer (or None for a layer scored from int8 ground truth only).
+    add(pred, gt) takes host arrays, add_device(...) device addresses; counts are uint64 and exact."""
+
+    def __init__(self, ctx, codings, missing_label=0):
+        self.ctx = ctx
+        self.class_counts = ctx.forest_info()["class_counts"]
+        if len(codings) != len(self.class_counts):
+            raise ValueError("one coding per label layer of the model (%d)" % len(self.class_counts))
+        self.conv = [RgbLabelConversion(ctx, c, l, missing_label) if c is not None else None for l, c in enumerate(codings)]
+        ctx.eval_reset()
+
+    def reset(self):
+        self.ctx.eval_reset()
+
+    def add(self, pred, gt, gt_format=None):
+        self.ctx.eval_accumulate(pred, gt, gt_format)
+
+    def add_device(self, n, d_pred, d_gt, gt_format=capi.GT_LABELS, stream=0):
+        self.ctx.eval_accumulate_device(n, d_pred, d_gt, gt_format, stream)
+
+    def confusion(self, layer):
+        return self.ctx.eval_confusion(layer)[0]
+
+    def out_of_range(self, layer):
+        return self.ctx.eval_confusion(layer)[1]
+
+    def scores(self, layer):
+        """dict(global_acc, class_avg_acc, iou, row_pct, counts) as test.cpp:203-228 computes them."""
+        counts = self.confusion(layer)
+        d = capi.eval_scores_from_counts(counts)
+        d["counts"] = counts
+        return d
+
+    def report(self, layer):
+        """The text test.cpp:206-228 prints (its spelling included)."""
+        s = self.scores(layer)
+        counts = s["counts"]
+        conv = self.conv[layer]
+        lines = ["confusion:"]
+        for i in range(counts.shape[0]):
+            name = conv.getLabelName(i) if conv is not None else ""
+            row = name.ljust(15) + "".join(" %6.2f" % v for v in s["row_pct"][i])
+            lines.append(row + "   out of %d pixels" % int(counts[i].sum()))
+        lines.append("Global accuracy:         %6.2f " % s["global_acc"])
+        lines.append("Class averge accuracy:   %6.2f " % s["class_avg_acc"])
+        lines.append("Intersection over union: %6.2f " % s["iou"])
+        return "\n".join(lines) + "\n"
