@@ -87,7 +87,9 @@ typedef struct rvseg_params {
     int32_t label_mode;             /* rvseg_label_mode                                             */
     int32_t unknown_label[RVSEG_MAX_LAYERS]; /* Segmenter::_layer_unknown_label, segmenter.cpp:88-96 */
     int32_t max_batch;              /* frames processed per launch group (device buffers are sized
-                                       for this many frames)                                        */
+                                       for this many frames); 1 .. 4096, and at most 1022 with
+                                       use_dense_crf (the lattice's 10-bit frame field): rvseg_create
+                                       refuses more with RVSEG_ERR_INVALID_ARG                      */
     int32_t device;                 /* HIP device ordinal                                           */
     int32_t lattice_capacity_log2;  /* hash-table slots per frame = 2^this; 0 = 2^12 (the Segmenter
                                        kernel gives ~300 vertices / frame on the synthetic scenes, up to

@@ -285,6 +285,9 @@ rvseg_status rvseg_create(const rvseg_params* params, rvseg_ctx** out) {
             return fail(RVSEG_ERR_INVALID_ARG, "patch ROI would leave the reflected border (depth_min too small or image too small)");
     }
     if (p.max_batch < 1 || p.max_batch > 4096) return fail(RVSEG_ERR_INVALID_ARG, "bad max_batch");
+    // the DenseCRF lattice of a chunk carries the frame in a 10-bit field of its launch-order sort key (lattice_prepare)
+    if (p.use_dense_crf && p.max_batch > 1022)
+        return fail(RVSEG_ERR_INVALID_ARG, "max_batch above 1022 with use_dense_crf: the DenseCRF lattice holds at most 1022 frames per chunk");
     if (p.label_mode < 0 || p.label_mode > 3) return fail(RVSEG_ERR_INVALID_ARG, "bad label_mode");
     if (p.dcrf_iterations < 0) return fail(RVSEG_ERR_INVALID_ARG, "bad dcrf_iterations");
 

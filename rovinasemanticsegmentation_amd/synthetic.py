@@ -57,9 +57,22 @@ def make_deep_frame(index=0, W=640, H=480, holes=False, seed=1234):
     return rgb, depth
 
 
+def make_random_frame(index=0, W=640, H=480, holes=False, seed=1234):
+    """Uniform random colour and depth (0.5 - 15 m) per pixel: with both CRF kernels scaled up (x16) nearly every
+    lattice entry is a vertex of its own -- the per-frame worst case of the hash table."""
+    rng = np.random.default_rng(seed + 104729 * (index + 1))
+    rgb = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    depth = rng.integers(500, 15001, (H, W)).astype(np.uint16)
+    if holes:
+        depth[rng.random((H, W)) < 0.10] = 0
+    return rgb, depth
+
+
 def make_frame(index=0, W=640, H=480, holes=False, seed=1234, scene="flat"):
     if scene == "deep":
         return make_deep_frame(index, W, H, holes, seed)
+    if scene == "random":
+        return make_random_frame(index, W, H, holes, seed)
     rng = np.random.default_rng(seed + index)
     ys, xs = np.mgrid[0:H, 0:W]
     base = np.array([[180, 60, 50], [60, 170, 70], [50, 80, 190]], np.float64)
@@ -84,6 +97,39 @@ def make_batch(n, W=640, H=480, holes=False, seed=1234, start=0, scene="flat"):
     for i in range(n):
         rgb[i], depth[i] = make_frame(start + i, W, H, holes, seed, scene)
     return rgb, depth
+
+
+# Lattice regimes of the DenseCRF frame path, each pinned to one side of a limit of the lattice code (csrc/rvseg_crf.h,
+# kernels_crf.hip).  Both pairwise kernels (dcrf_xyz_kernel, dcrf_rgb_kernel) are scaled by `s`; `bounds` holds, per
+# frame of `frames`, the inclusive range its oracle vertex count must fall in (holes on, the default seed).  The CPU
+# suite recomputes the counts (tests/test_oracle_crf.py), so a change of the generator fails there and never silently
+# moves a GPU test off its edge.  Limits: MF_LDS_BYTES = 24 KB of vertex values per frame (Mf <= 512 for 9 classes,
+# <= 768 for 8), RES_MAX_OWNV = 640 vertices per resident block, CS_MCAP = 4 096 (counting-sort CSR), 2^12 default
+# hash slots per frame at load factor 1/2 (2 048 vertices).
+LATTICE_BANDS = {
+    # 9-class mean-field update: one frame's values in LDS (<= 512), the other's sliced from L2
+    "mf_lds_c9": dict(scene="flat", s=1.5, W=640, H=480, frames=(1, 0), bounds=((400, 512), (513, 640))),
+    # 8-class mean-field update: the same edge at 768
+    "mf_lds_c8": dict(scene="flat", s=1.65, W=640, H=480, frames=(1, 2), bounds=((641, 768), (769, 1024))),
+    # resident schedule with B = 2: more than one block's worth of vertices, at most two
+    "resident_b2": dict(scene="flat", s=2.5, W=320, H=240, frames=tuple(range(11, 19)), bounds=((641, 1280),) * 8),
+    # the deep scene: overflows the default 2^12 slots, within B = 4 resident blocks (4 x 640)
+    "deep": dict(scene="deep", s=1.0, W=640, H=480, frames=(0, 1, 2, 3), bounds=((2049, 2560),) * 4),
+    # beyond 4 resident blocks, within the counting-sort CSR
+    "deep_planner": dict(scene="deep", s=1.1, W=640, H=480, frames=(0, 1, 2, 3), bounds=((2561, 3500),) * 4),
+    # just below the counting-sort ceiling (CS_MCAP, 2^13 slots per frame)
+    "deep_cs_ceiling": dict(scene="deep", s=1.2, W=640, H=480, frames=(0, 1, 2), bounds=((3501, 4096),) * 3),
+    # beyond it: 2^16 slots per frame and the radix-sort CSR
+    "deep_radix": dict(scene="deep", s=1.3, W=640, H=480, frames=(0, 1), bounds=((4097, 8192),) * 2),
+    # every entry (nearly) its own vertex: 160 x 120 x 7 = 134 400 entries, the worst-case capacity
+    "worst_case": dict(scene="random", s=16.0, W=160, H=120, frames=(0, 1, 2), bounds=((134000, 134400),) * 3),
+}
+
+
+def lattice_band(name):
+    """(scene, s, W, H, frames) of a named lattice band (LATTICE_BANDS)."""
+    b = LATTICE_BANDS[name]
+    return b["scene"], b["s"], b["W"], b["H"], b["frames"]
 
 
 def _feature_range(f, D):

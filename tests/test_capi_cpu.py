@@ -86,6 +86,12 @@ def test_create_rejects_bad_params_before_touching_the_device():
     for kw in ({"stride": 0}, {"width": 2}, {"depth_min": 0.1}, {"max_batch": 0}, {"label_mode": 9}):
         p = capi.default_params(**kw)
         assert capi.lib().rvseg_create(C.byref(p), C.byref(h)) == capi.ERR_INVALID_ARG, kw
+    # a DenseCRF chunk holds at most 1022 frames (10-bit frame field of the lattice's sort key): refused at creation,
+    # with a message that names the limit -- not on the first large call
+    p = capi.default_params(use_dense_crf=1, max_batch=1023)
+    assert capi.lib().rvseg_create(C.byref(p), C.byref(h)) == capi.ERR_INVALID_ARG
+    assert b"1022" in capi.lib().rvseg_last_error(None)
+    assert not h.value
 
 
 def test_cpp_facade_header_compiles():

@@ -19,10 +19,36 @@ def _features(seed, N, d, spread=4.0):
     return (rng.random((N, d)) * spread - spread / 3).astype(np.float32)
 
 
-@pytest.mark.parametrize("d,N", [(2, 4000), (5, 4000), (6, 4000), (6, 4003), (3, 10), (1, 64), (7, 512)])
+LP_SET, LP_CHUNKS = 512, 8   # kernels_crf.hip: lattice_points_kernel's block-local key set, 256-point chunks per block
+
+
+def lattice_points_chunks(N):
+    """kernels_crf.hip: launch_lattice_points -- 256-point chunks per block, as many (up to 8) as leave >= 1024 blocks."""
+    n_chunks = LP_CHUNKS
+    while n_chunks > 1 and (N + 255) // 256 // n_chunks < 1024:
+        n_chunks >>= 1
+    return n_chunks
+
+
+def distinct_vertices_per_block(offset, n_chunks):
+    """Distinct lattice vertices each block of lattice_points_kernel meets (oracle offsets, full blocks)."""
+    per = 256 * n_chunks
+    nb = offset.shape[0] // per
+    rows = np.sort(offset[:nb * per].reshape(nb, -1), axis=1)
+    return 1 + (np.diff(rows, axis=1) != 0).sum(1)
+
+
+@pytest.mark.parametrize("d,N", [(2, 4000), (5, 4000), (6, 4000), (6, 4003), (3, 10), (1, 64), (7, 512),
+                                 (6, 1 << 19), (6, 1 << 20), (6, 1 << 21)])
 def test_lattice_structure_matches_oracle(gpu_ctx_factory, oracle, d, N):
+    """Clouds of 2^19 .. 2^21 points give lattice_points_kernel 2, 4 and 8 chunks per block, and (random features of
+    spread 4) thousands of distinct vertices per block: its LDS key set saturates and is carried over between chunks."""
     F = _features(d * 100 + N, N, d)
     lat = oracle.Lattice(F)
+    if N >= 1 << 19:
+        n_chunks = lattice_points_chunks(N)
+        assert n_chunks == {1 << 19: 2, 1 << 20: 4, 1 << 21: 8}[N]
+        assert distinct_vertices_per_block(lat.offset, n_chunks).min() > LP_SET
     ctx = gpu_ctx_factory()
     off, bary, keys, M = ctx.lattice_build(F)
     assert M == lat.M
@@ -335,11 +361,14 @@ def test_counting_sort_block_sizes(gpu_ctx_factory, oracle, csr_block, splat):
         ctx.set_schedule(csr_block=300)
 
 
-@pytest.mark.parametrize("scale,B", [(1.0, 4), (3.0, 4), (3.0, 2)])
+@pytest.mark.parametrize("scale,B", [(1.0, 4), (3.0, 4), (2.5, 2)])
 def test_resident_band_splat_two_layers_and_fine_lattices(gpu_ctx_factory, oracle, scale, B):
     """The resident schedule for the 8-class layer too (two label layers: an 8- and a 9-class mean field over one
     lattice, on two streams), and on lattices with many more vertices per frame than the default kernel widths give
-    (both pairwise kernels scaled by 3: a finer lattice; B = 2 makes a block own hundreds of vertices)."""
+    (both pairwise kernels scaled by 2.5 or 3: a finer lattice; B = 2 makes a block own hundreds of vertices).  At 3.0 a
+    frame has up to 1 529 vertices, more than two blocks hold (2 x RES_MAX_OWNV = 1 280), so the B = 2 case runs at 2.5:
+    945 - 1 015 vertices, pinned by the band "resident_b2" (test_oracle_crf.py).  planner_fallback = 0 asserts that the
+    resident schedule did the splat, not just that it was chosen."""
     blob = synthetic.make_forest_bytes(seed=31, n_trees=3, leaves_per_tree=256, max_depth=12, single_classes=9, layer_classes=(8, 9))
     forest = oracle.Forest(blob)
     W, H = 320, 240
@@ -354,7 +383,8 @@ def test_resident_band_splat_two_layers_and_fine_lattices(gpu_ctx_factory, oracl
                           schedule=dict(splat=2, resident_blocks=B), **kw)
     ctx.forest_load(blob)
     out = ctx.segment_frames(rgb, depth, calib)
-    assert ctx.last_schedule()["splat"] == "resident"
+    info = ctx.last_schedule()
+    assert info["splat"] == "resident" and info["resident_blocks"] == B and info["planner_fallback"] == 0, info
     for i in range(8):
         post, marg, lab = oracle.segment_frame(p, forest, 1, rgb[i], depth[i], calib, label_mode=1, unknown=[7, 8])
         assert np.array_equal(out["marginals"][i], marg), i
@@ -421,6 +451,7 @@ def test_config5_chunk_resident_schedule_equals_list_major_walk(gpu_ctx_factory,
                                   torch.cuda.current_stream(dev).cuda_stream)
         assert ctx.poll_status(wait=True) == 0
         assert ctx.last_schedule()["splat"] == name
+        assert ctx.last_schedule()["planner_fallback"] == 0   # the resident run really ran resident
         torch.cuda.synchronize(dev)
         results.append((d_marg, d_lab))
         ctx.close()

@@ -241,3 +241,40 @@ def test_dense_inference_example_recipe(oracle, golden_dir):
         z = np.load(path)
         assert np.array_equal(mp.astype(np.int8), z["map"])
         assert np.array_equal(Q[::97], z["q_sub"])
+
+
+# ---- lattice bands: vertex counts that put the GPU tests on each side of the lattice code's limits ---------------------
+def band_params(oracle, name):
+    """Oracle parameters of a lattice band (synthetic.LATTICE_BANDS): default CRF kernels scaled by the band's s."""
+    from rovinasemanticsegmentation_amd import synthetic
+    _, s, W, H, _ = synthetic.lattice_band(name)
+    p = oracle.default_params(width=W, height=H)
+    return dict(width=W, height=H, dcrf_xyz_kernel=p.dcrf_xyz_kernel * s, dcrf_rgb_kernel=p.dcrf_rgb_kernel * s)
+
+
+def frame_vertices(oracle, kw, scene, index):
+    """Lattice vertices of one synthetic frame (holes on) under the CRF parameters kw, by the oracle."""
+    from rovinasemanticsegmentation_amd import synthetic
+    p = oracle.default_params(**kw)
+    rgb, depth = synthetic.make_frame(index, p.width, p.height, holes=True, scene=scene)
+    calib = synthetic.make_calib(p.width, p.height)
+    return oracle.Lattice(oracle.frame_crf_features(p, rgb, oracle.cloud(p, depth, calib))).M
+
+
+def band_vertices(oracle, name):
+    from concurrent.futures import ThreadPoolExecutor
+    from rovinasemanticsegmentation_amd import synthetic
+    scene, _, _, _, frames = synthetic.lattice_band(name)
+    kw = band_params(oracle, name)
+    with ThreadPoolExecutor(max(1, min(os.cpu_count() or 1, 16))) as ex:
+        return list(ex.map(lambda i: frame_vertices(oracle, kw, scene, i), frames))
+
+
+def test_lattice_bands_hold_their_vertex_counts(oracle):
+    """Each named band's frames land where synthetic.LATTICE_BANDS says -- on the side of a limit of the lattice code
+    that the GPU tests (test_gpu_lattice_limits.py, the resident-schedule tests) rely on."""
+    from rovinasemanticsegmentation_amd import synthetic
+    for name, band in synthetic.LATTICE_BANDS.items():
+        got = band_vertices(oracle, name)
+        for i, m, (lo, hi) in zip(band["frames"], got, band["bounds"]):
+            assert lo <= m <= hi, (name, i, m, (lo, hi))
