@@ -117,6 +117,9 @@ int32_t rvseg_feature_length(const rvseg_ctx *ctx);
 /* ---- forest: replaces libf::RandomForest::read (libforest classifier.cpp:222-235) ------------ */
 rvseg_status rvseg_forest_load(rvseg_ctx *ctx, const char *path);
 rvseg_status rvseg_forest_load_mem(rvseg_ctx *ctx, const void *buf, size_t size);
+/* A stream that does not parse is refused and the loaded model stays.  A forest that parses but is past the
+ * context's limits (more than 64 classes over all layers or 8 layers, no histograms for params.multi_layer) is
+ * refused and leaves ctx with no model: calls that need one return RVSEG_ERR_NO_FOREST until a load succeeds. */
 /* Host-only validation of a forest.dat image with the loader's own parser and limits (no context, no
  * GPU): format, child links, split features < feature_length (<= 0: not checked), at most 64 trees
  * (RVSEG_ERR_CAPACITY: libforest has no limit, the device evaluator does) and 64 classes.  err_out

@@ -101,22 +101,25 @@ static rvseg_status upload_forest(rvseg_ctx* ctx) {
         ctx->err = "params.multi_layer is 0 but the forest carries no single-label histograms";
         return RVSEG_ERR_FORMAT;
     }
+    // every limit is checked before the device model is touched: a refused load leaves no half-written layout behind
+    if (multi && m.layer_classes.size() > RVSEG_MAX_LAYERS) { ctx->err = "too many label layers"; return RVSEG_ERR_FORMAT; }
+    int sum_classes = 0;
+    if (multi) for (int c : m.layer_classes) sum_classes += c;
+    else sum_classes = m.single_classes;
+    if (sum_classes > kMaxClasses) { ctx->err = "more than 64 classes over all layers is not supported"; return RVSEG_ERR_FORMAT; }
+    if (m.n_trees > kMaxTrees) { ctx->err = "more than 64 trees are not supported"; return RVSEG_ERR_CAPACITY; }   // parse_forest refuses these already
     f.n_trees = m.n_trees;
     f.max_depth = m.max_depth;
     f.n_nodes = (int)m.nodes.size();
     f.n_leaves = m.n_leaves;
     if (multi) {
-        if (m.layer_classes.size() > RVSEG_MAX_LAYERS) { ctx->err = "too many label layers"; return RVSEG_ERR_FORMAT; }
         f.n_layers = (int)m.layer_classes.size();
-        f.sum_classes = 0;
-        for (int l = 0; l < f.n_layers; l++) { f.class_counts[l] = m.layer_classes[l]; f.sum_classes += m.layer_classes[l]; }
+        for (int l = 0; l < f.n_layers; l++) f.class_counts[l] = m.layer_classes[l];
     } else {
         f.n_layers = 1;
         f.class_counts[0] = m.single_classes;
-        f.sum_classes = m.single_classes;
     }
-    if (f.sum_classes > kMaxClasses) { ctx->err = "more than 64 classes over all layers is not supported"; return RVSEG_ERR_FORMAT; }
-    if (m.n_trees > kMaxTrees) { ctx->err = "more than 64 trees are not supported"; return RVSEG_ERR_CAPACITY; }   // parse_forest refuses these already
+    f.sum_classes = sum_classes;
     const std::vector<float>& hist = multi ? m.multi_hist : m.single_hist;
     rvseg_status st;
     if ((st = dev_alloc(ctx, f.nodes, m.nodes.size() * sizeof(DeviceNode))) != RVSEG_OK) return st;

@@ -561,6 +561,9 @@ class Segmenter:
         for the services (:711-713).  Returns (result_labels, unaries)."""
         p = self.ctx.params
         cc = self.layer_class_counts
+        # the layout comes from the context's model: none (a refused load raises ERR_NO_FOREST here) or another one
+        if self.ctx.forest_info()["class_counts"] != list(cc):
+            raise RuntimeError("model / config mismatch: layer or class counts (README.md:30 of the reference)")
         cloud_xyz = np.ascontiguousarray(cloud_xyz, np.float32)
         cloud_rgb = np.ascontiguousarray(cloud_rgb, np.float32)
         n_pts = cloud_xyz.shape[0]

@@ -104,8 +104,8 @@ def make_batch(n, W=640, H=480, holes=False, seed=1234, start=0, scene="flat"):
 # frame of `frames`, the inclusive range its oracle vertex count must fall in (holes on, the default seed).  The CPU
 # suite recomputes the counts (tests/test_oracle_crf.py), so a change of the generator fails there and never silently
 # moves a GPU test off its edge.  Limits: MF_LDS_BYTES = 24 KB of vertex values per frame (Mf <= 512 for 9 classes,
-# <= 768 for 8), RES_MAX_OWNV = 640 vertices per resident block, CS_MCAP = 4 096 (counting-sort CSR), 2^12 default
-# hash slots per frame at load factor 1/2 (2 048 vertices).
+# <= 768 for 8), BLUR_LDS_FLOATS = 6 144 vertex values per frame (Mf x C), RES_MAX_OWNV = 640 vertices per resident
+# block, CS_MCAP = 4 096 (counting-sort CSR), 2^12 default hash slots per frame at load factor 1/2 (2 048 vertices).
 LATTICE_BANDS = {
     # 9-class mean-field update: one frame's values in LDS (<= 512), the other's sliced from L2
     "mf_lds_c9": dict(scene="flat", s=1.5, W=640, H=480, frames=(1, 0), bounds=((400, 512), (513, 640))),
@@ -123,6 +123,15 @@ LATTICE_BANDS = {
     "deep_radix": dict(scene="deep", s=1.3, W=640, H=480, frames=(0, 1), bounds=((4097, 8192),) * 2),
     # every entry (nearly) its own vertex: 160 x 120 x 7 = 134 400 entries, the worst-case capacity
     "worst_case": dict(scene="random", s=16.0, W=160, H=120, frames=(0, 1, 2), bounds=((134000, 134400),) * 3),
+    # Per class count C, the update stages Mf x ceil(C/4)*4 floats in LDS (24 KB) and the blur Mf x C floats (6 144).
+    # For C = 4, 12 and 16 both edges are one: Mf = 1 536, 512 and 384.  For C = 21 they are 256 and 292.
+    "lds_c4": dict(scene="flat", s=3.0, W=320, H=240, frames=(0, 2), bounds=((1300, 1536), (1537, 2048))),
+    "lds_c12": dict(scene="flat", s=2.0, W=192, H=128, frames=(0, 1), bounds=((400, 512), (513, 640))),
+    "lds_c16": dict(scene="flat", s=1.5, W=320, H=240, frames=(1, 3), bounds=((300, 384), (385, 480))),
+    # 21 classes: the update's edge at 256, both frames' values within the blur's LDS (<= 292)
+    "mf_lds_c21": dict(scene="flat", s=0.9, W=320, H=240, frames=(0, 3), bounds=((200, 256), (257, 292))),
+    # 21 classes: the blur's edge at 292, both frames past the update's 256
+    "blur_lds_c21": dict(scene="flat", s=1.0, W=320, H=240, frames=(4, 2), bounds=((257, 292), (293, 360))),
 }
 
 

@@ -145,3 +145,23 @@ def test_forest_check_refuses_corrupt_streams_and_model_config_mismatch():
     assert capi.forest_check(b"\x00\x00\x00\x00")[0] == capi.ERR_NO_FOREST       # T = 0
     st, msg, _ = capi.forest_check(_golden("forest_multi.dat"), 3)               # D = 3: split features out of range
     assert st == capi.ERR_FORMAT and "mismatch" in msg
+
+
+def test_forest_check_refuses_more_than_64_classes_or_8_layers():
+    """The limits of a context (rvseg_api.cpp: kMaxClasses over all layers, RVSEG_MAX_LAYERS) on the host: 65 classes
+    over 4 layers, 9 layers and 65 single-layer classes are refused with ERR_FORMAT; exactly 64 classes and 8 layers pass.
+    The same forests on a context: tests/test_gpu_class_counts.py (test_refused_forests_leave_no_model)."""
+    capi = _lib()
+    from rovinasemanticsegmentation_amd import synthetic
+
+    def forest(seed, single, layers):
+        return synthetic.make_forest_bytes(seed=seed, n_trees=2, leaves_per_tree=16, max_depth=6, single_classes=single,
+                                           layer_classes=layers)
+    for blob, what in ((forest(71, 0, (16, 16, 16, 17)), "65 classes"), (forest(72, 0, (2,) * 9), "9 layers"),
+                       (forest(73, 65, None), "65 single-layer classes"), (forest(74, 9, (16, 16, 16, 17)), "65 classes beside a single layer")):
+        st, msg, _ = capi.forest_check(blob, 366)
+        assert st == capi.ERR_FORMAT and "64 classes or 8 layers" in msg, (what, st, msg)
+    for blob, what in ((forest(75, 0, (16, 16, 16, 16)), "64 classes"), (forest(76, 0, (2, 3, 4, 5, 6, 7, 8, 9)), "8 layers"),
+                       (forest(77, 64, None), "64 single-layer classes"), (forest(78, 64, (2, 3, 4, 5, 6, 7, 8, 9)), "both")):
+        st, msg, info = capi.forest_check(blob, 366)
+        assert st == capi.OK and info["n_trees"] == 2, (what, st, msg)
