@@ -249,6 +249,69 @@ rvseg_status rvseg_crf_features_gaussian(int32_t W, int32_t H, float sx, float s
 rvseg_status rvseg_crf_features_bilateral(int32_t W, int32_t H, float sx, float sy, float sr, float sg, float sb,
                                           const uint8_t *im, float *out);
 
+/* ---- learned DenseCRF models: any compatibility, normalisation and kernel parameters per pairwise term.
+ *      Replaces  DenseCRF crf(N, C); crf.setUnaryEnergy(U); crf.addPairwiseEnergy(f_k, compat_k, kernel_type_k,
+ *      normalization_k) ...; crf.setKernelParameters(p); Q = crf.inference(iters)  (densecrf.cpp:54-60,115-131,343-360),
+ *      as examples/dense_learning.cpp:128-182 builds and runs a learnt model.  Per term, t = the lattice-filtered input:
+ *        normalisation (pairwise.cpp:40-80; inference applies, never the transpose), n = lattice.compute(ones):
+ *          SYMMETRIC  norm = (float)(1 / sqrt((double)n + 1e-20)); input and output scaled by norm
+ *          BEFORE     norm = (float)(1 / ((double)n + 1e-20));     input scaled
+ *          AFTER      the same norm;                               output scaled
+ *          NONE       no scaling (the reference's mean norm is never read by filter, :63-80)
+ *        compatibility, then tmp1 -= out in term order (densecrf.cpp:124-127):
+ *          POTTS      out[c] = fl(-w * t[c])        (labelcompatibility.cpp:46-48); compat_params: w
+ *          DIAGONAL   out[c] = fl(v[c] * t[c])      (:65-67); compat_params: v, C values.  Potts(w) == Diagonal(-w, .., -w)
+ *          MATRIX     out[c] = sum_c' W[c][c'] t[c'] (:79-86); compat_params: m, C x C row-major; W = 0.5 (m + m^T),
+ *                     elementwise in fp32
+ *        kernel parameters (pairwise.cpp:116-152), applied to the term's features before the lattice is built:
+ *          CONST      ignored;  DIAG  f'[j] = fl(p[j] f[j]), d values;  FULL  f'[a] = sum_b P[a][b] f[b], d x d values
+ *                     column-major (P[a][b] = p[b*d + a], the resize of :147);  kernel_params == NULL: f as passed
+ *                     (the constructor's initLattice(f), :110-115)
+ *      Every sum is fp32 with separately rounded products and adds, starting at the index-0 product, index ascending.
+ *      The reference takes these products from Eigen, whose order is not reproducible here: that parity is unpinned. */
+typedef enum rvseg_norm_kind {          /* NormalizationType, pairwise.h:32-37 */
+    RVSEG_NO_NORMALIZATION = 0,
+    RVSEG_NORMALIZE_BEFORE = 1,
+    RVSEG_NORMALIZE_AFTER = 2,
+    RVSEG_NORMALIZE_SYMMETRIC = 3
+} rvseg_norm_kind;
+typedef enum rvseg_kernel_kind {        /* KernelType, pairwise.h:38-42 */
+    RVSEG_CONST_KERNEL = 0,
+    RVSEG_DIAG_KERNEL = 1,
+    RVSEG_FULL_KERNEL = 2
+} rvseg_kernel_kind;
+typedef enum rvseg_compat_kind {        /* PottsCompatibility, DiagonalCompatibility, MatrixCompatibility (labelcompatibility.h) */
+    RVSEG_COMPAT_POTTS = 0,
+    RVSEG_COMPAT_DIAGONAL = 1,
+    RVSEG_COMPAT_MATRIX = 2
+} rvseg_compat_kind;
+typedef struct rvseg_crf_term {
+    int32_t d, compat, kernel_type, normalization;   /* feature dimension 1..7; rvseg_compat_kind, _kernel_kind, _norm_kind */
+    const float *features;        /* N x d, point-major: host memory for rvseg_crf_infer_terms, device memory for _device */
+    const float *compat_params;   /* host: POTTS 1 value, DIAGONAL C values, MATRIX C x C row-major (symmetrised here) */
+    const float *kernel_params;   /* host: NULL, d values (DIAG) or d x d column-major (FULL) */
+} rvseg_crf_term;
+/* Host-only validation (no context, no GPU): 1 <= C <= 64, 0 <= n_terms <= 8, N > 0, 1 <= d <= 7, kinds in range,
+ * features and compat_params non-NULL.  Both inference entries call it first. */
+rvseg_status rvseg_crf_terms_check(int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term *terms);
+/* unary_energy: N x C host (the energy; Q0 = expAndNormalize(-U), densecrf.cpp:120).  Q_out: N x C; map_out (optional):
+ * labels under label_mode / unknown_label.  A lattice hash overflow is retried once at the safe capacity. */
+rvseg_status rvseg_crf_infer_terms(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term *terms,
+                                   const float *unary_energy, int32_t iterations, float *Q_out, int8_t *map_out,
+                                   int32_t label_mode, int32_t unknown_label);
+/* The same on device buffers with the contract of rvseg_crf_infer_device (unary_is_energy, d_Q_out / d_map_out, work on
+ * hip_stream, one synchronisation per lattice build for the overflow retry).  Term features are device memory. */
+rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term *terms,
+                                          const float *d_unary, int32_t unary_is_energy, int32_t iterations, float *d_Q_out,
+                                          int8_t *d_map_out, int32_t label_mode, int32_t unknown_label, void *hip_stream);
+/* LogisticUnaryEnergy::get (unary.cpp:50-52): U[i][m] = sum_k L[m][k] f[i][k] -- an energy.  L: C x K row-major, host
+ * (setUnaryParameters resizes column-major, :58-63: L[m][k] = v[k*C + m]); f: N x K.  The host entry takes host f / U_out;
+ * _device takes device f / d_U_out and enqueues on hip_stream. */
+rvseg_status rvseg_crf_logistic_unary(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *L, const float *f,
+                                      float *U_out);
+rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *L,
+                                             const float *d_f, float *d_U_out, void *hip_stream);
+
 /* ---- lattice introspection for parity tests: Permutohedral::init + compute
  *      (densecrf permutohedral.cpp:140-321,596-603).  offsets_out / bary_out: N x (d+1);
  *      keys_out: capacity M_cap x d int16; vertex numbering is arbitrary (results do not depend on

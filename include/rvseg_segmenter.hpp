@@ -32,6 +32,7 @@
 //                                                                 layer name or map id, layers concatenated
 //   /tmp/cloud<ID>_rgb.cld, _layer_<l>.cld dumps  :684-706    dumpClouds()
 //   DenseCRF2D::addPairwiseGaussian/Bilateral     densecrf.cpp:61-81   DenseCRF2D (rvseg_crf_features_*)
+//   DenseCRF + learned models (dense_learning)    densecrf.cpp:54-60,294-360   DenseCRF: compatibilities, kernel / unary parameters
 //   RgbLabelConversion (rgb_label_conversion.h)                RgbLabelConversion: full coding, negative labels included
 //   test.cpp / test_multi.cpp confusion + scores  :182-228    Evaluator: counts on the GPU, scores(), report()
 //
@@ -40,6 +41,7 @@
 #ifndef RVSEG_SEGMENTER_HPP
 #define RVSEG_SEGMENTER_HPP
 
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -609,41 +611,226 @@ private:
     std::string rf_error_, map_error_;
 };
 
-// DenseCRF2D as examples/dense_inference.cpp:83-107 drives it: the two image kernels, then map().
-class DenseCRF2D {
+// Label compatibilities of a learned model (labelcompatibility.h): Potts (1 value), Diagonal (M values), Matrix (M x M,
+// symmetrised W = 0.5 (m + m^T) in fp32 when created, labelcompatibility.cpp:79).  parameters() / setParameters() pack
+// them as the reference does (Matrix: the upper triangle of W row by row, :88-100).
+struct LabelCompatibility {
+    int32_t kind = RVSEG_COMPAT_POTTS;
+    int M = 0;                   // Matrix: the class count
+    std::vector<float> params;   // Potts {w}; Diagonal v; Matrix W row-major
+    std::vector<float> parameters() const {
+        if (kind != RVSEG_COMPAT_MATRIX) return params;
+        std::vector<float> r;
+        for (int i = 0; i < M; i++)
+            for (int j = i; j < M; j++) r.push_back(params[(size_t)i * M + j]);
+        return r;
+    }
+    void setParameters(const float* v) {
+        if (kind != RVSEG_COMPAT_MATRIX) { std::copy(v, v + params.size(), params.begin()); return; }
+        for (int i = 0, k = 0; i < M; i++)
+            for (int j = i; j < M; j++, k++) params[(size_t)i * M + j] = params[(size_t)j * M + i] = v[k];
+    }
+};
+struct PottsCompatibility : LabelCompatibility {
+    explicit PottsCompatibility(float w) { kind = RVSEG_COMPAT_POTTS; params = {w}; }
+};
+struct DiagonalCompatibility : LabelCompatibility {
+    explicit DiagonalCompatibility(std::vector<float> v) { kind = RVSEG_COMPAT_DIAGONAL; params = std::move(v); }
+};
+struct MatrixCompatibility : LabelCompatibility {
+    MatrixCompatibility(const float* m /* M x M row-major */, int classes) {
+        kind = RVSEG_COMPAT_MATRIX;
+        M = classes;
+        params.resize((size_t)M * M);
+        for (int i = 0; i < M; i++)
+            for (int j = 0; j < M; j++) {
+                const float sum = m[(size_t)i * M + j] + m[(size_t)j * M + i];
+                params[(size_t)i * M + j] = 0.5f * sum;
+            }
+    }
+};
+
+// DenseCRF (densecrf.h:36-121) over feature matrices the caller builds: N points, M labels.  addPairwiseEnergy with a bare
+// weight is PottsCompatibility; a model of bare weights with NORMALIZE_SYMMETRIC and no kernel parameters runs through
+// rvseg_crf_infer_multi as before, every other model (learned compatibilities, normalisations, kernel parameters, a
+// logistic unary) through rvseg_crf_infer_terms.
+class DenseCRF {
 public:
-    DenseCRF2D(rvseg_ctx* ctx, int W, int H, int M) : ctx_(ctx), W_(W), H_(H), M_(M) {}
-    void setUnaryEnergy(const float* unary /* N x M */) { unary_.assign(unary, unary + (size_t)W_ * H_ * M_); }
-    void addPairwiseGaussian(float sx, float sy, float potts_w) {                                   // densecrf.cpp:61-69
-        feats_.emplace_back((size_t)W_ * H_ * 2);
-        if (rvseg_crf_features_gaussian(W_, H_, sx, sy, feats_.back().data()) != RVSEG_OK) throw std::runtime_error("bad arguments");
-        ds_.push_back(2); ws_.push_back(potts_w);
+    DenseCRF(rvseg_ctx* ctx, int N, int M) : ctx_(ctx), N_(N), M_(M) {}
+    void setUnaryEnergy(const float* unary /* N x M */) { unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
+    // LogisticUnaryEnergy (unary.cpp:44-63): L M x K row-major, f N x K point-major
+    void setUnaryEnergy(const float* L, const float* f, int K) {
+        K_ = K;
+        logistic_L_.assign(L, L + (size_t)M_ * K);
+        logistic_f_.assign(f, f + (size_t)N_ * K);
+        unary_.clear();
     }
-    void addPairwiseBilateral(float sx, float sy, float sr, float sg, float sb, const unsigned char* im, float potts_w) {   // :70-81
-        feats_.emplace_back((size_t)W_ * H_ * 5);
-        if (rvseg_crf_features_bilateral(W_, H_, sx, sy, sr, sg, sb, im, feats_.back().data()) != RVSEG_OK) throw std::runtime_error("bad arguments");
-        ds_.push_back(5); ws_.push_back(potts_w);
+    void addPairwiseEnergy(const float* features /* N x d */, int d, float potts_w) {                       // densecrf.cpp:54-60
+        addTerm(features, d, PottsCompatibility(potts_w), RVSEG_DIAG_KERNEL, RVSEG_NORMALIZE_SYMMETRIC, true);
     }
-    // DenseCRF::inference (densecrf.cpp:115-131); map_out (optional) = DenseCRF::map (:132-137)
+    void addPairwiseEnergy(const float* features, int d, const LabelCompatibility& function, int kernel_type = RVSEG_DIAG_KERNEL,
+                           int normalization = RVSEG_NORMALIZE_SYMMETRIC) {
+        addTerm(features, d, function, kernel_type, normalization, false);
+    }
+    // ---- parameters (densecrf.cpp:294-360) ----
+    std::vector<float> unaryParameters() const {   // L column-major (unary.cpp:53-57)
+        std::vector<float> r;
+        if (logistic_f_.empty()) return r;
+        for (int k = 0; k < K_; k++)
+            for (int m = 0; m < M_; m++) r.push_back(logistic_L_[(size_t)m * K_ + k]);
+        return r;
+    }
+    void setUnaryParameters(const std::vector<float>& v) {
+        if (logistic_f_.empty()) return;
+        check(v.size() == logistic_L_.size());
+        for (int k = 0; k < K_; k++)
+            for (int m = 0; m < M_; m++) logistic_L_[(size_t)m * K_ + k] = v[(size_t)k * M_ + m];
+    }
+    std::vector<float> labelCompatibilityParameters() const {
+        std::vector<float> r;
+        for (const auto& t : terms_) { const auto p = t.compat.parameters(); r.insert(r.end(), p.begin(), p.end()); }
+        return r;
+    }
+    void setLabelCompatibilityParameters(const std::vector<float>& v) {
+        size_t i = 0;
+        for (auto& t : terms_) {
+            const size_t n = t.compat.parameters().size();
+            check(i + n <= v.size());
+            t.compat.setParameters(v.data() + i);
+            t.bare = false;
+            i += n;
+        }
+        check(i == v.size());
+    }
+    std::vector<float> kernelParameters() const {   // DenseKernel::parameters (pairwise.cpp:116-125)
+        std::vector<float> r;
+        for (const auto& t : terms_) { const auto p = kernelParams(t); r.insert(r.end(), p.begin(), p.end()); }
+        return r;
+    }
+    void setKernelParameters(const std::vector<float>& v) {   // pairwise.cpp:140-152
+        size_t i = 0;
+        for (auto& t : terms_) {
+            const size_t n = kernelParams(t).size();
+            check(i + n <= v.size());
+            if (t.kernel_type != RVSEG_CONST_KERNEL) t.kp.assign(v.begin() + i, v.begin() + i + n);
+            i += n;
+        }
+        check(i == v.size());
+    }
+    // DenseCRF::inference (densecrf.cpp:115-131); map_out (optional) = DenseCRF::map (:132-137).  A logistic unary is
+    // computed on the GPU and read back (N x M floats), then uploaded with the model like a constant unary; callers that
+    // keep everything in device memory use rvseg_crf_logistic_unary_device + rvseg_crf_infer_terms_device instead.
     std::vector<float> inference(int n_iterations, std::vector<int8_t>* map_out = nullptr) {
-        const size_t N = (size_t)W_ * H_;
-        if (unary_.empty()) unary_.assign(N * M_, 0.f);
+        const size_t N = (size_t)N_;
+        std::vector<float> U;
+        if (!logistic_f_.empty()) {
+            U.resize(N * M_);
+            status(rvseg_crf_logistic_unary(ctx_, N_, M_, K_, logistic_L_.data(), logistic_f_.data(), U.data()));
+        } else if (unary_.empty()) {
+            U.assign(N * M_, 0.f);
+        }
+        const float* u = unary_.empty() ? U.data() : unary_.data();
         std::vector<float> Q(N * M_);
-        std::vector<const float*> fp;
-        for (const auto& f : feats_) fp.push_back(f.data());
         if (map_out) map_out->resize(N);
-        const rvseg_status st = rvseg_crf_infer_multi(ctx_, (int32_t)N, M_, (int32_t)fp.size(), ds_.data(), fp.data(), ws_.data(), unary_.data(),
-                                                      n_iterations, Q.data(), map_out ? map_out->data() : nullptr, RVSEG_LABEL_ARGMAX, 0);
-        if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
+        int8_t* mp = map_out ? map_out->data() : nullptr;
+        bool plain = true;
+        for (const auto& t : terms_) plain = plain && t.bare && t.normalization == RVSEG_NORMALIZE_SYMMETRIC && t.kp.empty();
+        if (plain) {
+            std::vector<const float*> fp;
+            std::vector<int32_t> ds;
+            std::vector<float> ws;
+            for (const auto& t : terms_) { fp.push_back(t.f.data()); ds.push_back(t.d); ws.push_back(t.compat.params[0]); }
+            status(rvseg_crf_infer_multi(ctx_, (int32_t)N, M_, (int32_t)fp.size(), ds.data(), fp.data(), ws.data(), u, n_iterations,
+                                         Q.data(), mp, RVSEG_LABEL_ARGMAX, 0));
+            return Q;
+        }
+        std::vector<rvseg_crf_term> tt;
+        for (const auto& t : terms_) {
+            rvseg_crf_term r{};
+            r.d = t.d; r.compat = t.compat.kind; r.kernel_type = t.kernel_type; r.normalization = t.normalization;
+            r.features = t.f.data(); r.compat_params = t.compat.params.data();
+            r.kernel_params = t.kp.empty() ? nullptr : t.kp.data();
+            tt.push_back(r);
+        }
+        status(rvseg_crf_infer_terms(ctx_, (int32_t)N, M_, (int32_t)tt.size(), tt.data(), u, n_iterations, Q.data(), mp,
+                                     RVSEG_LABEL_ARGMAX, 0));
         return Q;
     }
-private:
+    std::vector<int8_t> map(int n_iterations) {   // densecrf.cpp:132-137
+        std::vector<int8_t> m;
+        inference(n_iterations, &m);
+        return m;
+    }
+protected:
+    struct Term {
+        std::vector<float> f;
+        int d = 0, kernel_type = RVSEG_DIAG_KERNEL, normalization = RVSEG_NORMALIZE_SYMMETRIC;
+        LabelCompatibility compat;
+        bool bare = false;        // added as a bare Potts weight
+        std::vector<float> kp;    // kernel parameters set by setKernelParameters (empty: the features as added)
+    };
+    void addTerm(const float* features, int d, const LabelCompatibility& c, int kernel_type, int normalization, bool bare) {
+        // the library reads 1, M or M x M compatibility values: a compatibility built for another class count is refused here
+        const size_t want = c.kind == RVSEG_COMPAT_POTTS ? 1 : c.kind == RVSEG_COMPAT_DIAGONAL ? (size_t)M_ : (size_t)M_ * M_;
+        if (c.params.size() != want || (c.kind == RVSEG_COMPAT_MATRIX && c.M != M_))
+            throw std::runtime_error("label compatibility does not match the class count");
+        Term t;
+        t.f.assign(features, features + (size_t)N_ * d);
+        t.d = d; t.compat = c; t.kernel_type = kernel_type; t.normalization = normalization; t.bare = bare;
+        terms_.push_back(std::move(t));
+    }
+    static std::vector<float> kernelParams(const Term& t) {
+        if (t.kernel_type == RVSEG_CONST_KERNEL) return {};
+        if (!t.kp.empty()) return t.kp;
+        std::vector<float> p(t.kernel_type == RVSEG_DIAG_KERNEL ? t.d : t.d * t.d, t.kernel_type == RVSEG_DIAG_KERNEL ? 1.f : 0.f);
+        if (t.kernel_type == RVSEG_FULL_KERNEL) for (int i = 0; i < t.d; i++) p[(size_t)i * t.d + i] = 1.f;
+        return p;
+    }
+    static void check(bool ok) { if (!ok) throw std::runtime_error("bad parameter vector"); }
+    void status(rvseg_status st) {
+        if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
+    }
     rvseg_ctx* ctx_;
-    int W_, H_, M_;
-    std::vector<float> unary_;
-    std::vector<std::vector<float>> feats_;
-    std::vector<int32_t> ds_;
-    std::vector<float> ws_;
+    int N_, M_, K_ = 0;
+    std::vector<float> unary_, logistic_L_, logistic_f_;
+    std::vector<Term> terms_;
+};
+
+// DenseCRF2D as examples/dense_inference.cpp:83-107 and examples/dense_learning.cpp:128-182 drive it: the two image kernels
+// (features by rvseg_crf_features_*), then map().
+class DenseCRF2D : public DenseCRF {
+public:
+    DenseCRF2D(rvseg_ctx* ctx, int W, int H, int M) : DenseCRF(ctx, W * H, M), W_(W), H_(H) {}
+    void addPairwiseGaussian(float sx, float sy, float potts_w) {                                   // densecrf.cpp:61-69
+        const auto f = gaussian(sx, sy);
+        addPairwiseEnergy(f.data(), 2, potts_w);
+    }
+    void addPairwiseGaussian(float sx, float sy, const LabelCompatibility& function, int kernel_type = RVSEG_DIAG_KERNEL,
+                             int normalization = RVSEG_NORMALIZE_SYMMETRIC) {
+        const auto f = gaussian(sx, sy);
+        addPairwiseEnergy(f.data(), 2, function, kernel_type, normalization);
+    }
+    void addPairwiseBilateral(float sx, float sy, float sr, float sg, float sb, const unsigned char* im, float potts_w) {   // :70-81
+        const auto f = bilateral(sx, sy, sr, sg, sb, im);
+        addPairwiseEnergy(f.data(), 5, potts_w);
+    }
+    void addPairwiseBilateral(float sx, float sy, float sr, float sg, float sb, const unsigned char* im, const LabelCompatibility& function,
+                              int kernel_type = RVSEG_DIAG_KERNEL, int normalization = RVSEG_NORMALIZE_SYMMETRIC) {
+        const auto f = bilateral(sx, sy, sr, sg, sb, im);
+        addPairwiseEnergy(f.data(), 5, function, kernel_type, normalization);
+    }
+private:
+    std::vector<float> gaussian(float sx, float sy) const {
+        std::vector<float> f((size_t)W_ * H_ * 2);
+        if (rvseg_crf_features_gaussian(W_, H_, sx, sy, f.data()) != RVSEG_OK) throw std::runtime_error("bad arguments");
+        return f;
+    }
+    std::vector<float> bilateral(float sx, float sy, float sr, float sg, float sb, const unsigned char* im) const {
+        std::vector<float> f((size_t)W_ * H_ * 5);
+        if (rvseg_crf_features_bilateral(W_, H_, sx, sy, sr, sg, sb, im, f.data()) != RVSEG_OK) throw std::runtime_error("bad arguments");
+        return f;
+    }
+    int W_, H_;
 };
 
 // ---- scoring: RgbLabelConversion (include/rgb_label_conversion.h) and the score block of src/test.cpp:182-228 --------

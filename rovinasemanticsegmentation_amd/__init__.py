@@ -7,8 +7,12 @@ without a GPU `Context()` raises.
 """
 from . import _capi as capi  # noqa: F401
 from .segmenter import (Context, DenseCRF, Evaluator, FeatureExtractor, LocalMapStore, RandomForest,  # noqa: F401
-                        RgbLabelConversion, Segmenter)
+                        RgbLabelConversion, Segmenter, PottsCompatibility, DiagonalCompatibility, MatrixCompatibility,
+                        CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL, NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER,
+                        NORMALIZE_SYMMETRIC)
 from . import synthetic  # noqa: F401
 
 __all__ = ["capi", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
-           "RgbLabelConversion", "Evaluator"]
+           "RgbLabelConversion", "Evaluator", "PottsCompatibility", "DiagonalCompatibility", "MatrixCompatibility",
+           "CONST_KERNEL", "DIAG_KERNEL", "FULL_KERNEL", "NO_NORMALIZATION", "NORMALIZE_BEFORE", "NORMALIZE_AFTER",
+           "NORMALIZE_SYMMETRIC"]

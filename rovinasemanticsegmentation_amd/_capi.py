@@ -16,6 +16,10 @@ RVSEG_MAX_LAYERS = 8
 OK, ERR_INVALID_ARG, ERR_IO, ERR_FORMAT, ERR_NO_FOREST, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY, NOT_READY = range(9)
 LABEL_EVAL, LABEL_CRF, LABEL_NOCRF, LABEL_ARGMAX = range(4)
 GT_LABELS, GT_RGB = range(2)
+# rvseg_norm_kind / rvseg_kernel_kind / rvseg_compat_kind (the reference's NormalizationType / KernelType order, pairwise.h:32-42)
+NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER, NORMALIZE_SYMMETRIC = range(4)
+CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL = range(3)
+COMPAT_POTTS, COMPAT_DIAGONAL, COMPAT_MATRIX = range(3)
 
 # every symbol include/rvseg.h declares
 SYMBOLS = [
@@ -38,6 +42,8 @@ SYMBOLS = [
     "rvseg_color_coding_set", "rvseg_labels_from_rgb_device", "rvseg_labels_to_rgb_device",
     "rvseg_labels_from_rgb", "rvseg_labels_to_rgb", "rvseg_eval_reset", "rvseg_eval_accumulate_device",
     "rvseg_eval_accumulate", "rvseg_eval_confusion", "rvseg_eval_scores_from_counts",
+    "rvseg_crf_terms_check", "rvseg_crf_infer_terms", "rvseg_crf_infer_terms_device",
+    "rvseg_crf_logistic_unary", "rvseg_crf_logistic_unary_device",
 ]
 
 
@@ -76,6 +82,14 @@ class RvsegScheduleInfo(C.Structure):
     _fields_ = [(k, C.c_int32) for k in (
         "splat", "planner_fallback", "csr_path", "n_frames", "points_per_frame", "vertices", "longest_list", "resident_blocks",
         "resident_band", "resident_chunk", "capacity_log2")]
+
+
+class RvsegCrfTerm(C.Structure):
+    """rvseg_crf_term: one pairwise term of a learned DenseCRF model."""
+    _fields_ = [
+        ("d", C.c_int32), ("compat", C.c_int32), ("kernel_type", C.c_int32), ("normalization", C.c_int32),
+        ("features", C.c_void_p), ("compat_params", C.c_void_p), ("kernel_params", C.c_void_p),
+    ]
 
 
 SPLAT_NAMES = {0: "none", 1: "list-major", 2: "resident"}
@@ -168,6 +182,12 @@ def lib():
     L.rvseg_eval_accumulate.argtypes = [vp, i32, vp, vp, i32]
     L.rvseg_eval_confusion.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64)]
     L.rvseg_eval_scores_from_counts.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(f32), C.POINTER(f32), vp]
+    TP = C.POINTER(RvsegCrfTerm)
+    L.rvseg_crf_terms_check.argtypes = [i32, i32, i32, TP]
+    L.rvseg_crf_infer_terms.argtypes = [vp, i32, i32, i32, TP, vp, i32, vp, vp, i32, i32]
+    L.rvseg_crf_infer_terms_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, i32, vp, vp, i32, i32, vp]
+    L.rvseg_crf_logistic_unary.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.rvseg_crf_logistic_unary_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)  # raises AttributeError if the library does not export it
     _lib = L
@@ -236,6 +256,12 @@ def crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im):
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return out
+
+
+def crf_terms_check(N, Cn, terms):
+    """Host-only validation of rvseg_crf_term records (no GPU): returns the status."""
+    arr = (RvsegCrfTerm * max(1, len(terms)))(*terms)
+    return lib().rvseg_crf_terms_check(N, Cn, len(terms), arr)
 
 
 def eval_scores_from_counts(counts):

@@ -2298,6 +2298,7 @@ float* launch_blur(const LatticeDev& L, int C, bool seq, bool reverse, float* a,
 //   OUT_MODE 0: out[p][c] = sliced                      (plain filter, rvseg_lattice_filter)
 //   OUT_MODE 1: norm[p]   = 1/sqrt(sliced + 1e-20)      (normaliser, pairwise.cpp:55-56; C == 1)
 //   OUT_MODE 2: tmp[p][c] = tmp[p][c] - (-w) * (sliced * norm[p])   (filter + Potts + inference)
+//   OUT_MODE 3: norm[p]   = 1/(sliced + 1e-20)          (NORMALIZE_BEFORE / _AFTER normaliser, pairwise.cpp:51-53; C == 1)
 // ---------------------------------------------------------------------------------------------
 template <bool SEQ, int OUT_MODE>
 __global__ void __launch_bounds__(256)
@@ -2328,6 +2329,8 @@ slice_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha,
         out[gid] = acc;
     } else if (OUT_MODE == 1) {
         out[gid] = (float)(1.0 / sqrt((double)acc + 1e-20));
+    } else if (OUT_MODE == 3) {
+        out[gid] = (float)(1.0 / ((double)acc + 1e-20));
     } else {
         const float t = acc * L.norm[p];   // out = out*norm_.asDiagonal(), pairwise.cpp:79
         const float m = neg_w * t;         // out = -w_*Q, labelcompatibility.cpp:47
@@ -2335,9 +2338,9 @@ slice_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha,
     }
 }
 
-// The normaliser's slice (C == 1, seqCompute rounding, OUT_MODE 1) with the d+1 offsets and weights of a
-// point fetched as two wide rows.
-template <int DP1>
+// The normaliser's slice (C == 1, seqCompute rounding, OUT_MODE 1; RECIP: OUT_MODE 3) with the d+1 offsets and weights
+// of a point fetched as two wide rows.
+template <int DP1, bool RECIP = false>
 __global__ void __launch_bounds__(256)
 slice_norm_kernel(LatticeDev L, const float* __restrict__ values, float alpha, float* __restrict__ out, long long n_points) {
     if (L.counters[1]) return;
@@ -2354,7 +2357,8 @@ slice_norm_kernel(LatticeDev L, const float* __restrict__ values, float alpha, f
         const float u = t * alpha;   // seqCompute :520
         acc += u;
     }
-    out[p] = (float)(1.0 / sqrt((double)acc + 1e-20));   // pairwise.cpp:55-56
+    if (RECIP) out[p] = (float)(1.0 / ((double)acc + 1e-20));   // pairwise.cpp:51-53
+    else out[p] = (float)(1.0 / sqrt((double)acc + 1e-20));      // pairwise.cpp:55-56
 }
 
 void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const float* values, float neg_w, float* out,
@@ -2368,13 +2372,21 @@ void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const floa
         RV_LAUNCHED("slice_norm_kernel");
         return;
     }
+    if (seq && out_mode == 3 && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
+        const dim3 g1((unsigned)((n_points + 255) / 256)), b1(256);
+        if (L.d == 6) slice_norm_kernel<7, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        else if (L.d == 5) slice_norm_kernel<6, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        else slice_norm_kernel<3, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        RV_LAUNCHED("slice_norm_kernel");
+        return;
+    }
     const long long total = n_points * C;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define RV_SLICE(SEQ, OM) slice_kernel<SEQ, OM><<<grid, block, 0, s>>>(L, C, values, alpha, neg_w, out, n_points)
     if (seq) {
-        if (out_mode == 0) RV_SLICE(true, 0); else if (out_mode == 1) RV_SLICE(true, 1); else RV_SLICE(true, 2);
+        if (out_mode == 0) RV_SLICE(true, 0); else if (out_mode == 1) RV_SLICE(true, 1); else if (out_mode == 3) RV_SLICE(true, 3); else RV_SLICE(true, 2);
     } else {
-        if (out_mode == 0) RV_SLICE(false, 0); else if (out_mode == 1) RV_SLICE(false, 1); else RV_SLICE(false, 2);
+        if (out_mode == 0) RV_SLICE(false, 0); else if (out_mode == 1) RV_SLICE(false, 1); else if (out_mode == 3) RV_SLICE(false, 3); else RV_SLICE(false, 2);
     }
 #undef RV_SLICE
     RV_LAUNCHED("slice_kernel");
@@ -2454,10 +2466,14 @@ __device__ __forceinline__ void mf_load(const LatticeDev& L, const ValueView& un
     load_row<C>(unary.base + unary.index((unsigned)p, 0, C, L.N), in.ur);
 }
 
-template <bool SEQ, int C, int DP1, bool USE_LDS>
+// TERM 0: Potts, t = sliced * norm, out = fl(-w * t) (the Segmenter's update).  TERM 1 / 2 (learned single-term models):
+// t = sliced, times norm when `post` (block-uniform); out = Diagonal fl(v[c] * t[c]) / Matrix sum_c' W[c][c'] t[c'] from
+// c' = 0 up, with v / W read from `compat` at compile-time offsets (uniform loads).  TERM 0 never reads compat / post.
+template <bool SEQ, int C, int DP1, bool USE_LDS, int TERM = 0>
 __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __restrict__ values, const float* tab, float alpha,
                                           float neg_w, const ValueView& unary, int negate, const ValueView& Q, int scale_out,
-                                          const MfLabels& lab, int frame, int f0, int i0) {
+                                          const MfLabels& lab, int frame, int f0, int i0,
+                                          const float* __restrict__ compat = nullptr, int post = 0) {
     constexpr int CP = (C + 3) / 4 * 4;
     constexpr int PER_THREAD = MF_PTS / 256;
     const int dp1 = DP1 > 0 ? DP1 : L.d + 1;
@@ -2496,12 +2512,34 @@ __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __re
         }
         const float nrm = cur.nrm;
         float b[C];
+        if (TERM == 0) {
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-            const float t = acc[c] * nrm;
-            const float m = neg_w * t;
-            const float u = cur.ur[c];
-            b[c] = (negate ? -u : u) - m;
+            for (int c = 0; c < C; c++) {
+                const float t = acc[c] * nrm;
+                const float m = neg_w * t;
+                const float u = cur.ur[c];
+                b[c] = (negate ? -u : u) - m;
+            }
+        } else {
+            float t[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) t[c] = post ? acc[c] * nrm : acc[c];
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                float o;
+                if (TERM == 1) {
+                    o = compat[c] * t[c];
+                } else {
+                    o = compat[c * C] * t[0];
+#pragma unroll
+                    for (int k = 1; k < C; k++) {
+                        const float m = compat[c * C + k] * t[k];
+                        o = o + m;
+                    }
+                }
+                const float u = cur.ur[c];
+                b[c] = (negate ? -u : u) - o;
+            }
         }
         float mx = b[0];
 #pragma unroll
@@ -2579,6 +2617,62 @@ bool launch_mf_update(const LatticeDev& L, int C, const float* values, float neg
 #undef RV_MF
 }
 
+// The fused update of ONE learned term (Diagonal: TERM 1, Matrix: TERM 2; Potts with a normalisation other than
+// SYMMETRIC is Diagonal(-w, .., -w)): the block structure of mf_update_kernel, runtime d.  post: scale the sliced values
+// by norm (SYMMETRIC / AFTER); scale_out: hand the next splat Q * norm (SYMMETRIC / BEFORE, not the last iteration).
+template <bool SEQ, int C, int TERM>
+__global__ void __launch_bounds__(256)
+mf_update_term_kernel(LatticeDev L, const float* __restrict__ values, float alpha, const float* __restrict__ compat, int post,
+                      ValueView unary, int negate, ValueView Q, int scale_out, MfLabels lab) {
+    extern __shared__ __attribute__((aligned(16))) float tab[];
+    if (L.counters[1]) return;   // uniform: hash overflow (flagged)
+    constexpr int CP = (C + 3) / 4 * 4;
+    const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
+    const int frame = blockIdx.x / bpf;
+    const int i0 = (blockIdx.x - frame * bpf) * MF_PTS + threadIdx.x;
+    const int f0 = L.fstart[frame], f1 = L.fstart[frame + 1];
+    const int Mf = f1 - f0;
+    const bool use_lds = (size_t)Mf * CP * sizeof(float) <= (size_t)MF_LDS_BYTES;   // block-uniform
+    if (use_lds) {
+        for (int idx = threadIdx.x; idx < Mf * C; idx += 256) {
+            const int r = idx / C, c = idx - r * C;
+            tab[r * CP + c] = values[(size_t)(f0 + r) * C + c];
+        }
+        __syncthreads();
+        mf_points<SEQ, C, 0, true, TERM>(L, values, tab, alpha, 0.f, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
+    } else {
+        mf_points<SEQ, C, 0, false, TERM>(L, values, tab, alpha, 0.f, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
+    }
+}
+
+bool launch_mf_update_term(const LatticeDev& L, int C, const float* values, bool matrix, const float* compat, bool post,
+                           const ValueView& unary, bool negate, const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s) {
+    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
+    const dim3 grid((unsigned)(bpf * L.n_frames)), block(256);
+#define RV_MFT(SEQ, CC)                                                                                            \
+    if (matrix) mf_update_term_kernel<SEQ, CC, 2><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, compat, post ? 1 : 0, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
+    else mf_update_term_kernel<SEQ, CC, 1><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, compat, post ? 1 : 0, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
+    RV_LAUNCHED("mf_update_term_kernel"); \
+    return true
+    switch (C) {
+        case 2: RV_MFT(true, 2);
+        case 3: RV_MFT(false, 3);
+        case 4: RV_MFT(false, 4);
+        case 5: RV_MFT(false, 5);
+        case 6: RV_MFT(false, 6);
+        case 7: RV_MFT(false, 7);
+        case 8: RV_MFT(false, 8);
+        case 9: RV_MFT(false, 9);
+        case 10: RV_MFT(false, 10);
+        case 12: RV_MFT(false, 12);
+        case 16: RV_MFT(false, 16);
+        case 21: RV_MFT(false, 21);
+        default: return false;
+    }
+#undef RV_MFT
+}
+
 // Q0 = expAndNormalize(-U) straight from the unary (densecrf.cpp:120), one thread per point
 // scale != nullptr: store fl(Q * scale[p]) instead of Q -- the input of the next splat
 // (DenseKernel::filter, pairwise.cpp:66), so the splat needs no per-entry normaliser
@@ -2631,6 +2725,158 @@ void launch_fill_int(int* p, int v, long long n, hipStream_t s) {
     if (n <= 0) return;
     fill_int_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(p, v, n);
     RV_LAUNCHED("fill_int_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------
+// General pairwise term of DenseCRF::inference (densecrf.cpp:123-126) for any compatibility and normalisation:
+//   t      = sliced (permutohedral.cpp:574-584 / :515-524), times norm[p] when `post` (DenseKernel::filter, pairwise.cpp:77-79)
+//   out[c] = Diagonal: fl(v[c] * t[c])      (labelcompatibility.cpp:66; Potts(w) is Diagonal(-w, .., -w), :47)
+//            Matrix:   sum_c' W[c][c'] * t[c'], from c' = 0 up, separately rounded (:85; W symmetric, :79)
+//   tmp[p][c] -= out[c]                      (densecrf.cpp:126)
+// A block stages the compatibility once (C x C floats at most: 16 KB) and walks groups of PB = 256 / C points; thread
+// (lp, c) slices class c of point lp.  A Matrix needs all C sliced values of a point: they meet in an LDS row.  W is
+// read as W[c'][c] (= W[c][c'], symmetric), so the lanes of a wave read consecutive LDS banks.
+// ---------------------------------------------------------------------------------------------
+constexpr int TERM_THREADS = 256;
+
+template <bool SEQ>
+__global__ void __launch_bounds__(TERM_THREADS)
+term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha, int post, int matrix,
+                   const float* __restrict__ compat, float* __restrict__ tmp, long long n_points) {
+    __shared__ float wt[64 * 64];
+    __shared__ float rows[TERM_THREADS];
+    if (L.counters[1]) return;   // uniform: hash overflow (flagged)
+    const int n_w = matrix ? C * C : C;
+    for (int i = threadIdx.x; i < n_w; i += TERM_THREADS) wt[i] = compat[i];
+    __syncthreads();
+    const int PB = TERM_THREADS / C;
+    const int lp = threadIdx.x / C, c = threadIdx.x - lp * C;
+    const int dp1 = L.d + 1;
+    for (long long p0 = (long long)blockIdx.x * PB; p0 < n_points; p0 += (long long)gridDim.x * PB) {   // block-uniform
+        const long long p = p0 + lp;
+        const bool live = lp < PB && p < n_points;
+        float t = 0.0f;
+        if (live) {
+            float acc = 0.0f;
+            for (int j = 0; j < dp1; j++) {
+                const int o = L.offsets[p * dp1 + j];
+                const float bw = L.bary[p * dp1 + j];
+                const float val = values[(size_t)o * C + c];
+                if (SEQ) {
+                    const float q = bw * val;
+                    const float u = q * alpha;
+                    acc += u;
+                } else {
+                    const float w = bw * alpha;
+                    const float prod = w * val;
+                    acc += prod;
+                }
+            }
+            t = post ? acc * L.norm[p] : acc;
+        }
+        if (matrix) {
+            rows[threadIdx.x] = t;
+            __syncthreads();
+        }
+        if (live) {
+            float out;
+            if (matrix) {
+                const float* r = rows + lp * C;
+                out = wt[c] * r[0];
+                for (int k = 1; k < C; k++) {
+                    const float m = wt[k * C + c] * r[k];
+                    out = out + m;
+                }
+            } else {
+                out = wt[c] * t;
+            }
+            const size_t g = (size_t)p * C + c;
+            tmp[g] = tmp[g] - out;
+        }
+        if (matrix) __syncthreads();   // the row is rewritten by the next group
+    }
+}
+
+void launch_term_update(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
+                        float* tmp, long long n_points, hipStream_t s) {
+    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const int PB = TERM_THREADS / C;
+    long long blocks = (n_points + PB - 1) / PB;
+    if (blocks > 4096) blocks = 4096;   // each block loads the compatibility once
+    const dim3 grid((unsigned)blocks), block(TERM_THREADS);
+    if (seq) term_update_kernel<true><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, tmp, n_points);
+    else term_update_kernel<false><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, tmp, n_points);
+    RV_LAUNCHED("term_update_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Kernel parameters of a term (DenseKernel::setParameters, pairwise.cpp:140-152), one point per thread, d <= 7:
+//   kind 1 (DIAG): f'[j] = fl(p[j] * f[j])
+//   kind 2 (FULL): f'[a] = sum_b P[a][b] * f[b], b from 0 up; P column-major: P[a][b] = p[b * d + a] (the resize of :147)
+// ---------------------------------------------------------------------------------------------
+template <int D>   // feature dimension at compile time: the row stays in registers
+__global__ void __launch_bounds__(256)
+kernel_params_kernel(const float* __restrict__ f, int N, int kind, KernelParams kp, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float x[D], y[D];
+#pragma unroll
+    for (int j = 0; j < D; j++) x[j] = f[i * D + j];
+#pragma unroll
+    for (int a = 0; a < D; a++) {
+        if (kind == 1) {
+            y[a] = kp.p[a] * x[a];
+        } else {
+            float r = kp.p[a] * x[0];
+#pragma unroll
+            for (int b = 1; b < D; b++) {
+                const float m = kp.p[b * D + a] * x[b];
+                r = r + m;
+            }
+            y[a] = r;
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < D; a++) out[i * D + a] = y[a];
+}
+
+void launch_kernel_params(const float* f, int N, int d, int kind, const KernelParams& kp, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+    switch (d) {
+        case 1: kernel_params_kernel<1><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        case 2: kernel_params_kernel<2><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        case 3: kernel_params_kernel<3><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        case 4: kernel_params_kernel<4><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        case 5: kernel_params_kernel<5><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        case 6: kernel_params_kernel<6><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+        default: kernel_params_kernel<7><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
+    }
+    RV_LAUNCHED("kernel_params_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------
+// LogisticUnaryEnergy::get (unary.cpp:50-52): U[i][m] = sum_k L[m][k] * f[i][k], k from 0 up, one point per thread.
+// L (C x K row-major) is the same for every lane: uniform loads.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+logistic_unary_kernel(const float* __restrict__ Lm, const float* __restrict__ f, int N, int C, int K, float* __restrict__ U) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float* fi = f + i * K;
+    for (int m = 0; m < C; m++) {
+        const float* lr = Lm + (size_t)m * K;
+        float acc = lr[0] * fi[0];
+        for (int k = 1; k < K; k++) {
+            const float prod = lr[k] * fi[k];
+            acc = acc + prod;
+        }
+        U[i * C + m] = acc;
+    }
+}
+
+void launch_logistic_unary(const float* Lm, const float* f, int N, int C, int K, float* U, hipStream_t s) {
+    logistic_unary_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(Lm, f, N, C, K, U);
+    RV_LAUNCHED("logistic_unary_kernel");
 }
 
 }  // namespace rvseg

@@ -129,7 +129,8 @@ void launch_resident_plan(const LatticeDev& L, const SplatResidentDev& r, hipStr
 int resident_block_capacity(int chunk);
 int resident_cu_count();
 float* launch_blur(const LatticeDev& L, int C, bool seq, bool reverse, float* a, float* b, hipStream_t s, bool small_blocks = false);
-// out_mode 0: plain, 1: normaliser, 2: inference update (tmp -= (-w) * (sliced * norm))
+// out_mode 0: plain, 1: normaliser, 2: inference update (tmp -= (-w) * (sliced * norm)),
+// 3: normaliser 1/(sliced + 1e-20) (NORMALIZE_BEFORE / NORMALIZE_AFTER)
 void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const float* values, float neg_w, float* out,
                   long long n_points, hipStream_t s);
 // fused slice + Potts + softmax for a single pairwise kernel; false if C is not instantiated
@@ -142,9 +143,22 @@ struct MfLabels {
 bool mf_fused_supported(int C);
 bool launch_mf_update(const LatticeDev& L, int C, const float* values, float neg_w, const ValueView& unary, bool negate,
                       const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s);
+// fused update of one learned term (Diagonal or symmetric Matrix compatibility, runtime pre / post scales); false if C
+// has no fused instantiation
+bool launch_mf_update_term(const LatticeDev& L, int C, const float* values, bool matrix, const float* compat, bool post,
+                           const ValueView& unary, bool negate, const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s);
 void launch_neg_unary(const ValueView& unary, bool negate, int C, int N, float* tmp, long long n_points, hipStream_t s);
 bool launch_softmax_unary(const ValueView& unary, bool negate, int C, int N, const ValueView& q, long long n_points,
                           const float* scale, hipStream_t s);
 void launch_softmax(const float* tmp, int C, int N, const ValueView& q, long long n_points, hipStream_t s);
+// one general pairwise term: slice, optional post-scale by L.norm, Diagonal (compat: C floats) or symmetric Matrix (C x C)
+// compatibility, tmp -= result
+void launch_term_update(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
+                        float* tmp, long long n_points, hipStream_t s);
+// kernel parameters of a term: kind 1 DIAG (d values), 2 FULL (d x d column-major)
+struct KernelParams { float p[49]; };
+void launch_kernel_params(const float* f, int N, int d, int kind, const KernelParams& kp, float* out, hipStream_t s);
+// U (N x C) = f (N x K) times L^T (L: C x K row-major, device)
+void launch_logistic_unary(const float* Lm, const float* f, int N, int C, int K, float* U, hipStream_t s);
 
 }  // namespace rvseg

@@ -29,6 +29,9 @@ struct CrfState {
     std::vector<LatticeBufs> lat;  // one per pairwise kernel
     // slot 1 of the scratch buffers: a second label layer's mean field runs beside the first on its own stream
     DevBuf val_a, val_b, tmp, q, qn, unary, feat, labels, val_a2, val_b2, tmp2, qn2;
+    // learned-model terms (rvseg_crf_infer_terms*): compatibilities of all terms, transformed features, logistic L
+    DevBuf compat, kfeat, lmat;
+    std::vector<float> h_compat;   // host copy of `compat` (the source of its asynchronous upload)
     hipStream_t layer_stream = nullptr;       // the second layer's stream
     hipEvent_t layer_fork = nullptr, layer_join = nullptr;
     // pinned read-back of a build: [0] M, [1] overflow, [2] longest vertex list, [3] frames the splat planner gave up on.
@@ -72,7 +75,8 @@ void crf_state_free(Pipeline* im) {
     if (!im->crf) return;
     for (auto& l : im->crf->lat) lattice_free(l);
     DevBuf* all[] = {&im->crf->val_a, &im->crf->val_b, &im->crf->tmp, &im->crf->q, &im->crf->qn, &im->crf->unary, &im->crf->feat, &im->crf->labels,
-                     &im->crf->val_a2, &im->crf->val_b2, &im->crf->tmp2, &im->crf->qn2};
+                     &im->crf->val_a2, &im->crf->val_b2, &im->crf->tmp2, &im->crf->qn2, &im->crf->compat, &im->crf->kfeat,
+                     &im->crf->lmat};
     if (im->crf->layer_stream) (void)hipStreamDestroy(im->crf->layer_stream);
     if (im->crf->layer_fork) (void)hipEventDestroy(im->crf->layer_fork);
     if (im->crf->layer_join) (void)hipEventDestroy(im->crf->layer_join);
@@ -282,7 +286,10 @@ static rvseg_status lattice_clear(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s)
     return RVSEG_OK;
 }
 
-static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s) {
+// norm_kind: the normaliser the term needs (rvseg_norm_kind): SYMMETRIC 1/sqrt(n + 1e-20), BEFORE / AFTER 1/(n + 1e-20),
+// NONE none at all (pairwise.cpp:40-56; the mean norm NO_NORMALIZATION computes is never read in inference)
+static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s,
+                                  int norm_kind = RVSEG_NORMALIZE_SYMMETRIC) {
     const LatticeDev& L = b.dev;
     if (!b.cleared) { rvseg_status stc = lattice_clear(ctx, b, s); if (stc != RVSEG_OK) return stc; }
     b.cleared = false;
@@ -314,12 +321,14 @@ static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, 
     }
     st = values_reserve(ctx, cs, L.m_bound, 1);
     if (st != RVSEG_OK) { if (plan_forked) (void)hipStreamWaitEvent(s, cs->layer_join, 0); return st; }
-    // norm = lattice.compute(ones) through seqCompute (1 row), then 1/sqrt(norm + 1e-20)
-    ValueView none{nullptr, 0, 0};
-    launch_splat(L, none, 1, 2, cs->val_a.as<float>(), s);
-    float* blurred = launch_blur(L, 1, true, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s, true);
-    launch_slice(L, 1, true, 1, blurred, 0.f, L.norm, b.n_points, s);
-    tr("normaliser");
+    // norm = lattice.compute(ones) through seqCompute (1 row), then 1/sqrt(norm + 1e-20) (or 1/(norm + 1e-20))
+    if (norm_kind != RVSEG_NO_NORMALIZATION) {
+        ValueView none{nullptr, 0, 0};
+        launch_splat(L, none, 1, 2, cs->val_a.as<float>(), s);
+        float* blurred = launch_blur(L, 1, true, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s, true);
+        launch_slice(L, 1, true, norm_kind == RVSEG_NORMALIZE_SYMMETRIC ? 1 : 3, blurred, 0.f, L.norm, b.n_points, s);
+        tr("normaliser");
+    }
     if (plan_forked) RV_HIP(ctx, hipStreamWaitEvent(s, cs->layer_join, 0));
     RV_LAUNCH_OK(ctx);
     b.built = true;
@@ -468,6 +477,121 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, int n_kernels, cons
         for (int k = 0; k < n_kernels; k++) filter_into(ctx, cs->lat[k], cs, Q, C, ws[k], tmp, s);
         mark("softmax");
         launch_softmax(tmp, C, N, Q, n_points, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// One pairwise term of a learned model, as the mean field runs it.  Potts, and a Diagonal whose entries are all equal,
+// are the same term (Potts(w) == Diagonal(-w, .., -w) bit for bit).
+struct TermPlan {
+    int norm = RVSEG_NORMALIZE_SYMMETRIC;
+    bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
+    float w = 0.f;
+    bool matrix = false;
+    size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
+};
+
+// PottsCompatibility / DiagonalCompatibility / MatrixCompatibility (labelcompatibility.cpp:38-100) as diagonals and
+// symmetric matrices: W = 0.5 * (m + m^T) elementwise in fp32 when the term is created (:79)
+static void plan_terms(int C, int n_terms, const rvseg_crf_term* terms, std::vector<TermPlan>& plan, std::vector<float>& hc) {
+    plan.assign((size_t)n_terms, TermPlan{});
+    hc.clear();
+    for (int k = 0; k < n_terms; k++) {
+        const rvseg_crf_term& t = terms[k];
+        TermPlan& tp = plan[k];
+        tp.norm = t.normalization;
+        tp.off = hc.size();
+        if (t.compat == RVSEG_COMPAT_MATRIX) {
+            tp.uniform = false;
+            tp.matrix = true;
+            for (int i = 0; i < C; i++)
+                for (int j = 0; j < C; j++) {
+                    const float sum = t.compat_params[(size_t)i * C + j] + t.compat_params[(size_t)j * C + i];
+                    hc.push_back(0.5f * sum);
+                }
+        } else if (t.compat == RVSEG_COMPAT_DIAGONAL) {
+            for (int c = 0; c < C; c++) {
+                hc.push_back(t.compat_params[c]);
+                if (!(t.compat_params[c] == t.compat_params[0] && std::signbit(t.compat_params[c]) == std::signbit(t.compat_params[0])))
+                    tp.uniform = false;
+            }
+            tp.w = -t.compat_params[0];
+        } else {
+            tp.w = t.compat_params[0];
+            for (int c = 0; c < C; c++) hc.push_back(-tp.w);
+        }
+    }
+}
+
+// DenseCRF::inference (densecrf.cpp:115-131) over learned terms.  Models made of Potts terms with NORMALIZE_SYMMETRIC only
+// are the models mean_field() runs: they go there unchanged (fused update for one term).  Every other model takes the
+// general loop: per term, the splat (pre-scaled per entry for SYMMETRIC / BEFORE, a plain gather otherwise), the blur,
+// then term_update_kernel (slice, post-scale for SYMMETRIC / AFTER, compatibility, tmp -= out).  A single term with a fused
+// class count runs fused instead: splat, blur, then mf_update_term_kernel (slice + scales + compatibility + unary +
+// softmax in one pass), with Q holding fl(Q * norm) between iterations when the term pre-scales.
+static rvseg_status mean_field_terms(rvseg_ctx* ctx, CrfState* cs, const std::vector<TermPlan>& plan, const float* d_compat,
+                                     const ValueView& unary, bool unary_is_energy, int C, int N, int iterations, const ValueView& Q,
+                                     hipStream_t s, const MfLabels* lab, bool* labels_done) {
+    const int n_terms = (int)plan.size();
+    bool potts = true;
+    std::vector<float> ws((size_t)n_terms);
+    for (int k = 0; k < n_terms; k++) {
+        potts = potts && plan[k].uniform && plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC;
+        ws[k] = plan[k].w;
+    }
+    if (potts) return mean_field(ctx, cs, n_terms, ws.data(), unary, unary_is_energy, C, N, N, iterations, Q, s, lab, labels_done);
+    if (labels_done) *labels_done = false;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, cs->tmp, (size_t)N * C * 4)) != RVSEG_OK) return st;
+    long long mb = 0;
+    for (int k = 0; k < n_terms; k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
+    if ((st = values_reserve(ctx, cs, mb, C)) != RVSEG_OK) return st;
+    float* tmp = cs->tmp.as<float>();
+    auto pre = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_BEFORE; };
+    auto post = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_AFTER; };
+    if (n_terms == 1 && iterations > 0 && mf_fused_supported(C) && Q.frame_stride == (size_t)N * C && Q.layer_off == 0) {
+        const LatticeBufs& b = cs->lat[0];
+        timer_mark(ctx, "softmax", s);
+        launch_softmax_unary(unary, unary_is_energy, C, N, Q, N, pre(0) ? b.dev.norm : nullptr, s);
+        for (int it = 0; it < iterations; it++) {
+            const bool last = it + 1 == iterations;
+            timer_mark(ctx, "splat", s);
+            launch_splat(b.dev, Q, C, 0, cs->val_a.as<float>(), s, true, b.resident_on ? &b.resident : nullptr);
+            timer_mark(ctx, "blur", s);
+            float* blurred = launch_blur(b.dev, C, C <= 2, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
+            timer_mark(ctx, "mf_update", s);
+            MfLabels none{nullptr, 0, 0, 0, 0};
+            launch_mf_update_term(b.dev, C, blurred, plan[0].matrix, d_compat + plan[0].off, post(0), unary, unary_is_energy, Q,
+                                  !last && pre(0), last && lab ? *lab : none, s);
+        }
+        if (lab && labels_done) *labels_done = true;
+        RV_LAUNCH_OK(ctx);
+        return RVSEG_OK;
+    }
+    timer_mark(ctx, "softmax", s);
+    if (!launch_softmax_unary(unary, unary_is_energy, C, N, Q, N, nullptr, s)) {
+        launch_neg_unary(unary, unary_is_energy, C, N, tmp, N, s);
+        launch_softmax(tmp, C, N, Q, N, s);
+    }
+    for (int k = 0; k < n_terms; k++)
+        if (pre(k) && (st = ensure_csr_nrm(ctx, cs->lat[k], s)) != RVSEG_OK) return st;
+    const bool seq = C <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
+    for (int it = 0; it < iterations; it++) {
+        timer_mark(ctx, "softmax", s);
+        launch_neg_unary(unary, unary_is_energy, C, N, tmp, N, s);
+        for (int k = 0; k < n_terms; k++) {
+            const LatticeBufs& b = cs->lat[k];
+            timer_mark(ctx, "splat", s);
+            launch_splat(b.dev, Q, C, pre(k) ? 1 : 0, cs->val_a.as<float>(), s);
+            timer_mark(ctx, "blur", s);
+            float* blurred = launch_blur(b.dev, C, seq, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
+            timer_mark(ctx, "term_update", s);
+            launch_term_update(b.dev, C, seq, blurred, post(k), plan[k].matrix, d_compat + plan[k].off, tmp, N, s);
+        }
+        timer_mark(ctx, "softmax", s);
+        // expAndNormalize(tmp1) with the row in registers where C has an instantiation (same operations, same bits)
+        if (!launch_softmax_unary(ValueView{tmp, (size_t)N * C, 0}, false, C, N, Q, N, nullptr, s)) launch_softmax(tmp, C, N, Q, N, s);
     }
     RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
@@ -644,6 +768,57 @@ static rvseg_status lattice_build_retry(rvseg_ctx* ctx, CrfState* cs, LatticeBuf
     return RVSEG_ERR_CAPACITY;
 }
 
+// The lattices of learned terms: the features (host: copied in; device: read in place), transformed by the term's kernel
+// parameters (pairwise.cpp:140-152) into context memory, then built with the normaliser the term needs.  A hash overflow
+// of any term rebuilds all of them once at the safe capacity, as rvseg_crf_infer_multi does.
+static rvseg_status build_terms(rvseg_ctx* ctx, CrfState* cs, int N, int n_terms, const rvseg_crf_term* terms, bool host_features,
+                                hipStream_t s) {
+    if ((int)cs->lat.size() < n_terms) cs->lat.resize(n_terms);
+    rvseg_status st;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        bool overflow = false;
+        for (int k = 0; k < n_terms && !overflow; k++) {
+            const rvseg_crf_term& t = terms[k];
+            LatticeBufs& lb = cs->lat[k];
+            if ((st = lattice_prepare(ctx, lb, t.d, N, 1, attempt == 1)) != RVSEG_OK) return st;
+            const float* f = t.features;
+            if (host_features) {
+                if ((st = dev_reserve(ctx, cs->feat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
+                RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, t.features, (size_t)N * t.d * 4, hipMemcpyHostToDevice, s));
+                f = cs->feat.as<float>();
+            }
+            if (t.kernel_params && t.kernel_type != RVSEG_CONST_KERNEL) {
+                KernelParams kp{};
+                const int np = t.kernel_type == RVSEG_DIAG_KERNEL ? t.d : t.d * t.d;
+                for (int i = 0; i < np; i++) kp.p[i] = t.kernel_params[i];
+                if ((st = dev_reserve(ctx, cs->kfeat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
+                launch_kernel_params(f, N, t.d, t.kernel_type, kp, cs->kfeat.as<float>(), s);
+                f = cs->kfeat.as<float>();
+            }
+            FeatureSource fs{};
+            fs.mode = 0; fs.feat = f;
+            if ((st = lattice_build(ctx, cs, lb, fs, s, t.normalization)) != RVSEG_OK) return st;
+            int cnt[3];
+            if ((st = lattice_counters(ctx, cs, lb, s, cnt)) != RVSEG_OK) return st;
+            overflow = cnt[1] != 0;
+        }
+        if (!overflow) return RVSEG_OK;
+    }
+    ctx->err = "lattice hash table overflow";
+    return RVSEG_ERR_CAPACITY;
+}
+
+// the terms' compatibilities in context memory (uploaded from CrfState::h_compat, which outlives the copy)
+static rvseg_status upload_terms(rvseg_ctx* ctx, CrfState* cs, int C, int n_terms, const rvseg_crf_term* terms,
+                                 std::vector<TermPlan>& plan, hipStream_t s) {
+    plan_terms(C, n_terms, terms, plan, cs->h_compat);
+    if (cs->h_compat.empty()) return RVSEG_OK;
+    rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
+    if (st != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(cs->compat.p, cs->h_compat.data(), cs->h_compat.size() * 4, hipMemcpyHostToDevice, s));
+    return RVSEG_OK;
+}
+
 static rvseg_status crf_bare_state(rvseg_ctx* ctx, Pipeline** im_out, CrfState** cs_out) {
     if (!ctx->impl) {
         Pipeline* im = new Pipeline();
@@ -759,6 +934,130 @@ rvseg_status rvseg_crf_infer_multi(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
         RV_HIP(ctx, hipMemcpyAsync(map_out, cs->labels.p, (size_t)N, hipMemcpyDeviceToHost, s));
     }
     RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_terms_check(int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms) {
+    if (N <= 0 || C < 1 || C > 64 || n_terms < 0 || n_terms > 8 || (n_terms > 0 && !terms)) return RVSEG_ERR_INVALID_ARG;
+    for (int k = 0; k < n_terms; k++) {
+        const rvseg_crf_term& t = terms[k];
+        if (t.d < 1 || t.d > 7 || !t.features || !t.compat_params) return RVSEG_ERR_INVALID_ARG;
+        if (t.compat < RVSEG_COMPAT_POTTS || t.compat > RVSEG_COMPAT_MATRIX) return RVSEG_ERR_INVALID_ARG;
+        if (t.kernel_type < RVSEG_CONST_KERNEL || t.kernel_type > RVSEG_FULL_KERNEL) return RVSEG_ERR_INVALID_ARG;
+        if (t.normalization < RVSEG_NO_NORMALIZATION || t.normalization > RVSEG_NORMALIZE_SYMMETRIC) return RVSEG_ERR_INVALID_ARG;
+    }
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
+                                   const float* unary_energy, int32_t iterations, float* Q_out, int8_t* map_out,
+                                   int32_t label_mode, int32_t unknown_label) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !unary_energy || !Q_out || label_mode < 0 ||
+        label_mode > 3) {
+        ctx->err = "bad arguments";
+        return RVSEG_ERR_INVALID_ARG;
+    }
+    Pipeline* im; CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &im, &cs);
+    if (st != RVSEG_OK) return st;
+    hipStream_t s = ctx->stream;
+    std::vector<TermPlan> plan;
+    if ((st = upload_terms(ctx, cs, C, n_terms, terms, plan, s)) != RVSEG_OK) return st;
+    if ((st = build_terms(ctx, cs, N, n_terms, terms, true, s)) != RVSEG_OK) return st;
+    const size_t tot = (size_t)N * C;
+    if ((st = dev_reserve(ctx, cs->unary, tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_energy, tot * 4, hipMemcpyHostToDevice, s));
+    ValueView U{cs->unary.as<float>(), tot, 0}, Q{cs->q.as<float>(), tot, 0};
+    timer_reset(ctx);
+    if ((st = mean_field_terms(ctx, cs, plan, cs->compat.as<float>(), U, true, C, N, iterations, Q, s, nullptr, nullptr)) != RVSEG_OK) return st;
+    timer_mark(ctx, "end", s);
+    RV_HIP(ctx, hipMemcpyAsync(Q_out, cs->q.p, tot * 4, hipMemcpyDeviceToHost, s));
+    if (map_out) {
+        if ((st = dev_reserve(ctx, cs->labels, (size_t)N)) != RVSEG_OK) return st;
+        launch_labels(cs->q.as<float>(), (size_t)N, C, label_mode, unknown_label, cs->labels.as<int8_t>(), s);
+        RV_HIP(ctx, hipMemcpyAsync(map_out, cs->labels.p, (size_t)N, hipMemcpyDeviceToHost, s));
+    }
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
+                                          const float* d_unary, int32_t unary_is_energy, int32_t iterations, float* d_Q_out,
+                                          int8_t* d_map_out, int32_t label_mode, int32_t unknown_label, void* hip_stream) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !d_unary || (!d_Q_out && !d_map_out) ||
+        label_mode < 0 || label_mode > 3) {
+        ctx->err = "bad arguments";
+        return RVSEG_ERR_INVALID_ARG;
+    }
+    Pipeline* im; CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &im, &cs);
+    if (st != RVSEG_OK) return st;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    timer_reset(ctx);
+    timer_mark(ctx, "lattice_build", s);
+    std::vector<TermPlan> plan;
+    if ((st = upload_terms(ctx, cs, C, n_terms, terms, plan, s)) != RVSEG_OK) return st;
+    if ((st = build_terms(ctx, cs, N, n_terms, terms, false, s)) != RVSEG_OK) return st;
+    float* q = d_Q_out;
+    if (!q) {
+        if ((st = dev_reserve(ctx, cs->q, (size_t)N * C * 4)) != RVSEG_OK) return st;
+        q = cs->q.as<float>();
+    }
+    ValueView U{const_cast<float*>(d_unary), (size_t)N * C, 0}, Q{q, (size_t)N * C, 0};
+    MfLabels lab{d_map_out, label_mode, unknown_label, 1, 0};
+    bool done = false;
+    if ((st = mean_field_terms(ctx, cs, plan, cs->compat.as<float>(), U, unary_is_energy != 0, C, N, iterations, Q, s,
+                               d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
+    if (d_map_out && !done) {
+        timer_mark(ctx, "labels", s);
+        launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map_out, s);
+    }
+    timer_mark(ctx, "end", s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+static rvseg_status logistic_args(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* L, const float* f, const float* U) {
+    if (N <= 0 || C < 1 || C > 64 || K < 1 || !L || !f || !U) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_logistic_unary(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* L, const float* f, float* U_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    rvseg_status st = logistic_args(ctx, N, C, K, L, f, U_out);
+    if (st != RVSEG_OK) return st;
+    Pipeline* im; CrfState* cs;
+    if ((st = crf_enter(ctx, &im, &cs)) != RVSEG_OK) return st;
+    hipStream_t s = ctx->stream;
+    if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->feat, (size_t)N * K * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->unary, (size_t)N * C * 4)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(cs->lmat.p, L, (size_t)C * K * 4, hipMemcpyHostToDevice, s));
+    RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, f, (size_t)N * K * 4, hipMemcpyHostToDevice, s));
+    launch_logistic_unary(cs->lmat.as<float>(), cs->feat.as<float>(), N, C, K, cs->unary.as<float>(), s);
+    RV_LAUNCH_OK(ctx);
+    RV_HIP(ctx, hipMemcpyAsync(U_out, cs->unary.p, (size_t)N * C * 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* L, const float* d_f,
+                                             float* d_U_out, void* hip_stream) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    rvseg_status st = logistic_args(ctx, N, C, K, L, d_f, d_U_out);
+    if (st != RVSEG_OK) return st;
+    Pipeline* im; CrfState* cs;
+    if ((st = crf_enter(ctx, &im, &cs)) != RVSEG_OK) return st;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
+    // L is caller memory that may be gone once this returns: its copy is complete before the call returns
+    RV_HIP(ctx, hipMemcpyAsync(cs->lmat.p, L, (size_t)C * K * 4, hipMemcpyHostToDevice, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    launch_logistic_unary(cs->lmat.as<float>(), d_f, N, C, K, d_U_out, s);
+    RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
 }
 

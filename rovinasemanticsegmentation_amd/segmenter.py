@@ -5,6 +5,8 @@ Names follow the reference so that the parity tests read like its call sites:
   RandomForest.read / classLogPosterior / multiClassLogPosterior   (libforest classifiers.h:274-344)
   FeatureExtractor.extract                                         (include/feature_extractor.h:41)
   DenseCRF(N, C).setUnaryEnergy / addPairwiseEnergy / inference / map  (densecrf.h:36-121)
+    + learned models: Potts / Diagonal / MatrixCompatibility, kernel types, normalisations, logistic unary and the
+      parameter vectors of densecrf.cpp:294-360 (labelcompatibility.h, pairwise.h:32-42, unary.h)
   Segmenter.processFrames                                          (src/segmenter.cpp:323-443)
   RgbLabelConversion.rgbToLabel / labelToRgb / getLabelName / ...  (include/rgb_label_conversion.h)
   Evaluator: the confusion matrix and scores of src/test.cpp:182-228 (test_multi.cpp:222-268)
@@ -271,6 +273,45 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_infer_multi(self.h, N, Cn, len(feats), ds, ptrs, wsa, _ptr(U), iterations, _ptr(Q), _ptr(mp), label_mode, unknown_label))
         return Q, mp
 
+    def crf_infer_terms(self, unary_energy, terms, iterations, label_mode=capi.LABEL_ARGMAX, unknown_label=0):
+        """rvseg_crf_infer_terms.  terms: [(features N x d, compatibility, kernel_type, normalization, kernel_params or None)];
+        a compatibility is a float (Potts weight) or a Potts / Diagonal / MatrixCompatibility."""
+        U = np.ascontiguousarray(unary_energy, np.float32)
+        N, Cn = U.shape
+        arr, keep = _crf_terms(terms, Cn, N)
+        Q = np.empty_like(U)
+        mp = np.empty(N, np.int8)
+        capi.check(self.h, self.L.rvseg_crf_infer_terms(self.h, N, Cn, len(terms), arr, _ptr(U), iterations, _ptr(Q), _ptr(mp),
+                                                        label_mode, unknown_label))
+        del keep
+        return Q, mp
+
+    def crf_infer_terms_device(self, N, Cn, terms, d_unary, unary_is_energy, iterations, d_Q=0, d_map=0,
+                               label_mode=capi.LABEL_ARGMAX, unknown_label=0, stream=0):
+        """rvseg_crf_infer_terms_device: the term features are integer device addresses (N x d each), enqueues only."""
+        arr, keep = _crf_terms(terms, Cn, N, device=True)
+        capi.check(self.h, self.L.rvseg_crf_infer_terms_device(
+            self.h, N, Cn, len(terms), arr, C.c_void_p(d_unary), 1 if unary_is_energy else 0, iterations,
+            C.c_void_p(d_Q or None), C.c_void_p(d_map or None), label_mode, unknown_label, C.c_void_p(stream or None)))
+        del keep
+
+    def crf_logistic_unary(self, L, f):
+        """LogisticUnaryEnergy::get (unary.cpp:50-52): L (C x K), f (N x K) -> the energy U (N x C)."""
+        Lm = np.ascontiguousarray(L, np.float32)
+        F = np.ascontiguousarray(f, np.float32)
+        Cn, K = Lm.shape
+        N = F.shape[0]
+        assert F.shape == (N, K)
+        U = np.empty((N, Cn), np.float32)
+        capi.check(self.h, self.L.rvseg_crf_logistic_unary(self.h, N, Cn, K, _ptr(Lm), _ptr(F), _ptr(U)))
+        return U
+
+    def crf_logistic_unary_device(self, N, L, d_f, d_U, stream=0):
+        Lm = np.ascontiguousarray(L, np.float32)
+        Cn, K = Lm.shape
+        capi.check(self.h, self.L.rvseg_crf_logistic_unary_device(self.h, N, Cn, K, _ptr(Lm), C.c_void_p(d_f), C.c_void_p(d_U),
+                                                                  C.c_void_p(stream or None)))
+
     # ---- local-map fusion -------------------------------------------------------------------
     def fuse_posteriors(self, index_images, posteriors, class_counts, cloud_size):
         p = self.params
@@ -459,34 +500,205 @@ class FeatureExtractor:
         return self.ctx.extract_features(color, depth, calib)
 
 
+CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL = capi.CONST_KERNEL, capi.DIAG_KERNEL, capi.FULL_KERNEL
+NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER, NORMALIZE_SYMMETRIC = (
+    capi.NO_NORMALIZATION, capi.NORMALIZE_BEFORE, capi.NORMALIZE_AFTER, capi.NORMALIZE_SYMMETRIC)
+
+
+class PottsCompatibility:
+    """out = -w * Q (labelcompatibility.cpp:43-55); parameters: [w]."""
+    kind = capi.COMPAT_POTTS
+
+    def __init__(self, weight):
+        self.w = np.float32(weight)
+
+    def parameters(self):
+        return np.array([self.w], np.float32)
+
+    def setParameters(self, v):
+        self.w = np.float32(v[0])
+
+    def array(self, M):
+        return np.array([self.w], np.float32)
+
+
+class DiagonalCompatibility:
+    """out = diag(v) * Q (labelcompatibility.cpp:61-73); parameters: v."""
+    kind = capi.COMPAT_DIAGONAL
+
+    def __init__(self, v):
+        self.v = np.array(v, np.float32).reshape(-1)
+
+    def parameters(self):
+        return self.v.copy()
+
+    def setParameters(self, v):
+        self.v = np.array(v, np.float32).reshape(-1)
+
+    def array(self, M):
+        assert self.v.shape == (M,)
+        return self.v
+
+
+class MatrixCompatibility:
+    """out = W * Q with W = 0.5 (m + m^T) in fp32 (labelcompatibility.cpp:79-100); parameters: the upper triangle of W
+    row by row (W[i][j], j >= i), as parameters() / setParameters() pack it (:88-100)."""
+    kind = capi.COMPAT_MATRIX
+
+    def __init__(self, m):
+        m = np.array(m, np.float32)
+        assert m.ndim == 2 and m.shape[0] == m.shape[1]
+        self.W = np.float32(0.5) * (m + m.T)
+
+    def parameters(self):
+        M = self.W.shape[0]
+        return np.array([self.W[i, j] for i in range(M) for j in range(i, M)], np.float32)
+
+    def setParameters(self, v):
+        M = self.W.shape[0]
+        v = np.asarray(v, np.float32)
+        assert v.shape == (M * (M + 1) // 2,)
+        k = 0
+        for i in range(M):
+            for j in range(i, M):
+                self.W[i, j] = self.W[j, i] = v[k]
+                k += 1
+
+    def array(self, M):
+        assert self.W.shape == (M, M)
+        return np.ascontiguousarray(self.W)   # symmetric: the library's 0.5 (W + W^T) is W again
+
+
+def _compat(c):
+    return c if hasattr(c, "kind") else PottsCompatibility(c)
+
+
+def _crf_terms(terms, M, N, device=False):
+    """ctypes rvseg_crf_term array for [(features, compatibility, kernel_type, normalization, kernel_params)]; the second
+    value keeps the numpy buffers alive for the call."""
+    arr = (capi.RvsegCrfTerm * max(1, len(terms)))()
+    keep = []
+    for k, (f, comp, kt, nt, kp) in enumerate(terms):
+        comp = _compat(comp)
+        cp = np.ascontiguousarray(comp.array(M), np.float32)
+        keep.append(cp)
+        t = arr[k]
+        if device:
+            t.d, t.features = int(f[1]), C.c_void_p(f[0])   # (device address, d)
+        else:
+            fa = np.ascontiguousarray(f, np.float32)
+            assert fa.shape[0] == N
+            keep.append(fa)
+            t.d, t.features = fa.shape[1], fa.ctypes.data
+        t.compat, t.kernel_type, t.normalization = comp.kind, int(kt), int(nt)
+        t.compat_params = cp.ctypes.data
+        if kp is not None and int(kt) != CONST_KERNEL:
+            kpa = np.ascontiguousarray(kp, np.float32).reshape(-1)
+            assert kpa.shape == ((t.d if int(kt) == DIAG_KERNEL else t.d * t.d),)
+            keep.append(kpa)
+            t.kernel_params = kpa.ctypes.data
+    return arr, keep
+
+
 class DenseCRF:
-    """DenseCRF as Segmenter::processMapFromQueue drives it (src/segmenter.cpp:641-644)."""
+    """DenseCRF as Segmenter::processMapFromQueue drives it (src/segmenter.cpp:641-644), and as
+    examples/dense_learning.cpp:128-182 builds a learned model (compatibilities, kernel types and parameters,
+    normalisations, a logistic unary)."""
 
     def __init__(self, ctx, N, M):
         self.ctx, self.N, self.M = ctx, N, M
         self.unary = None
+        self.logistic = None    # (L: M x K, f: N x K) of setUnaryEnergy(L, f)
+        # per term: [features, compatibility (float = Potts), kernel_type, normalization, kernel parameters or None]
         self.kernels = []
 
-    def setUnaryEnergy(self, unary):  # densecrf.cpp:89-91; unary is N x M energy (= -log-posterior)
+    def setUnaryEnergy(self, unary, f=None):  # densecrf.cpp:85-91; unary is N x M energy (= -log-posterior)
+        if f is not None:   # setUnaryEnergy(L, f): LogisticUnaryEnergy, unary.cpp:44-52 (L: M x K, f: N x K point-major)
+            L = np.array(unary, np.float32)
+            f = np.ascontiguousarray(f, np.float32)
+            assert L.shape[0] == self.M and f.shape == (self.N, L.shape[1])
+            self.logistic, self.unary = (L, f), None
+            return
         unary = np.ascontiguousarray(unary, np.float32)
         assert unary.shape == (self.N, self.M)
-        self.unary = unary
+        self.unary, self.logistic = unary, None
 
-    def addPairwiseEnergy(self, features, potts_weight):  # densecrf.cpp:54-60 + PottsCompatibility
+    def addPairwiseEnergy(self, features, function, kernel_type=DIAG_KERNEL, normalization=NORMALIZE_SYMMETRIC):  # densecrf.cpp:54-60
         features = np.ascontiguousarray(features, np.float32)
         assert features.shape[0] == self.N  # assert(features.cols() == N_), densecrf.cpp:55
-        self.kernels.append((features, float(potts_weight)))
+        if not hasattr(function, "kind"):
+            function = float(function)   # a bare weight: PottsCompatibility(w)
+        self.kernels.append([features, function, int(kernel_type), int(normalization), None])
 
-    def addPairwiseGaussian(self, W, H, sx, sy, w):  # densecrf.cpp:61-69 (features built by the C ABI)
-        self.addPairwiseEnergy(capi.crf_features_gaussian(W, H, sx, sy), w)
+    def addPairwiseGaussian(self, W, H, sx, sy, w, kernel_type=DIAG_KERNEL, normalization=NORMALIZE_SYMMETRIC):  # densecrf.cpp:61-69
+        self.addPairwiseEnergy(capi.crf_features_gaussian(W, H, sx, sy), w, kernel_type, normalization)
 
-    def addPairwiseBilateral(self, W, H, sx, sy, sr, sg, sb, im, w):  # densecrf.cpp:70-81
-        self.addPairwiseEnergy(capi.crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im), w)
+    def addPairwiseBilateral(self, W, H, sx, sy, sr, sg, sb, im, w, kernel_type=DIAG_KERNEL,
+                             normalization=NORMALIZE_SYMMETRIC):  # densecrf.cpp:70-81
+        self.addPairwiseEnergy(capi.crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im), w, kernel_type, normalization)
+
+    # ---- parameters (densecrf.cpp:294-360) ----
+    def unaryParameters(self):   # LogisticUnaryEnergy::parameters, unary.cpp:53-57: L column-major
+        if self.logistic is None:
+            return np.zeros(0, np.float32)
+        return np.ascontiguousarray(self.logistic[0].T).reshape(-1)
+
+    def setUnaryParameters(self, v):   # unary.cpp:58-63
+        if self.logistic is None:
+            return
+        L, f = self.logistic
+        v = np.asarray(v, np.float32)
+        assert v.shape == (L.size,)
+        self.logistic = (np.ascontiguousarray(v.reshape(L.shape[1], L.shape[0]).T), f)
+
+    def labelCompatibilityParameters(self):
+        return np.concatenate([np.zeros(0, np.float32)] + [_compat(k[1]).parameters() for k in self.kernels]).astype(np.float32)
+
+    def setLabelCompatibilityParameters(self, v):
+        v = np.asarray(v, np.float32)
+        i = 0
+        for k in self.kernels:
+            k[1] = _compat(k[1])
+            n = k[1].parameters().shape[0]
+            k[1].setParameters(v[i:i + n])
+            i += n
+        assert i == v.shape[0]
+
+    def _kernel_parameters(self, k):   # DenseKernel::parameters, pairwise.cpp:116-125
+        d = k[0].shape[1]
+        if k[2] == CONST_KERNEL:
+            return np.zeros(0, np.float32)
+        if k[4] is not None:
+            return k[4].copy()
+        return np.ones(d, np.float32) if k[2] == DIAG_KERNEL else np.eye(d, dtype=np.float32).reshape(-1)
+
+    def kernelParameters(self):
+        return np.concatenate([np.zeros(0, np.float32)] + [self._kernel_parameters(k) for k in self.kernels]).astype(np.float32)
+
+    def setKernelParameters(self, v):   # pairwise.cpp:140-152: DIAG d values, FULL d x d column-major, CONST none
+        v = np.asarray(v, np.float32)
+        i = 0
+        for k in self.kernels:
+            n = self._kernel_parameters(k).shape[0]
+            if k[2] != CONST_KERNEL:
+                k[4] = v[i:i + n].copy()
+            i += n
+        assert i == v.shape[0]
+
+    def _unary_energy(self):
+        # A logistic unary is computed on the GPU and read back, then uploaded with the model (an N x M round trip per
+        # inference); device-resident callers use Context.crf_logistic_unary_device + crf_infer_terms_device instead.
+        if self.logistic is not None:
+            return self.ctx.crf_logistic_unary(*self.logistic)
+        return self.unary if self.unary is not None else np.zeros((self.N, self.M), np.float32)
 
     def inference(self, n_iterations, label_mode=capi.LABEL_ARGMAX, unknown_label=0):  # densecrf.cpp:115-131
-        U = self.unary if self.unary is not None else np.zeros((self.N, self.M), np.float32)
+        U = self._unary_energy()
+        plain = all(isinstance(k[1], float) and k[3] == NORMALIZE_SYMMETRIC and k[4] is None for k in self.kernels)
+        if not plain:
+            return self.ctx.crf_infer_terms(U, [tuple(k) for k in self.kernels], n_iterations, label_mode, unknown_label)
         if len(self.kernels) == 1:
-            f, w = self.kernels[0]
+            f, w = self.kernels[0][:2]
             return self.ctx.crf_infer(U, f, w, n_iterations, label_mode, unknown_label)
         return self.ctx.crf_infer_multi(U, [k[0] for k in self.kernels], [k[1] for k in self.kernels], n_iterations, label_mode, unknown_label)
 
