@@ -2468,12 +2468,13 @@ __device__ __forceinline__ void mf_load(const LatticeDev& L, const ValueView& un
 
 // TERM 0: Potts, t = sliced * norm, out = fl(-w * t) (the Segmenter's update).  TERM 1 / 2 (learned single-term models):
 // t = sliced, times norm when `post` (block-uniform); out = Diagonal fl(v[c] * t[c]) / Matrix sum_c' W[c][c'] t[c'] from
-// c' = 0 up, with v / W read from `compat` at compile-time offsets (uniform loads).  TERM 0 never reads compat / post.
-template <bool SEQ, int C, int DP1, bool USE_LDS, int TERM = 0>
+// c' = 0 up, with v / W read from `compat` at compile-time offsets (uniform loads).  TERM 0 never reads compat / post,
+// TERM 1 / 2 never neg_w.
+template <bool SEQ, int C, int DP1, bool USE_LDS, int TERM>
 __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __restrict__ values, const float* tab, float alpha,
                                           float neg_w, const ValueView& unary, int negate, const ValueView& Q, int scale_out,
                                           const MfLabels& lab, int frame, int f0, int i0,
-                                          const float* __restrict__ compat = nullptr, int post = 0) {
+                                          const float* __restrict__ compat, int post) {
     constexpr int CP = (C + 3) / 4 * 4;
     constexpr int PER_THREAD = MF_PTS / 256;
     const int dp1 = DP1 > 0 ? DP1 : L.d + 1;
@@ -2560,10 +2561,14 @@ __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __re
     }
 }
 
-template <bool SEQ, int C, int DP1>   // DP1 = d+1 at compile time (wide offset / weight loads), 0 = runtime d
+// DP1 = d+1 at compile time (wide offset / weight loads), 0 = runtime d.  TERM 0 is the Segmenter's update; the fused
+// update of ONE learned term is TERM 1 (Diagonal; Potts with a normalisation other than SYMMETRIC is Diagonal(-w, .., -w))
+// or TERM 2 (Matrix), at runtime d.  post: scale the sliced values by norm (SYMMETRIC / AFTER); scale_out: hand the
+// next splat Q * norm (SYMMETRIC / BEFORE, not the last iteration).
+template <bool SEQ, int C, int DP1, int TERM = 0>
 __global__ void __launch_bounds__(256)
 mf_update_kernel(LatticeDev L, const float* __restrict__ values, float alpha, float neg_w, ValueView unary, int negate,
-                 ValueView Q, int scale_out, MfLabels lab) {
+                 ValueView Q, int scale_out, MfLabels lab, const float* __restrict__ compat, int post) {
     extern __shared__ __attribute__((aligned(16))) float tab[];
     if (L.counters[1]) return;   // uniform: hash overflow (flagged)
     constexpr int CP = (C + 3) / 4 * 4;
@@ -2579,98 +2584,52 @@ mf_update_kernel(LatticeDev L, const float* __restrict__ values, float alpha, fl
             tab[r * CP + c] = values[(size_t)(f0 + r) * C + c];
         }
         __syncthreads();
-        mf_points<SEQ, C, DP1, true>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0);
+        mf_points<SEQ, C, DP1, true, TERM>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
     } else {
-        mf_points<SEQ, C, DP1, false>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0);
+        mf_points<SEQ, C, DP1, false, TERM>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
     }
 }
 
-// class counts with a fused softmax_unary / mf_update instantiation (the switch lists below)
-bool mf_fused_supported(int C) { return (C >= 2 && C <= 10) || C == 12 || C == 16 || C == 21; }
+// The class counts with a fused softmax_unary / mf_update instantiation, spelled once: calls
+// f(std::integral_constant<int, C>) and returns true for one of them, returns false for any other C.
+template <typename F>
+static bool with_fused_class_count(int C, F&& f) {
+    switch (C) {
+        case 2: f(std::integral_constant<int, 2>{}); return true;
+        case 3: f(std::integral_constant<int, 3>{}); return true;
+        case 4: f(std::integral_constant<int, 4>{}); return true;
+        case 5: f(std::integral_constant<int, 5>{}); return true;
+        case 6: f(std::integral_constant<int, 6>{}); return true;
+        case 7: f(std::integral_constant<int, 7>{}); return true;
+        case 8: f(std::integral_constant<int, 8>{}); return true;
+        case 9: f(std::integral_constant<int, 9>{}); return true;
+        case 10: f(std::integral_constant<int, 10>{}); return true;
+        case 12: f(std::integral_constant<int, 12>{}); return true;
+        case 16: f(std::integral_constant<int, 16>{}); return true;
+        case 21: f(std::integral_constant<int, 21>{}); return true;
+        default: return false;
+    }
+}
+
+bool mf_fused_supported(int C) { return with_fused_class_count(C, [](auto) {}); }
 
 // returns false when C has no fused instantiation (the caller then runs the unfused kernels)
-bool launch_mf_update(const LatticeDev& L, int C, const float* values, float neg_w, const ValueView& unary, bool negate,
+bool launch_mf_update(const LatticeDev& L, int C, const float* values, const MfTerm& term, const ValueView& unary, bool negate,
                       const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s) {
     const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
     const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
     const dim3 grid((unsigned)(bpf * L.n_frames)), block(256);
-#define RV_MF(SEQ, CC)                                                                                            \
-    if (L.d == 6) mf_update_kernel<SEQ, CC, 7><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, neg_w, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
-    else mf_update_kernel<SEQ, CC, 0><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, neg_w, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
-    RV_LAUNCHED("mf_update_kernel"); \
-    return true
-    switch (C) {
-        case 2: RV_MF(true, 2);
-        case 3: RV_MF(false, 3);
-        case 4: RV_MF(false, 4);
-        case 5: RV_MF(false, 5);
-        case 6: RV_MF(false, 6);
-        case 7: RV_MF(false, 7);
-        case 8: RV_MF(false, 8);
-        case 9: RV_MF(false, 9);
-        case 10: RV_MF(false, 10);
-        case 12: RV_MF(false, 12);
-        case 16: RV_MF(false, 16);
-        case 21: RV_MF(false, 21);
-        default: return false;
-    }
-#undef RV_MF
-}
-
-// The fused update of ONE learned term (Diagonal: TERM 1, Matrix: TERM 2; Potts with a normalisation other than
-// SYMMETRIC is Diagonal(-w, .., -w)): the block structure of mf_update_kernel, runtime d.  post: scale the sliced values
-// by norm (SYMMETRIC / AFTER); scale_out: hand the next splat Q * norm (SYMMETRIC / BEFORE, not the last iteration).
-template <bool SEQ, int C, int TERM>
-__global__ void __launch_bounds__(256)
-mf_update_term_kernel(LatticeDev L, const float* __restrict__ values, float alpha, const float* __restrict__ compat, int post,
-                      ValueView unary, int negate, ValueView Q, int scale_out, MfLabels lab) {
-    extern __shared__ __attribute__((aligned(16))) float tab[];
-    if (L.counters[1]) return;   // uniform: hash overflow (flagged)
-    constexpr int CP = (C + 3) / 4 * 4;
-    const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
-    const int frame = blockIdx.x / bpf;
-    const int i0 = (blockIdx.x - frame * bpf) * MF_PTS + threadIdx.x;
-    const int f0 = L.fstart[frame], f1 = L.fstart[frame + 1];
-    const int Mf = f1 - f0;
-    const bool use_lds = (size_t)Mf * CP * sizeof(float) <= (size_t)MF_LDS_BYTES;   // block-uniform
-    if (use_lds) {
-        for (int idx = threadIdx.x; idx < Mf * C; idx += 256) {
-            const int r = idx / C, c = idx - r * C;
-            tab[r * CP + c] = values[(size_t)(f0 + r) * C + c];
-        }
-        __syncthreads();
-        mf_points<SEQ, C, 0, true, TERM>(L, values, tab, alpha, 0.f, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
-    } else {
-        mf_points<SEQ, C, 0, false, TERM>(L, values, tab, alpha, 0.f, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
-    }
-}
-
-bool launch_mf_update_term(const LatticeDev& L, int C, const float* values, bool matrix, const float* compat, bool post,
-                           const ValueView& unary, bool negate, const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
-    const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
-    const dim3 grid((unsigned)(bpf * L.n_frames)), block(256);
-#define RV_MFT(SEQ, CC)                                                                                            \
-    if (matrix) mf_update_term_kernel<SEQ, CC, 2><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, compat, post ? 1 : 0, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
-    else mf_update_term_kernel<SEQ, CC, 1><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, compat, post ? 1 : 0, unary, negate ? 1 : 0, Q, scale_out ? 1 : 0, lab); \
-    RV_LAUNCHED("mf_update_term_kernel"); \
-    return true
-    switch (C) {
-        case 2: RV_MFT(true, 2);
-        case 3: RV_MFT(false, 3);
-        case 4: RV_MFT(false, 4);
-        case 5: RV_MFT(false, 5);
-        case 6: RV_MFT(false, 6);
-        case 7: RV_MFT(false, 7);
-        case 8: RV_MFT(false, 8);
-        case 9: RV_MFT(false, 9);
-        case 10: RV_MFT(false, 10);
-        case 12: RV_MFT(false, 12);
-        case 16: RV_MFT(false, 16);
-        case 21: RV_MFT(false, 21);
-        default: return false;
-    }
-#undef RV_MFT
+    const int neg = negate ? 1 : 0, so = scale_out ? 1 : 0;
+    const int post = term.post ? 1 : 0;
+    return with_fused_class_count(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        constexpr bool SEQ = CC <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
+        if (!term.compat && L.d == 6) mf_update_kernel<SEQ, CC, 7><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        else if (!term.compat) mf_update_kernel<SEQ, CC, 0><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        else if (term.matrix) mf_update_kernel<SEQ, CC, 0, 2><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        else mf_update_kernel<SEQ, CC, 0, 1><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        RV_LAUNCHED("mf_update_kernel");
+    });
 }
 
 // Q0 = expAndNormalize(-U) straight from the unary (densecrf.cpp:120), one thread per point
@@ -2706,13 +2665,10 @@ softmax_unary_kernel(ValueView unary, int negate, int N, ValueView q, long long 
 bool launch_softmax_unary(const ValueView& unary, bool negate, int C, int N, const ValueView& q, long long n_points,
                           const float* scale, hipStream_t s) {
     const dim3 grid((unsigned)((n_points + 255) / 256)), block(256);
-#define RV_SU(CC) softmax_unary_kernel<CC><<<grid, block, 0, s>>>(unary, negate ? 1 : 0, N, q, n_points, scale); RV_LAUNCHED("softmax_unary_kernel"); return true
-    switch (C) {
-        case 2: RV_SU(2); case 3: RV_SU(3); case 4: RV_SU(4); case 5: RV_SU(5); case 6: RV_SU(6); case 7: RV_SU(7);
-        case 8: RV_SU(8); case 9: RV_SU(9); case 10: RV_SU(10); case 12: RV_SU(12); case 16: RV_SU(16); case 21: RV_SU(21);
-        default: return false;
-    }
-#undef RV_SU
+    return with_fused_class_count(C, [&](auto cc) {
+        softmax_unary_kernel<decltype(cc)::value><<<grid, block, 0, s>>>(unary, negate ? 1 : 0, N, q, n_points, scale);
+        RV_LAUNCHED("softmax_unary_kernel");
+    });
 }
 
 __global__ void __launch_bounds__(256)

@@ -133,20 +133,24 @@ float* launch_blur(const LatticeDev& L, int C, bool seq, bool reverse, float* a,
 // 3: normaliser 1/(sliced + 1e-20) (NORMALIZE_BEFORE / NORMALIZE_AFTER)
 void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const float* values, float neg_w, float* out,
                   long long n_points, hipStream_t s);
-// fused slice + Potts + softmax for a single pairwise kernel; false if C is not instantiated
 // labels of the final marginals straight from the last update (the values are in registers there):
 // labels[(frame * n_layers + layer) * N + point]; labels == nullptr: none
 struct MfLabels {
     int8_t* labels;
     int mode, unknown, n_layers, layer;
 };
+// The compatibility of the one term of a fused update.  compat == nullptr: Potts / uniform Diagonal with
+// NORMALIZE_SYMMETRIC, out = fl(neg_w * (sliced * norm)) (the Segmenter's term).  Else a Diagonal (C floats) or symmetric
+// Matrix (C x C) read from `compat`, the sliced values scaled by norm first when `post`.
+struct MfTerm {
+    float neg_w;
+    const float* compat;
+    bool matrix, post;
+};
 bool mf_fused_supported(int C);
-bool launch_mf_update(const LatticeDev& L, int C, const float* values, float neg_w, const ValueView& unary, bool negate,
+// fused slice + compatibility + unary + softmax for a single pairwise term; false if C is not instantiated
+bool launch_mf_update(const LatticeDev& L, int C, const float* values, const MfTerm& term, const ValueView& unary, bool negate,
                       const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s);
-// fused update of one learned term (Diagonal or symmetric Matrix compatibility, runtime pre / post scales); false if C
-// has no fused instantiation
-bool launch_mf_update_term(const LatticeDev& L, int C, const float* values, bool matrix, const float* compat, bool post,
-                           const ValueView& unary, bool negate, const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s);
 void launch_neg_unary(const ValueView& unary, bool negate, int C, int N, float* tmp, long long n_points, hipStream_t s);
 bool launch_softmax_unary(const ValueView& unary, bool negate, int C, int N, const ValueView& q, long long n_points,
                           const float* scale, hipStream_t s);

@@ -372,17 +372,6 @@ static rvseg_status lattice_counters(rvseg_ctx* ctx, CrfState* cs, const Lattice
     return RVSEG_OK;
 }
 
-// DenseKernel::filter + PottsCompatibility::apply folded into tmp (pairwise.cpp:63-80,173-178)
-static void filter_into(rvseg_ctx* ctx, const LatticeBufs& b, CrfState* cs, const ValueView& Q, int C, float w, float* tmp, hipStream_t s) {
-    const bool seq = C <= 2;  // Permutohedral::compute dispatch, permutohedral.cpp:600-603
-    timer_mark(ctx, "splat", s);
-    launch_splat(b.dev, Q, C, 1, cs->val_a.as<float>(), s);
-    timer_mark(ctx, "blur", s);
-    float* blurred = launch_blur(b.dev, C, seq, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
-    timer_mark(ctx, "slice", s);
-    launch_slice(b.dev, C, seq, 2, blurred, -w, tmp, b.n_points, s);
-}
-
 // per-entry copy of the normaliser for the unfused splat (MODE 1); filled once per lattice
 static rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s) {
     if (b.has_csr_nrm) return RVSEG_OK;
@@ -403,87 +392,8 @@ static rvseg_status csr_nrm_before_fork(rvseg_ctx* ctx, CrfState* cs, int n_laye
     return RVSEG_OK;
 }
 
-// DenseCRF::inference (densecrf.cpp:115-131)
-// `lab` (optional): where the last fused update may write the labels; *labels_done tells whether it did
-// slot: which set of scratch buffers (0 / 1; two layers may run side by side on two streams);
-// timed: record stage marks (only one of two concurrent loops may: the marks are a sequence on ONE stream)
-static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, int n_kernels, const float* ws, const ValueView& unary,
-                               bool unary_is_energy, int C, int N, long long n_points, int iterations,
-                               const ValueView& Q, hipStream_t s, const MfLabels* lab = nullptr, bool* labels_done = nullptr,
-                               int slot = 0, bool timed = true) {
-    if (labels_done) *labels_done = false;
-    rvseg_status st;
-    DevBuf& b_tmp = slot ? cs->tmp2 : cs->tmp;
-    DevBuf& b_qn = slot ? cs->qn2 : cs->qn;
-    DevBuf& b_va = slot ? cs->val_a2 : cs->val_a;
-    DevBuf& b_vb = slot ? cs->val_b2 : cs->val_b;
-    auto mark = [&](const char* name) { if (timed) timer_mark(ctx, name, s); };
-    if ((st = dev_reserve(ctx, b_tmp, (size_t)n_points * C * 4)) != RVSEG_OK) return st;
-    long long mb = 0;
-    for (int k = 0; k < n_kernels; k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
-    if ((st = values_reserve(ctx, cs, mb, C, slot)) != RVSEG_OK) return st;
-    float* tmp = b_tmp.as<float>();
-    // Single Potts kernel with a fused instantiation: between iterations Q holds fl(Q * norm), the
-    // input of the next splat (pairwise.cpp:66), so the splat is a plain gather; only the last
-    // update stores the marginals themselves.
-    bool fused = n_kernels == 1 && iterations > 0;
-    // Where the fused loop keeps fl(Q * norm) between iterations: Q itself when that is one contiguous
-    // [point][C] matrix, else (a layer inside the reference's [layer][y][x][class] frames) a contiguous scratch
-    // matrix -- the splat then addresses a row as point * C without splitting the point index per frame, and
-    // its gathers stay inside one array.  The last update writes the marginals into Q in either case.
-    ValueView Qs = Q;
-    if (fused && !(Q.frame_stride == (size_t)N * (size_t)C && Q.layer_off == 0)) {
-        if ((st = dev_reserve(ctx, b_qn, (size_t)n_points * C * 4)) != RVSEG_OK) return st;
-        Qs = ValueView{b_qn.as<float>(), (size_t)N * (size_t)C, 0};
-    }
-    mark("softmax");
-    if (!launch_softmax_unary(unary, unary_is_energy, C, N, fused ? Qs : Q, n_points, fused ? cs->lat[0].dev.norm : nullptr, s)) {
-        fused = false;
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
-        launch_softmax(tmp, C, N, Q, n_points, s);
-    }
-    if (!fused) {
-        // the general path scales by the normaliser inside the splat: per-entry copy of norm
-        for (int k = 0; k < n_kernels; k++)
-            if ((st = ensure_csr_nrm(ctx, cs->lat[k], s)) != RVSEG_OK) return st;
-    }
-    for (int it = 0; it < iterations; it++) {
-        if (n_kernels == 1) {
-            // single Potts kernel: splat, blur, then one fused slice + update + softmax pass
-            const LatticeBufs& b = cs->lat[0];
-            const bool seq = C <= 2;
-            mark("splat");
-            launch_splat(b.dev, fused ? Qs : Q, C, fused ? 0 : 1, b_va.as<float>(), s, fused, b.resident_on ? &b.resident : nullptr, slot);
-            mark("blur");
-            float* blurred = launch_blur(b.dev, C, seq, false, b_va.as<float>(), b_vb.as<float>(), s);
-            if (fused) {
-                mark("mf_update");
-                const bool last = it + 1 == iterations;
-                MfLabels none{nullptr, 0, 0, 0, 0};
-                launch_mf_update(b.dev, C, blurred, -ws[0], unary, unary_is_energy, last ? Q : Qs, !last, last && lab ? *lab : none, s);
-                if (last && lab && labels_done) *labels_done = true;
-                continue;
-            }
-            mark("softmax");
-            launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
-            mark("slice");
-            launch_slice(b.dev, C, seq, 2, blurred, -ws[0], tmp, n_points, s);
-            mark("softmax");
-            launch_softmax(tmp, C, N, Q, n_points, s);
-            continue;
-        }
-        mark("softmax");
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
-        for (int k = 0; k < n_kernels; k++) filter_into(ctx, cs->lat[k], cs, Q, C, ws[k], tmp, s);
-        mark("softmax");
-        launch_softmax(tmp, C, N, Q, n_points, s);
-    }
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// One pairwise term of a learned model, as the mean field runs it.  Potts, and a Diagonal whose entries are all equal,
-// are the same term (Potts(w) == Diagonal(-w, .., -w) bit for bit).
+// One pairwise term as the mean field runs it.  Potts, and a Diagonal whose entries are all equal, are the same term
+// (Potts(w) == Diagonal(-w, .., -w) bit for bit).
 struct TermPlan {
     int norm = RVSEG_NORMALIZE_SYMMETRIC;
     bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
@@ -491,6 +401,105 @@ struct TermPlan {
     bool matrix = false;
     size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
 };
+
+// the Potts term of the Segmenter and of rvseg_crf_infer[_multi|_device] (pairwise.cpp:173-178): needs no compatibility table
+static TermPlan potts_term(float w) {
+    TermPlan t;
+    t.w = w;
+    return t;
+}
+
+// DenseCRF::inference (densecrf.cpp:115-131) over the terms of `plan`, term k on cs->lat[k]; d_compat: the device copy of
+// the terms' compatibilities (may be null when every term is uniform with NORMALIZE_SYMMETRIC)
+// `lab` (optional): where the last fused update may write the labels; *labels_done tells whether it did
+// slot: which set of scratch buffers (0 / 1; two layers may run side by side on two streams);
+// timed: record stage marks (only one of two concurrent loops may: the marks are a sequence on ONE stream)
+static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<TermPlan>& plan, const float* d_compat,
+                               const ValueView& unary, bool unary_is_energy, int C, int N, long long n_points, int iterations,
+                               const ValueView& Q, hipStream_t s, const MfLabels* lab = nullptr, bool* labels_done = nullptr,
+                               int slot = 0, bool timed = true) {
+    if (labels_done) *labels_done = false;
+    rvseg_status st;
+    const int n_terms = (int)plan.size();
+    DevBuf& b_tmp = slot ? cs->tmp2 : cs->tmp;
+    DevBuf& b_qn = slot ? cs->qn2 : cs->qn;
+    DevBuf& b_va = slot ? cs->val_a2 : cs->val_a;
+    DevBuf& b_vb = slot ? cs->val_b2 : cs->val_b;
+    auto mark = [&](const char* name) { if (timed) timer_mark(ctx, name, s); };
+    // DenseKernel::filter (pairwise.cpp:63-80): the input scaled by the normaliser (SYMMETRIC / BEFORE), the output (SYMMETRIC / AFTER)
+    auto pre = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_BEFORE; };
+    auto post = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_AFTER; };
+    if ((st = dev_reserve(ctx, b_tmp, (size_t)n_points * C * 4)) != RVSEG_OK) return st;
+    long long mb = 0;
+    for (int k = 0; k < n_terms; k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
+    if ((st = values_reserve(ctx, cs, mb, C, slot)) != RVSEG_OK) return st;
+    float* tmp = b_tmp.as<float>();
+    const bool seq = C <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
+    if (n_terms == 1 && iterations > 0 && mf_fused_supported(C)) {
+        // Single term with a fused instantiation: splat, blur, then one fused slice + update + softmax pass.  When the
+        // term pre-scales, Q holds fl(Q * norm) between iterations, the input of the next splat (pairwise.cpp:66), so
+        // the splat is a plain gather; only the last update stores the marginals themselves.
+        const LatticeBufs& b = cs->lat[0];
+        const TermPlan& t = plan[0];
+        // Where the fused loop keeps Q between iterations: Q itself when that is one contiguous
+        // [point][C] matrix, else (a layer inside the reference's [layer][y][x][class] frames) a contiguous scratch
+        // matrix -- the splat then addresses a row as point * C without splitting the point index per frame, and
+        // its gathers stay inside one array.  The last update writes the marginals into Q in either case.
+        ValueView Qs = Q;
+        if (!(Q.frame_stride == (size_t)N * (size_t)C && Q.layer_off == 0)) {
+            if ((st = dev_reserve(ctx, b_qn, (size_t)n_points * C * 4)) != RVSEG_OK) return st;
+            Qs = ValueView{b_qn.as<float>(), (size_t)N * (size_t)C, 0};
+        }
+        const bool potts = t.uniform && t.norm == RVSEG_NORMALIZE_SYMMETRIC;
+        const MfTerm term{-t.w, potts ? nullptr : d_compat + t.off, t.matrix, post(0)};
+        const MfLabels none{nullptr, 0, 0, 0, 0};
+        mark("softmax");
+        launch_softmax_unary(unary, unary_is_energy, C, N, Qs, n_points, pre(0) ? b.dev.norm : nullptr, s);
+        for (int it = 0; it < iterations; it++) {
+            const bool last = it + 1 == iterations;
+            mark("splat");
+            launch_splat(b.dev, Qs, C, 0, b_va.as<float>(), s, true, b.resident_on ? &b.resident : nullptr, slot);
+            mark("blur");
+            float* blurred = launch_blur(b.dev, C, seq, false, b_va.as<float>(), b_vb.as<float>(), s);
+            mark("mf_update");
+            launch_mf_update(b.dev, C, blurred, term, unary, unary_is_energy, last ? Q : Qs, !last && pre(0), last && lab ? *lab : none, s);
+        }
+        if (lab && labels_done) *labels_done = true;
+        RV_LAUNCH_OK(ctx);
+        return RVSEG_OK;
+    }
+    // The general loop: several terms, or a class count without a fused update.
+    mark("softmax");
+    if (!launch_softmax_unary(unary, unary_is_energy, C, N, Q, n_points, nullptr, s)) {
+        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
+        launch_softmax(tmp, C, N, Q, n_points, s);
+    }
+    // it scales by the normaliser inside the splat: per-entry copy of norm
+    for (int k = 0; k < n_terms; k++)
+        if (pre(k) && (st = ensure_csr_nrm(ctx, cs->lat[k], s)) != RVSEG_OK) return st;
+    for (int it = 0; it < iterations; it++) {
+        mark("softmax");
+        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
+        for (int k = 0; k < n_terms; k++) {
+            const LatticeBufs& b = cs->lat[k];
+            const TermPlan& t = plan[k];
+            mark("splat");
+            launch_splat(b.dev, Q, C, pre(k) ? 1 : 0, b_va.as<float>(), s, false, b.resident_on ? &b.resident : nullptr, slot);
+            mark("blur");
+            float* blurred = launch_blur(b.dev, C, seq, false, b_va.as<float>(), b_vb.as<float>(), s);
+            // DenseKernel::filter's output scale + the compatibility folded into tmp (pairwise.cpp:77-80, labelcompatibility.cpp:47-85);
+            // which kernel: DESIGN.md section 4, "Learned models"
+            mark("slice");
+            if (t.uniform && post(k)) launch_slice(b.dev, C, seq, 2, blurred, -t.w, tmp, n_points, s);
+            else launch_term_update(b.dev, C, seq, blurred, post(k), t.matrix, d_compat + t.off, tmp, n_points, s);
+        }
+        mark("softmax");
+        // expAndNormalize(tmp1) with the row in registers where C has an instantiation (same operations, same bits)
+        if (!launch_softmax_unary(ValueView{tmp, (size_t)N * C, 0}, false, C, N, Q, n_points, nullptr, s)) launch_softmax(tmp, C, N, Q, n_points, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
 
 // PottsCompatibility / DiagonalCompatibility / MatrixCompatibility (labelcompatibility.cpp:38-100) as diagonals and
 // symmetric matrices: W = 0.5 * (m + m^T) elementwise in fp32 when the term is created (:79)
@@ -522,79 +531,6 @@ static void plan_terms(int C, int n_terms, const rvseg_crf_term* terms, std::vec
             for (int c = 0; c < C; c++) hc.push_back(-tp.w);
         }
     }
-}
-
-// DenseCRF::inference (densecrf.cpp:115-131) over learned terms.  Models made of Potts terms with NORMALIZE_SYMMETRIC only
-// are the models mean_field() runs: they go there unchanged (fused update for one term).  Every other model takes the
-// general loop: per term, the splat (pre-scaled per entry for SYMMETRIC / BEFORE, a plain gather otherwise), the blur,
-// then term_update_kernel (slice, post-scale for SYMMETRIC / AFTER, compatibility, tmp -= out).  A single term with a fused
-// class count runs fused instead: splat, blur, then mf_update_term_kernel (slice + scales + compatibility + unary +
-// softmax in one pass), with Q holding fl(Q * norm) between iterations when the term pre-scales.
-static rvseg_status mean_field_terms(rvseg_ctx* ctx, CrfState* cs, const std::vector<TermPlan>& plan, const float* d_compat,
-                                     const ValueView& unary, bool unary_is_energy, int C, int N, int iterations, const ValueView& Q,
-                                     hipStream_t s, const MfLabels* lab, bool* labels_done) {
-    const int n_terms = (int)plan.size();
-    bool potts = true;
-    std::vector<float> ws((size_t)n_terms);
-    for (int k = 0; k < n_terms; k++) {
-        potts = potts && plan[k].uniform && plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC;
-        ws[k] = plan[k].w;
-    }
-    if (potts) return mean_field(ctx, cs, n_terms, ws.data(), unary, unary_is_energy, C, N, N, iterations, Q, s, lab, labels_done);
-    if (labels_done) *labels_done = false;
-    rvseg_status st;
-    if ((st = dev_reserve(ctx, cs->tmp, (size_t)N * C * 4)) != RVSEG_OK) return st;
-    long long mb = 0;
-    for (int k = 0; k < n_terms; k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
-    if ((st = values_reserve(ctx, cs, mb, C)) != RVSEG_OK) return st;
-    float* tmp = cs->tmp.as<float>();
-    auto pre = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_BEFORE; };
-    auto post = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_AFTER; };
-    if (n_terms == 1 && iterations > 0 && mf_fused_supported(C) && Q.frame_stride == (size_t)N * C && Q.layer_off == 0) {
-        const LatticeBufs& b = cs->lat[0];
-        timer_mark(ctx, "softmax", s);
-        launch_softmax_unary(unary, unary_is_energy, C, N, Q, N, pre(0) ? b.dev.norm : nullptr, s);
-        for (int it = 0; it < iterations; it++) {
-            const bool last = it + 1 == iterations;
-            timer_mark(ctx, "splat", s);
-            launch_splat(b.dev, Q, C, 0, cs->val_a.as<float>(), s, true, b.resident_on ? &b.resident : nullptr);
-            timer_mark(ctx, "blur", s);
-            float* blurred = launch_blur(b.dev, C, C <= 2, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
-            timer_mark(ctx, "mf_update", s);
-            MfLabels none{nullptr, 0, 0, 0, 0};
-            launch_mf_update_term(b.dev, C, blurred, plan[0].matrix, d_compat + plan[0].off, post(0), unary, unary_is_energy, Q,
-                                  !last && pre(0), last && lab ? *lab : none, s);
-        }
-        if (lab && labels_done) *labels_done = true;
-        RV_LAUNCH_OK(ctx);
-        return RVSEG_OK;
-    }
-    timer_mark(ctx, "softmax", s);
-    if (!launch_softmax_unary(unary, unary_is_energy, C, N, Q, N, nullptr, s)) {
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, N, s);
-        launch_softmax(tmp, C, N, Q, N, s);
-    }
-    for (int k = 0; k < n_terms; k++)
-        if (pre(k) && (st = ensure_csr_nrm(ctx, cs->lat[k], s)) != RVSEG_OK) return st;
-    const bool seq = C <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
-    for (int it = 0; it < iterations; it++) {
-        timer_mark(ctx, "softmax", s);
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, N, s);
-        for (int k = 0; k < n_terms; k++) {
-            const LatticeBufs& b = cs->lat[k];
-            timer_mark(ctx, "splat", s);
-            launch_splat(b.dev, Q, C, pre(k) ? 1 : 0, cs->val_a.as<float>(), s);
-            timer_mark(ctx, "blur", s);
-            float* blurred = launch_blur(b.dev, C, seq, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
-            timer_mark(ctx, "term_update", s);
-            launch_term_update(b.dev, C, seq, blurred, post(k), plan[k].matrix, d_compat + plan[k].off, tmp, N, s);
-        }
-        timer_mark(ctx, "softmax", s);
-        // expAndNormalize(tmp1) with the row in registers where C has an instantiation (same operations, same bits)
-        if (!launch_softmax_unary(ValueView{tmp, (size_t)N * C, 0}, false, C, N, Q, N, nullptr, s)) launch_softmax(tmp, C, N, Q, N, s);
-    }
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
 }
 
 // The label layers of one lattice are independent mean fields (the reference runs one DenseCRF per layer,
@@ -720,7 +656,7 @@ rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, int n, const float* 
         marg = cs->q.as<float>();
     }
     int prefix = 0;
-    const float w = p.dcrf_kernel_weight;
+    const std::vector<TermPlan> plan{potts_term(p.dcrf_kernel_weight)};
     bool all_labelled = true;   // the last fused update of every layer wrote its labels
     hipStream_t s2;
     if ((st = csr_nrm_before_fork(ctx, cs, f.n_layers, f.class_counts, p.dcrf_iterations, s)) != RVSEG_OK) return st;
@@ -739,7 +675,7 @@ rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, int n, const float* 
         MfLabels lab{d_labels, p.label_mode, p.unknown_label[l], f.n_layers, l};
         bool done = false;
         const int slot = l & 1;
-        if ((st = mean_field(ctx, cs, 1, &w, U, false, C, N, (long long)N * n, p.dcrf_iterations, Q, slot ? s2 : s, d_labels ? &lab : nullptr,
+        if ((st = mean_field(ctx, cs, plan, nullptr, U, false, C, N, (long long)N * n, p.dcrf_iterations, Q, slot ? s2 : s, d_labels ? &lab : nullptr,
                              &done, slot, slot == 0 || s2 == s)) != RVSEG_OK) { (void)layer_stream_join(ctx, cs, s, s2); return st; }
         all_labelled = all_labelled && done;
     }
@@ -843,6 +779,7 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
     // marginals of even / odd layers in two halves of cs->q (the odd layers run on the second stream)
     if ((st = dev_reserve(ctx, cs->q, (size_t)N * cmax * 4 * 2)) != RVSEG_OK) return st;
     hipStream_t s2;
+    const std::vector<TermPlan> plan{potts_term(potts_w)};
     if ((st = csr_nrm_before_fork(ctx, cs, n_layers, class_counts, iterations, s)) != RVSEG_OK) return st;
     if ((st = layer_stream_fork(ctx, cs, s, n_layers, &s2)) != RVSEG_OK) return st;
     for (int li = 0; li < n_layers; li++) {
@@ -858,7 +795,7 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
         MfLabels lab{d_labels ? d_labels + (size_t)l * N : nullptr, label_mode, unknown[l], 1, 0};
         bool done = false;
         // crf.setUnaryEnergy(-unaries[l]) (segmenter.cpp:642): the accumulated posteriors ARE -energy
-        if ((st = mean_field(ctx, cs, 1, &potts_w, U, false, C, N, N, iterations, Q, sl, d_labels ? &lab : nullptr, &done, slot,
+        if ((st = mean_field(ctx, cs, plan, nullptr, U, false, C, N, N, iterations, Q, sl, d_labels ? &lab : nullptr, &done, slot,
                              slot == 0 || s2 == s)) != RVSEG_OK) { (void)layer_stream_join(ctx, cs, s, s2); return st; }
         if (d_labels && !done) {
             if (slot == 0 || s2 == s) timer_mark(ctx, "labels", sl);
@@ -924,8 +861,10 @@ rvseg_status rvseg_crf_infer_multi(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
     if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
     RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_energy, tot * 4, hipMemcpyHostToDevice, s));
     ValueView U{cs->unary.as<float>(), tot, 0}, Q{cs->q.as<float>(), tot, 0};
+    std::vector<TermPlan> plan;
+    for (int k = 0; k < n_kernels; k++) plan.push_back(potts_term(ws[k]));
     timer_reset(ctx);
-    if ((st = mean_field(ctx, cs, n_kernels, ws, U, true, C, N, N, iterations, Q, s)) != RVSEG_OK) return st;
+    if ((st = mean_field(ctx, cs, plan, nullptr, U, true, C, N, N, iterations, Q, s)) != RVSEG_OK) return st;
     timer_mark(ctx, "end", s);
     RV_HIP(ctx, hipMemcpyAsync(Q_out, cs->q.p, tot * 4, hipMemcpyDeviceToHost, s));
     if (map_out) {
@@ -971,7 +910,7 @@ rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
     RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_energy, tot * 4, hipMemcpyHostToDevice, s));
     ValueView U{cs->unary.as<float>(), tot, 0}, Q{cs->q.as<float>(), tot, 0};
     timer_reset(ctx);
-    if ((st = mean_field_terms(ctx, cs, plan, cs->compat.as<float>(), U, true, C, N, iterations, Q, s, nullptr, nullptr)) != RVSEG_OK) return st;
+    if ((st = mean_field(ctx, cs, plan, cs->compat.as<float>(), U, true, C, N, N, iterations, Q, s)) != RVSEG_OK) return st;
     timer_mark(ctx, "end", s);
     RV_HIP(ctx, hipMemcpyAsync(Q_out, cs->q.p, tot * 4, hipMemcpyDeviceToHost, s));
     if (map_out) {
@@ -1009,8 +948,8 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
     ValueView U{const_cast<float*>(d_unary), (size_t)N * C, 0}, Q{q, (size_t)N * C, 0};
     MfLabels lab{d_map_out, label_mode, unknown_label, 1, 0};
     bool done = false;
-    if ((st = mean_field_terms(ctx, cs, plan, cs->compat.as<float>(), U, unary_is_energy != 0, C, N, iterations, Q, s,
-                               d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
+    if ((st = mean_field(ctx, cs, plan, cs->compat.as<float>(), U, unary_is_energy != 0, C, N, N, iterations, Q, s,
+                         d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
     if (d_map_out && !done) {
         timer_mark(ctx, "labels", s);
         launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map_out, s);
@@ -1085,7 +1024,8 @@ rvseg_status rvseg_crf_infer_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_
     ValueView U{const_cast<float*>(d_unary), (size_t)N * C, 0}, Q{q, (size_t)N * C, 0};
     MfLabels lab{d_map_out, label_mode, unknown_label, 1, 0};
     bool done = false;
-    if ((st = mean_field(ctx, cs, 1, &potts_w, U, unary_is_energy != 0, C, N, N, iterations, Q, s, d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
+    const std::vector<TermPlan> plan{potts_term(potts_w)};
+    if ((st = mean_field(ctx, cs, plan, nullptr, U, unary_is_energy != 0, C, N, N, iterations, Q, s, d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
     if (d_map_out && !done) {
         timer_mark(ctx, "labels", s);
         launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map_out, s);
