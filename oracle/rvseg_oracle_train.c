@@ -33,8 +33,10 @@
  *      :220-258) is the same quantity plus a rounding drift that depends on the unspecified order of equal keys.
  *   3. Bootstrap duplicates are kept as one example with a multiplicity (the reference stores copies: adjacent equal
  *      values, which never yield a cut, :578-585).
- *   4. threshold = (left + right) * 0.5f (:592,607); if that rounds down to `left` (adjacent floats) the threshold is
- *      `right`, so that `x < threshold` still separates the two (the reference would write past its child lists).
+ *   4. threshold = (left + right) * 0.5f (:592,607); if that does not satisfy left < threshold <= right the threshold is
+ *      `right`, so that `x < threshold` still separates the two (the reference would write past its child lists).  Two
+ *      ways to get there: adjacent floats, where the midpoint rounds down to `left`; and finite values near +-3e38 whose
+ *      sum overflows, where the "midpoint" is +-inf and every example would go to one child.
  */
 #include <math.h>
 #include <stdint.h>
@@ -198,7 +200,7 @@ int orc_forest_train(const float *X, int P, int D, const int32_t *labels, int n_
             }
             float thr = best_left_v + best_right_v;   /* :592 */
             thr *= 0.5f;                              /* :607 */
-            if (best_feature >= 0 && !(best_left_v < thr)) thr = best_right_v;
+            if (best_feature >= 0 && !(best_left_v < thr && thr <= best_right_v)) thr = best_right_v;
             if (best_feature < 0 || best_lm < min_child_split_examples || best_rm < min_child_split_examples) { free(ex); continue; }   /* :610-617 */
             int nl = 0;
             for (int m = 0; m < n; m++) nl += X[(size_t)ex[m] * D + best_feature] < thr ? 1 : 0;

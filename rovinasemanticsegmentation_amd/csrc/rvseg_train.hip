@@ -31,7 +31,7 @@
 // byte for byte.  Both sides implement the same build-owned definitions, written down in that file's header: random
 // choices from a counter-based generator keyed by (seed, tree, node path); the objective evaluated from the class counts
 // by the expression of initEntropies (learning.cpp:279-293) with fastlog2 (fastlog.h:47-58), in float, classes in
-// ascending order; bootstrap duplicates as multiplicities; the adjacent-floats threshold guard.
+// ascending order; bootstrap duplicates as multiplicities; the threshold guard (adjacent floats, overflowing sums).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -597,7 +597,8 @@ rvseg_status train_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_par
                     const int f = slot_feat[(size_t)q * K + best_k];
                     float th = c.left_value + c.right_value;                                    // :592
                     th *= 0.5f;                                                                 // :607
-                    if (!(c.left_value < th)) th = c.right_value;   // two adjacent floats: keep `x < th` separating them
+                    // adjacent floats (th rounds to left) or an overflowing sum (th = +-inf): keep `x < th` separating the two
+                    if (!(c.left_value < th && th <= c.right_value)) th = c.right_value;
                     const int lc = (int)left.size();
                     for (int side = 0; side < 2; side++) {                                      // DecisionTree::splitNode, classifier.cpp:77-95
                         feat.push_back(0); thr.push_back(0.f); left.push_back(0); depth.push_back(depth[node] + 1);

@@ -44,3 +44,21 @@ def test_projector_stand_in_is_a_zbuffer():
     assert idx[24, 32] == 0                      # the nearer of the two points on the optical axis
     assert (idx == 1).sum() == 0
     assert (idx == 2).sum() == 1 and np.argwhere(idx == 2)[0][1] < 32   # +y (left of the camera) lands left of centre
+
+
+def test_chain_recipe_depends_on_the_order_of_its_additions(oracle):
+    """The recipe of test_gpu_fusion_limits.py's longest run (every pixel of 6 images on one point: 115 200 additions per
+    class): the oracle's front-to-back sum differs from the same hits summed back to front and from numpy's pairwise
+    sum, so a fusion that reorders the chain cannot pass the bit-for-bit comparison."""
+    import fusion_cases as fc
+    idx, post, cc, P = fc.chain()
+    n, H, W = idx.shape
+    assert n * H * W == 115200 and np.all(idx == 1)
+    got = oracle.fuse_posteriors(idx, post, cc, P).reshape(P, sum(cc))
+    hits = post.reshape(n * H * W, sum(cc))                         # one layer: [pixel][class] per image, images in order
+    for c in range(sum(cc)):
+        col = np.ascontiguousarray(hits[:, c])
+        assert got[1, c] == np.cumsum(col, dtype=np.float32)[-1]   # front to back
+        assert got[1, c] != np.cumsum(col[::-1], dtype=np.float32)[-1]
+        assert got[1, c] != col.sum(dtype=np.float32)               # pairwise
+    assert np.all(got[[0, 2]] == 0)
