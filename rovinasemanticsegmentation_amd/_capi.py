@@ -188,6 +188,9 @@ def lib():
     L.rvseg_crf_infer_terms_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, i32, vp, vp, i32, i32, vp]
     L.rvseg_crf_logistic_unary.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.rvseg_crf_logistic_unary_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
+    L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
+    L.rvseg_debug_live_resources.restype = None
     for name in SYMBOLS:
         getattr(L, name)  # raises AttributeError if the library does not export it
     _lib = L
@@ -256,6 +259,14 @@ def crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im):
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return out
+
+
+def debug_live_resources():
+    """Owning handles alive in this process, over all contexts: the library's own device buffers, pinned host buffers,
+    events and streams.  A context that has been closed leaves all four where they were before it was created."""
+    out = (C.c_longlong * 4)()
+    lib().rvseg_debug_live_resources(out)
+    return dict(zip(("device_buffers", "pinned_buffers", "events", "streams"), out))
 
 
 def crf_terms_check(N, Cn, terms):

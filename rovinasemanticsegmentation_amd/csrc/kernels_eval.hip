@@ -244,7 +244,7 @@ struct EvalState {
     DevBuf tables;     // EvalTable[RVSEG_MAX_LAYERS]
     DevBuf counts;     // uint64: [RVSEG_MAX_LAYERS][64 * 64], then [RVSEG_MAX_LAYERS] out of range
     DevBuf stage_a, stage_b;   // host entry points
-    std::vector<std::pair<hipStream_t, hipEvent_t>> pending;   // last event recorded per caller stream
+    std::vector<std::pair<hipStream_t, Event>> pending;   // last event recorded per caller stream
 };
 
 constexpr size_t kCountWords = (size_t)RVSEG_MAX_LAYERS * kMaxEvalClasses * kMaxEvalClasses + RVSEG_MAX_LAYERS;
@@ -252,12 +252,7 @@ constexpr size_t kCountWords = (size_t)RVSEG_MAX_LAYERS * kMaxEvalClasses * kMax
 void eval_destroy(rvseg_ctx* ctx) {
     EvalState* e = ctx->eval;
     if (!e) return;
-    for (auto& pe : e->pending) (void)hipEventSynchronize(pe.second);
-    for (auto& pe : e->pending) (void)hipEventDestroy(pe.second);
-    dev_free(e->tables);
-    dev_free(e->counts);
-    dev_free(e->stage_a);
-    dev_free(e->stage_b);
+    for (auto& pe : e->pending) (void)hipEventSynchronize(pe.second);   // before the events and the tables go
     delete e;
     ctx->eval = nullptr;
 }
@@ -271,16 +266,15 @@ rvseg_status eval_state(rvseg_ctx* ctx, EvalState** out) {
     }
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     if (!ctx->eval) {
-        EvalState* e = new EvalState();
+        // tables and zeroed counters first: a failure leaves nothing behind and the next call tries again
+        DevBuf tables, counts;
         rvseg_status st;
-        if ((st = dev_alloc(ctx, e->tables, sizeof(EvalTable) * RVSEG_MAX_LAYERS)) != RVSEG_OK ||
-            (st = dev_alloc(ctx, e->counts, kCountWords * sizeof(uint64_t))) != RVSEG_OK) {
-            dev_free(e->tables);
-            delete e;
-            return st;
-        }
-        ctx->eval = e;
-        if (!hip_ok(ctx, hipMemset(e->counts.p, 0, kCountWords * sizeof(uint64_t)), "hipMemset eval counters")) return RVSEG_ERR_HIP;
+        if ((st = dev_alloc(ctx, tables, sizeof(EvalTable) * RVSEG_MAX_LAYERS)) != RVSEG_OK) return st;
+        if ((st = dev_alloc(ctx, counts, kCountWords * sizeof(uint64_t))) != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemset(counts.p, 0, kCountWords * sizeof(uint64_t)));
+        ctx->eval = new EvalState();
+        ctx->eval->tables = std::move(tables);
+        ctx->eval->counts = std::move(counts);
     }
     *out = ctx->eval;
     return RVSEG_OK;
@@ -294,10 +288,10 @@ rvseg_status wait_pending(rvseg_ctx* ctx, EvalState* e) {
 rvseg_status record_pending(rvseg_ctx* ctx, EvalState* e, hipStream_t s) {
     for (auto& pe : e->pending)
         if (pe.first == s) { RV_HIP(ctx, hipEventRecord(pe.second, s)); return RVSEG_OK; }
-    hipEvent_t ev;
-    RV_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->pending.emplace_back(s, ev);
-    RV_HIP(ctx, hipEventRecord(ev, s));
+    Event ev;
+    RV_HIP(ctx, event_create(ev, hipEventDisableTiming));
+    e->pending.emplace_back(s, std::move(ev));
+    RV_HIP(ctx, hipEventRecord(e->pending.back().second, s));
     return RVSEG_OK;
 }
 

@@ -37,16 +37,19 @@ rvseg_status launch_error_take(rvseg_ctx* ctx) {
     return RVSEG_ERR_HIP;
 }
 
+std::atomic<long long> g_live[4];
+
 rvseg_status dev_alloc(rvseg_ctx* ctx, DevBuf& b, size_t bytes) {
     dev_free(b);
     if (bytes == 0) bytes = 16;
     RV_HIP(ctx, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    g_live[LIVE_DEVICE]++;
     return RVSEG_OK;
 }
 
-void dev_free(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
+void dev_free(DevBuf& b) {   // the one release of a DevBuf: its destructor and its move assignment come here too
+    if (b.p) { (void)hipFree(b.p); g_live[LIVE_DEVICE]--; }
     b.p = nullptr;
     b.bytes = 0;
 }
@@ -54,6 +57,32 @@ void dev_free(DevBuf& b) {
 rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return RVSEG_OK;
     return dev_alloc(ctx, b, bytes);
+}
+
+rvseg_status PinnedBuf::reserve(rvseg_ctx* ctx, size_t n) {
+    if (bytes >= n && p) return RVSEG_OK;
+    release();
+    RV_HIP(ctx, hipHostMalloc(&p, n, hipHostMallocDefault));
+    bytes = n;
+    g_live[LIVE_PINNED]++;
+    return RVSEG_OK;
+}
+
+void PinnedBuf::release() {
+    if (p) { (void)hipHostFree(p); g_live[LIVE_PINNED]--; }
+    p = nullptr;
+    bytes = 0;
+}
+
+// creation into an empty handle: counted when the HIP call succeeded, left empty when it failed
+template <class T> static hipError_t created(T& into, hipError_t r, LiveKind k) {
+    if (r == hipSuccess) g_live[k]++; else into.h = nullptr;
+    return r;
+}
+hipError_t event_create(Event& e, unsigned flags) { return created(e, hipEventCreateWithFlags(&e.h, flags), LIVE_EVENT); }
+hipError_t stream_create(Stream& s, unsigned flags) { return created(s, hipStreamCreateWithFlags(&s.h, flags), LIVE_STREAM); }
+hipError_t stream_create(Stream& s, unsigned flags, int priority) {
+    return created(s, hipStreamCreateWithPriority(&s.h, flags, priority), LIVE_STREAM);
 }
 
 // ---- Lab tables: OpenCV 2.4 RGB2Lab_b constants (imgproc/color.cpp), see DESIGN.md ------------
@@ -305,7 +334,7 @@ rvseg_status rvseg_create(const rvseg_params* params, rvseg_ctx** out) {
     ctx->params = p;
     rvseg_schedule_default(&ctx->sched);
     ctx->feature_length = feature_length_of(p);
-    if (!hip_ok(nullptr, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    if (!hip_ok(nullptr, stream_create(ctx->stream, hipStreamNonBlocking), "hipStreamCreate")) {
         delete ctx;
         return RVSEG_ERR_HIP;
     }
@@ -334,18 +363,12 @@ void rvseg_destroy(rvseg_ctx* ctx) {
     rvseg_comm_destroy(ctx);
     rvseg_pipeline_destroy(ctx);
     eval_destroy(ctx);
-    dev_free(ctx->forest.nodes);
-    dev_free(ctx->forest.nodes8);
-    dev_free(ctx->forest.roots);
-    dev_free(ctx->forest.hist);
-    dev_free(ctx->lab.gamma);
-    dev_free(ctx->lab.cbrt);
-    for (auto& b : ctx->pool) dev_free(b);
-    for (auto ev : ctx->timer.events) (void)hipEventDestroy(ev);
-    if (ctx->timer.side0) (void)hipEventDestroy(ctx->timer.side0);
-    if (ctx->timer.side1) (void)hipEventDestroy(ctx->timer.side1);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // forest, Lab tables, the timer's events, the stream: the members' destructors
+}
+
+// debug (not in rvseg.h): handles alive in this process: device buffers, pinned buffers, events, streams
+void rvseg_debug_live_resources(long long out[4]) {
+    for (int k = 0; k < 4; k++) out[k] = g_live[k];
 }
 
 int32_t rvseg_feature_length(const rvseg_ctx* ctx) { return ctx ? ctx->feature_length : 0; }
@@ -445,22 +468,17 @@ rvseg_status rvseg_forest_eval(rvseg_ctx* ctx, const float* X, int32_t P, int32_
     if (D != ctx->feature_length) { ctx->err = "D does not match the configured feature length"; return RVSEG_ERR_INVALID_ARG; }
     if (P == 0) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    DevBuf dX, dO;
+    DevBuf dX, dO;   // freed on every return (hipFree waits for the device)
     rvseg_status st;
     const size_t S = (size_t)ctx->forest.sum_classes;
     if ((st = dev_alloc(ctx, dX, (size_t)P * D * sizeof(float))) != RVSEG_OK) return st;
-    if ((st = dev_alloc(ctx, dO, (size_t)P * S * sizeof(float))) != RVSEG_OK) { dev_free(dX); return st; }
-    rvseg_status rc = RVSEG_OK;
-    do {
-        if (!hip_ok(ctx, hipMemcpyAsync(dX.p, X, (size_t)P * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D X")) { rc = RVSEG_ERR_HIP; break; }
-        launch_forest_eval(ctx->forest, dX.as<float>(), P, D, dO.as<float>(), ctx->stream);
-        if (launch_error_take(ctx) != RVSEG_OK) { rc = RVSEG_ERR_HIP; break; }
-        if (!hip_ok(ctx, hipMemcpyAsync(out, dO.p, (size_t)P * S * sizeof(float), hipMemcpyDeviceToHost, ctx->stream), "D2H out")) { rc = RVSEG_ERR_HIP; break; }
-        if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) { rc = RVSEG_ERR_HIP; break; }
-    } while (0);
-    dev_free(dX);
-    dev_free(dO);
-    return rc;
+    if ((st = dev_alloc(ctx, dO, (size_t)P * S * sizeof(float))) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(dX.p, X, (size_t)P * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    launch_forest_eval(ctx->forest, dX.as<float>(), P, D, dO.as<float>(), ctx->stream);
+    RV_LAUNCH_OK(ctx);
+    RV_HIP(ctx, hipMemcpyAsync(out, dO.p, (size_t)P * S * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RVSEG_OK;
 }
 
 // DenseCRF2D::addPairwiseGaussian / addPairwiseBilateral (densecrf.cpp:61-81): the feature matrices they

@@ -27,19 +27,20 @@ struct LatticeBufs {
 
 struct CrfState {
     std::vector<LatticeBufs> lat;  // one per pairwise kernel
-    // slot 1 of the scratch buffers: a second label layer's mean field runs beside the first on its own stream
-    DevBuf val_a, val_b, tmp, q, qn, unary, feat, labels, val_a2, val_b2, tmp2, qn2;
+    // two slots of mean-field scratch: a second label layer's mean field runs beside the first on its own stream
+    struct { DevBuf val_a, val_b, tmp, qn; } scratch[2];
+    DevBuf q, unary, feat, labels;
     // learned-model terms (rvseg_crf_infer_terms*): compatibilities of all terms, transformed features, logistic L
     DevBuf compat, kfeat, lmat;
     std::vector<float> h_compat;   // host copy of `compat` (the source of its asynchronous upload)
-    hipStream_t layer_stream = nullptr;       // the second layer's stream
-    hipEvent_t layer_fork = nullptr, layer_join = nullptr;
+    Stream layer_stream;   // the second layer's stream; created together with its two events (second_stream)
+    Event layer_fork, layer_join;
     // pinned read-back of a build: [0] M, [1] overflow, [2] longest vertex list, [3] frames the splat planner gave up on.
     // Slot 0 (words 0..3) belongs to the asynchronous frame builds (consumed by crf_frames_status), slot 1 (words 4..7)
     // to the synchronous entry points -- a cloud or host CRF call on the same context must not overwrite a frame
     // build's status that nobody has polled yet.
-    int* h_counters = nullptr;
-    hipEvent_t counters_ev = nullptr;
+    PinnedBuf h_counters;   // int[8]
+    Event counters_ev;
     bool counters_pending = false;
     rvseg_schedule_info info{};    // what the last build ran with (rvseg_last_schedule)
     int frame_vertices_seen = 0;   // vertices per frame of the last frame build whose status was read (0: none yet)
@@ -47,42 +48,26 @@ struct CrfState {
     bool info_async = false;       // info.vertices / planner_fallback still travel with the pending frame-build status
 };
 
-static rvseg_status crf_state(rvseg_ctx* ctx, Pipeline* im, CrfState** out) {
+// the context's CRF state, created by the first call: the pinned counters and their event first, so that a failure
+// leaves nothing behind and the next call tries again
+static rvseg_status crf_state(rvseg_ctx* ctx, CrfState** out) {
+    Pipeline* im = pipeline_of(ctx);
     if (!im->crf) {
-        CrfState* cs = new CrfState();
-        if (!hip_ok(ctx, hipHostMalloc((void**)&cs->h_counters, 8 * sizeof(int), hipHostMallocDefault), "hipHostMalloc(counters)") ||
-            !hip_ok(ctx, hipEventCreateWithFlags(&cs->counters_ev, hipEventDisableTiming), "hipEventCreate(counters)")) {
-            if (cs->h_counters) (void)hipHostFree(cs->h_counters);
-            delete cs;
-            return RVSEG_ERR_HIP;
-        }
-        for (int i = 0; i < 8; i++) cs->h_counters[i] = 0;
-        im->crf = cs;
+        PinnedBuf h;
+        Event ev;
+        rvseg_status st = h.reserve(ctx, 8 * sizeof(int));
+        if (st != RVSEG_OK) return st;
+        RV_HIP(ctx, event_create(ev, hipEventDisableTiming));
+        std::memset(h.p, 0, 8 * sizeof(int));
+        im->crf = new CrfState();
+        im->crf->h_counters = std::move(h);
+        im->crf->counters_ev = std::move(ev);
     }
     *out = im->crf;
     return RVSEG_OK;
 }
 
-static void lattice_free(LatticeBufs& b) {
-    DevBuf* all[] = {&b.state, &b.tkeys, &b.slot_to_id, &b.counters, &b.vkeys, &b.offsets, &b.bary, &b.nb1, &b.nb2,
-                     &b.csr_pw, &b.csr_nrm, &b.vstart, &b.vend, &b.norm, &b.keys_in, &b.keys_out, &b.vals_in,
-                     &b.vals_out, &b.sort_temp, &b.scan_temp, &b.fstart, &b.vorder, &b.block_hist,
-                     &b.r_desc, &b.r_vl, &b.r_info, &b.r_small, &b.r_verts, &b.r_jb, &b.r_trace};
-    for (DevBuf* x : all) dev_free(*x);
-}
-
-void crf_state_free(Pipeline* im) {
-    if (!im->crf) return;
-    for (auto& l : im->crf->lat) lattice_free(l);
-    DevBuf* all[] = {&im->crf->val_a, &im->crf->val_b, &im->crf->tmp, &im->crf->q, &im->crf->qn, &im->crf->unary, &im->crf->feat, &im->crf->labels,
-                     &im->crf->val_a2, &im->crf->val_b2, &im->crf->tmp2, &im->crf->qn2, &im->crf->compat, &im->crf->kfeat,
-                     &im->crf->lmat};
-    if (im->crf->layer_stream) (void)hipStreamDestroy(im->crf->layer_stream);
-    if (im->crf->layer_fork) (void)hipEventDestroy(im->crf->layer_fork);
-    if (im->crf->layer_join) (void)hipEventDestroy(im->crf->layer_join);
-    for (DevBuf* x : all) dev_free(*x);
-    if (im->crf->h_counters) (void)hipHostFree(im->crf->h_counters);
-    if (im->crf->counters_ev) (void)hipEventDestroy(im->crf->counters_ev);
+void crf_state_free(Pipeline* im) {   // the one delete of a CrfState
     delete im->crf;
     im->crf = nullptr;
 }
@@ -101,7 +86,7 @@ static int capacity_log2_per_frame(const rvseg_ctx* ctx, int Npad, int d, bool s
     int want = ctx->params.lattice_capacity_log2;
     if (safe || want < 0) return safe_log2;
     if (want == 0) want = 12;   // the Segmenter kernel yields ~300 vertices per synthetic 640x480 frame
-    if (ctx->impl) want += reinterpret_cast<const Pipeline*>(ctx->impl)->cap_boost;
+    if (ctx->impl) want += ctx->impl->cap_boost;
     return want < safe_log2 ? want : safe_log2;
 }
 
@@ -261,8 +246,8 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
 
 static rvseg_status values_reserve(rvseg_ctx* ctx, CrfState* cs, long long m_bound, int C, int slot = 0) {
     rvseg_status st;
-    if ((st = dev_reserve(ctx, slot ? cs->val_a2 : cs->val_a, (size_t)m_bound * C * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, slot ? cs->val_b2 : cs->val_b, (size_t)m_bound * C * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->scratch[slot].val_a, (size_t)m_bound * C * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->scratch[slot].val_b, (size_t)m_bound * C * 4)) != RVSEG_OK) return st;
     return RVSEG_OK;
 }
 
@@ -271,9 +256,14 @@ static rvseg_status second_stream(rvseg_ctx* ctx, CrfState* cs) {
     if (cs->layer_stream) return RVSEG_OK;
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    RV_HIP(ctx, hipStreamCreateWithPriority(&cs->layer_stream, hipStreamNonBlocking, prio_hi));
-    RV_HIP(ctx, hipEventCreateWithFlags(&cs->layer_fork, hipEventDisableTiming));
-    RV_HIP(ctx, hipEventCreateWithFlags(&cs->layer_join, hipEventDisableTiming));
+    Stream stream;
+    Event fork, join;
+    RV_HIP(ctx, stream_create(stream, hipStreamNonBlocking, prio_hi));
+    RV_HIP(ctx, event_create(fork, hipEventDisableTiming));
+    RV_HIP(ctx, event_create(join, hipEventDisableTiming));
+    cs->layer_stream = std::move(stream);
+    cs->layer_fork = std::move(fork);
+    cs->layer_join = std::move(join);
     return RVSEG_OK;
 }
 
@@ -324,8 +314,8 @@ static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, 
     // norm = lattice.compute(ones) through seqCompute (1 row), then 1/sqrt(norm + 1e-20) (or 1/(norm + 1e-20))
     if (norm_kind != RVSEG_NO_NORMALIZATION) {
         ValueView none{nullptr, 0, 0};
-        launch_splat(L, none, 1, 2, cs->val_a.as<float>(), s);
-        float* blurred = launch_blur(L, 1, true, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s, true);
+        launch_splat(L, none, 1, 2, cs->scratch[0].val_a.as<float>(), s);
+        float* blurred = launch_blur(L, 1, true, false, cs->scratch[0].val_a.as<float>(), cs->scratch[0].val_b.as<float>(), s, true);
         launch_slice(L, 1, true, norm_kind == RVSEG_NORMALIZE_SYMMETRIC ? 1 : 3, blurred, 0.f, L.norm, b.n_points, s);
         tr("normaliser");
     }
@@ -350,7 +340,7 @@ static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, 
 // enqueues the read-back of a build's counters (+ the planner's flag) into pinned slot `slot` (0: async frame builds,
 // 1: synchronous entry points)
 static rvseg_status counters_readback(rvseg_ctx* ctx, CrfState* cs, const LatticeBufs& b, int slot, hipStream_t s) {
-    int* h = cs->h_counters + 4 * slot;
+    int* h = cs->h_counters.as<int>() + 4 * slot;
     RV_HIP(ctx, hipMemcpyAsync(h, b.dev.counters, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     RV_HIP(ctx, hipMemcpyAsync(h + 2, b.dev.counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
     if (b.resident_on) RV_HIP(ctx, hipMemcpyAsync(h + 3, b.resident.flags, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -363,7 +353,7 @@ static rvseg_status lattice_counters(rvseg_ctx* ctx, CrfState* cs, const Lattice
     rvseg_status st = counters_readback(ctx, cs, b, 1, s);
     if (st != RVSEG_OK) return st;
     RV_HIP(ctx, hipStreamSynchronize(s));
-    const int* h = cs->h_counters + 4;
+    const int* h = cs->h_counters.as<int>() + 4;
     out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
     cs->info.vertices = h[0];
     cs->info.longest_list = h[2];
@@ -421,10 +411,7 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<T
     if (labels_done) *labels_done = false;
     rvseg_status st;
     const int n_terms = (int)plan.size();
-    DevBuf& b_tmp = slot ? cs->tmp2 : cs->tmp;
-    DevBuf& b_qn = slot ? cs->qn2 : cs->qn;
-    DevBuf& b_va = slot ? cs->val_a2 : cs->val_a;
-    DevBuf& b_vb = slot ? cs->val_b2 : cs->val_b;
+    DevBuf &b_tmp = cs->scratch[slot].tmp, &b_qn = cs->scratch[slot].qn, &b_va = cs->scratch[slot].val_a, &b_vb = cs->scratch[slot].val_b;
     auto mark = [&](const char* name) { if (timed) timer_mark(ctx, name, s); };
     // DenseKernel::filter (pairwise.cpp:63-80): the input scaled by the normaliser (SYMMETRIC / BEFORE), the output (SYMMETRIC / AFTER)
     auto pre = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_BEFORE; };
@@ -575,14 +562,15 @@ rvseg_status crf_frames_status(rvseg_ctx* ctx, Pipeline* im, bool wait) {
         RV_HIP(ctx, e);
     }
     cs->counters_pending = false;
-    if (cs->pending_frames > 0 && !cs->h_counters[1]) cs->frame_vertices_seen = cs->h_counters[0] / cs->pending_frames;
+    const int* h = cs->h_counters.as<int>();
+    if (cs->pending_frames > 0 && !h[1]) cs->frame_vertices_seen = h[0] / cs->pending_frames;
     if (cs->info_async) {   // no other lattice has been built on this context since
-        cs->info.vertices = cs->h_counters[0];
-        cs->info.longest_list = cs->h_counters[2];
-        cs->info.planner_fallback = cs->h_counters[3];
+        cs->info.vertices = h[0];
+        cs->info.longest_list = h[2];
+        cs->info.planner_fallback = h[3];
         cs->info_async = false;
     }
-    if (cs->h_counters[1]) {
+    if (h[1]) {
         const FrameGeom& g = im->geom;
         const bool was_worst = capacity_is_worst_case(ctx, g.W * g.H, 6);
         // x8 slots per step, but stop at 2^13 on the way up: the largest capacity the counting-sort CSR path serves
@@ -605,7 +593,7 @@ rvseg_status crf_frames_status(rvseg_ctx* ctx, Pipeline* im, bool wait) {
 // (40 us of a single frame's 2 ms).  `s` must already be ordered behind the previous user of the lattice.
 rvseg_status crf_frames_build_begin(rvseg_ctx* ctx, Pipeline* im, int n, hipStream_t s) {
     CrfState* cs;
-    rvseg_status st = crf_state(ctx, im, &cs);
+    rvseg_status st = crf_state(ctx, &cs);
     if (st != RVSEG_OK) return st;
     const FrameGeom& g = im->geom;
     const int N = g.W * g.H;
@@ -620,7 +608,7 @@ rvseg_status crf_frames_build_begin(rvseg_ctx* ctx, Pipeline* im, int n, hipStre
 
 rvseg_status crf_frames_build(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t* d_rgb, hipStream_t s) {
     CrfState* cs;
-    rvseg_status st = crf_state(ctx, im, &cs);
+    rvseg_status st = crf_state(ctx, &cs);
     if (st != RVSEG_OK) return st;
     const rvseg_params& p = ctx->params;
     if (cs->lat.size() < 1 || !cs->lat[0].cleared) {
@@ -642,7 +630,7 @@ rvseg_status crf_frames_build(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
 rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, int n, const float* d_post, float* d_marg, int8_t* d_labels,
                               hipStream_t s) {
     CrfState* cs;
-    rvseg_status st0 = crf_state(ctx, im, &cs);
+    rvseg_status st0 = crf_state(ctx, &cs);
     if (st0 != RVSEG_OK) return st0;
     const FrameGeom& g = im->geom;
     const rvseg_params& p = ctx->params;
@@ -755,21 +743,11 @@ static rvseg_status upload_terms(rvseg_ctx* ctx, CrfState* cs, int C, int n_term
     return RVSEG_OK;
 }
 
-static rvseg_status crf_bare_state(rvseg_ctx* ctx, Pipeline** im_out, CrfState** cs_out) {
-    if (!ctx->impl) {
-        Pipeline* im = new Pipeline();
-        ctx->impl = reinterpret_cast<rvseg_ctx::Impl*>(im);
-        im->bare = true;
-    }
-    *im_out = reinterpret_cast<Pipeline*>(ctx->impl);
-    return crf_state(ctx, *im_out, cs_out);
-}
-
 rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* class_counts, const float* d_unaries,
                               const float* d_features, float potts_w, int iterations, int label_mode, const int* unknown,
                               int8_t* d_labels, hipStream_t s) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_bare_state(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_state(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (cs->lat.size() < 1) cs->lat.resize(1);
     timer_mark(ctx, "lattice_build", s);
@@ -811,17 +789,11 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
 
 using namespace rvseg;
 
-static rvseg_status crf_enter(rvseg_ctx* ctx, Pipeline** im_out, CrfState** cs_out) {
+// entry of the C-ABI CRF calls: selects the device; they do not need the frame tables (a bare pipeline will do)
+static rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    if (!ctx->impl) {
-        // the CRF entry points do not need the frame tables; create a bare pipeline object
-        Pipeline* im = new Pipeline();
-        ctx->impl = reinterpret_cast<rvseg_ctx::Impl*>(im);
-        im->bare = true;
-    }
-    *im_out = reinterpret_cast<Pipeline*>(ctx->impl);
-    return crf_state(ctx, *im_out, cs_out);
+    return crf_state(ctx, cs_out);
 }
 
 extern "C" {
@@ -829,8 +801,8 @@ extern "C" {
 rvseg_status rvseg_crf_infer_multi(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_kernels, const int32_t* ds,
                                    const float* const* features, const float* ws, const float* unary_energy,
                                    int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || n_kernels < 0 || n_kernels > 8 || iterations < 0 || !unary_energy || !Q_out ||
         (n_kernels > 0 && (!ds || !features || !ws)) || label_mode < 0 || label_mode > 3) {
@@ -897,8 +869,8 @@ rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
         ctx->err = "bad arguments";
         return RVSEG_ERR_INVALID_ARG;
     }
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     hipStream_t s = ctx->stream;
     std::vector<TermPlan> plan;
@@ -931,8 +903,8 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
         ctx->err = "bad arguments";
         return RVSEG_ERR_INVALID_ARG;
     }
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     timer_reset(ctx);
@@ -968,8 +940,8 @@ rvseg_status rvseg_crf_logistic_unary(rvseg_ctx* ctx, int32_t N, int32_t C, int3
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     rvseg_status st = logistic_args(ctx, N, C, K, L, f, U_out);
     if (st != RVSEG_OK) return st;
-    Pipeline* im; CrfState* cs;
-    if ((st = crf_enter(ctx, &im, &cs)) != RVSEG_OK) return st;
+    CrfState* cs;
+    if ((st = crf_enter(ctx, &cs)) != RVSEG_OK) return st;
     hipStream_t s = ctx->stream;
     if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
     if ((st = dev_reserve(ctx, cs->feat, (size_t)N * K * 4)) != RVSEG_OK) return st;
@@ -988,8 +960,8 @@ rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx* ctx, int32_t N, int32_t 
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     rvseg_status st = logistic_args(ctx, N, C, K, L, d_f, d_U_out);
     if (st != RVSEG_OK) return st;
-    Pipeline* im; CrfState* cs;
-    if ((st = crf_enter(ctx, &im, &cs)) != RVSEG_OK) return st;
+    CrfState* cs;
+    if ((st = crf_enter(ctx, &cs)) != RVSEG_OK) return st;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
     // L is caller memory that may be gone once this returns: its copy is complete before the call returns
@@ -1003,8 +975,8 @@ rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx* ctx, int32_t N, int32_t 
 rvseg_status rvseg_crf_infer_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t d, const float* d_unary, int32_t unary_is_energy,
                                     const float* d_features, float potts_w, int32_t iterations, float* d_Q_out, int8_t* d_map_out,
                                     int32_t label_mode, int32_t unknown_label, void* hip_stream) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || d < 1 || d > 7 || iterations < 0 || !d_unary || !d_features || (!d_Q_out && !d_map_out) ||
         label_mode < 0 || label_mode > 3) {
@@ -1044,8 +1016,8 @@ rvseg_status rvseg_crf_infer(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t d, co
 
 rvseg_status rvseg_lattice_build(rvseg_ctx* ctx, const float* features, int32_t N, int32_t d, int32_t* offsets_out,
                                  float* bary_out, int16_t* keys_out, int32_t keys_capacity, int32_t* M_out) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (!features || N <= 0 || !M_out) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     hipStream_t s = ctx->stream;
@@ -1081,8 +1053,8 @@ rvseg_status rvseg_lattice_build(rvseg_ctx* ctx, const float* features, int32_t 
 
 rvseg_status rvseg_lattice_neighbours(rvseg_ctx* ctx, int32_t* n1_out, int32_t* n2_out, uint32_t* csr_point,
                                       uint32_t* vstart, uint32_t* vend) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (cs->lat.empty() || !cs->lat[0].built || cs->lat[0].dev.n_frames != 1) { ctx->err = "no lattice built on this context"; return RVSEG_ERR_INVALID_ARG; }
     LatticeBufs& lb = cs->lat[0];
@@ -1106,7 +1078,7 @@ rvseg_status rvseg_lattice_neighbours(rvseg_ctx* ctx, int32_t* n1_out, int32_t* 
 // debug (not in rvseg.h): per-block trace of the last resident splat of the frame path's lattice, and the tile ranges
 extern "C" rvseg_status rvseg_debug_resident(rvseg_ctx* ctx, void* trace_out, size_t trace_cap, unsigned* tile0_out, size_t tile0_cap, int meta[6]) {
     if (!ctx || !ctx->impl) return RVSEG_ERR_INVALID_ARG;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     if (!im->crf || im->crf->lat.empty() || !im->crf->lat[0].resident_on) return RVSEG_ERR_INVALID_ARG;
     LatticeBufs& b = im->crf->lat[0];
     RV_HIP(ctx, hipDeviceSynchronize());
@@ -1129,14 +1101,14 @@ rvseg_status rvseg_last_schedule(rvseg_ctx* ctx, rvseg_schedule_info* out) {
     out->vertices = -1;
     out->longest_list = -1;
     if (!ctx->impl) return RVSEG_OK;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     if (im->crf) *out = im->crf->info;
     return RVSEG_OK;
 }
 
 rvseg_status rvseg_lattice_filter(rvseg_ctx* ctx, const float* in, int32_t C, float* out) {
-    Pipeline* im; CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &im, &cs);
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (cs->lat.empty() || !cs->lat[0].built || cs->lat[0].dev.n_frames != 1) { ctx->err = "no lattice built on this context"; return RVSEG_ERR_INVALID_ARG; }
     if (!in || !out || C <= 0 || C > 64) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
@@ -1145,16 +1117,17 @@ rvseg_status rvseg_lattice_filter(rvseg_ctx* ctx, const float* in, int32_t C, fl
     hipStream_t s = ctx->stream;
     const size_t tot = (size_t)N * C;
     if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, cs->tmp, tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->scratch[0].tmp, tot * 4)) != RVSEG_OK) return st;
     if ((st = values_reserve(ctx, cs, lb.dev.m_bound, C)) != RVSEG_OK) return st;
     RV_HIP(ctx, hipMemcpyAsync(cs->q.p, in, tot * 4, hipMemcpyHostToDevice, s));
     const bool seq = C <= 2;
     ValueView V{cs->q.as<float>(), tot, 0};
-    launch_splat(lb.dev, V, C, 0, cs->val_a.as<float>(), s);
-    float* blurred = launch_blur(lb.dev, C, seq, false, cs->val_a.as<float>(), cs->val_b.as<float>(), s);
-    launch_slice(lb.dev, C, seq, 0, blurred, 0.f, cs->tmp.as<float>(), N, s);
+    auto& sc = cs->scratch[0];
+    launch_splat(lb.dev, V, C, 0, sc.val_a.as<float>(), s);
+    float* blurred = launch_blur(lb.dev, C, seq, false, sc.val_a.as<float>(), sc.val_b.as<float>(), s);
+    launch_slice(lb.dev, C, seq, 0, blurred, 0.f, sc.tmp.as<float>(), N, s);
     RV_LAUNCH_OK(ctx);
-    RV_HIP(ctx, hipMemcpyAsync(out, cs->tmp.p, tot * 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipMemcpyAsync(out, sc.tmp.p, tot * 4, hipMemcpyDeviceToHost, s));
     RV_HIP(ctx, hipStreamSynchronize(s));
     return RVSEG_OK;
 }

@@ -83,42 +83,32 @@ struct FusionState {
     DevBuf kin, kout, vin, vout, temp, start, end, bad;
     DevBuf idx, post, un;          // staging of the host entry point
     DevBuf map_un, map_feat, map_q, map_lab;   // intermediates of rvseg_process_map_device
-    int* h_bad = nullptr;          // pinned copy of the "index beyond cloud_size" flag
-    hipEvent_t bad_ev = nullptr;
+    PinnedBuf h_bad;               // int: pinned copy of the "index beyond cloud_size" flag
+    Event bad_ev;
     bool bad_pending = false;
 };
 
+// the context's fusion state, created by the first call: the pinned flag and its event first, so that a failure leaves
+// nothing behind and the next call tries again
 static rvseg_status fusion_state(rvseg_ctx* ctx, FusionState** out) {
-    if (!ctx->impl) {
-        Pipeline* im = new Pipeline();
-        ctx->impl = reinterpret_cast<rvseg_ctx::Impl*>(im);
-        im->bare = true;
-    }
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = pipeline_of(ctx);
     if (!im->fusion) {
-        FusionState* fs = new FusionState();
-        if (!hip_ok(ctx, hipHostMalloc((void**)&fs->h_bad, sizeof(int), hipHostMallocDefault), "hipHostMalloc(fusion flag)") ||
-            !hip_ok(ctx, hipEventCreateWithFlags(&fs->bad_ev, hipEventDisableTiming), "hipEventCreate(fusion flag)")) {
-            if (fs->h_bad) (void)hipHostFree(fs->h_bad);
-            delete fs;
-            return RVSEG_ERR_HIP;
-        }
-        *fs->h_bad = 0;
-        im->fusion = fs;
+        PinnedBuf h;
+        Event ev;
+        rvseg_status st = h.reserve(ctx, sizeof(int));
+        if (st != RVSEG_OK) return st;
+        RV_HIP(ctx, event_create(ev, hipEventDisableTiming));
+        *h.as<int>() = 0;
+        im->fusion = new FusionState();
+        im->fusion->h_bad = std::move(h);
+        im->fusion->bad_ev = std::move(ev);
     }
     *out = im->fusion;
     return RVSEG_OK;
 }
 
-void fusion_state_free(Pipeline* im) {
-    FusionState* fs = im->fusion;
-    if (!fs) return;
-    DevBuf* all[] = {&fs->kin, &fs->kout, &fs->vin, &fs->vout, &fs->temp, &fs->start, &fs->end, &fs->bad, &fs->idx, &fs->post, &fs->un,
-                     &fs->map_un, &fs->map_feat, &fs->map_q, &fs->map_lab};
-    for (DevBuf* b : all) dev_free(*b);
-    if (fs->h_bad) (void)hipHostFree(fs->h_bad);
-    if (fs->bad_ev) (void)hipEventDestroy(fs->bad_ev);
-    delete fs;
+void fusion_state_free(Pipeline* im) {   // the one delete of a FusionState
+    delete im->fusion;
     im->fusion = nullptr;
 }
 
@@ -133,7 +123,7 @@ rvseg_status fusion_status(rvseg_ctx* ctx, Pipeline* im, bool wait) {
         RV_HIP(ctx, e);
     }
     fs->bad_pending = false;
-    if (*fs->h_bad) {
+    if (*fs->h_bad.as<int>()) {
         ctx->err = "index image refers to a point beyond cloud_size";
         return RVSEG_ERR_INVALID_ARG;
     }
@@ -192,7 +182,7 @@ static rvseg_status fuse_device(rvseg_ctx* ctx, FusionState* fs, const FusionLay
     fusion_gather_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(
         fl, cloud_size, (unsigned)pixels, fs->vout.as<unsigned>(), fs->start.as<unsigned>(), fs->end.as<unsigned>(), d_posteriors, d_unaries);
     RV_LAUNCH_OK(ctx);
-    RV_HIP(ctx, hipMemcpyAsync(fs->h_bad, fs->bad.p, 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipMemcpyAsync(fs->h_bad.p, fs->bad.p, 4, hipMemcpyDeviceToHost, s));
     RV_HIP(ctx, hipEventRecord(fs->bad_ev, s));
     fs->bad_pending = true;
     return RVSEG_OK;
@@ -216,7 +206,7 @@ extern "C" rvseg_status rvseg_fuse_posteriors_device(rvseg_ctx* ctx, int32_t n_i
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     FusionState* fs;
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     if ((st = fusion_status(ctx, im, true)) != RVSEG_OK) return st;   // an unpolled failure of the previous fusion
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     timer_reset(ctx);
@@ -248,7 +238,7 @@ extern "C" rvseg_status rvseg_fuse_posteriors(rvseg_ctx* ctx, int32_t n_images, 
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     FusionState* fs;
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     hipStream_t s = ctx->stream;
     if ((st = dev_reserve(ctx, fs->idx, n_hits * 4)) != RVSEG_OK) return st;
     if ((st = dev_reserve(ctx, fs->post, n_hits * S * 4)) != RVSEG_OK) return st;
@@ -311,7 +301,7 @@ extern "C" rvseg_status rvseg_process_map_device(rvseg_ctx* ctx, int32_t n_image
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     FusionState* fs;
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     if ((st = fusion_status(ctx, im, true)) != RVSEG_OK) return st;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     const int S = f.sum_classes;
@@ -356,20 +346,14 @@ extern "C" rvseg_status rvseg_label_values(rvseg_ctx* ctx, const float* values, 
     if (N == 0) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     hipStream_t s = ctx->stream;
-    DevBuf d_v, d_l;
-    rvseg_status rc = dev_alloc(ctx, d_v, (size_t)N * C * 4);
-    if (rc == RVSEG_OK) rc = dev_alloc(ctx, d_l, (size_t)N);
-    do {
-        if (rc != RVSEG_OK) break;
-#define RV_TRY(call) if (!hip_ok(ctx, (call), #call)) { rc = RVSEG_ERR_HIP; break; }
-        RV_TRY(hipMemcpyAsync(d_v.p, values, (size_t)N * C * 4, hipMemcpyHostToDevice, s));
-        launch_labels(d_v.as<float>(), (size_t)N, C, label_mode, unknown_label, d_l.as<int8_t>(), s);
-        if ((rc = launch_error_take(ctx)) != RVSEG_OK) break;
-        RV_TRY(hipMemcpyAsync(labels_out, d_l.p, (size_t)N, hipMemcpyDeviceToHost, s));
-        RV_TRY(hipStreamSynchronize(s));
-#undef RV_TRY
-    } while (0);
-    dev_free(d_v);
-    dev_free(d_l);
-    return rc;
+    DevBuf d_v, d_l;   // freed on every return (hipFree waits for the device)
+    rvseg_status st;
+    if ((st = dev_alloc(ctx, d_v, (size_t)N * C * 4)) != RVSEG_OK) return st;
+    if ((st = dev_alloc(ctx, d_l, (size_t)N)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(d_v.p, values, (size_t)N * C * 4, hipMemcpyHostToDevice, s));
+    launch_labels(d_v.as<float>(), (size_t)N, C, label_mode, unknown_label, d_l.as<int8_t>(), s);
+    RV_LAUNCH_OK(ctx);
+    RV_HIP(ctx, hipMemcpyAsync(labels_out, d_l.p, (size_t)N, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -12,13 +13,58 @@
 namespace rvseg {
 
 // ---------------------------------------------------------------------------------------------
-// device buffer with explicit ownership
+// The four owning handle types.  Each releases what it holds in its destructor and is move-only (declaring the moves
+// deletes the copies; a move leaves the source empty), so a state struct made of them needs no teardown code: a new
+// buffer is a new member.  g_live counts the handles that currently hold something, per type
+// (rvseg_debug_live_resources).
 // ---------------------------------------------------------------------------------------------
+enum LiveKind { LIVE_DEVICE, LIVE_PINNED, LIVE_EVENT, LIVE_STREAM };
+extern std::atomic<long long> g_live[4];
+
+// device memory: dev_alloc / dev_reserve / dev_free below
+struct DevBuf;
+void dev_free(DevBuf& b);
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { dev_free(*this); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { dev_free(*this); }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// page-locked host memory, grow-only
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~PinnedBuf() { release(); }
+    rvseg_status reserve(rvseg_ctx* ctx, size_t n);   // a reallocation frees first; the contents are not kept
+    void release();
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// an event / a stream: converts to the HIP handle, so it is passed to HIP calls as such.  Created by event_create /
+// stream_create where it is first needed; a group that belongs together (a stream and the events that order it) is
+// created into locals and moved into the state only when all of it exists.
+template <class H, hipError_t (*Destroy)(H), LiveKind K>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { if (this != &o) { release(); h = o.h; o.h = nullptr; } return *this; }
+    ~Handle() { release(); }
+    void release() { if (h) { (void)Destroy(h); g_live[K]--; } h = nullptr; }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy, LIVE_EVENT>;
+using Stream = Handle<hipStream_t, hipStreamDestroy, LIVE_STREAM>;
+hipError_t event_create(Event& e, unsigned flags);
+hipError_t stream_create(Stream& s, unsigned flags);
+hipError_t stream_create(Stream& s, unsigned flags, int priority);
 
 // ---------------------------------------------------------------------------------------------
 // device-side forest (breadth-first node array in HBM, leaf histogram table)
@@ -46,16 +92,17 @@ struct LabTables {
 
 struct StageTimer {
     std::vector<std::string> names;  // names[i] = stage that starts at events[i]
-    std::vector<hipEvent_t> events;  // pool; events[i] .. events[i+1] bracket stage i
+    std::vector<Event> events;       // pool; events[i] .. events[i+1] bracket stage i
     size_t used = 0;
     std::vector<float> ms;
     // one stage may run on a side stream, overlapped with the stages above (the lattice build of the
     // frame path): its own pair of events, reported under side_name
-    hipEvent_t side0 = nullptr, side1 = nullptr;
+    Event side0, side1;
     std::string side_name;
     bool side_used = false;
 };
 
+struct Pipeline;    // state of the frame / CRF / fusion pipelines (rvseg_pipeline.h)
 struct EvalState;   // colour codings + confusion counters of the scoring calls (kernels_eval.hip)
 
 }  // namespace rvseg
@@ -69,12 +116,9 @@ struct rvseg_ctx {
     bool forest_loaded = false;
     rvseg::DeviceForest forest;
     rvseg::LabTables lab;
-    hipStream_t stream = nullptr;  // ctx-owned stream for the host entry points
-    // workspace: grows on demand, owned by the ctx
-    std::vector<rvseg::DevBuf> pool;
+    rvseg::Stream stream;          // ctx-owned stream for the host entry points
     rvseg::StageTimer timer;
-    struct Impl;
-    Impl* impl = nullptr;  // frame / crf pipeline state (rvseg_pipeline.hip)
+    rvseg::Pipeline* impl = nullptr;  // frame / crf / fusion state: pipeline_of (rvseg_pipeline.hip)
     std::vector<uint8_t> trained_model;   // forest.dat image of the last rvseg_forest_train* call (rvseg_forest_train_result)
     void* comm = nullptr;  // RCCL communicator of the local-map gather (rvseg_comm.cpp), or null
     int comm_rank = 0, comm_world = 0;
@@ -103,7 +147,6 @@ rvseg_status launch_error_take(rvseg_ctx* ctx);
     } while (0)
 
 rvseg_status dev_alloc(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
-void dev_free(DevBuf& b);
 // grow-only allocation: reallocates when the buffer is too small
 rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 

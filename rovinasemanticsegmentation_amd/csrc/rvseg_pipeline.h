@@ -13,12 +13,10 @@ struct FusionState;  // rvseg_fusion.hip
 // chunk k (three streams: in, compute, out).
 struct HostStage {
     static constexpr int SLOTS = 2;
-    void* h_rgb[SLOTS] = {}; void* h_depth[SLOTS] = {}; void* h_post[SLOTS] = {}; void* h_marg[SLOTS] = {}; void* h_lab[SLOTS] = {};
-    size_t c_rgb[SLOTS] = {}, c_depth[SLOTS] = {}, c_post[SLOTS] = {}, c_marg[SLOTS] = {}, c_lab[SLOTS] = {};
+    PinnedBuf h_rgb[SLOTS], h_depth[SLOTS], h_post[SLOTS], h_marg[SLOTS], h_lab[SLOTS];
     DevBuf d_rgb[SLOTS], d_depth[SLOTS], d_post[SLOTS], d_marg[SLOTS], d_lab[SLOTS];
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_in[SLOTS] = {}, ev_done[SLOTS] = {}, ev_out[SLOTS] = {};
-    bool ready = false;
+    Stream s_in, s_out;   // created together with the six events (stage_init): s_in set = all of them exist
+    Event ev_in[SLOTS], ev_done[SLOTS], ev_out[SLOTS];
 };
 
 struct Pipeline {
@@ -32,23 +30,25 @@ struct Pipeline {
     // synchronising, so a slot may only be rewritten once the copy that read it has run: a small ring,
     // each slot guarded by an event recorded behind its H2D copy
     static constexpr int CALIB_RING = 4;
-    float* h_calibA[CALIB_RING] = {};
-    size_t h_calibA_bytes[CALIB_RING] = {};
-    hipEvent_t calib_ev[CALIB_RING] = {};
+    PinnedBuf h_calibA[CALIB_RING];
+    Event calib_ev[CALIB_RING];
     bool calib_ev_live[CALIB_RING] = {};
     int calib_next = 0;
     // raised (by 3 = x8 slots) every time a lattice build overflows its hash table; applies to all later
     // builds of this context (include/rvseg.h, lattice_capacity_log2)
     int cap_boost = 0;
-    CrfState* crf = nullptr;
-    FusionState* fusion = nullptr;
+    CrfState* crf = nullptr;        // deleted by crf_state_free
+    FusionState* fusion = nullptr;  // deleted by fusion_state_free
     bool bare = false;  // created by a CRF entry point: frame tables not initialised yet
     // the lattice build depends only on the cloud and the colours, not on the forest: it runs on a
     // side stream beside feature extraction + forest evaluation (fork after prep, join before inference)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_entry = nullptr;   // ev_entry: everything before this chunk on the caller's stream
+    // (created together with timer.side0 / side1 by run_chunk: side set = all of them exist)
+    Stream side;
+    Event ev_fork, ev_join, ev_entry;   // ev_entry: everything before this chunk on the caller's stream
 };
 
+// the context's pipeline state; the first caller creates it bare
+Pipeline* pipeline_of(rvseg_ctx* ctx);
 rvseg_status pipeline_init(rvseg_ctx* ctx);
 // stages the per-frame A = R*Kinv, t of n calibrations (21 floats each) and enqueues their copy to im->calibA
 rvseg_status upload_calib(rvseg_ctx* ctx, Pipeline* im, const float* calib, int n, hipStream_t s);

@@ -39,7 +39,7 @@ static rvseg_status upload(rvseg_ctx* ctx, DevBuf& b, const void* src, size_t by
 }
 
 rvseg_status pipeline_init(rvseg_ctx* ctx) {
-    if (ctx->impl && !reinterpret_cast<Pipeline*>(ctx->impl)->bare) return RVSEG_OK;
+    if (ctx->impl && !ctx->impl->bare) return RVSEG_OK;
     const rvseg_params& p = ctx->params;
     if (p.width % p.stride != 0 || p.height % p.stride != 0) {
         // the reference would scatter outside its low-res image (segmenter.cpp:357,370)
@@ -47,9 +47,7 @@ rvseg_status pipeline_init(rvseg_ctx* ctx) {
         return RVSEG_ERR_INVALID_ARG;
     }
     if (p.patch_size_reduce > 16) { ctx->err = "patch_size_reduce > 16 is not supported"; return RVSEG_ERR_INVALID_ARG; }
-    Pipeline* im = ctx->impl ? reinterpret_cast<Pipeline*>(ctx->impl) : new Pipeline();
-    ctx->impl = reinterpret_cast<rvseg_ctx::Impl*>(im);
-    im->bare = false;
+    Pipeline* im = pipeline_of(ctx);
     FrameGeom& g = im->geom;
     g.W = p.width; g.H = p.height; g.stride = p.stride;
     g.lw = p.width / p.stride; g.lh = p.height / p.stride;
@@ -108,37 +106,16 @@ rvseg_status pipeline_init(rvseg_ctx* ctx) {
         if ((st = upload(ctx, im->up.ay0, w0.data(), w0.size() * 4)) != RVSEG_OK) return st;
         if ((st = upload(ctx, im->up.ay1, w1.data(), w1.size() * 4)) != RVSEG_OK) return st;
     }
+    im->bare = false;
     return RVSEG_OK;
 }
 
-static void pipeline_free(Pipeline* im) {
-    DevBuf* all[] = {&im->resize_rows, &im->up.xofs, &im->up.ax0, &im->up.ax1, &im->up.yofs, &im->up.ay0, &im->up.ay1,
-                     &im->calibA, &im->lab, &im->lab2, &im->cloud, &im->rect, &im->nfeat, &im->low, &im->post, &im->marg,
-                     &im->labels, &im->in_rgb, &im->in_depth, &im->dump, &im->valid, &im->change};
-    for (DevBuf* b : all) dev_free(*b);
-    for (int i = 0; i < Pipeline::CALIB_RING; i++) {
-        if (im->calib_ev[i]) { (void)hipEventSynchronize(im->calib_ev[i]); (void)hipEventDestroy(im->calib_ev[i]); }
-        if (im->h_calibA[i]) (void)hipHostFree(im->h_calibA[i]);
+Pipeline* pipeline_of(rvseg_ctx* ctx) {
+    if (!ctx->impl) {
+        ctx->impl = new Pipeline();
+        ctx->impl->bare = true;
     }
-    {
-        HostStage& hs = im->stage;
-        for (int i = 0; i < HostStage::SLOTS; i++) {
-            void* hp[] = {hs.h_rgb[i], hs.h_depth[i], hs.h_post[i], hs.h_marg[i], hs.h_lab[i]};
-            for (void* p : hp) if (p) (void)hipHostFree(p);
-            DevBuf* db[] = {&hs.d_rgb[i], &hs.d_depth[i], &hs.d_post[i], &hs.d_marg[i], &hs.d_lab[i]};
-            for (DevBuf* b : db) dev_free(*b);
-            hipEvent_t ev[] = {hs.ev_in[i], hs.ev_done[i], hs.ev_out[i]};
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        }
-        if (hs.s_in) (void)hipStreamDestroy(hs.s_in);
-        if (hs.s_out) (void)hipStreamDestroy(hs.s_out);
-    }
-    crf_state_free(im);
-    fusion_state_free(im);
-    if (im->side) (void)hipStreamDestroy(im->side);
-    if (im->ev_fork) (void)hipEventDestroy(im->ev_fork);
-    if (im->ev_entry) (void)hipEventDestroy(im->ev_entry);
-    if (im->ev_join) (void)hipEventDestroy(im->ev_join);
+    return ctx->impl;
 }
 
 // A = R*Kinv, Eigen fixed 3x3 product accumulated left to right (feature_extractor.h:223)
@@ -153,21 +130,15 @@ static void calib_to_A(const float* calib, float* out12) {
 rvseg_status upload_calib(rvseg_ctx* ctx, Pipeline* im, const float* calib, int n, hipStream_t s) {
     const int slot = im->calib_next;
     im->calib_next = (slot + 1) % Pipeline::CALIB_RING;
-    if (!im->calib_ev[slot]) RV_HIP(ctx, hipEventCreateWithFlags(&im->calib_ev[slot], hipEventDisableTiming));
+    if (!im->calib_ev[slot]) RV_HIP(ctx, event_create(im->calib_ev[slot], hipEventDisableTiming));
     // the copy that last read this slot must have run before the host rewrites (or frees) it
     if (im->calib_ev_live[slot]) { RV_HIP(ctx, hipEventSynchronize(im->calib_ev[slot])); im->calib_ev_live[slot] = false; }
     const size_t bytes = (size_t)n * 12 * sizeof(float);
-    if (bytes > im->h_calibA_bytes[slot]) {
-        if (im->h_calibA[slot]) (void)hipHostFree(im->h_calibA[slot]);
-        im->h_calibA[slot] = nullptr;
-        im->h_calibA_bytes[slot] = 0;
-        RV_HIP(ctx, hipHostMalloc((void**)&im->h_calibA[slot], bytes, hipHostMallocDefault));
-        im->h_calibA_bytes[slot] = bytes;
-    }
-    float* h = im->h_calibA[slot];
-    for (int i = 0; i < n; i++) calib_to_A(calib + (size_t)i * 21, h + (size_t)i * 12);
-    rvseg_status st = dev_reserve(ctx, im->calibA, bytes);   // (a reallocation frees with hipFree, which waits for the device)
+    rvseg_status st = im->h_calibA[slot].reserve(ctx, bytes);
     if (st != RVSEG_OK) return st;
+    float* h = im->h_calibA[slot].as<float>();
+    for (int i = 0; i < n; i++) calib_to_A(calib + (size_t)i * 21, h + (size_t)i * 12);
+    if ((st = dev_reserve(ctx, im->calibA, bytes)) != RVSEG_OK) return st;   // (a reallocation frees with hipFree, which waits for the device)
     RV_HIP(ctx, hipMemcpyAsync(im->calibA.p, h, bytes, hipMemcpyHostToDevice, s));
     RV_HIP(ctx, hipEventRecord(im->calib_ev[slot], s));
     im->calib_ev_live[slot] = true;
@@ -185,9 +156,9 @@ void timer_reset(rvseg_ctx* ctx) {
 void timer_mark(rvseg_ctx* ctx, const char* name, hipStream_t s) {
     StageTimer& t = ctx->timer;
     if (t.used >= t.events.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        t.events.push_back(e);
+        Event e;
+        if (event_create(e, hipEventDefault) != hipSuccess) return;
+        t.events.push_back(std::move(e));
     }
     (void)hipEventRecord(t.events[t.used++], s);
     t.names.push_back(name);
@@ -229,12 +200,20 @@ static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
             // 13.85 vs 13.98 ms per step; since the feature branch is the longer one (5.2 vs 3.6 ms) the lowest is, by
             // a little: 13.31 / 13.33 vs 13.37 / 13.42 ms (rvseg_schedule.build_priority_high restores the old choice;
             // it is read when the stream is created, i.e. before the first frame call of the context)
-            RV_HIP(ctx, hipStreamCreateWithPriority(&im->side, hipStreamNonBlocking, ctx->sched.build_priority_high ? prio_hi : prio_lo));
-            RV_HIP(ctx, hipEventCreateWithFlags(&im->ev_fork, hipEventDisableTiming));
-            RV_HIP(ctx, hipEventCreateWithFlags(&im->ev_join, hipEventDisableTiming));
-            RV_HIP(ctx, hipEventCreateWithFlags(&im->ev_entry, hipEventDisableTiming));
-            RV_HIP(ctx, hipEventCreate(&ctx->timer.side0));
-            RV_HIP(ctx, hipEventCreate(&ctx->timer.side1));
+            Stream side;
+            Event fork, join, entry, side0, side1;
+            RV_HIP(ctx, stream_create(side, hipStreamNonBlocking, ctx->sched.build_priority_high ? prio_hi : prio_lo));
+            RV_HIP(ctx, event_create(fork, hipEventDisableTiming));
+            RV_HIP(ctx, event_create(join, hipEventDisableTiming));
+            RV_HIP(ctx, event_create(entry, hipEventDisableTiming));
+            RV_HIP(ctx, event_create(side0, hipEventDefault));
+            RV_HIP(ctx, event_create(side1, hipEventDefault));
+            im->side = std::move(side);
+            im->ev_fork = std::move(fork);
+            im->ev_join = std::move(join);
+            im->ev_entry = std::move(entry);
+            ctx->timer.side0 = std::move(side0);
+            ctx->timer.side1 = std::move(side1);
         }
         RV_HIP(ctx, hipEventRecord(im->ev_entry, s));
         RV_HIP(ctx, hipStreamWaitEvent(im->side, im->ev_entry, 0));
@@ -294,8 +273,11 @@ extern "C" {
 
 void rvseg_pipeline_destroy(rvseg_ctx* ctx) {
     if (!ctx || !ctx->impl) return;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
-    pipeline_free(im);
+    Pipeline* im = ctx->impl;
+    // the copy that last read a calibration slot must have run before the slot's event and pinned block go
+    for (Event& ev : im->calib_ev) if (ev) (void)hipEventSynchronize(ev);
+    crf_state_free(im);
+    fusion_state_free(im);
     delete im;
     ctx->impl = nullptr;
 }
@@ -310,7 +292,7 @@ rvseg_status rvseg_segment_frames_device(rvseg_ctx* ctx, int32_t n_frames, const
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     timer_reset(ctx);
     if ((st = upload_calib(ctx, im, calib, n_frames, s)) != RVSEG_OK) return st;
@@ -351,15 +333,6 @@ void host_copy(void* dst, const void* src, size_t bytes) {
     for (auto& x : th) x.join();
 }
 
-rvseg_status pinned_reserve(rvseg_ctx* ctx, void*& p, size_t& cap, size_t bytes) {
-    if (cap >= bytes && p) return RVSEG_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    RV_HIP(ctx, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    cap = bytes;
-    return RVSEG_OK;
-}
-
 // is p page-locked host memory (hipHostMalloc / hipHostRegister, e.g. through rvseg_host_register)?  Then the DMA engines
 // reach it directly and the pinned staging copy is skipped.
 bool is_pinned_host(const void* p) {
@@ -370,15 +343,23 @@ bool is_pinned_host(const void* p) {
 }
 
 rvseg_status stage_init(rvseg_ctx* ctx, HostStage& hs) {
-    if (hs.ready) return RVSEG_OK;
-    RV_HIP(ctx, hipStreamCreateWithFlags(&hs.s_in, hipStreamNonBlocking));
-    RV_HIP(ctx, hipStreamCreateWithFlags(&hs.s_out, hipStreamNonBlocking));
+    if (hs.s_in) return RVSEG_OK;
+    Stream s_in, s_out;
+    Event in[HostStage::SLOTS], done[HostStage::SLOTS], out[HostStage::SLOTS];
+    RV_HIP(ctx, stream_create(s_in, hipStreamNonBlocking));
+    RV_HIP(ctx, stream_create(s_out, hipStreamNonBlocking));
     for (int i = 0; i < HostStage::SLOTS; i++) {
-        RV_HIP(ctx, hipEventCreateWithFlags(&hs.ev_in[i], hipEventDisableTiming));
-        RV_HIP(ctx, hipEventCreateWithFlags(&hs.ev_done[i], hipEventDisableTiming));
-        RV_HIP(ctx, hipEventCreateWithFlags(&hs.ev_out[i], hipEventDisableTiming));
+        RV_HIP(ctx, event_create(in[i], hipEventDisableTiming));
+        RV_HIP(ctx, event_create(done[i], hipEventDisableTiming));
+        RV_HIP(ctx, event_create(out[i], hipEventDisableTiming));
     }
-    hs.ready = true;
+    for (int i = 0; i < HostStage::SLOTS; i++) {   // all eight exist: hand them over
+        hs.ev_in[i] = std::move(in[i]);
+        hs.ev_done[i] = std::move(done[i]);
+        hs.ev_out[i] = std::move(out[i]);
+    }
+    hs.s_out = std::move(s_out);
+    hs.s_in = std::move(s_in);
     return RVSEG_OK;
 }
 
@@ -393,7 +374,7 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     HostStage& hs = im->stage;
     if ((st = stage_init(ctx, hs)) != RVSEG_OK) return st;
     const FrameGeom& g = im->geom;
@@ -416,9 +397,9 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
         const int slot = c % HostStage::SLOTS, n = chunk_n(c);
         const size_t start = (size_t)c * chunk;
         RV_HIP(ctx, hipEventSynchronize(hs.ev_out[slot]));
-        if (posteriors_out && !post_pinned) host_copy(posteriors_out + start * npix * S, hs.h_post[slot], npix * S * 4 * n);
-        if (want_marg && !marg_pinned) host_copy(marginals_out + start * npix * S, hs.h_marg[slot], npix * S * 4 * n);
-        if (labels_out && !lab_pinned) host_copy(labels_out + start * npix * L, hs.h_lab[slot], npix * L * n);
+        if (posteriors_out && !post_pinned) host_copy(posteriors_out + start * npix * S, hs.h_post[slot].p, npix * S * 4 * n);
+        if (want_marg && !marg_pinned) host_copy(marginals_out + start * npix * S, hs.h_marg[slot].p, npix * S * 4 * n);
+        if (labels_out && !lab_pinned) host_copy(labels_out + start * npix * L, hs.h_lab[slot].p, npix * L * n);
         return RVSEG_OK;
     };
     auto drain = [&]() { (void)hipStreamSynchronize(hs.s_in); (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(hs.s_out); };
@@ -437,25 +418,25 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
         const int slot = c % HostStage::SLOTS, n = chunk_n(c);
         const size_t start = (size_t)c * chunk;
         // staging + device buffers of this slot (grow only; the slot's previous chunk c - 2 has been retired)
-        if ((!in_pinned && ((st = pinned_reserve(ctx, hs.h_rgb[slot], hs.c_rgb[slot], npix * 3 * n)) != RVSEG_OK ||
-                            (st = pinned_reserve(ctx, hs.h_depth[slot], hs.c_depth[slot], npix * 2 * n)) != RVSEG_OK)) ||
+        if ((!in_pinned && ((st = hs.h_rgb[slot].reserve(ctx, npix * 3 * n)) != RVSEG_OK ||
+                            (st = hs.h_depth[slot].reserve(ctx, npix * 2 * n)) != RVSEG_OK)) ||
             (st = dev_reserve(ctx, hs.d_rgb[slot], npix * 3 * n)) != RVSEG_OK ||
             (st = dev_reserve(ctx, hs.d_depth[slot], npix * 2 * n)) != RVSEG_OK) { drain(); return st; }
         const bool need_post_dev = posteriors_out != nullptr;
-        if (need_post_dev && ((!post_pinned && (st = pinned_reserve(ctx, hs.h_post[slot], hs.c_post[slot], npix * S * 4 * n)) != RVSEG_OK) ||
+        if (need_post_dev && ((!post_pinned && (st = hs.h_post[slot].reserve(ctx, npix * S * 4 * n)) != RVSEG_OK) ||
                               (st = dev_reserve(ctx, hs.d_post[slot], npix * S * 4 * n)) != RVSEG_OK)) { drain(); return st; }
-        if (want_marg && ((!marg_pinned && (st = pinned_reserve(ctx, hs.h_marg[slot], hs.c_marg[slot], npix * S * 4 * n)) != RVSEG_OK) ||
+        if (want_marg && ((!marg_pinned && (st = hs.h_marg[slot].reserve(ctx, npix * S * 4 * n)) != RVSEG_OK) ||
                           (st = dev_reserve(ctx, hs.d_marg[slot], npix * S * 4 * n)) != RVSEG_OK)) { drain(); return st; }
-        if (labels_out && ((!lab_pinned && (st = pinned_reserve(ctx, hs.h_lab[slot], hs.c_lab[slot], npix * L * n)) != RVSEG_OK) ||
+        if (labels_out && ((!lab_pinned && (st = hs.h_lab[slot].reserve(ctx, npix * L * n)) != RVSEG_OK) ||
                            (st = dev_reserve(ctx, hs.d_lab[slot], npix * L * n)) != RVSEG_OK)) { drain(); return st; }
         // 1. caller's pageable buffers -> pinned (host threads; the GPU is busy with chunk c - 1 meanwhile)
         const void* src_rgb = rgb + start * npix * 3;
         const void* src_depth = depth_mm + start * npix;
         if (!in_pinned) {
-            host_copy(hs.h_rgb[slot], src_rgb, npix * 3 * n);
-            host_copy(hs.h_depth[slot], src_depth, npix * 2 * n);
-            src_rgb = hs.h_rgb[slot];
-            src_depth = hs.h_depth[slot];
+            host_copy(hs.h_rgb[slot].p, src_rgb, npix * 3 * n);
+            host_copy(hs.h_depth[slot].p, src_depth, npix * 2 * n);
+            src_rgb = hs.h_rgb[slot].p;
+            src_depth = hs.h_depth[slot].p;
         }
         // 2. H2D on the input stream, after the compute of chunk c - 2 (the last reader of these device buffers)
         if (c >= HostStage::SLOTS) RV_HIP(ctx, hipStreamWaitEvent(hs.s_in, hs.ev_done[slot], 0));
@@ -482,11 +463,11 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
         RV_HIP(ctx, hipEventRecord(hs.ev_done[slot], s));
         // 4. D2H on the output stream
         RV_HIP(ctx, hipStreamWaitEvent(hs.s_out, hs.ev_done[slot], 0));
-        if (posteriors_out) RV_HIP(ctx, hipMemcpyAsync(post_pinned ? (void*)(posteriors_out + start * npix * S) : hs.h_post[slot], hs.d_post[slot].p,
+        if (posteriors_out) RV_HIP(ctx, hipMemcpyAsync(post_pinned ? (void*)(posteriors_out + start * npix * S) : hs.h_post[slot].p, hs.d_post[slot].p,
                                                        npix * S * 4 * n, hipMemcpyDeviceToHost, hs.s_out));
-        if (want_marg) RV_HIP(ctx, hipMemcpyAsync(marg_pinned ? (void*)(marginals_out + start * npix * S) : hs.h_marg[slot], hs.d_marg[slot].p,
+        if (want_marg) RV_HIP(ctx, hipMemcpyAsync(marg_pinned ? (void*)(marginals_out + start * npix * S) : hs.h_marg[slot].p, hs.d_marg[slot].p,
                                                   npix * S * 4 * n, hipMemcpyDeviceToHost, hs.s_out));
-        if (labels_out) RV_HIP(ctx, hipMemcpyAsync(lab_pinned ? (void*)(labels_out + start * npix * L) : hs.h_lab[slot], hs.d_lab[slot].p,
+        if (labels_out) RV_HIP(ctx, hipMemcpyAsync(lab_pinned ? (void*)(labels_out + start * npix * L) : hs.h_lab[slot].p, hs.d_lab[slot].p,
                                                    npix * L * n, hipMemcpyDeviceToHost, hs.s_out));
         RV_HIP(ctx, hipEventRecord(hs.ev_out[slot], hs.s_out));
         // 5. hand chunk c - 1 to the caller while chunk c runs (its build status was checked by run_chunk above)
@@ -512,7 +493,7 @@ rvseg_status rvseg_poll_status(rvseg_ctx* ctx, int32_t wait) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     if (!ctx->impl) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     const rvseg_status a = crf_frames_status(ctx, im, wait != 0);
     if (a != RVSEG_OK) return a;
     return fusion_status(ctx, im, wait != 0);
@@ -525,7 +506,7 @@ rvseg_status rvseg_extract_features(rvseg_ctx* ctx, const uint8_t* rgb, const ui
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     const FrameGeom& g = im->geom;
     const rvseg_params& p = ctx->params;
     const size_t npix = (size_t)g.W * g.H;
@@ -550,8 +531,7 @@ rvseg_status rvseg_extract_features(rvseg_ctx* ctx, const uint8_t* rgb, const ui
         launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), 1, s);
     }
     // the dump variant never touches the forest; a context without a model can still extract
-    DeviceForest none = ctx->forest;
-    launch_rf_frames(g, none, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), im->in_depth.as<uint16_t>(),
+    launch_rf_frames(g, ctx->forest, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), im->in_depth.as<uint16_t>(),
                      im->cloud.as<float4>(), im->nfeat.as<float>(), nullptr, im->dump.as<float>(), im->valid.as<uint8_t>(), 1, s);
     RV_LAUNCH_OK(ctx);
     std::vector<float> dump((size_t)P * g.D);

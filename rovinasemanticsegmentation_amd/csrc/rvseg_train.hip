@@ -125,29 +125,28 @@ struct TrainSet {
 };
 
 struct DevArena {   // frees on scope exit
-    std::vector<void*> ptrs;
-    ~DevArena() { for (void* p : ptrs) (void)hipFree(p); }
+    std::vector<DevBuf> bufs;
     template <class T> T* alloc(rvseg_ctx* ctx, size_t n, bool* ok) {
-        void* p = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)), "hipMalloc(train)")) { *ok = false; return nullptr; }
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
+        DevBuf b;
+        if (dev_alloc(ctx, b, std::max<size_t>(n, 1) * sizeof(T)) != RVSEG_OK) { *ok = false; return nullptr; }
+        bufs.push_back(std::move(b));
+        return bufs.back().as<T>();
     }
 };
 
 // grow-only device buffer that lives across levels and trees (no allocation per level)
 template <class T>
 struct GrowBuf {
+    DevBuf buf;
     T* p = nullptr;
     size_t cap = 0;
-    ~GrowBuf() { if (p) (void)hipFree(p); }
     bool reserve(rvseg_ctx* ctx, size_t n) {
         if (n <= cap) return true;
-        if (p) (void)hipFree(p);
         p = nullptr; cap = 0;
         size_t want = std::max<size_t>(n, 1024);
         want += want / 2;
-        if (!hip_ok(ctx, hipMalloc((void**)&p, want * sizeof(T)), "hipMalloc(train level)")) return false;
+        if (dev_alloc(ctx, buf, want * sizeof(T)) != RVSEG_OK) return false;   // (frees the old block first)
+        p = buf.as<T>();
         cap = want;
         return true;
     }
@@ -834,7 +833,7 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
-    Pipeline* im = reinterpret_cast<Pipeline*>(ctx->impl);
+    Pipeline* im = ctx->impl;
     const FrameGeom& g = im->geom;
     const rvseg_params& p = ctx->params;
     if ((st = check_train_args(ctx, n_layers, class_counts, tp, g.D)) != RVSEG_OK) return st;
