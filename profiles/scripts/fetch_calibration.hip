@@ -1,7 +1,7 @@
 // fetch_calibration -- what does rocprofv3's FETCH_SIZE mean for the access shapes of this repo?
 //
 // MI355X_MICROARCH.md (HBM section): on gfx950 FETCH_SIZE reports half the bytes of a 16-B-per-lane
-// streaming read and is "uncalibrated" for other shapes.  The splat (kernels_crf.hip,
+// streaming read and is "uncalibrated" for other shapes.  The splat (kernels_splat.hip,
 // splat_group_kernel) reads an 8-byte-per-lane coalesced stream (CSR pairs) and gathers one 36-byte
 // row per lane as dwordx4 + dwordx4 + dword.  This program runs kernels with exactly those shapes over
 // buffers far larger than the 256 MiB Infinity Cache, on byte counts known in advance, and prints per

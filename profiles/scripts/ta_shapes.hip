@@ -1,6 +1,6 @@
 // ta_shapes -- what does a row gather cost the texture addresser when the data is cache resident?
 //
-// The resident splat (kernels_crf.hip) is bound by its vector-memory instructions, not by bytes (PMC: TA busy 77 %).
+// The resident splat (kernels_resident.hip) is bound by its vector-memory instructions, not by bytes (PMC: TA busy 77 %).
 // Its row gather is one 36-byte row per lane as dwordx4 + dwordx4 + dword.  This program times that shape and
 // alternatives on a table small enough to stay in L2 (so that HBM is out of the picture), with the splat's occupancy
 // (7 gathering waves per CU, 8 gathers in flight per wave) and its index pattern (runs of consecutive rows):

@@ -1,0 +1,863 @@
+// Permutohedral lattice build for gfx950: hash table, per-point simplex, compaction, blur neighbours, vertex-major CSR.
+//
+// Reference semantics (third-party/densecrf/src):
+//   Permutohedral::init  SSE branch   permutohedral.cpp:140-321   (elevate, round-half-even,
+//                                     rank, barycentric, d+1 vertex keys per point, blur neighbours)
+//
+// MI355X design notes
+//   * One open-addressing hash table in HBM holds the lattice vertices of ALL frames of a chunk
+//     (the frame index is an extra key coordinate), so every later kernel is a flat launch over
+//     global vertex / point indices with no per-frame loop.
+//   * Vertex numbering is whatever the atomics produce; no result depends on it.
+//   * The splat (kernels_splat.hip) adds a vertex's contributions in ascending point order: the sort by vertex is STABLE.
+#include <string.h>   // rocprim's texture iterator calls the host memset without including it
+
+#include <rocprim/rocprim.hpp>
+
+#include "device_math.h"
+#include "rvseg_crf.h"
+
+namespace rvseg {
+
+// ---------------------------------------------------------------------------------------------
+// hash table
+// ---------------------------------------------------------------------------------------------
+constexpr int ST_EMPTY = -1, ST_LOCKED = -2, ST_FILLED = 0;
+
+// d coordinates, then the frame index at k[7]; unused = 0.  A union so that the short / word /
+// quad-word views alias legally (plain reinterpret_casts let the compiler drop the short stores).
+struct Key8 {
+    union {
+        short k[8];
+        unsigned w[4];
+        unsigned long long q[2];
+    };
+};
+
+__device__ __forceinline__ unsigned hash_key(const Key8& key) {
+    unsigned h = 0x9E3779B9u;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        h ^= key.w[i];
+        h *= 0x85EBCA6Bu;
+        h ^= h >> 15;
+    }
+    return h;
+}
+
+__device__ __forceinline__ bool key_equal_at(const unsigned long long* tkeys, unsigned slot, const Key8& key) {
+    const unsigned long long* mine = key.q;
+    // agent-scope loads: another CU may have written the key after this CU cached the line
+    const unsigned long long a = __hip_atomic_load(tkeys + 2 * (size_t)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long b = __hip_atomic_load(tkeys + 2 * (size_t)slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return a == mine[0] && b == mine[1];
+}
+
+// The table is partitioned by frame: frame f owns slots [f*cap_f, (f+1)*cap_f).  Slot order is
+// therefore frame-major, and the scan-based compaction below numbers a frame's vertices
+// contiguously (the fused update kernel stages one frame's vertex values in LDS).
+// find-or-create; returns the global slot.  On overflow sets counters[1] and returns the region base.
+__device__ __forceinline__ unsigned hash_insert(int* state, unsigned long long* tkeys, unsigned base, unsigned mask,
+                                                int* counters, const Key8& key) {
+    unsigned hl = hash_key(key) & mask;
+    for (unsigned probes = 0; probes <= mask; ) {
+        const unsigned h = base + hl;
+        int st = __hip_atomic_load(state + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == ST_EMPTY) {
+            int expected = ST_EMPTY;
+            if (__hip_atomic_compare_exchange_strong(state + h, &expected, ST_LOCKED, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT)) {
+                const unsigned long long* mine = key.q;
+                __hip_atomic_store(tkeys + 2 * (size_t)h, mine[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(tkeys + 2 * (size_t)h + 1, mine[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(state + h, ST_FILLED, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                return h;
+            }
+            continue;  // lost the race: look at the same slot again
+        }
+        if (st == ST_LOCKED) continue;  // the owner publishes within its own loop iteration
+        if (key_equal_at(tkeys, h, key)) return h;
+        hl = (hl + 1) & mask;
+        probes++;
+    }
+    counters[1] = 1;
+    return base;
+}
+
+// read-only lookup (table complete, written by earlier kernels)
+__device__ __forceinline__ int hash_lookup(const int* state, const unsigned long long* tkeys, unsigned base, unsigned mask,
+                                           const Key8& key) {
+    unsigned hl = hash_key(key) & mask;
+    const unsigned long long* mine = key.q;
+    for (unsigned probes = 0; probes <= mask; probes++) {
+        const unsigned h = base + hl;
+        if (state[h] == ST_EMPTY) return -1;
+        if (tkeys[2 * (size_t)h] == mine[0] && tkeys[2 * (size_t)h + 1] == mine[1]) return (int)h;
+        hl = (hl + 1) & mask;
+    }
+    return -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Permutohedral::init per point (SSE branch semantics, fp32, no contraction)
+// ---------------------------------------------------------------------------------------------
+constexpr int LP_SET = 512;        // block-local vertex set (LP_CHUNKS x 256 points x (d+1) keys, few distinct)
+constexpr int LP_MAX_PROBE = 24;
+constexpr int LP_CHUNKS = 8;       // consecutive 256-point chunks per block (at most): the set (and its global slots) carries over
+
+template <int D>
+__global__ void __launch_bounds__(256)
+lattice_points_kernel(LatticeDev L, FeatureSource fs, int n_chunks) {
+    // block-local vertex set: tag (EMPTY / LOCKED / FILLED), key, global slot; `lnew` lists the set
+    // entries in creation order, so each chunk resolves only the entries it added
+    __shared__ int ltag[LP_SET];
+    __shared__ unsigned long long lkey[LP_SET][2];
+    __shared__ unsigned lslot[LP_SET];
+    __shared__ unsigned short lnew[LP_SET];
+    __shared__ unsigned n_new;
+    for (int t = threadIdx.x; t < LP_SET; t += 256) ltag[t] = ST_EMPTY;
+    if (threadIdx.x == 0) n_new = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    unsigned resolved = 0;   // set entries [0, resolved) of lnew already have their global slot
+    const long long per_frame = L.Npad;
+
+  for (int chunk = 0; chunk < n_chunks; chunk++) {
+    const long long gid0 = ((long long)blockIdx.x * n_chunks + chunk) * 256 + threadIdx.x;
+    const bool active = gid0 < per_frame * L.n_frames;   // all threads stay for the barriers
+    const long long gid = active ? gid0 : 0;
+    const int frame = (int)(gid / per_frame);
+    const int i = (int)(gid - (long long)frame * per_frame);
+    const bool real = active && i < L.N;
+    const long long gp = (long long)frame * L.N + i;  // global point index (valid when real)
+
+    float f[D];
+    if (!real) {
+#pragma unroll
+        for (int k = 0; k < D; k++) f[k] = 0.0f;  // padded lanes carry zero features (permutohedral.cpp:196)
+    } else if (fs.mode == 0) {
+#pragma unroll
+        for (int k = 0; k < D; k++) f[k] = fs.feat[gp * D + k];
+    } else {
+        // frame mode (D == 6): segmenter.cpp:629-637 on the frame's own points
+        const float4 c = fs.cloud[gp];
+        float x = c.x, y = c.y, z = c.z;
+        if (!(finite_f(x) && finite_f(y) && finite_f(z))) x = y = z = 0.0f;
+        const uint8_t* px = fs.rgb + gp * 3;
+        const float v[6] = {x * fs.xyz_kernel, y * fs.xyz_kernel, z * fs.xyz_kernel,
+                            ((float)px[0] / 255.0f) * fs.rgb_kernel, ((float)px[1] / 255.0f) * fs.rgb_kernel,
+                            ((float)px[2] / 255.0f) * fs.rgb_kernel};
+#pragma unroll
+        for (int k = 0; k < D; k++) f[k] = v[k < 6 ? k : 0];
+    }
+
+    const float invdplus1 = 1.0f / (D + 1), dplus1 = (float)(D + 1);
+    float el[D + 1], rem0[D + 1], rank[D + 1];
+    // elevate (permutohedral.cpp:201-207)
+    float sm = 0.0f;
+#pragma unroll
+    for (int j = D; j > 0; j--) {
+        const float cf = f[j - 1] * L.scale[j - 1];
+        el[j] = sm - (float)j * cf;
+        sm += cf;
+    }
+    el[0] = sm;
+    // closest 0-coloured simplex (:210-220), cvtps_epi32 = round half to even
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= D; k++) {
+        float v = invdplus1 * el[k];
+        v = rintf(v);
+        rem0[k] = v * dplus1;
+        sum += v;
+    }
+    // rank (:223-233)
+#pragma unroll
+    for (int k = 0; k <= D; k++) rank[k] = 0.0f;
+#pragma unroll
+    for (int a = 0; a < D; a++) {
+        const float di = el[a] - rem0[a];
+#pragma unroll
+        for (int b = a + 1; b <= D; b++) {
+            const float dj = el[b] - rem0[b];
+            const float c = di < dj ? 1.0f : 0.0f;
+            rank[a] += c;
+            rank[b] += 1.0f - c;
+        }
+    }
+    // back onto the plane (:236-242)
+#pragma unroll
+    for (int k = 0; k <= D; k++) {
+        rank[k] += sum;
+        const float add = rank[k] < 0.0f ? dplus1 : 0.0f;
+        const float sub = rank[k] >= dplus1 ? dplus1 : 0.0f;
+        rank[k] += add - sub;
+        rem0[k] += add - sub;
+    }
+    // barycentric (:245-263); the scatter index D - rank is data dependent, so walk it with
+    // compile-time indices to keep the array in registers
+    float bary[D + 2];
+#pragma unroll
+    for (int k = 0; k < D + 2; k++) bary[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= D; k++) {
+        const float v = (el[k] - rem0[k]) * invdplus1;
+        const int p = D - (int)rank[k];
+#pragma unroll
+        for (int q = 0; q <= D; q++) {
+            if (q == p) { bary[q] += v; bary[q + 1] -= v; }
+        }
+    }
+    bary[0] += 1.0f + bary[D + 1];
+    // vertices (:266-275).  Neighbouring points share almost all their vertices, so the block first
+    // collects its distinct keys in an LDS set (phase 1), then one lane per distinct key does the
+    // global find-or-create -- all global round trips of a block overlap (phase 2) -- and finally
+    // every point reads the global slots of its d+1 vertices back from LDS (phase 3).
+    int lidx[D + 1];   // index into the LDS set, or -1 - (global slot) when the set was too full
+#pragma unroll
+    for (int r = 0; r <= D; r++) {
+        Key8 key;
+#pragma unroll
+        for (int k = 0; k < 8; k++) key.k[k] = 0;
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            const int rk = (int)rank[k];
+            const int canon = rk <= D - r ? r : r - (D + 1);
+            key.k[k] = (short)(rem0[k] + (float)canon);
+        }
+        key.k[7] = (short)frame;
+        // equal keys inside the wave first (neighbouring points share most vertices): one lane per
+        // distinct key goes to the LDS set, the others take its answer
+        int leader_of = lane;
+        {
+            bool pending = active;
+            for (;;) {
+                const unsigned long long todo = __ballot(pending);
+                if (!todo) break;
+                const int ld = __ffsll((long long)todo) - 1;
+                const unsigned a0 = __builtin_amdgcn_readlane(key.w[0], ld), a1 = __builtin_amdgcn_readlane(key.w[1], ld);
+                const unsigned a2 = __builtin_amdgcn_readlane(key.w[2], ld), a3 = __builtin_amdgcn_readlane(key.w[3], ld);
+                const bool same = pending && key.w[0] == a0 && key.w[1] == a1 && key.w[2] == a2 && key.w[3] == a3;
+                if (same) leader_of = ld;
+                pending = pending && !same;
+            }
+        }
+        int found = 0;
+        if (active && leader_of == lane) {
+            unsigned h = (hash_key(key) >> 7) & (LP_SET - 1);
+            found = -1;
+            for (int probes = 0; probes < LP_MAX_PROBE; ) {
+                const int t = __hip_atomic_load(&ltag[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (t == ST_EMPTY) {
+                    int expected = ST_EMPTY;
+                    if (__hip_atomic_compare_exchange_strong(&ltag[h], &expected, ST_LOCKED, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                        __hip_atomic_store(&lkey[h][0], key.q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_store(&lkey[h][1], key.q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_store(&ltag[h], ST_FILLED, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        lnew[atomicAdd(&n_new, 1u)] = (unsigned short)h;   // at most LP_SET entries are ever created
+                        found = (int)h;
+                        break;
+                    }
+                    continue;
+                }
+                if (t == ST_LOCKED) continue;
+                const unsigned long long a = __hip_atomic_load(&lkey[h][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                const unsigned long long b = __hip_atomic_load(&lkey[h][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (a == key.q[0] && b == key.q[1]) { found = (int)h; break; }
+                h = (h + 1) & (LP_SET - 1);
+                probes++;
+            }
+            if (found < 0)  // set too crowded around this key: go to the global table directly
+                found = -1 - (int)hash_insert(L.state, L.tkeys, (unsigned)frame << L.cap_f_log2, L.cap_f_mask, L.counters, key);
+        }
+        lidx[r] = __shfl(found, leader_of, 64);
+    }
+    __syncthreads();
+    const unsigned created = n_new;   // stable until the next chunk's phase 1, which starts after the barrier below
+    for (unsigned t = resolved + threadIdx.x; t < created; t += 256) {
+        const unsigned h = lnew[t];
+        Key8 key;
+        key.q[0] = lkey[h][0];
+        key.q[1] = lkey[h][1];
+        const unsigned fr = (unsigned)(unsigned short)key.k[7];
+        lslot[h] = hash_insert(L.state, L.tkeys, fr << L.cap_f_log2, L.cap_f_mask, L.counters, key);
+    }
+    resolved = created;
+    __syncthreads();
+    if (real) {
+        int so[D + 1];
+#pragma unroll
+        for (int r = 0; r <= D; r++) {
+            const int li = lidx[r];
+            so[r] = li >= 0 ? (int)lslot[li] : -1 - li;
+        }
+        store_row<D + 1>(L.offsets + gp * (D + 1), so);
+        store_row<D + 1>(L.bary + gp * (D + 1), bary);
+    }
+  }
+}
+
+void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStream_t s) {
+    const long long total = (long long)L.Npad * L.n_frames;
+    // chunks per block: as many as leave >= 1024 blocks (a single frame or a cloud is a latency case: 150 blocks of
+    // 8 chunks kept three quarters of the chip idle for 106 us)
+    int n_chunks = LP_CHUNKS;
+    while (n_chunks > 1 && (total + 255) / 256 / n_chunks < 1024) n_chunks >>= 1;
+    const long long per_block = 256ll * n_chunks;
+    const dim3 grid((unsigned)((total + per_block - 1) / per_block)), block(256);
+    switch (L.d) {
+        case 1: lattice_points_kernel<1><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 2: lattice_points_kernel<2><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 3: lattice_points_kernel<3><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 4: lattice_points_kernel<4><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 5: lattice_points_kernel<5><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 6: lattice_points_kernel<6><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 7: lattice_points_kernel<7><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        default: break;
+    }
+    RV_LAUNCHED("lattice_points_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------
+// compaction: an exclusive scan over the slot occupancy numbers the vertices in slot order, i.e.
+// deterministically and frame by frame
+// ---------------------------------------------------------------------------------------------
+struct SlotFilled {
+    __device__ __forceinline__ int operator()(int st) const { return st == ST_FILLED ? 1 : 0; }
+};
+
+__global__ void __launch_bounds__(256)
+lattice_compact_kernel(LatticeDev L) {
+    const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= L.cap_total) return;
+    const bool filled = L.state[slot] == ST_FILLED;
+    const int id = L.slot_to_id[slot];
+    if (filled && (unsigned)id < (unsigned)L.m_bound) {
+        L.vkeys[2 * (size_t)id] = L.tkeys[2 * (size_t)slot];
+        L.vkeys[2 * (size_t)id + 1] = L.tkeys[2 * (size_t)slot + 1];
+    }
+    const unsigned cap_f = L.cap_f_mask + 1;
+    if ((slot & L.cap_f_mask) == 0) L.fstart[slot >> L.cap_f_log2] = id;   // first vertex id of the frame
+    if (slot == L.cap_total - 1) {
+        const int M = id + (filled ? 1 : 0);
+        L.counters[0] = M;
+        L.fstart[L.n_frames] = M;
+        if (M > L.m_bound) L.counters[1] = 1;
+    }
+    // load factor above 1/2 in a frame's region counts as overflow (checked at the region's last slot)
+    if ((slot & L.cap_f_mask) == L.cap_f_mask) {
+        const int first = L.slot_to_id[slot - L.cap_f_mask];
+        const int Mf = id + (filled ? 1 : 0) - first;
+        if ((unsigned)Mf > cap_f / 2) L.counters[1] = 1;
+    }
+}
+
+// offsets: slot -> vertex id; sort keys / payloads for the stable vertex-major ordering
+__global__ void __launch_bounds__(256)
+lattice_remap_kernel(LatticeDev L, unsigned* __restrict__ sort_keys, unsigned* __restrict__ sort_vals, long long n_entries) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_entries) return;
+    int id = L.slot_to_id[L.offsets[e]];
+    id = id < L.m_bound ? id : L.m_bound - 1;   // only after a (flagged) hash overflow
+    L.offsets[e] = id;
+    sort_keys[e] = (unsigned)id;
+    sort_vals[e] = (unsigned)e;
+}
+
+// blur neighbours (permutohedral.cpp:296-318).  For axis j == d the +-d write of the reference
+// lands on the coordinate that the d-length key ignores.
+__global__ void __launch_bounds__(256)
+lattice_neighbours_kernel(LatticeDev L) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int M = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
+    const int d = L.d;
+    if (gid >= (long long)M * (d + 1)) return;
+    const int j = (int)(gid / M);
+    const int id = (int)(gid - (long long)j * M);
+    Key8 key;
+    const unsigned long long* src = L.vkeys + 2 * (size_t)id;
+    key.q[0] = src[0];
+    key.q[1] = src[1];
+    Key8 n1 = key, n2 = key;
+    for (int k = 0; k < d; k++) { n1.k[k] = (short)(key.k[k] - 1); n2.k[k] = (short)(key.k[k] + 1); }
+    if (j < d) { n1.k[j] = (short)(key.k[j] + d); n2.k[j] = (short)(key.k[j] - d); }
+    const unsigned fbase = (unsigned)(unsigned short)key.k[7] << L.cap_f_log2;
+    const int s1 = hash_lookup(L.state, L.tkeys, fbase, L.cap_f_mask, n1);
+    const int s2 = hash_lookup(L.state, L.tkeys, fbase, L.cap_f_mask, n2);
+    L.nb1[(size_t)j * L.m_bound + id] = s1 < 0 ? -1 : L.slot_to_id[s1];
+    L.nb2[(size_t)j * L.m_bound + id] = s2 < 0 ? -1 : L.slot_to_id[s2];
+}
+
+// CSR over the sorted entries: point index, barycentric weight, per-vertex [start, end)
+__global__ void __launch_bounds__(256)
+lattice_csr_kernel(LatticeDev L, const unsigned* __restrict__ keys_sorted, const unsigned* __restrict__ vals_sorted,
+                   long long n_entries) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_entries) return;
+    const unsigned e = vals_sorted[k];
+    const unsigned key = keys_sorted[k];
+    L.csr_pw[k] = make_uint2(e / (unsigned)(L.d + 1), __float_as_uint(L.bary[e]));
+    if (k == 0 || keys_sorted[k - 1] != key) L.vstart[key] = (unsigned)k;
+    if (k == n_entries - 1 || keys_sorted[k + 1] != key) L.vend[key] = (unsigned)(k + 1);
+}
+
+void launch_vertex_order(const LatticeDev& L, SortBuffers& sb, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Vertex-major ordering by a counting sort (fast path, used when a frame has at most CS_MCAP
+// vertices -- the Segmenter kernel has ~300).  The entries of a frame are cut into wave-blocks of
+// CS_PIX points; every wave walks its block in order, 64 entries at a time, and ranks equal vertex
+// ids inside the chunk with ballots, so the order inside a vertex stays ascending in the point
+// index without any comparison sort:
+//   pass 1 (count)   per wave-block histogram over the frame's vertices (LDS) + slot -> id remap
+//   scan             per frame: vertex start offsets and per-(wave-block, vertex) bases
+//   pass 2 (scatter) same walk, entries land at base + rank
+// ---------------------------------------------------------------------------------------------
+constexpr int CS_PIX_MIN = 256;   // points per wave-block (LatticeDev::cs_pix): 256 .. 4096, a power of two
+constexpr int CS_MCAP = 4096;   // 4 waves x 4096 counters = 64 KB of LDS at the largest fast-path capacity (2^13 slots per frame)
+
+// bh holds, per frame, a dense [wave-block][vertex] matrix with row stride M_f; the frame's matrix
+// starts at wbpf * fstart[frame] (so the whole array needs wbpf * M_total words).
+template <bool SCATTER>
+__global__ void __launch_bounds__(256)
+csr_pass_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
+    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long gwb = (long long)blockIdx.x * 4 + wave;
+    const int frame = (int)(gwb / wbpf);
+    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
+    const int wb = (int)(gwb - (long long)frame * wbpf);
+    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const unsigned n_entries_total = (unsigned)((long long)L.n_frames * L.N * (L.d + 1));
+    unsigned* my = cs_cnt + (size_t)wave * mcap;
+    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    for (int lv = lane; lv < Mf; lv += 64) my[lv] = SCATTER ? row[lv] : 0u;
+    if (Mf == 0 && lane == 0) my[0] = 0xFFFFFFFFu;   // no vertices (overflow only): positions fail the bound check
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int dp1 = L.d + 1;
+    const long long p0 = (long long)wb * L.cs_pix;
+    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
+    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    // software pipeline: the next chunk's loads are in flight while the current chunk is ranked
+    auto fetch = [&](long long e, int& id, float& wgt) {
+        id = 0; wgt = 0.f;
+        if (e < eend) {
+            // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that
+            // every later kernel stays in bounds; the host discards the result
+            if (!SCATTER) { id = L.slot_to_id[L.offsets[e]]; id = id < L.m_bound ? id : L.m_bound - 1; }
+            else { id = L.offsets[e]; wgt = L.bary[e]; }
+        }
+    };
+    int id_n; float w_n;
+    fetch(ebeg + lane, id_n, w_n);
+    for (long long base = ebeg; base < eend; base += 64) {
+        const long long e = base + lane;
+        const bool valid = e < eend;
+        const int id = id_n;
+        const float wgt = w_n;
+        fetch(e + 64, id_n, w_n);
+        if (!SCATTER && valid) L.offsets[e] = id;    // slot -> vertex id, in place
+        int lv = valid ? id - f0 : -1;
+        if (lv >= Mf) lv = Mf - 1;                   // overflow case (flagged elsewhere): stay in bounds
+        if (valid && lv < 0) lv = 0;
+        if (!SCATTER) {
+            // counting needs no order: LDS atomics (same-address lanes serialise in hardware, still an
+            // order of magnitude cheaper than ranking the chunk with ballots)
+            if (valid) atomicAdd(&my[lv], 1u);
+            continue;
+        }
+        bool pending = valid;
+        // distinct vertex ids of a chunk touch distinct counters, so the loop needs no ordering
+        // inside a chunk; one fence per chunk orders the counters between chunks
+        for (;;) {
+            const unsigned long long todo = __ballot(pending);
+            if (!todo) break;
+            const int leader = __ffsll((long long)todo) - 1;
+            const int k = __shfl(lv, leader, 64);
+            const bool same = pending && lv == k;
+            const unsigned long long m = __ballot(same);
+            const unsigned c = (unsigned)__popcll(m);
+            if (SCATTER) {
+                const unsigned b = my[k];
+                if (same) {
+                    const unsigned pos = b + (unsigned)__popcll(m & lt);
+                    if (pos < n_entries_total) {
+                        L.csr_pw[pos] = make_uint2((unsigned)(e / dp1), __float_as_uint(wgt));   // one 8-byte store
+                    }
+                }
+                if (lane == leader) my[k] = b + c;
+            } else {
+                if (lane == leader) my[k] = my[k] + c;
+            }
+            pending = pending && !same;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+    if (!SCATTER) {
+        for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
+    }
+}
+
+// Count pass, four entries per lane.  The generic pass above walks a wave-block 64 entries at a time with two DEPENDENT
+// loads per step (slot, then slot -> vertex id): PMC showed its waves waiting 91 % of their cycles.  Counting needs no
+// order, so a lane takes four consecutive entries at once -- one 16-byte load, four id gathers in flight together, one
+// 16-byte store of the remapped ids -- and a wave-block is done in 7 steps instead of 28.
+__global__ void __launch_bounds__(256)
+csr_count_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
+    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long gwb = (long long)blockIdx.x * 4 + wave;
+    const int frame = (int)(gwb / wbpf);
+    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
+    const int wb = (int)(gwb - (long long)frame * wbpf);
+    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    unsigned* my = cs_cnt + (size_t)wave * mcap;
+    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    for (int lv = lane; lv < Mf; lv += 64) my[lv] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int dp1 = L.d + 1;
+    const long long p0 = (long long)wb * L.cs_pix;
+    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
+    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
+    auto fetch = [&](long long e, int (&sl)[4]) {   // slots of entries e .. e + 3 (clamped into the wave-block)
+        if (e + 4 <= eend) {
+            load_row<4>(L.offsets + e, sl);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) sl[k] = e + k < eend ? L.offsets[e + k] : 0;
+        }
+    };
+    int sl_n[4];
+    fetch(ebeg + 4 * lane < eend ? ebeg + 4 * lane : ebeg, sl_n);
+    for (long long base = ebeg; base < eend; base += 256) {
+        const long long e = base + 4 * lane;
+        int sl[4], id[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sl[k] = sl_n[k];
+        const bool any = e < eend;
+        if (any) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) id[k] = L.slot_to_id[sl[k]];   // four gathers in flight
+        }
+        const long long en = e + 256;
+        fetch(en < eend ? en : ebeg, sl_n);                             // the next step's slots travel meanwhile
+        if (!any) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that every later
+            // kernel stays in bounds; the host discards the result
+            id[k] = id[k] < L.m_bound ? id[k] : L.m_bound - 1;
+        }
+        if (e + 4 <= eend) {
+            store_row<4>(L.offsets + e, id);                            // slot -> vertex id, in place
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (e + k < eend) L.offsets[e + k] = id[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (e + k >= eend) continue;
+            int lv = id[k] - f0;
+            lv = lv < Mf ? lv : Mf - 1;   // overflow case (flagged elsewhere): stay in bounds
+            lv = lv < 0 ? 0 : lv;
+            if (Mf > 0) atomicAdd(&my[lv], 1u);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
+}
+
+// Scatter pass with one lane per POINT (the generic pass above has one lane per entry and ranks ~10
+// distinct vertices per 64 entries; PMC: 438 vector instructions per 64 entries).  A chunk is 64
+// consecutive points x DP1 entries.  For every distinct vertex k of the chunk the lanes that hold k
+// -- in any of their DP1 slots, at most one per lane since a point's vertices are distinct -- are
+// found with DP1 ballots; their union, masked to the lower lanes, is the rank of a point among the
+// chunk's entries of k, i.e. ascending point order again.  Neighbouring points share their simplex,
+// so a chunk has ~12-20 distinct vertices for 448 entries.
+template <int DP1>
+__global__ void __launch_bounds__(256)
+csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int mcap) {
+    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long gwb = (long long)blockIdx.x * 4 + wave;
+    const int frame = (int)(gwb / wbpf);
+    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
+    const int wb = (int)(gwb - (long long)frame * wbpf);
+    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const unsigned n_entries_total = (unsigned)((long long)L.n_frames * L.N * DP1);
+    unsigned* my = cs_cnt + (size_t)wave * mcap;
+    const unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    for (int lv = lane; lv < Mf; lv += 64) my[lv] = row[lv];
+    if (Mf == 0 && lane == 0) my[0] = 0xFFFFFFFFu;   // no vertices (overflow only): positions fail the bound check
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int p0 = wb * L.cs_pix;
+    const int p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    for (int pc = p0; pc < p1; pc += 64) {
+        const int p = pc + lane;
+        const bool valid = p < p1;
+        const size_t gp = (size_t)frame * L.N + (valid ? p : p1 - 1);
+        int lv[DP1];
+        float w[DP1];
+        load_row<DP1>(L.offsets + gp * DP1, lv);
+        load_row<DP1>(L.bary + gp * DP1, w);
+#pragma unroll
+        for (int j = 0; j < DP1; j++) {
+            lv[j] -= f0;
+            lv[j] = lv[j] < Mf ? lv[j] : Mf - 1;   // overflow case (flagged elsewhere): stay in bounds
+            lv[j] = lv[j] < 0 ? 0 : lv[j];
+        }
+        unsigned pend = valid ? (1u << DP1) - 1u : 0u;
+#pragma unroll
+        for (int j = 0; j < DP1; j++) {
+            for (;;) {
+                const unsigned long long todo = __ballot((pend >> j) & 1u);
+                if (!todo) break;
+                const int leader = __ffsll((long long)todo) - 1;
+                const int k = __builtin_amdgcn_readlane(lv[j], leader);
+                // slots below j are already empty for every lane; a vertex handled in an earlier pass
+                // was removed from all slots then, so it cannot come up again in this chunk
+                unsigned long long all = 0ull;
+                float wsel = 0.0f;
+                bool hit = false;
+#pragma unroll
+                for (int jj = j; jj < DP1; jj++) {
+                    const bool same = ((pend >> jj) & 1u) && lv[jj] == k;
+                    all |= __ballot(same);
+                    if (same) { wsel = w[jj]; hit = true; pend &= ~(1u << jj); }
+                }
+                const unsigned b = my[k];
+                if (hit) {
+                    const unsigned pos = b + (unsigned)__popcll(all & lt);
+                    if (pos < n_entries_total) L.csr_pw[pos] = make_uint2((unsigned)gp, __float_as_uint(wsel));
+                }
+                if (lane == leader) my[k] = b + (unsigned)__popcll(all);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+}
+
+// per frame: bh[wb][lv] (counts) -> absolute base of (wave-block, vertex) in the csr arrays; vstart / vend per vertex.
+// Two launches over (frame, group of 64 vertices) blocks of 1024 threads = 16 wave-block segments x 64 vertices: the
+// first adds up the columns (per segment and whole), the second turns them into running bases.  The only thing a group
+// needs from the others is the number of entries of the vertices before it, which it adds up itself from the column
+// totals -- so the groups of a frame run side by side.  (Until round 3 one block per frame walked its groups one after
+// the other: 139 us for a single 640x480 frame, 461 us for a 1.1 M-point cloud, on the critical path of both.)
+constexpr int CS_SEGS = 16;
+__device__ __forceinline__ size_t csr_aux_offset(const LatticeDev& L, int wbpf) { return (size_t)wbpf * ((size_t)L.m_bound + 64); }
+
+__global__ void __launch_bounds__(1024)
+csr_total_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap, int n_groups) {
+    __shared__ unsigned sseg[CS_SEGS][64];
+    const int frame = blockIdx.x / n_groups, grp = blockIdx.x - frame * n_groups;
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const int lv0 = grp * 64;
+    if (lv0 >= Mf) return;                   // whole block
+    const int lvl = threadIdx.x & 63, seg = threadIdx.x >> 6;
+    const int sw = (wbpf + CS_SEGS - 1) / CS_SEGS;
+    const int w0 = seg * sw, w1 = (w0 + sw < wbpf) ? w0 + sw : wbpf;
+    const unsigned* fb = bh + (size_t)wbpf * f0;   // dense [wave-block][vertex] matrix, row stride Mf
+    unsigned* vtot = bh + csr_aux_offset(L, wbpf);
+    unsigned* segsum = vtot + L.m_bound;
+    const int lv = lv0 + lvl;
+    const bool ok = lv < Mf;
+    unsigned sum = 0;
+    if (ok) for (int w = w0; w < w1; w++) sum += fb[(size_t)w * Mf + lv];
+    sseg[seg][lvl] = sum;
+    if (ok) segsum[(size_t)(f0 + lv) * CS_SEGS + seg] = sum;
+    __syncthreads();
+    if (seg == 0 && ok) {
+        unsigned total = 0;
+#pragma unroll
+        for (int q = 0; q < CS_SEGS; q++) total += sseg[q][lvl];
+        vtot[f0 + lv] = total;
+    }
+}
+
+__global__ void __launch_bounds__(1024)
+csr_scan_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap, int n_groups) {
+    __shared__ unsigned red[16];
+    __shared__ unsigned vbase[64];
+    const int frame = blockIdx.x / n_groups, grp = blockIdx.x - frame * n_groups;
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const int lv0 = grp * 64;
+    if (lv0 >= Mf) return;                   // whole block
+    const int lvl = threadIdx.x & 63, seg = threadIdx.x >> 6;
+    const int sw = (wbpf + CS_SEGS - 1) / CS_SEGS;
+    const int w0 = seg * sw, w1 = (w0 + sw < wbpf) ? w0 + sw : wbpf;
+    unsigned* fb = bh + (size_t)wbpf * f0;
+    const unsigned* vtot = bh + csr_aux_offset(L, wbpf);
+    const unsigned* segsum = vtot + L.m_bound;
+    const unsigned frame_base = (unsigned)((long long)frame * L.N * (L.d + 1));
+    // entries of the frame's vertices before this group
+    unsigned part = 0;
+    for (int v = threadIdx.x; v < lv0; v += 1024) part += vtot[f0 + v];
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+    if (lvl == 0) red[seg] = part;
+    __syncthreads();
+    unsigned carry = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) carry += red[q];
+    const int lv = lv0 + lvl;
+    const bool ok = lv < Mf;
+    if (seg == 0) {
+        const unsigned total = ok ? vtot[f0 + lv] : 0u;
+        unsigned incl = total;                // inclusive scan of the 64 column totals (one wave)
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned t = __shfl_up(incl, off, 64);
+            if (lvl >= off) incl += t;
+        }
+        vbase[lvl] = carry + incl - total;
+        if (ok) {
+            L.vstart[f0 + lv] = frame_base + carry + incl - total;
+            L.vend[f0 + lv] = frame_base + carry + incl;
+        }
+    }
+    __syncthreads();
+    if (ok) {
+        unsigned run = frame_base + vbase[lvl];
+        for (int q = 0; q < seg; q++) run += segsum[(size_t)(f0 + lv) * CS_SEGS + q];
+        for (int w = w0; w < w1; w++) {
+            const unsigned t = fb[(size_t)w * Mf + lv];
+            fb[(size_t)w * Mf + lv] = run;
+            run += t;
+        }
+    }
+}
+
+bool csr_fast_path(const LatticeDev& L) { return ((L.cap_f_mask + 1) / 2) <= (unsigned)CS_MCAP; }
+size_t csr_fast_bytes(const LatticeDev& L) {
+    const size_t wbpf = ((size_t)L.N + L.cs_pix - 1) / L.cs_pix;
+    // the [wave-block][vertex] matrices of all frames, then per vertex its column total and CS_SEGS segment sums
+    return (wbpf * ((size_t)L.m_bound + 64) + (size_t)L.m_bound * (1 + CS_SEGS)) * sizeof(unsigned);
+}
+
+// phase 0: everything; 1: everything but the scatter of the counting-sort path (vertex numbering, neighbours, counts,
+// list bounds, launch order: all the splat planner needs); 2: that scatter.  (The radix-sort path does it all in 0 / 1.)
+void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_entries, hipStream_t s, int phase) {
+    const bool fast = csr_fast_path(L) && sb.block_hist;
+    if (phase == 2) {
+        if (!fast) return;
+        const int mcap = (int)((L.cap_f_mask + 1) / 2);
+        const int wbpf = (L.N + L.cs_pix - 1) / L.cs_pix;
+        const long long waves = (long long)wbpf * L.n_frames;
+        const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+        const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
+        if (L.d == 6) csr_scatter_kernel<7><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        else if (L.d == 5) csr_scatter_kernel<6><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        else if (L.d == 2) csr_scatter_kernel<3><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        else csr_pass_kernel<true><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        RV_LAUNCHED("csr_scatter_kernel");
+        return;
+    }
+    const unsigned cap = L.cap_total;
+    {
+        size_t temp = sb.scan_temp_bytes;
+        auto in = rocprim::make_transform_iterator(L.state, SlotFilled());
+        (void)rocprim::exclusive_scan(sb.scan_temp, temp, in, L.slot_to_id, 0, (size_t)cap, rocprim::plus<int>(), s);
+    }
+    lattice_compact_kernel<<<dim3((cap + 255) / 256), dim3(256), 0, s>>>(L);
+    const long long nb_threads = (long long)L.m_bound * (L.d + 1);
+    lattice_neighbours_kernel<<<dim3((unsigned)((nb_threads + 255) / 256)), dim3(256), 0, s>>>(L);
+    RV_LAUNCHED("lattice_compact_kernel / lattice_neighbours_kernel");
+    if (fast) {
+        const int mcap = (int)((L.cap_f_mask + 1) / 2);
+        const int wbpf = (L.N + L.cs_pix - 1) / L.cs_pix;
+        const long long waves = (long long)wbpf * L.n_frames;
+        const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+        const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
+        csr_count_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        const int n_groups = (mcap + 63) / 64;
+        csr_total_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);
+        csr_scan_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);
+        RV_LAUNCHED("csr_count_kernel / csr_total_kernel / csr_scan_kernel");
+        if (phase == 0) launch_lattice_finish(L, sb, n_entries, s, 2);
+    } else {
+        lattice_remap_kernel<<<dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s>>>(L, sb.keys_in, sb.vals_in, n_entries);
+        // stable radix sort by vertex id: equal keys keep ascending entry (= point) order
+        size_t temp = sb.temp_bytes;
+        (void)rocprim::radix_sort_pairs(sb.temp, temp, sb.keys_in, sb.keys_out, sb.vals_in, sb.vals_out, (size_t)n_entries, 0,
+                                        (unsigned)sb.key_bits, s);
+        lattice_csr_kernel<<<dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s>>>(L, sb.keys_out, sb.vals_out, n_entries);
+        RV_LAUNCHED("lattice_remap_kernel / radix sort / lattice_csr_kernel");
+    }
+    launch_vertex_order(L, sb, s);
+}
+
+// Launch order of the vertices for the splat: per frame, longest list first.  vorder[fstart[f] + k]
+// is the k-th longest vertex of frame f (ids are frame-contiguous, so a sort by (frame, -length)
+// keeps every frame in its own id range).  The splat forms its groups of G vertices inside a frame
+// and starts all frames' heaviest groups first (LPT: the serial chains of the heaviest vertices
+// start at t = 0).
+__global__ void __launch_bounds__(256)
+vertex_len_kernel(LatticeDev L, unsigned* __restrict__ key, unsigned* __restrict__ ids, int len_shift) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= L.m_bound) return;
+    const int M = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
+    unsigned k = 0xFFFFFFFFu;  // unused ids sort to the end
+    if (v < M) {
+        atomicMax(&L.counters[3], (int)(L.vend[v] - L.vstart[v]));   // the longest chain of the chunk (rvseg_last_schedule)
+        const unsigned len = (L.vend[v] - L.vstart[v]) >> len_shift;
+        const unsigned frame = (unsigned)(unsigned short)(L.vkeys[2 * (size_t)v + 1] >> 48);
+        k = ((frame < 1023u ? frame : 1022u) << 22) | (0x3FFFFFu - (len < 0x3FFFFFu ? len : 0x3FFFFFu));
+    }
+    key[v] = k;
+    ids[v] = (unsigned)v;
+}
+
+void launch_vertex_order(const LatticeDev& L, SortBuffers& sb, hipStream_t s) {
+    int len_shift = 0;   // a list has at most N entries
+    while (((long long)L.N >> len_shift) >= (1 << 22)) len_shift++;
+    vertex_len_kernel<<<dim3((unsigned)((L.m_bound + 255) / 256)), dim3(256), 0, s>>>(L, sb.keys_in, sb.vals_in, len_shift);
+    size_t temp = sb.temp_bytes;
+    (void)rocprim::radix_sort_pairs(sb.temp, temp, sb.keys_in, sb.keys_out, sb.vals_in, L.vorder, (size_t)L.m_bound, 0, 32, s);
+    RV_LAUNCHED("vertex_len_kernel / radix sort");
+}
+
+size_t scan_temp_bytes(unsigned cap) {
+    size_t temp = 0;
+    int* nul = nullptr;
+    auto in = rocprim::make_transform_iterator(nul, SlotFilled());
+    (void)rocprim::exclusive_scan(nullptr, temp, in, nul, 0, (size_t)cap, rocprim::plus<int>(), (hipStream_t)0);
+    return temp;
+}
+
+size_t sort_temp_bytes(long long n_entries, int key_bits) {
+    size_t temp = 0;
+    unsigned* nul = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, temp, nul, nul, nul, nul, (size_t)n_entries, 0, (unsigned)key_bits, (hipStream_t)0);
+    return temp;
+}
+
+// norm values gathered into CSR order once the normaliser exists
+__global__ void __launch_bounds__(256)
+csr_norm_kernel(const uint2* __restrict__ csr_pw, const float* __restrict__ norm, float* __restrict__ csr_nrm, long long n_entries,
+                const int* __restrict__ counters) {
+    if (counters[1]) return;   // hash overflow (flagged): the csr arrays are incomplete
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_entries) csr_nrm[k] = norm[csr_pw[k].x];
+}
+
+void launch_csr_norm(const LatticeDev& L, long long n_entries, hipStream_t s) {
+    csr_norm_kernel<<<dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s>>>(L.csr_pw, L.norm, L.csr_nrm, n_entries, L.counters);
+    RV_LAUNCHED("csr_norm_kernel");
+}
+int csr_pix_min() { return CS_PIX_MIN; }
+
+}  // namespace rvseg

@@ -1,4 +1,5 @@
-// Device-side views and launch interface of the lattice / mean-field kernels (kernels_crf.hip).
+// Device-side views and launch interface of the lattice / splat / mean-field kernels
+// (kernels_lattice.hip, kernels_splat.hip, kernels_resident.hip, kernels_meanfield.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -123,11 +124,17 @@ void launch_csr_norm(const LatticeDev& L, long long n_entries, hipStream_t s);
 // own_q: src is the mean-field loop's own Q * norm (finite, non-negative): enables the select-free producer
 void launch_splat(const LatticeDev& L, const ValueView& src, int C, int mode, float* values, hipStream_t s, bool own_q = false,
                   const SplatResidentDev* resident = nullptr, int slot = 0);
+// blocks ("items") of the list-major walk with `per_item` vertices each
+unsigned splat_walk_items(const LatticeDev& L, int per_item);
 // builds the resident band schedule from the counting-sort table (after launch_lattice_finish)
 void launch_resident_plan(const LatticeDev& L, const SplatResidentDev& r, hipStream_t s);
 // how many blocks of the resident splat kernel fit on the device at once (0: unknown)
 int resident_block_capacity(int chunk);
 int resident_cu_count();
+// the splat of C = 8 / 9 classes over the resident schedule; false: the kernel could not be set up or launched, the
+// caller walks the lists the list-major way
+bool launch_splat_resident(const LatticeDev& L, const SplatResidentDev& R, int C, const float* src, float* values, int slot,
+                           hipStream_t s);
 float* launch_blur(const LatticeDev& L, int C, bool seq, bool reverse, float* a, float* b, hipStream_t s, bool small_blocks = false);
 // out_mode 0: plain, 1: normaliser, 2: inference update (tmp -= (-w) * (sliced * norm)),
 // 3: normaliser 1/(sliced + 1e-20) (NORMALIZE_BEFORE / NORMALIZE_AFTER)

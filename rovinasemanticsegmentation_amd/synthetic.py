@@ -100,7 +100,7 @@ def make_batch(n, W=640, H=480, holes=False, seed=1234, start=0, scene="flat"):
 
 
 # Lattice regimes of the DenseCRF frame path, each pinned to one side of a limit of the lattice code (csrc/rvseg_crf.h,
-# kernels_crf.hip).  Both pairwise kernels (dcrf_xyz_kernel, dcrf_rgb_kernel) are scaled by `s`; `bounds` holds, per
+# kernels_lattice.hip).  Both pairwise kernels (dcrf_xyz_kernel, dcrf_rgb_kernel) are scaled by `s`; `bounds` holds, per
 # frame of `frames`, the inclusive range its oracle vertex count must fall in (holes on, the default seed).  The CPU
 # suite recomputes the counts (tests/test_oracle_crf.py), so a change of the generator fails there and never silently
 # moves a GPU test off its edge.  Limits: MF_LDS_BYTES = 24 KB of vertex values per frame (Mf <= 512 for 9 classes,

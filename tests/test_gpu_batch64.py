@@ -3,7 +3,7 @@ the GPU: one chunk of 64 synthetic 640x480 key frames (holes on) through rvseg_s
 with max_batch = 64, RF (bench forest: 4 trees x 2^14 leaves, C = 9) + 5-iteration DenseCRF.
 
   (a) every frame bit-exact against the CPU oracle (labels, and marginals well inside the north star's
-      1e-4) -- frames 0, 9, 31, 63 sit in different XCD launch groups of the splat (kernels_crf.hip),
+      1e-4) -- frames 0, 9, 31, 63 sit in different XCD launch groups of the splat (kernels_splat.hip),
       all 64 are compared; the oracle frames run in a thread pool (ctypes releases the GIL);
   (b) all 64 frames against single-frame GPU runs of the same context parameters.
 """
@@ -62,7 +62,7 @@ def test_batch64_headline_config_matches_oracle_and_single_frame_runs(gpu_ctx_fa
         assert np.array_equal(marg[i], wm), "marginals of frame %d are not bit-identical to the oracle" % i
 
     # (b) the same frames one at a time on the GPU (chunk of 1: other launch shapes, no XCD groups; the long lists of
-    # such a launch are summed by scan blocks, kernels_crf.hip: splat_scan_item), and again with the serial adder only
+    # such a launch are summed by scan blocks, kernels_splat.hip: splat_scan_item), and again with the serial adder only
     one_ctx = gpu_ctx_factory(max_batch=1, **kw)
     one_ctx.forest_load(blob)
     for i in range(N_FRAMES):

@@ -11,12 +11,12 @@ buffers and streams by the layer index.  Coverage of each switch, and the test t
                               test_layer_schedules_agree.
   launch_softmax_unary,       fused C (2-10, 12, 16, 21) with DP1 = 7 (d = 6) and runtime d (d = 5), and unfused C (1,
   launch_mf_update            11, 13-15, 17, 20, 24, 25, 32, 33, 48, 64): test_crf_infer_every_class_count.  In the
-  (kernels_crf.hip)           frame path: every C of the layouts of test_frame_path_every_layer_layout, the fused (21)
+  (kernels_meanfield.hip)     frame path: every C of the layouts of test_frame_path_every_layer_layout, the fused (21)
                               and unfused (22) layer side by side in (21, 22).
   seq = C <= 2                double-precision blur and sequential slice: C = 1, 2 in test_crf_infer_every_class_count,
                               (2,), (1, 9), (2, .., 9) and single 2 in the frame path, (2,) and (1, 9) in the cloud path.
   splat_group_pass            the classes of a pass (16 at most) by bucket, FULL where n fills it: n = 1, 2, 3 and 4 (FULL),
-  (kernels_crf.hip)           5-7 and 8 (FULL, 24 = 16 + 8), 9 (FULL, 25 = 16 + 9), 10-15 and 16 (FULL); 2, 3 and 4 passes
+  (kernels_splat.hip)         5-7 and 8 (FULL, 24 = 16 + 8), 9 (FULL, 25 = 16 + 9), 10-15 and 16 (FULL); 2, 3 and 4 passes
                               (C = 17-32, 33-48, 64), fused (mode 0) and unfused (mode 1) counts:
                               test_crf_infer_every_class_count; crf_infer_multi (mode 1 for every C):
                               test_crf_infer_multi_class_counts.
@@ -48,7 +48,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
 _POOL = max(1, min(os.cpu_count() or 1, 16))
-# kernels_crf.hip: mf_fused_supported -- class counts with a fused softmax_unary / mf_update instantiation
+# kernels_meanfield.hip: mf_fused_supported -- class counts with a fused softmax_unary / mf_update instantiation
 FUSED = frozenset([2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21])
 
 

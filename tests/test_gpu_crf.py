@@ -19,11 +19,11 @@ def _features(seed, N, d, spread=4.0):
     return (rng.random((N, d)) * spread - spread / 3).astype(np.float32)
 
 
-LP_SET, LP_CHUNKS = 512, 8   # kernels_crf.hip: lattice_points_kernel's block-local key set, 256-point chunks per block
+LP_SET, LP_CHUNKS = 512, 8   # kernels_lattice.hip: lattice_points_kernel's block-local key set, 256-point chunks per block
 
 
 def lattice_points_chunks(N):
-    """kernels_crf.hip: launch_lattice_points -- 256-point chunks per block, as many (up to 8) as leave >= 1024 blocks."""
+    """kernels_lattice.hip: launch_lattice_points -- 256-point chunks per block, as many (up to 8) as leave >= 1024 blocks."""
     n_chunks = LP_CHUNKS
     while n_chunks > 1 and (N + 255) // 256 // n_chunks < 1024:
         n_chunks >>= 1
@@ -102,7 +102,7 @@ def _chain_features(kind, N, d, rng):
 def test_normaliser_ordered_sums_by_wave_scans_equal_the_serial_chain(gpu_ctx_factory, oracle, kind):
     """The normaliser's splat adds a vertex's barycentric weights in list order in fp32.  The default kernel does that
     with exact wave scans inside a binade and falls back to one addition per entry where a tile crosses a binade, holds
-    a round-to-even tie or a negative weight (kernels_crf.hip: ordered_tile_sum); rvseg_schedule.serial_chains = 1 is
+    a round-to-even tie or a negative weight (kernels_splat.hip: ordered_tile_sum); rvseg_schedule.serial_chains = 1 is
     the plain dependent chain.  Both must give the oracle's marginals bit for bit on lists of 10^5 entries -- a single
     wrong rounding of a normaliser shows in every marginal of its simplex."""
     rng = np.random.default_rng(len(kind))
@@ -123,7 +123,7 @@ def test_normaliser_ordered_sums_by_wave_scans_equal_the_serial_chain(gpu_ctx_fa
 def test_long_lists_summed_by_scan_blocks_equal_the_serial_adder(gpu_ctx_factory, oracle, C, kind):
     """Launches of a few frames (here: one cloud) give every list of 16 384 entries and more a scan block: one wave per
     class adds the tile's products with ordered_tile_sum instead of the serial adder's 128 dependent additions
-    (kernels_crf.hip: splat_scan_item).  Lists of 10^5 entries, 8 and 9 classes (the two block shapes), against the
+    (kernels_splat.hip: splat_scan_item).  Lists of 10^5 entries, 8 and 9 classes (the two block shapes), against the
     oracle bit for bit, with rvseg_schedule.serial_chains = 1 (the serial adder everywhere) as the second witness."""
     rng = np.random.default_rng(C * 7 + len(kind))
     N, d = 120000, 6

@@ -280,7 +280,7 @@ def test_lattice_bands_hold_their_vertex_counts(oracle):
             assert lo <= m <= hi, (name, i, m, (lo, hi))
 
 
-# class count of each band that straddles the LDS edges of the mean-field update and the blur (kernels_crf.hip), and
+# class count of each band that straddles the LDS edges of the mean-field update and the blur (kernels_meanfield.hip), and
 # which of the two edges it straddles
 LDS_BANDS = {"lds_c4": (4, "both"), "lds_c12": (12, "both"), "lds_c16": (16, "both"),
              "mf_lds_c21": (21, "update"), "blur_lds_c21": (21, "blur")}
