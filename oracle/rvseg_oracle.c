@@ -563,7 +563,8 @@ void orc_normals_nz(int W, int H, const float *cloud, float *nz_out, float *dist
             if (!(smoothing > 2.0f)) continue;
             int rect = (int)smoothing, rect2 = rect / 2;
             int sx = ci - rect2, sy = ri - rect2;
-            int64_t gx[3] = { 0, 0, 0 }, gy[3] = { 0, 0, 0 };
+            /* unsigned: a sum of clamped outliers may pass 2^63, which wraps (defined) and is reinterpreted below */
+            uint64_t gx[3] = { 0, 0, 0 }, gy[3] = { 0, 0, 0 };
             unsigned cnt_x = 0, cnt_y = 0;
             for (int y = sy; y < sy + rect; y++)
                 for (int x = sx; x < sx + rect; x++) {
@@ -574,12 +575,12 @@ void orc_normals_nz(int W, int H, const float *cloud, float *nz_out, float *dist
                         const float *dn = cloud + ((size_t)(y + 1) * W + x) * 3, *up = cloud + ((size_t)(y - 1) * W + x) * 3;
                         for (int k = 0; k < 3; k++) { dx[k] = r[k] - l[k]; dy[k] = dn[k] - up[k]; }
                     }
-                    if (finite3(dx)) { cnt_x++; for (int k = 0; k < 3; k++) gx[k] += to_fix32(dx[k]); }
-                    if (finite3(dy)) { cnt_y++; for (int k = 0; k < 3; k++) gy[k] += to_fix32(dy[k]); }
+                    if (finite3(dx)) { cnt_x++; for (int k = 0; k < 3; k++) gx[k] += (uint64_t)to_fix32(dx[k]); }
+                    if (finite3(dy)) { cnt_y++; for (int k = 0; k < 3; k++) gy[k] += (uint64_t)to_fix32(dy[k]); }
                 }
             if (cnt_x == 0 || cnt_y == 0) continue;
             double GX[3], GY[3];
-            for (int k = 0; k < 3; k++) { GX[k] = (double)gx[k] * (1.0 / 4294967296.0); GY[k] = (double)gy[k] * (1.0 / 4294967296.0); }
+            for (int k = 0; k < 3; k++) { GX[k] = (double)(int64_t)gx[k] * (1.0 / 4294967296.0); GY[k] = (double)(int64_t)gy[k] * (1.0 / 4294967296.0); }
             /* normal_vector = gradient_y.cross(gradient_x) */
             double n0 = GY[1] * GX[2] - GY[2] * GX[1];
             double n1 = GY[2] * GX[0] - GY[0] * GX[2];

@@ -291,7 +291,8 @@ normal_feature_kernel(FrameGeom g, const float4* __restrict__ cloud_all, const u
         if (rect > 0 && finite_f(zc)) {
             const int rect2 = rect >> 1;
             const int sx = ci - rect2, sy = ri - rect2;
-            long long gx0 = 0, gx1 = 0, gx2 = 0, gy0 = 0, gy1 = 0, gy2 = 0;
+            // unsigned like the tiled kernel's table: a sum of clamped outliers may pass 2^63, which wraps and is reinterpreted below
+            unsigned long long gx0 = 0, gx1 = 0, gx2 = 0, gy0 = 0, gy1 = 0, gy2 = 0;
             int cnt_x = 0, cnt_y = 0;
             for (int y = sy; y < sy + rect; y++) {
                 for (int x = sx; x < sx + rect; x++) {
@@ -303,17 +304,17 @@ normal_feature_kernel(FrameGeom g, const float4* __restrict__ cloud_all, const u
                         dy0 = dn.x - up.x; dy1 = dn.y - up.y; dy2 = dn.z - up.z;
                     }
                     if (finite_f(dx0) && finite_f(dx1) && finite_f(dx2)) {
-                        cnt_x++; gx0 += to_fix32(dx0); gx1 += to_fix32(dx1); gx2 += to_fix32(dx2);
+                        cnt_x++; gx0 += (unsigned long long)to_fix32(dx0); gx1 += (unsigned long long)to_fix32(dx1); gx2 += (unsigned long long)to_fix32(dx2);
                     }
                     if (finite_f(dy0) && finite_f(dy1) && finite_f(dy2)) {
-                        cnt_y++; gy0 += to_fix32(dy0); gy1 += to_fix32(dy1); gy2 += to_fix32(dy2);
+                        cnt_y++; gy0 += (unsigned long long)to_fix32(dy0); gy1 += (unsigned long long)to_fix32(dy1); gy2 += (unsigned long long)to_fix32(dy2);
                     }
                 }
             }
             if (cnt_x > 0 && cnt_y > 0) {
                 const double k = 1.0 / 4294967296.0;
-                const double GX0 = (double)gx0 * k, GX1 = (double)gx1 * k, GX2 = (double)gx2 * k;
-                const double GY0 = (double)gy0 * k, GY1 = (double)gy1 * k, GY2 = (double)gy2 * k;
+                const double GX0 = (double)(long long)gx0 * k, GX1 = (double)(long long)gx1 * k, GX2 = (double)(long long)gx2 * k;
+                const double GY0 = (double)(long long)gy0 * k, GY1 = (double)(long long)gy1 * k, GY2 = (double)(long long)gy2 * k;
                 const double n0 = GY1 * GX2 - GY2 * GX1;
                 const double n1 = GY2 * GX0 - GY0 * GX2;
                 const double n2 = GY0 * GX1 - GY1 * GX0;

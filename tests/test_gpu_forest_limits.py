@@ -1,0 +1,215 @@
+"""The forest walk (csrc/kernels_rf.hip, rvseg_api.cpp: upload_forest) at every limit of its code: tree counts and shapes
+at the lane arithmetic, degenerate trees, the strict '<' at special values on all three walkers (forest_eval_kernel,
+the 8-byte and the 16-byte lazy walk), the node formats on both sides of 2^20 nodes, the `wave_inside` fast path at its
+own boundary, the resize table in LDS and through L1, patch_size_reduce 1 and 16.  The recipes come from frame_cases.py
+and are pinned to their edges by test_frame_cases_cpu.py.  Every comparison is of float32 bit patterns of the whole
+output against the CPU oracle (which the CPU pins hold against the plain walker of frame_cases)."""
+import numpy as np
+import pytest
+
+import frame_cases as fc
+from rovinasemanticsegmentation_amd import synthetic
+
+pytestmark = pytest.mark.gpu
+
+
+def same(got, want, what=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == np.float32, what
+    diff = fc.bits(got) != fc.bits(want)
+    assert not diff.any(), "%s: %d of %d values differ, first at %s" % (what, diff.sum(), diff.size, np.argwhere(diff)[0])
+
+
+def frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb, depth, calib, what=""):
+    """segment_frames (no labels, no CRF) of n frames against oracle.rf_frame; returns the oracle's point counts"""
+    n = len(rgb)
+    ctx = gpu_ctx_factory(max_batch=max(n, 1), **kw)
+    try:
+        ctx.forest_load(blob)
+        out = ctx.segment_frames(rgb, depth, calib, want_labels=False)
+        info = ctx.forest_info()
+    finally:
+        ctx.close()
+    forest = oracle.Forest(blob)
+    p = oracle.default_params(**kw)
+    counts = []
+    for i in range(n):
+        want, P = oracle.rf_frame(p, forest, 1, rgb[i], depth[i], calib)
+        same(out["posteriors"][i], want, "%s frame %d" % (what, i))
+        counts.append(P)
+    return counts, info
+
+
+@pytest.fixture(scope="module")
+def eval_ctx(gpu_ctx_factory):
+    ctx = gpu_ctx_factory(width=64, height=48, patch_size=9, patch_size_reduce=1)
+    assert ctx.feature_length == fc.EVAL_D
+    return ctx
+
+
+@pytest.fixture(scope="module")
+def big3():
+    return fc.big_models(3)
+
+
+@pytest.fixture(scope="module")
+def big4():
+    return fc.big_models(4)
+
+
+@pytest.fixture(scope="module")
+def frame1():
+    rgb, depth = fc.small_frame(1)
+    return rgb[None], depth[None], synthetic.make_calib(64, 48)
+
+
+# ---- 1. tree counts --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", fc.EVAL_TREES)
+def test_forest_eval_tree_counts(eval_ctx, oracle, T):
+    trees, blob = fc.small_forest(T, T, 3, fc.EVAL_D)
+    X = fc.eval_points(T, 257)
+    eval_ctx.forest_load(blob)
+    assert eval_ctx.forest_info()["n_trees"] == T
+    same(eval_ctx.forest_eval(X), oracle.Forest(blob).eval(X, multi=True))
+
+
+@pytest.mark.parametrize("T", fc.FRAME_TREES)
+def test_frame_path_tree_counts(gpu_ctx_factory, oracle, frame1, T):
+    trees, blob = fc.small_forest(100 + T, T, 2, fc.layout(3)[4])
+    counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, fc.FRAME_KW, blob, *frame1)
+    assert info["n_trees"] == T and 2000 < counts[0] < 64 * 48
+
+
+# ---- 2. shapes of the lane arithmetic -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [3, 5])
+@pytest.mark.parametrize("S", fc.CLASS_SUMS)
+def test_forest_eval_class_sums_and_point_counts(eval_ctx, oracle, S, T):
+    trees, blob = fc.small_forest(10 * S + T, T, S, fc.EVAL_D)
+    X = fc.eval_points(S, max(fc.POINT_COUNTS))
+    want = oracle.Forest(blob).eval(X, multi=True)
+    eval_ctx.forest_load(blob)
+    assert eval_ctx.forest_info()["class_counts"] == [S]
+    for P in fc.POINT_COUNTS:      # a block holds 64 or 16 points; the inactive lanes take part in the shuffles
+        same(eval_ctx.forest_eval(X[:P]), want[:P], "P=%d" % P)
+
+
+@pytest.mark.parametrize("T", [3, 5])
+@pytest.mark.parametrize("S", fc.CLASS_SUMS)
+def test_frame_path_class_sums_and_partial_waves(gpu_ctx_factory, oracle, S, T):
+    """60 x 36 at stride 4: 135 sample points per frame -- a last wave of 7 points, one block, and with two frames a wave
+    that spans both (270 points, 135 not a multiple of 16)."""
+    W, H = 60, 36
+    kw = dict(width=W, height=H, stride=4, patch_size=9, patch_size_reduce=3)
+    trees, blob = fc.small_forest(20 * S + T, T, S, fc.layout(3)[4])
+    fr = [fc.small_frame(s, W, H) for s in (2, 3)]
+    rgb, depth = np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr])
+    calib = synthetic.make_calib(W, H)
+    assert (W // 4) * (H // 4) % 16 != 0
+    frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb[:1], depth[:1], calib, "one frame")
+    frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb, depth, calib, "two frames")
+
+
+# ---- 3. degenerate trees -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["all_roots_leaves", "one_root_leaf", "left_chain", "right_chain"])
+def test_degenerate_trees(eval_ctx, oracle, name):
+    trees, blob, depth = fc.degenerate_forests(2)[name]
+    X = fc.eval_points(9, 65)
+    eval_ctx.forest_load(blob)
+    assert eval_ctx.forest_info()["max_depth"] == depth
+    same(eval_ctx.forest_eval(X), oracle.Forest(blob).eval(X, multi=True))
+
+
+def test_degenerate_trees_on_the_frame_path(gpu_ctx_factory, oracle, frame1):
+    """Root leaves and the two chains in one forest (features < 6 are patch cells of r = 3 here)"""
+    d = fc.degenerate_forests(2)
+    trees = d["all_roots_leaves"][0][:2] + d["left_chain"][0] + d["right_chain"][0] + d["one_root_leaf"][0]
+    blob = fc.write_forest(trees, [3])
+    counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, fc.FRAME_KW, blob, *frame1)
+    assert info["max_depth"] == fc.CHAIN_DEPTH
+
+
+# ---- 4. special values --------------------------------------------------------------------------------------------------
+def test_forest_eval_special_thresholds_and_special_inputs(eval_ctx, oracle):
+    X, specials = fc.special_eval_case()
+    for trees, blob in fc.stump_forests(specials, 4):
+        eval_ctx.forest_load(blob)
+        same(eval_ctx.forest_eval(X), oracle.Forest(blob).eval(X, multi=True))
+
+
+@pytest.mark.parametrize("nodes", ["8-byte", "16-byte"])
+def test_frame_path_special_thresholds(gpu_ctx_factory, oracle, frame1, big3, nodes):
+    """Ties on bytes, on the depth feature (float32(d) / float32(1000) and its neighbours) and on the normal's -2.0, -0.0
+    against +0.0, +-inf and NaN; with a 2^20 + 1-node tree appended the same stumps are walked as 16-byte nodes."""
+    rgb, depth, calib = frame1
+    X, _, _ = oracle.extract(oracle.default_params(**fc.FRAME_KW), rgb[0], depth[0], calib)
+    specials = fc.special_frame_thresholds(X, 3, fc.special_depths(depth[0]))
+    filler = big3["wide_plus_one_split"][0][0] if nodes == "16-byte" else None
+    for trees, blob in fc.stump_forests(specials, 4, S=2, filler=filler):
+        counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, fc.FRAME_KW, blob, rgb, depth, calib)
+        assert (info["n_nodes"] >= fc.NODES8_LIMIT) == (nodes == "16-byte")
+
+
+# ---- 5. node formats -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["compact_full", "wide_plus_one_split", "wide_two_trees"])
+def test_node_formats_on_both_sides_of_2_20_nodes(gpu_ctx_factory, oracle, frame1, big3, name):
+    trees, blob, total = big3[name]
+    counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, fc.FRAME_KW, blob, *frame1, what=name)
+    assert info["n_nodes"] == total and info["max_depth"] == max(int(fc.node_levels(t["left"]).max()) for t in trees)
+
+
+def test_forest_eval_with_2_20_nodes(gpu_ctx_factory, oracle, frame1, big3):
+    rgb, depth, calib = frame1
+    X, _, _ = oracle.extract(oracle.default_params(**fc.FRAME_KW), rgb[0], depth[0], calib)
+    ctx = gpu_ctx_factory(**fc.FRAME_KW)
+    try:
+        for name in ("compact_full", "wide_plus_one_split"):
+            ctx.forest_load(big3[name][1])
+            same(ctx.forest_eval(X), oracle.Forest(big3[name][1]).eval(X, multi=True), name)
+    finally:
+        ctx.close()
+
+
+# ---- 6. wave_inside at its boundary -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", ["dense", "compact_full", "wide_plus_one_split"])
+@pytest.mark.parametrize("r", [3, 4])
+def test_wave_inside_at_its_boundary(gpu_ctx_factory, oracle, big3, big4, r, model):
+    """Single valid points decide per wave whether patch_value_inside2 / patch_value_inside (16-byte model) or the
+    reflecting patch_value runs.  `dense` is a 32-tree forest in which every point tests 160 cells (8-byte nodes)."""
+    rgb, depth, pts = fc.wave_inside_frames(r)
+    blob = fc.patch_forest(r, r)[1] if model == "dense" else (big3 if r == 3 else big4)[model][1]
+    assert fc.split_features(blob) == set(range(fc.layout(r)[4]))
+    kw = dict(fc.FRAME_KW, patch_size_reduce=r)
+    counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb, depth, synthetic.make_calib(64, 48), model)
+    assert sum(counts) == len(pts)
+
+
+# ---- 7. resize table in LDS and through L1 ----------------------------------------------------------------------------
+@pytest.mark.parametrize("patch_size", [159, 161])
+def test_resize_table_in_lds_and_through_l1(gpu_ctx_factory, oracle, patch_size):
+    W, H = 192, 164
+    rgb, depth = fc.near_plane_frame(patch_size)
+    trees, blob = fc.patch_forest(7, 11, T=4, depth=8)
+    assert fc.split_features(blob) == set(range(366))
+    kw = dict(width=W, height=H, patch_size=patch_size, depth_min=0.5)
+    frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb[None], depth[None], synthetic.make_calib(W, H))
+
+
+# ---- 8. patch_size_reduce 1 and 16 ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("r", [1, 16])
+def test_patch_size_reduce_1_and_16(gpu_ctx_factory, oracle, r):
+    W, H = 64, 48
+    rgb, depth = fc.halves_frame(r)
+    calib = synthetic.make_calib(W, H)
+    kw = dict(width=W, height=H, stride=2, patch_size=9, patch_size_reduce=r)
+    D = fc.layout(r)[4]
+    want, wx, wy = oracle.extract(oracle.default_params(**kw), rgb, depth, calib)
+    ctx = gpu_ctx_factory(**kw)
+    try:
+        got, gx, gy = ctx.extract_features(rgb, depth, calib)      # the dump kernel: all cells
+    finally:
+        ctx.close()
+    assert np.array_equal(gx, wx) and np.array_equal(gy, wy) and want.shape == (W * H // 4, D)
+    same(got, want)
+    trees, blob = fc.patch_forest(r, r, *((4, 8) if r == 16 else (32, 5)))
+    assert fc.split_features(blob) == set(range(D))
+    frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb[None], depth[None], calib)
