@@ -217,7 +217,49 @@ rvseg_status rvseg_segment_frames_device(rvseg_ctx *ctx, int32_t n_frames, const
                                          float *d_posteriors_out, float *d_marginals_out,
                                          int8_t *d_labels_out, void *hip_stream);
 
-/* Status of the asynchronous work of the last rvseg_segment_frames_device call on this context (the
+/* ---- external semantics: replaces Segmenter::processFramesFromQueueExternal (src/segmenter.cpp:445-514), the second
+ *      single-frame provider (`external_semantics`, launch/semantics.launch): any per-pixel classifier -- a CNN's
+ *      softmax, for instance -- reaches the frame CRF through these calls.  None of them needs a loaded forest.
+ *
+ * rvseg_rectify_depth: the request's `depth` image (:466-488; srv/SingleFrameSegmentation.srv, TYPE_32FC3).
+ *   xyz_out  n x H x W x 3 float32: (R*Kinv)*(d*x, d*y, d) + t with d = depth_mm / 1000.0f; NaN in all three channels
+ *            where d < depth_min || d > depth_max (compared in float against the arguments).  The reference hard-codes
+ *            0.5 and 15.0 here (:472); they are arguments, and need not be the context's depth_min / depth_max.
+ *   Products and sums are rounded one by one, left to right (row . column), like the cloud of the forest path.
+ *   Geometry is the context's width / height (the stride plays no part); calib: n x 21 HOST floats in both variants. */
+rvseg_status rvseg_rectify_depth(rvseg_ctx *ctx, int32_t n_frames, const uint16_t *depth_mm, const float *calib,
+                                 float depth_min, float depth_max, float *xyz_out);
+rvseg_status rvseg_rectify_depth_device(rvseg_ctx *ctx, int32_t n_frames, const uint16_t *d_depth_mm, const float *calib,
+                                        float depth_min, float depth_max, float *d_xyz_out, void *hip_stream);
+/* The layer layout of the external provider's distributions: what single_frame_segmentation_server.py:68-71 reads from
+ * `color_codings`.  Limits of the forest loader: 1..8 layers, every count >= 1, sum <= 64 (else RVSEG_ERR_INVALID_ARG, and
+ * the previous layout stays).  Independent of any loaded forest: rvseg_forest_load does not disturb it, and it does not
+ * disturb the forest -- rvseg_segment_frames and rvseg_segment_external can alternate on one context. */
+rvseg_status rvseg_external_layers_set(rvseg_ctx *ctx, int32_t n_layers, const int32_t *class_counts);
+/* The frame path with the provider's `float32[] label_distribution` in the place of the forest's posteriors (:505-512):
+ *   distributions  one block per frame, layers concatenated, each [y][x][class] float32 -- the layout of `posteriors`
+ *                  above.  dist_stride == 1: at full resolution, H x W.  dist_stride == params.stride (> 1): at
+ *                  H/stride x W/stride, for a network that predicts at reduced resolution; they are up-sampled exactly
+ *                  as the forest path up-samples its low-resolution images (cv::resize INTER_LINEAR, :380-382).  Any
+ *                  other value: RVSEG_ERR_INVALID_ARG.
+ *   The values are used as the forest's log-posteriors are: unary energy = -value (:642).  This call never takes a
+ *   logarithm: whether to supply log-probabilities (what the forest supplies) or probabilities (what the reference's
+ *   placeholder server supplies) is the caller's choice, and the CRF sees exp(value) up to normalisation either way.
+ *   With use_dense_crf: cloud and lattice from depth + rgb (the context's depth_min / depth_max / dcrf_*), then the mean
+ *   field per layer; marginals_out n x sumC*H*W and / or labels_out n x L*H*W under params.label_mode / unknown_label.
+ *   Without: labels of the (up-sampled) distributions under label_mode; marginals_out is ignored.
+ *   Chunks of max_batch, page-locked buffers, the overflow contract (host entry redoes the chunk, _device reports through
+ *   rvseg_poll_status), rvseg_last_schedule and rvseg_last_timing: as for rvseg_segment_frames[_device].
+ *   Without a layout set (rvseg_external_layers_set): RVSEG_ERR_INVALID_ARG.  RVSEG_ERR_NO_FOREST does not occur here. */
+rvseg_status rvseg_segment_external(rvseg_ctx *ctx, int32_t n_frames, const uint8_t *rgb, const uint16_t *depth_mm,
+                                    const float *calib, const float *distributions, int32_t dist_stride,
+                                    float *marginals_out, int8_t *labels_out);
+rvseg_status rvseg_segment_external_device(rvseg_ctx *ctx, int32_t n_frames, const uint8_t *d_rgb,
+                                           const uint16_t *d_depth_mm, const float *calib, const float *d_distributions,
+                                           int32_t dist_stride, float *d_marginals_out, int8_t *d_labels_out,
+                                           void *hip_stream);
+
+/* Status of the asynchronous work of the last rvseg_segment_frames_device / rvseg_segment_external_device call on this context (the
  * lattice build is the only stage that can fail on the device: hash-table overflow).  wait != 0 blocks
  * until that status is known (it does NOT wait for the outputs: synchronise the stream for those);
  * wait == 0 returns RVSEG_NOT_READY while the build is still running.  RVSEG_ERR_CAPACITY: the outputs

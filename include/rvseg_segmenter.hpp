@@ -15,6 +15,10 @@
 //       pops ONE frame per iteration              :340-346        body; pops up to max_batch frames over all cameras into
 //       pushes (seq, posteriors) per camera       :434            ONE rvseg_segment_frames call, pushes per camera in order
 //       posteriors vector [layer][y][x][class]    :413-431    processFrames(): the body for an explicit batch, same layout
+//   processFramesFromQueueExternal()              :445-514    Config::external_semantics: no forest; rectifyDepth() builds the
+//       rectified 32FC3 xyz image, calls the      :466-488        request's depth image, processFramesExternal[Device]() takes
+//       SingleFrameSegmentation service, stores   :490-512        the provider's label_distribution into the frame CRF / label
+//       its label_distribution as the posteriors                  rules (rvseg_segment_external); SingleFrameSegmentation* structs
 //   onNewLocalMap(): push onto _local_map_queue   :300-304    onNewLocalMap(LocalMap)
 //   processMapFromQueue(): wait for the newest    :518-719    processMapFromQueue(): false while the map has to be postponed
 //       result of every camera, drop skipped      :527-553        (:527-553), else drops skipped results, matches by seq
@@ -90,6 +94,13 @@ struct Config {
     int dcrf_iterations = 10;
     int max_batch = 8;
     int device = 0;
+    // launch/semantics.launch `external_semantics` (segmenter.cpp:101-103, 227-228): the single-frame semantics come
+    // from an external provider.  No forest is loaded (forest_file_name is not read); `layers` alone gives the layout,
+    // as single_frame_segmentation_server.py:68-71 takes it from the config.  processFrames* then throw; use
+    // processFramesExternal*.  per_frame_crf / label_mode: the frame CRF and label rule of those calls.
+    bool external_semantics = false;
+    bool per_frame_crf = false;
+    int label_mode = RVSEG_LABEL_NOCRF;
 };
 
 // srv/SegmentationInformationSrv.srv response (segmenter.cpp:776-791)
@@ -103,6 +114,25 @@ struct SegmentationInformation {
 // srv/IdsSrv.srv response
 struct IdsSrvResponse {
     std::vector<int32_t> local_map_ids;
+};
+
+// srv/SingleFrameSegmentation.srv: `sensor_msgs/Image rgb`, `sensor_msgs/Image depth` --- `float32[] label_distribution`.
+// Image carries the sensor_msgs/Image fields the request fills (segmenter.cpp:490-502), in message order (the header's
+// seq is the frame's sequence number, :492).
+struct Image {
+    uint32_t seq = 0;           // header.seq
+    uint32_t height = 0, width = 0;
+    std::string encoding;       // "rgb8" (RGB8) / "32FC3" (TYPE_32FC3)
+    uint8_t is_bigendian = 0;
+    uint32_t step = 0;          // bytes per row
+    std::vector<uint8_t> data;
+};
+struct SingleFrameSegmentationRequest {
+    Image rgb;                  // RGB8, H x W x 3 uint8
+    Image depth;                // TYPE_32FC3: the rectified xyz image, NaN outside 0.5 .. 15 m (:472)
+};
+struct SingleFrameSegmentationResponse {
+    std::vector<float> label_distribution;   // layers concatenated, each [y][x][class]
 };
 
 // srv/LocalMapSegmentationSrv.srv
@@ -226,11 +256,19 @@ public:
         p.dcrf_kernel_weight = conf.dcrf_kernel_weight; p.dcrf_iterations = conf.dcrf_iterations;
         p.multi_layer = 1;              // shared forest, multiClassLogPosterior (segmenter.cpp:368)
         p.label_mode = RVSEG_LABEL_NOCRF;
+        if (conf.external_semantics) { p.use_dense_crf = conf.per_frame_crf ? 1 : 0; p.label_mode = conf.label_mode; }
         if (conf.layers.size() > RVSEG_MAX_LAYERS) throw std::runtime_error("too many label layers");
         for (size_t l = 0; l < conf.layers.size(); l++) p.unknown_label[l] = conf.layers[l].unknown_label;
         p.max_batch = conf.max_batch;
         p.device = conf.device;
         if (rvseg_create(&p, &ctx_) != RVSEG_OK) throw std::runtime_error(std::string("rvseg_create: ") + rvseg_last_error(nullptr));
+        if (conf.external_semantics) {   // the layout comes from the config, not from a model
+            std::vector<int32_t> counts;
+            total_labels_ = 0;
+            for (const Layer& l : conf.layers) { counts.push_back((int32_t)l.classes.size()); total_labels_ += (unsigned)l.classes.size(); }
+            if (rvseg_external_layers_set(ctx_, (int32_t)counts.size(), counts.data()) != RVSEG_OK) fail(std::string("layers: ") + rvseg_last_error(ctx_));
+            return;
+        }
         if (rvseg_forest_load(ctx_, conf.forest_file_name.c_str()) != RVSEG_OK) {
             const std::string msg = rvseg_last_error(ctx_);
             rvseg_destroy(ctx_);
@@ -420,6 +458,49 @@ public:
         return out;
     }
 
+    // ---- the external provider (processFramesFromQueueExternal, segmenter.cpp:445-514) ---------------------------------
+    // The rectified xyz image of :466-488 for n frames: n x H x W x 3 floats, NaN where the depth is outside
+    // [depth_min, depth_max] (the reference's 0.5 / 15.0 by default).
+    std::vector<float> rectifyDepth(int n, const uint16_t* depth, const float* calib, float depth_min = 0.5f, float depth_max = 15.0f) {
+        std::vector<float> xyz((size_t)n * conf_.width * conf_.height * 3);
+        check(rvseg_rectify_depth(ctx_, n, depth, calib, depth_min, depth_max, xyz.data()));
+        return xyz;
+    }
+    // The request of :490-502 for one frame
+    SingleFrameSegmentationRequest externalRequest(int seq, const uint8_t* color, const uint16_t* depth, const float* calib) {
+        SingleFrameSegmentationRequest req;
+        const uint32_t W = (uint32_t)conf_.width, H = (uint32_t)conf_.height;
+        req.rgb.seq = req.depth.seq = (uint32_t)seq;
+        req.rgb.height = req.depth.height = H;
+        req.rgb.width = req.depth.width = W;
+        req.rgb.encoding = "rgb8";
+        req.rgb.step = W * 3;
+        req.rgb.data.assign(color, color + (size_t)W * H * 3);
+        req.depth.encoding = "32FC3";
+        req.depth.step = W * 12;
+        const std::vector<float> xyz = rectifyDepth(1, depth, calib);
+        req.depth.data.resize(xyz.size() * sizeof(float));
+        std::memcpy(req.depth.data.data(), xyz.data(), req.depth.data.size());
+        return req;
+    }
+    // The layer layout of the provider (also set by the constructor with Config::external_semantics)
+    void setExternalLayers(const std::vector<int32_t>& class_counts) {
+        check(rvseg_external_layers_set(ctx_, (int32_t)class_counts.size(), class_counts.data()));
+    }
+    // The provider's distributions of n frames (n x S x h x w floats; dist_stride 1: h x w = H x W, rf_prediction_stride:
+    // H/stride x W/stride) through the frame CRF (Config::per_frame_crf) and the label rule.  marginals_out (n x S x H x W)
+    // and labels_out (n x L x H x W) are optional.
+    void processFramesExternal(int n, const uint8_t* color, const uint16_t* depth, const float* calib, const float* label_distribution,
+                               int dist_stride, float* marginals_out, int8_t* labels_out) {
+        check(rvseg_segment_external(ctx_, n, color, depth, calib, label_distribution, dist_stride, marginals_out, labels_out));
+    }
+    void processFramesExternalDevice(int n, const uint8_t* d_color, const uint16_t* d_depth, const float* calib,
+                                     const float* d_label_distribution, int dist_stride, float* d_marginals_out, int8_t* d_labels_out,
+                                     void* hip_stream) {
+        check(rvseg_segment_external_device(ctx_, n, d_color, d_depth, calib, d_label_distribution, dist_stride, d_marginals_out,
+                                            d_labels_out, hip_stream));
+    }
+
     // CRF branch of processMapFromQueue for one layer: `unaries` is the accumulated posterior
     // matrix C x cloud_size (Eigen column-major == cloud_size x C point-major), `pairwise` the
     // 6 x cloud_size feature matrix of segmenter.cpp:629-637.  Returns result_labels[l].
@@ -555,7 +636,8 @@ public:
         for (size_t l = 0; l < conf_.layers.size(); l++) p.unknown_label[l] = conf_.layers[l].unknown_label;
         p.device = conf_.device;
         if (rvseg_create(&p, &map_ctx_) != RVSEG_OK) throw std::runtime_error(std::string("rvseg_create: ") + rvseg_last_error(nullptr));
-        if (rvseg_forest_load(map_ctx_, conf_.forest_file_name.c_str()) != RVSEG_OK) {
+        // (with external semantics there is no model: the calls that take the layout from one -- processMapDevice -- refuse)
+        if (!conf_.external_semantics && rvseg_forest_load(map_ctx_, conf_.forest_file_name.c_str()) != RVSEG_OK) {
             const std::string msg = rvseg_last_error(map_ctx_);
             rvseg_destroy(map_ctx_);
             map_ctx_ = nullptr;

@@ -44,6 +44,8 @@ SYMBOLS = [
     "rvseg_eval_accumulate", "rvseg_eval_confusion", "rvseg_eval_scores_from_counts",
     "rvseg_crf_terms_check", "rvseg_crf_infer_terms", "rvseg_crf_infer_terms_device",
     "rvseg_crf_logistic_unary", "rvseg_crf_logistic_unary_device",
+    "rvseg_rectify_depth", "rvseg_rectify_depth_device", "rvseg_external_layers_set",
+    "rvseg_segment_external", "rvseg_segment_external_device",
 ]
 
 
@@ -188,6 +190,11 @@ def lib():
     L.rvseg_crf_infer_terms_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, i32, vp, vp, i32, i32, vp]
     L.rvseg_crf_logistic_unary.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.rvseg_crf_logistic_unary_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.rvseg_rectify_depth.argtypes = [vp, i32, vp, vp, f32, f32, vp]
+    L.rvseg_rectify_depth_device.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp]
+    L.rvseg_external_layers_set.argtypes = [vp, i32, vp]
+    L.rvseg_segment_external.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    L.rvseg_segment_external_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
     L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
     L.rvseg_debug_live_resources.restype = None

@@ -679,7 +679,7 @@ upsample_pack_generic_kernel(int W, int H, int lw, int lh, int C, size_t low_fra
     post_all[(size_t)frame * post_frame_stride + post_layer_off + e] = h0 * ay0[y] + h1 * ay1[y];
 }
 
-void launch_upsample_pack(const FrameGeom& g, const DeviceForest& f, const UpsampleTables& t,
+void launch_upsample_pack(const FrameGeom& g, const LayerLayout& f, const UpsampleTables& t,
                           const float* d_low, float* d_post, int n, hipStream_t s) {
     const size_t low_frame = (size_t)g.lw * g.lh * f.sum_classes;
     const size_t post_frame = (size_t)g.W * g.H * f.sum_classes;
@@ -750,7 +750,7 @@ labels_frames_kernel(const float* __restrict__ values, int n_frames, int N, int 
     labels[(frame * n_layers + layer) * (size_t)N + i] = (int8_t)best;
 }
 
-void launch_labels_frames(const float* d_values, int n_frames, int N, const DeviceForest& f, int mode, const int* unknown,
+void launch_labels_frames(const float* d_values, int n_frames, int N, const LayerLayout& f, int mode, const int* unknown,
                           int8_t* d_labels, hipStream_t s) {
     const size_t total = (size_t)n_frames * N;
     int prefix = 0;

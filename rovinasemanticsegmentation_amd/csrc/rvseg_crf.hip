@@ -627,14 +627,13 @@ rvseg_status crf_frames_build(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
     return RVSEG_OK;
 }
 
-rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, int n, const float* d_post, float* d_marg, int8_t* d_labels,
-                              hipStream_t s) {
+rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& f, int n, const float* d_post, float* d_marg,
+                              int8_t* d_labels, hipStream_t s) {
     CrfState* cs;
     rvseg_status st0 = crf_state(ctx, &cs);
     if (st0 != RVSEG_OK) return st0;
     const FrameGeom& g = im->geom;
     const rvseg_params& p = ctx->params;
-    const DeviceForest& f = ctx->forest;
     const int N = g.W * g.H;
     rvseg_status st;
     const size_t frame_stride = (size_t)N * f.sum_classes;

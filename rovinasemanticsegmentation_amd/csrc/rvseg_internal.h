@@ -67,16 +67,23 @@ hipError_t stream_create(Stream& s, unsigned flags);
 hipError_t stream_create(Stream& s, unsigned flags, int priority);
 
 // ---------------------------------------------------------------------------------------------
+// Label layers of a per-pixel distribution image: what the up-sampler, the per-frame CRF and the label rules need to
+// know about a provider.  The loaded forest supplies one (DeviceForest), rvseg_external_layers_set the other.
+// ---------------------------------------------------------------------------------------------
+struct LayerLayout {
+    int n_layers = 0;                       // forest: layers of the ACTIVE mode
+    int class_counts[RVSEG_MAX_LAYERS] = {}; // per layer
+    int sum_classes = 0;                    // S
+};
+
+// ---------------------------------------------------------------------------------------------
 // device-side forest (breadth-first node array in HBM, leaf histogram table)
 // ---------------------------------------------------------------------------------------------
-struct DeviceForest {
+struct DeviceForest : LayerLayout {
     int n_trees = 0;
     int max_depth = 0;
     int n_nodes = 0;
     int n_leaves = 0;
-    int n_layers = 0;                       // layers of the ACTIVE mode
-    int class_counts[RVSEG_MAX_LAYERS] = {}; // per layer
-    int sum_classes = 0;                    // S
     DevBuf nodes;                           // DeviceNode[n_nodes]
     DevBuf nodes8;                          // the same nodes in 8 bytes each (frame kernel), or empty: see upload_forest
     DevBuf roots;                           // int32[n_trees]
@@ -115,6 +122,7 @@ struct rvseg_ctx {
     rvseg::ForestModel host_forest;
     bool forest_loaded = false;
     rvseg::DeviceForest forest;
+    rvseg::LayerLayout external;   // rvseg_external_layers_set; n_layers == 0: not set.  Independent of `forest`
     rvseg::LabTables lab;
     rvseg::Stream stream;          // ctx-owned stream for the host entry points
     rvseg::StageTimer timer;

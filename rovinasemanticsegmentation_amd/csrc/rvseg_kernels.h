@@ -61,10 +61,10 @@ void launch_rf_frames(const FrameGeom& g, const DeviceForest& f, const ResizeRow
 // true when the frame kernel can use the row-pair Lab image (8-byte nodes exist for this model)
 bool rf_frames_wants_lab2(const DeviceForest& f);
 // cv::resize to full resolution + pack [layer][y][x][class] (segmenter.cpp:380-431)
-void launch_upsample_pack(const FrameGeom& g, const DeviceForest& f, const UpsampleTables& t,
+void launch_upsample_pack(const FrameGeom& g, const LayerLayout& f, const UpsampleTables& t,
                           const float* d_low, float* d_post, int n, hipStream_t s);
 // label rules (rvseg_label_mode) over N points x C classes, class-contiguous
-void launch_labels_frames(const float* d_values, int n_frames, int N, const DeviceForest& f, int mode, const int* unknown,
+void launch_labels_frames(const float* d_values, int n_frames, int N, const LayerLayout& f, int mode, const int* unknown,
                           int8_t* d_labels, hipStream_t s);
 void launch_labels(const float* d_values, size_t n_points, int C, int mode, int unknown, int8_t* d_labels,
                    hipStream_t s);

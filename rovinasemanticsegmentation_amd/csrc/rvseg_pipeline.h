@@ -15,6 +15,8 @@ struct HostStage {
     static constexpr int SLOTS = 2;
     PinnedBuf h_rgb[SLOTS], h_depth[SLOTS], h_post[SLOTS], h_marg[SLOTS], h_lab[SLOTS];
     DevBuf d_rgb[SLOTS], d_depth[SLOTS], d_post[SLOTS], d_marg[SLOTS], d_lab[SLOTS];
+    PinnedBuf h_dist[SLOTS];   // the third input of the external provider's path (rvseg_segment_external)
+    DevBuf d_dist[SLOTS];
     Stream s_in, s_out;   // created together with the six events (stage_init): s_in set = all of them exist
     Event ev_in[SLOTS], ev_done[SLOTS], ev_out[SLOTS];
 };
@@ -55,6 +57,20 @@ rvseg_status upload_calib(rvseg_ctx* ctx, Pipeline* im, const float* calib, int 
 void timer_reset(rvseg_ctx* ctx);
 void timer_mark(rvseg_ctx* ctx, const char* name, hipStream_t s);
 
+// The two frame entry points behind rvseg_segment_frames[_device] and rvseg_segment_external[_device]: chunking by
+// max_batch, the staging ring of the host entry, the overflow contract.  ext == nullptr: features + forest produce the
+// posteriors (layout = the forest's).  Otherwise the caller's distributions take their place (layout = ctx->external)
+// and nothing of the forest is touched: `dist` is n x S x (H x W, or H/stride x W/stride with dist_stride > 1) floats,
+// host memory for segment_host, device memory for segment_device.  Arguments are checked by the callers.
+struct ExternalInput {
+    const float* dist;
+    int dist_stride;   // 1 or params.stride
+};
+rvseg_status segment_device(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames, const uint8_t* d_rgb, const uint16_t* d_depth_mm,
+                            const float* calib, float* d_posteriors_out, float* d_marginals_out, int8_t* d_labels_out, void* hip_stream);
+rvseg_status segment_host(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames, const uint8_t* rgb, const uint16_t* depth_mm,
+                          const float* calib, float* posteriors_out, float* marginals_out, int8_t* labels_out);
+
 // rvseg_fusion.hip
 void fusion_state_free(Pipeline* im);
 rvseg_status fusion_status(rvseg_ctx* ctx, Pipeline* im, bool wait);   // like crf_frames_status, for the index-range flag
@@ -75,7 +91,8 @@ rvseg_status crf_frames_build(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
 // Status of the last enqueued frame build (consumes it): RVSEG_OK, RVSEG_NOT_READY (only without `wait`)
 // or RVSEG_ERR_CAPACITY after raising im->cap_boost.  RVSEG_OK when nothing is pending.
 rvseg_status crf_frames_status(rvseg_ctx* ctx, Pipeline* im, bool wait);
-rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, int n, const float* d_post, float* d_marg, int8_t* d_labels,
-                              hipStream_t s);
+// `layers`: the layout of d_post -- the loaded forest's, or the external provider's
+rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& layers, int n, const float* d_post, float* d_marg,
+                              int8_t* d_labels, hipStream_t s);
 
 }  // namespace rvseg

@@ -254,7 +254,7 @@ static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
             timer_mark(ctx, "lattice_build", s);
             if ((st = crf_frames_build(ctx, im, n, d_rgb, s)) != RVSEG_OK) return st;
         }
-        st = crf_frames_infer(ctx, im, n, post, d_marg, d_labels, s);
+        st = crf_frames_infer(ctx, im, f, n, post, d_marg, d_labels, s);
         if (st != RVSEG_OK) return st;
     } else if (d_labels) {
         timer_mark(ctx, "labels", s);
@@ -262,6 +262,69 @@ static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
     }
     timer_mark(ctx, "end", s);
     RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// ---- the same for an external provider: its distributions are the posteriors (segmenter.cpp:445-514) -------------
+// No Lab image, no change map, no features, no forest.  There is nothing for the lattice build to hide under, so it runs
+// on the caller's stream without the fork.
+static rvseg_status run_chunk_external(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t* d_rgb, const uint16_t* d_depth,
+                                       const float* d_calibA, const float* d_dist, int dist_stride, float* d_marg,
+                                       int8_t* d_labels, hipStream_t s) {
+    const FrameGeom& g = im->geom;
+    const rvseg_params& p = ctx->params;
+    const LayerLayout& f = ctx->external;
+    const size_t npix = (size_t)g.W * g.H;
+    rvseg_status st;
+    const float* post = d_dist;   // full resolution: the wire layout is the posterior layout
+    if (dist_stride > 1) {
+        // the wire layout at low resolution is the up-sampler's `low` layout ([layer][ly][lx][class] per frame): no repack
+        if ((st = dev_reserve(ctx, im->post, npix * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
+        timer_mark(ctx, "upsample_pack", s);
+        launch_upsample_pack(g, f, im->up, d_dist, im->post.as<float>(), n, s);
+        post = im->post.as<float>();
+    }
+    if (p.use_dense_crf) {
+        if ((st = dev_reserve(ctx, im->cloud, npix * 16 * n)) != RVSEG_OK) return st;
+        timer_mark(ctx, "prep", s);
+        launch_prep(g, ctx->lab, d_rgb, d_depth, d_calibA, nullptr, im->cloud.as<float4>(), nullptr, n, s);
+        timer_mark(ctx, "lattice_build", s);
+        if ((st = crf_frames_build(ctx, im, n, d_rgb, s)) != RVSEG_OK) return st;
+        if ((st = crf_frames_infer(ctx, im, f, n, post, d_marg, d_labels, s)) != RVSEG_OK) return st;
+    } else if (d_labels) {
+        timer_mark(ctx, "labels", s);
+        launch_labels_frames(post, n, (int)npix, f, p.label_mode, p.unknown_label, d_labels, s);
+    }
+    timer_mark(ctx, "end", s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+rvseg_status segment_device(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames, const uint8_t* d_rgb, const uint16_t* d_depth_mm,
+                            const float* calib, float* d_posteriors_out, float* d_marginals_out, int8_t* d_labels_out, void* hip_stream) {
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    rvseg_status st = pipeline_init(ctx);
+    if (st != RVSEG_OK) return st;
+    Pipeline* im = ctx->impl;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    timer_reset(ctx);
+    if ((st = upload_calib(ctx, im, calib, n_frames, s)) != RVSEG_OK) return st;
+    const FrameGeom& g = im->geom;
+    const size_t npix = (size_t)g.W * g.H;
+    const LayerLayout& lay = ext ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
+    const size_t S = (size_t)lay.sum_classes, L = (size_t)lay.n_layers;
+    const size_t dist_frame = ext ? S * (ext->dist_stride > 1 ? (size_t)g.lw * g.lh : npix) : 0;
+    for (int start = 0; start < n_frames; start += ctx->params.max_batch) {
+        const int n = std::min(ctx->params.max_batch, n_frames - start);
+        const uint8_t* c_rgb = d_rgb + (size_t)start * npix * 3;
+        const uint16_t* c_depth = d_depth_mm + (size_t)start * npix;
+        const float* c_calib = im->calibA.as<float>() + (size_t)start * 12;
+        float* c_marg = d_marginals_out ? d_marginals_out + (size_t)start * npix * S : nullptr;
+        int8_t* c_lab = d_labels_out ? d_labels_out + (size_t)start * npix * L : nullptr;
+        if (ext) st = run_chunk_external(ctx, im, n, c_rgb, c_depth, c_calib, ext->dist + (size_t)start * dist_frame, ext->dist_stride, c_marg, c_lab, s);
+        else st = run_chunk(ctx, im, n, c_rgb, c_depth, c_calib, d_posteriors_out ? d_posteriors_out + (size_t)start * npix * S : nullptr, c_marg, c_lab, s);
+        if (st != RVSEG_OK) return st;
+    }
     return RVSEG_OK;
 }
 
@@ -289,27 +352,10 @@ rvseg_status rvseg_segment_frames_device(rvseg_ctx* ctx, int32_t n_frames, const
     if (!ctx->forest_loaded) { ctx->err = "no forest loaded"; return RVSEG_ERR_NO_FOREST; }
     if (n_frames < 0 || (n_frames > 0 && (!d_rgb || !d_depth_mm || !calib))) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     if (n_frames == 0) return RVSEG_OK;
-    RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    rvseg_status st = pipeline_init(ctx);
-    if (st != RVSEG_OK) return st;
-    Pipeline* im = ctx->impl;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    timer_reset(ctx);
-    if ((st = upload_calib(ctx, im, calib, n_frames, s)) != RVSEG_OK) return st;
-    const FrameGeom& g = im->geom;
-    const size_t npix = (size_t)g.W * g.H;
-    const size_t S = (size_t)ctx->forest.sum_classes, L = (size_t)ctx->forest.n_layers;
-    for (int start = 0; start < n_frames; start += ctx->params.max_batch) {
-        const int n = std::min(ctx->params.max_batch, n_frames - start);
-        st = run_chunk(ctx, im, n, d_rgb + (size_t)start * npix * 3, d_depth_mm + (size_t)start * npix,
-                       im->calibA.as<float>() + (size_t)start * 12,
-                       d_posteriors_out ? d_posteriors_out + (size_t)start * npix * S : nullptr,
-                       d_marginals_out ? d_marginals_out + (size_t)start * npix * S : nullptr,
-                       d_labels_out ? d_labels_out + (size_t)start * npix * L : nullptr, s);
-        if (st != RVSEG_OK) return st;
-    }
-    return RVSEG_OK;
+    return segment_device(ctx, nullptr, n_frames, d_rgb, d_depth_mm, calib, d_posteriors_out, d_marginals_out, d_labels_out, hip_stream);
 }
+
+}  // extern "C"
 
 // ---- host-buffer entry: pinned staging ring, copies of neighbouring chunks under the compute ----
 namespace {
@@ -365,12 +411,8 @@ rvseg_status stage_init(rvseg_ctx* ctx, HostStage& hs) {
 
 }  // namespace
 
-rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_t* rgb, const uint16_t* depth_mm,
-                                  const float* calib, float* posteriors_out, float* marginals_out, int8_t* labels_out) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    if (!ctx->forest_loaded) { ctx->err = "no forest loaded"; return RVSEG_ERR_NO_FOREST; }
-    if (n_frames < 0 || (n_frames > 0 && (!rgb || !depth_mm || !calib))) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    if (n_frames == 0) return RVSEG_OK;
+rvseg_status rvseg::segment_host(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames, const uint8_t* rgb, const uint16_t* depth_mm,
+                                 const float* calib, float* posteriors_out, float* marginals_out, int8_t* labels_out) {
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
@@ -379,7 +421,11 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
     if ((st = stage_init(ctx, hs)) != RVSEG_OK) return st;
     const FrameGeom& g = im->geom;
     const size_t npix = (size_t)g.W * g.H;
-    const size_t S = (size_t)ctx->forest.sum_classes, L = (size_t)ctx->forest.n_layers;
+    const LayerLayout& lay = ext ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
+    const size_t S = (size_t)lay.sum_classes, L = (size_t)lay.n_layers;
+    // the external provider's distributions: a third input, staged like the other two
+    const size_t dist_frame = ext ? S * (ext->dist_stride > 1 ? (size_t)g.lw * g.lh : npix) : 0;
+    const bool dist_pinned = ext && is_pinned_host(ext->dist);
     const bool want_marg = marginals_out && ctx->params.use_dense_crf;
     // page-locked caller buffers are read / written by the copy engines directly (no staging copy on the host):
     // the 11 MB of marginals per frame otherwise cross the host memory twice, which bounds the call at ~10 GB/s
@@ -422,6 +468,8 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
                             (st = hs.h_depth[slot].reserve(ctx, npix * 2 * n)) != RVSEG_OK)) ||
             (st = dev_reserve(ctx, hs.d_rgb[slot], npix * 3 * n)) != RVSEG_OK ||
             (st = dev_reserve(ctx, hs.d_depth[slot], npix * 2 * n)) != RVSEG_OK) { drain(); return st; }
+        if (ext && ((!dist_pinned && (st = hs.h_dist[slot].reserve(ctx, dist_frame * 4 * n)) != RVSEG_OK) ||
+                    (st = dev_reserve(ctx, hs.d_dist[slot], dist_frame * 4 * n)) != RVSEG_OK)) { drain(); return st; }
         const bool need_post_dev = posteriors_out != nullptr;
         if (need_post_dev && ((!post_pinned && (st = hs.h_post[slot].reserve(ctx, npix * S * 4 * n)) != RVSEG_OK) ||
                               (st = dev_reserve(ctx, hs.d_post[slot], npix * S * 4 * n)) != RVSEG_OK)) { drain(); return st; }
@@ -438,19 +486,30 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
             src_rgb = hs.h_rgb[slot].p;
             src_depth = hs.h_depth[slot].p;
         }
+        const void* src_dist = ext ? ext->dist + start * dist_frame : nullptr;
+        if (ext && !dist_pinned) {
+            host_copy(hs.h_dist[slot].p, src_dist, dist_frame * 4 * n);
+            src_dist = hs.h_dist[slot].p;
+        }
         // 2. H2D on the input stream, after the compute of chunk c - 2 (the last reader of these device buffers)
         if (c >= HostStage::SLOTS) RV_HIP(ctx, hipStreamWaitEvent(hs.s_in, hs.ev_done[slot], 0));
         RV_HIP(ctx, hipMemcpyAsync(hs.d_rgb[slot].p, src_rgb, npix * 3 * n, hipMemcpyHostToDevice, hs.s_in));
         RV_HIP(ctx, hipMemcpyAsync(hs.d_depth[slot].p, src_depth, npix * 2 * n, hipMemcpyHostToDevice, hs.s_in));
+        if (ext) RV_HIP(ctx, hipMemcpyAsync(hs.d_dist[slot].p, src_dist, dist_frame * 4 * n, hipMemcpyHostToDevice, hs.s_in));
         RV_HIP(ctx, hipEventRecord(hs.ev_in[slot], hs.s_in));
         // 3. compute: after its inputs arrived and after the D2H of chunk c - 2 released the output buffers
         RV_HIP(ctx, hipStreamWaitEvent(s, hs.ev_in[slot], 0));
         if (c >= HostStage::SLOTS) RV_HIP(ctx, hipStreamWaitEvent(s, hs.ev_out[slot], 0));
         timer_reset(ctx);
         if ((st = upload_calib(ctx, im, calib + start * 21, n, s)) != RVSEG_OK) { drain(); return st; }
-        st = run_chunk(ctx, im, n, hs.d_rgb[slot].as<uint8_t>(), hs.d_depth[slot].as<uint16_t>(), im->calibA.as<float>(),
-                       need_post_dev ? hs.d_post[slot].as<float>() : nullptr, want_marg ? hs.d_marg[slot].as<float>() : nullptr,
-                       labels_out ? hs.d_lab[slot].as<int8_t>() : nullptr, s);
+        if (ext)
+            st = run_chunk_external(ctx, im, n, hs.d_rgb[slot].as<uint8_t>(), hs.d_depth[slot].as<uint16_t>(), im->calibA.as<float>(),
+                                    hs.d_dist[slot].as<float>(), ext->dist_stride, want_marg ? hs.d_marg[slot].as<float>() : nullptr,
+                                    labels_out ? hs.d_lab[slot].as<int8_t>() : nullptr, s);
+        else
+            st = run_chunk(ctx, im, n, hs.d_rgb[slot].as<uint8_t>(), hs.d_depth[slot].as<uint16_t>(), im->calibA.as<float>(),
+                           need_post_dev ? hs.d_post[slot].as<float>() : nullptr, want_marg ? hs.d_marg[slot].as<float>() : nullptr,
+                           labels_out ? hs.d_lab[slot].as<int8_t>() : nullptr, s);
         if (st == RVSEG_ERR_CAPACITY && retries++ < 16) {
             // the lattice build of chunk c - 1 overflowed its hash table (its status is read at the start of this
             // chunk's build): nothing of chunk c has been enqueued past the feature branch.  The context has raised
@@ -474,6 +533,17 @@ rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_
         if (c >= 1 && (st = retire(c - 1)) != RVSEG_OK) { drain(); return st; }
     }
     return RVSEG_OK;
+}
+
+extern "C" {
+
+rvseg_status rvseg_segment_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_t* rgb, const uint16_t* depth_mm,
+                                  const float* calib, float* posteriors_out, float* marginals_out, int8_t* labels_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!ctx->forest_loaded) { ctx->err = "no forest loaded"; return RVSEG_ERR_NO_FOREST; }
+    if (n_frames < 0 || (n_frames > 0 && (!rgb || !depth_mm || !calib))) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    if (n_frames == 0) return RVSEG_OK;
+    return segment_host(ctx, nullptr, n_frames, rgb, depth_mm, calib, posteriors_out, marginals_out, labels_out);
 }
 
 rvseg_status rvseg_host_register(void* p, size_t bytes) {

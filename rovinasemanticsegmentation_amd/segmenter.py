@@ -7,7 +7,8 @@ Names follow the reference so that the parity tests read like its call sites:
   DenseCRF(N, C).setUnaryEnergy / addPairwiseEnergy / inference / map  (densecrf.h:36-121)
     + learned models: Potts / Diagonal / MatrixCompatibility, kernel types, normalisations, logistic unary and the
       parameter vectors of densecrf.cpp:294-360 (labelcompatibility.h, pairwise.h:32-42, unary.h)
-  Segmenter.processFrames                                          (src/segmenter.cpp:323-443)
+  Segmenter.processFrames                                          (src/segmenter.cpp:323-443; with
+    external_semantics the other provider, processFramesFromQueueExternal, :445-514)
   RgbLabelConversion.rgbToLabel / labelToRgb / getLabelName / ...  (include/rgb_label_conversion.h)
   Evaluator: the confusion matrix and scores of src/test.cpp:182-228 (test_multi.cpp:222-268)
 
@@ -249,6 +250,65 @@ class Context:
             self.h, n, C.c_void_p(d_rgb), C.c_void_p(d_depth), _ptr(calib),
             C.c_void_p(d_post or None), C.c_void_p(d_marg or None), C.c_void_p(d_labels or None),
             C.c_void_p(stream or None)))
+
+    # ---- external semantics (src/segmenter.cpp:445-514) --------------------------------------------
+    def rectify_depth(self, depth, calib, depth_min=0.5, depth_max=15.0):
+        """rvseg_rectify_depth: depth (n, H, W) uint16 mm -> (n, H, W, 3) float32, the TYPE_32FC3 `depth` image of a
+        SingleFrameSegmentation request; NaN outside [depth_min, depth_max] (the reference's 0.5 / 15.0 by default)."""
+        p = self.params
+        depth = np.ascontiguousarray(depth, np.uint16)
+        n = depth.shape[0]
+        assert depth.shape == (n, p.height, p.width)
+        calib = np.ascontiguousarray(np.broadcast_to(np.asarray(calib, np.float32).reshape(-1, 21), (n, 21)))
+        out = np.empty((n, p.height, p.width, 3), np.float32)
+        capi.check(self.h, self.L.rvseg_rectify_depth(self.h, n, _ptr(depth), _ptr(calib), C.c_float(depth_min), C.c_float(depth_max), _ptr(out)))
+        return out
+
+    def rectify_depth_device(self, n, d_depth, calib, d_xyz, depth_min=0.5, depth_max=15.0, stream=0):
+        """Device-pointer variant (integer addresses): enqueues only."""
+        calib = np.ascontiguousarray(np.broadcast_to(np.asarray(calib, np.float32).reshape(-1, 21), (n, 21)))
+        capi.check(self.h, self.L.rvseg_rectify_depth_device(self.h, n, C.c_void_p(d_depth), _ptr(calib), C.c_float(depth_min),
+                                                             C.c_float(depth_max), C.c_void_p(d_xyz), C.c_void_p(stream or None)))
+
+    def external_layers_set(self, class_counts):
+        """rvseg_external_layers_set: the layer layout of the external provider's distributions."""
+        cc = [int(c) for c in class_counts]
+        arr = (C.c_int32 * max(1, len(cc)))(*cc)
+        capi.check(self.h, self.L.rvseg_external_layers_set(self.h, len(cc), arr))
+        self.external_class_counts = cc
+
+    def segment_external(self, rgb, depth, calib, distributions, dist_stride=1, want_marginals=None, want_labels=True):
+        """rvseg_segment_external: distributions (n, S * h * w) float32 with h x w = H x W (dist_stride 1) or
+        H/stride x W/stride (dist_stride == params.stride), per frame [layer][y][x][class].  Returns marginals (with
+        use_dense_crf) and labels like segment_frames."""
+        p = self.params
+        cc = getattr(self, "external_class_counts", None)
+        if cc is None:
+            capi.check(self.h, self.L.rvseg_segment_external(self.h, 0, None, None, None, None, dist_stride, None, None))   # raises: no layout
+            raise capi.RvsegError(capi.ERR_INVALID_ARG, "no external layer layout set")
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        n = rgb.shape[0]
+        assert rgb.shape == (n, p.height, p.width, 3) and depth.shape == (n, p.height, p.width)
+        calib = np.ascontiguousarray(np.broadcast_to(np.asarray(calib, np.float32).reshape(-1, 21), (n, 21)))
+        S, Lc, N = sum(cc), len(cc), p.width * p.height
+        dist = np.ascontiguousarray(distributions, np.float32).reshape(n, -1)
+        if dist_stride in (1, p.stride):   # any other stride is the library's to refuse
+            assert dist.shape[1] == S * (N if dist_stride == 1 else (p.height // p.stride) * (p.width // p.stride)), dist.shape
+        if want_marginals is None:
+            want_marginals = bool(p.use_dense_crf)
+        marg = np.empty((n, S * N), np.float32) if want_marginals else None
+        lab = np.empty((n, Lc, p.height, p.width), np.int8) if want_labels else None
+        capi.check(self.h, self.L.rvseg_segment_external(self.h, n, _ptr(rgb), _ptr(depth), _ptr(calib), _ptr(dist), dist_stride,
+                                                         _ptr(marg), _ptr(lab)))
+        return {"marginals": marg, "labels": lab, "class_counts": list(cc)}
+
+    def segment_external_device(self, n, d_rgb, d_depth, calib, d_dist, dist_stride=1, d_marg=0, d_labels=0, stream=0):
+        """Device-pointer variant (integer addresses): enqueues only; the caller synchronises and polls (poll_status)."""
+        calib = np.ascontiguousarray(np.broadcast_to(np.asarray(calib, np.float32).reshape(-1, 21), (n, 21)))
+        capi.check(self.h, self.L.rvseg_segment_external_device(
+            self.h, n, C.c_void_p(d_rgb or None), C.c_void_p(d_depth or None), _ptr(calib), C.c_void_p(d_dist or None), dist_stride,
+            C.c_void_p(d_marg or None), C.c_void_p(d_labels or None), C.c_void_p(stream or None)))
 
     # ---- CRF ---------------------------------------------------------------------------------
     def crf_infer(self, unary_energy, features, potts_w, iterations, label_mode=capi.LABEL_ARGMAX, unknown_label=0):
@@ -745,13 +805,32 @@ class Segmenter:
     (:722-792) over plain Python values.
 
     layers (optional): [{"name": str, "classes": [(class name, (r, g, b)), ...]}, ...] -- the
-    `color_codings` of config.json (:73-98); needed only by the services and the cloud dumps."""
+    `color_codings` of config.json (:73-98); needed only by the services and the cloud dumps.
 
-    def __init__(self, forest, layers=None, **params):
+    external_semantics=True selects the other single-frame provider (launch/semantics.launch; :101-103, 227-228):
+    forest may be None, `layers` gives the layout (as single_frame_segmentation_server.py:68-71 reads it from the
+    config), and processFrames takes the provider's label_distribution -- or a provider callable -- instead of running
+    the forest (processFramesFromQueueExternal, :445-514)."""
+
+    def __init__(self, forest, layers=None, external_semantics=False, **params):
+        self.external_semantics = bool(external_semantics)
+        if self.external_semantics and layers is None:
+            raise RuntimeError("external_semantics needs the label layers (the layout comes from the config, not from a model)")
         self.ctx = Context(**params)
-        self.ctx.forest_load(forest)
-        info = self.ctx.forest_info()
-        self.layer_class_counts = info["class_counts"]
+        if forest is not None:
+            self.ctx.forest_load(forest)
+        elif not self.external_semantics:
+            self.ctx.close()
+            raise RuntimeError("no forest given (only external_semantics runs without one)")
+        if self.external_semantics:
+            self.layer_class_counts = [len(l["classes"]) for l in layers]
+            try:
+                self.ctx.external_layers_set(self.layer_class_counts)
+            except capi.RvsegError:
+                self.ctx.close()
+                raise
+        else:
+            self.layer_class_counts = self.ctx.forest_info()["class_counts"]
         self.layer_count = len(self.layer_class_counts)
         if layers is None:
             layers = [{"name": "layer%d" % l, "classes": [("class%d" % c, (0, 0, 0)) for c in range(n)]}
@@ -762,8 +841,27 @@ class Segmenter:
         self.layers = layers
         self.store = LocalMapStore([l["name"] for l in layers])
 
-    def processFrames(self, color, depth, calib, **kw):
-        return self.ctx.segment_frames(color, depth, calib, **kw)
+    def processFrames(self, color, depth, calib, label_distribution=None, provider=None, dist_stride=1, **kw):
+        """Internal forest: segment_frames.  With external_semantics: label_distribution (n, S * h * w), or `provider`,
+        a callable taking the request of externalRequest() and returning it; a provider that fails raises, as the
+        reference throws when the service call fails (:505)."""
+        if not self.external_semantics:
+            if label_distribution is not None or provider is not None:
+                raise RuntimeError("label_distribution / provider need external_semantics=True")
+            return self.ctx.segment_frames(color, depth, calib, **kw)
+        if label_distribution is None:
+            if provider is None:
+                raise RuntimeError("external_semantics: pass label_distribution or a provider")
+            try:
+                label_distribution = provider(self.externalRequest(color, depth, calib))
+            except Exception as e:
+                raise RuntimeError("Calling the segmentation service failed!") from e
+        return self.ctx.segment_external(color, depth, calib, label_distribution, dist_stride, **kw)
+
+    def externalRequest(self, color, depth, calib):
+        """The SingleFrameSegmentation request of :490-502 for a batch: {"rgb": (n, H, W, 3) uint8 (RGB8),
+        "depth": (n, H, W, 3) float32 (TYPE_32FC3, the rectified xyz image; NaN outside 0.5 .. 15 m, :472)}."""
+        return {"rgb": np.ascontiguousarray(color, np.uint8), "depth": self.ctx.rectify_depth(depth, calib, 0.5, 15.0)}
 
     def processMap(self, index_images, posteriors, cloud_xyz, cloud_rgb, unknown_labels=None, local_map_id=None):
         """The body of processMapFromQueue for one local map (src/segmenter.cpp:561-682): fuse the frames'
@@ -774,7 +872,7 @@ class Segmenter:
         p = self.ctx.params
         cc = self.layer_class_counts
         # the layout comes from the context's model: none (a refused load raises ERR_NO_FOREST here) or another one
-        if self.ctx.forest_info()["class_counts"] != list(cc):
+        if not self.external_semantics and self.ctx.forest_info()["class_counts"] != list(cc):
             raise RuntimeError("model / config mismatch: layer or class counts (README.md:30 of the reference)")
         cloud_xyz = np.ascontiguousarray(cloud_xyz, np.float32)
         cloud_rgb = np.ascontiguousarray(cloud_rgb, np.float32)
