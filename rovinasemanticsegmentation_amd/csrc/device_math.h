@@ -117,6 +117,52 @@ __device__ __forceinline__ void store_row(T* __restrict__ p, const T* __restrict
     if (i < N) p[i] = in[i];
 }
 
+// Rows of seven 16-bit frame-local ids (LatticeDev::ids16, d = 6): point p's row starts at byte 14 * p of the array, which
+// is 4-byte aligned only for even p.  A row therefore travels as the four dwords that contain it, the one at dword
+// (7 * p) >> 1 and the three after it: one dwordx4 request per lane, 14-byte lane stride, so a wave still reads one
+// contiguous run.  An odd row starts in the upper half of the first dword and ends with the fourth.  An even row ends in
+// the lower half of the fourth, whose upper half belongs to the next row -- or, behind the last point, to the unused second
+// half of the allocation, which keeps the size of the 32-bit form.
+typedef unsigned u32x4_ids __attribute__((ext_vector_type(4), aligned(4), may_alias));
+typedef unsigned u32x2_ids __attribute__((ext_vector_type(2), aligned(4), may_alias));
+typedef unsigned u32_ids __attribute__((may_alias));
+typedef unsigned short u16_ids __attribute__((may_alias));
+typedef unsigned short u16x8_ids __attribute__((ext_vector_type(8), aligned(16), may_alias));
+
+// the raw dwords: shifting them into place (unpack_ids16) is left to the point of use, so that a row fetched ahead stays
+// in flight
+__device__ __forceinline__ void load_ids16(const int* __restrict__ ids, size_t p, unsigned (&w)[4]) {
+    const u32x4_ids t = *reinterpret_cast<const u32x4_ids*>(reinterpret_cast<const unsigned*>(ids) + ((7 * p) >> 1));
+    w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+}
+
+__device__ __forceinline__ void unpack_ids16(const unsigned (&w)[4], size_t p, int (&id)[7]) {
+    const unsigned s = ((unsigned)p & 1u) << 4;
+    unsigned x[4];
+#pragma unroll
+    for (int i = 0; i < 3; i++) x[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], s);   // ({w[i+1], w[i]} >> s), low dword
+    x[3] = w[3] >> s;
+#pragma unroll
+    for (int j = 0; j < 7; j++) id[j] = (int)((j & 1) ? x[j >> 1] >> 16 : x[j >> 1] & 0xFFFFu);
+}
+
+// six ids as three aligned dwords, the seventh (the first of an odd row, the last of an even one) as a 16-bit store.
+// (The row is packed for an even point first and then shifted by one id, the way unpack_ids16 shifts it back: selecting
+// between id[k] and id[k + 1] instead makes the compiler index the array and spill it to scratch.)
+__device__ __forceinline__ void store_ids16(int* __restrict__ ids, size_t p, const int (&id)[7]) {
+    u16_ids* row = reinterpret_cast<u16_ids*>(ids) + 7 * p;
+    const unsigned odd = (unsigned)p & 1u;
+    const unsigned e0 = ((unsigned)id[0] & 0xFFFFu) | ((unsigned)id[1] << 16), e1 = ((unsigned)id[2] & 0xFFFFu) | ((unsigned)id[3] << 16);
+    const unsigned e2 = ((unsigned)id[4] & 0xFFFFu) | ((unsigned)id[5] << 16), e3 = (unsigned)id[6] & 0xFFFFu;
+    const unsigned s = odd << 4;
+    u32_ids* q = reinterpret_cast<u32_ids*>(row + odd);
+    u32x2_ids t;
+    t.x = __builtin_amdgcn_alignbit(e1, e0, s); t.y = __builtin_amdgcn_alignbit(e2, e1, s);
+    *reinterpret_cast<u32x2_ids*>(q) = t;
+    q[2] = __builtin_amdgcn_alignbit(e3, e2, s);
+    row[odd ? 0 : 6] = (unsigned short)(odd ? e0 : e3);
+}
+
 // The four label rules (rvseg_label_mode in include/rvseg.h) over one point's C class values:
 //   0 eval tool   src/test.cpp:160-175       strict '>' from -1000, -1 when nothing wins
 //   1 CRF         src/segmenter.cpp:646-657  strict '>' from 2.0/C, else the layer's "Unknown"

@@ -105,7 +105,8 @@ constexpr int LP_SET = 512;        // block-local vertex set (LP_CHUNKS x 256 po
 constexpr int LP_MAX_PROBE = 24;
 constexpr int LP_CHUNKS = 8;       // consecutive 256-point chunks per block (at most): the set (and its global slots) carries over
 
-template <int D>
+// NARROW (LatticeDev::ids16, D == 6): the row holds the frame-local slots as uint16_t
+template <int D, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 lattice_points_kernel(LatticeDev L, FeatureSource fs, int n_chunks) {
     // block-local vertex set: tag (EMPTY / LOCKED / FILLED), key, global slot; `lnew` lists the set
@@ -291,8 +292,10 @@ lattice_points_kernel(LatticeDev L, FeatureSource fs, int n_chunks) {
         for (int r = 0; r <= D; r++) {
             const int li = lidx[r];
             so[r] = li >= 0 ? (int)lslot[li] : -1 - li;
+            if (NARROW) so[r] &= (int)L.cap_f_mask;   // slot = frame * cap_f + h
         }
-        store_row<D + 1>(L.offsets + gp * (D + 1), so);
+        if constexpr (NARROW) store_ids16(L.offsets, (size_t)gp, so);
+        else store_row<D + 1>(L.offsets + gp * (D + 1), so);
         store_row<D + 1>(L.bary + gp * (D + 1), bary);
     }
   }
@@ -312,7 +315,10 @@ void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStre
         case 3: lattice_points_kernel<3><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
         case 4: lattice_points_kernel<4><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
         case 5: lattice_points_kernel<5><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 6: lattice_points_kernel<6><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
+        case 6:
+            if (L.ids16) lattice_points_kernel<6, true><<<grid, block, 0, s>>>(L, fs, n_chunks);
+            else lattice_points_kernel<6><<<grid, block, 0, s>>>(L, fs, n_chunks);
+            break;
         case 7: lattice_points_kernel<7><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
         default: break;
     }
@@ -449,8 +455,9 @@ csr_pass_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
         if (e < eend) {
             // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that
             // every later kernel stays in bounds; the host discards the result
-            if (!SCATTER) { id = L.slot_to_id[L.offsets[e]]; id = id < L.m_bound ? id : L.m_bound - 1; }
-            else { id = L.offsets[e]; wgt = L.bary[e]; }
+            // (ids16: the stored values are local to the frame's slot region / id range)
+            if (!SCATTER) { id = L.slot_to_id[lattice_entry(L, e) + (L.ids16 ? frame << L.cap_f_log2 : 0)]; id = id < L.m_bound ? id : L.m_bound - 1; }
+            else { id = lattice_entry(L, e) + (L.ids16 ? f0 : 0); wgt = L.bary[e]; }
         }
     };
     int id_n; float w_n;
@@ -461,10 +468,10 @@ csr_pass_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
         const int id = id_n;
         const float wgt = w_n;
         fetch(e + 64, id_n, w_n);
-        if (!SCATTER && valid) L.offsets[e] = id;    // slot -> vertex id, in place
         int lv = valid ? id - f0 : -1;
         if (lv >= Mf) lv = Mf - 1;                   // overflow case (flagged elsewhere): stay in bounds
         if (valid && lv < 0) lv = 0;
+        if (!SCATTER && valid) lattice_entry_store(L, e, L.ids16 ? lv : id);    // slot -> vertex id, in place
         if (!SCATTER) {
             // counting needs no order: LDS atomics (same-address lanes serialise in hardware, still an
             // order of magnitude cheaper than ranking the chunk with ballots)
@@ -575,6 +582,88 @@ csr_count_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
     for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
 }
 
+// The count pass over 16-bit frame-local values (LatticeDev::ids16): eight entries per lane and step.  A wave-block walks
+// the 16-byte units of the id array that hold its entries, so a unit is always aligned although a frame's first entry
+// (frame * N * (d+1)) need not be a multiple of eight.  A unit that lies wholly inside the wave-block is one 16-byte load
+// and one 16-byte store; the unit a wave-block shares with its neighbour (only at a frame boundary: a wave-block has a
+// multiple of 256 points) is read and written element by element, each wave its own entries.  The slot -> id gather adds the
+// frame's region base, the stored id is local to the frame's id range, with the same clamps as the counters.
+__global__ void __launch_bounds__(256)
+csr_count16_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
+    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long gwb = (long long)blockIdx.x * 4 + wave;
+    const int frame = (int)(gwb / wbpf);
+    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
+    const int wb = (int)(gwb - (long long)frame * wbpf);
+    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
+    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
+    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
+    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    unsigned* my = cs_cnt + (size_t)wave * mcap;
+    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    for (int lv = lane; lv < Mf; lv += 64) my[lv] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int dp1 = L.d + 1;
+    const long long p0 = (long long)wb * L.cs_pix;
+    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
+    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
+    const long long abeg = ebeg & ~7ll;    // first unit; every unit [e, e + 8) below has e + 8 > ebeg
+    u16_ids* ids = reinterpret_cast<u16_ids*>(L.offsets);
+    const int* s2i = L.slot_to_id + ((size_t)frame << L.cap_f_log2);
+    auto fetch = [&](long long e, int (&sl)[8]) {   // slots of the unit at e; 0 outside the wave-block
+        if (e >= ebeg && e + 8 <= eend) {
+            const u16x8_ids t = *reinterpret_cast<const u16x8_ids*>(ids + e);
+#pragma unroll
+            for (int k = 0; k < 8; k++) sl[k] = t[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) sl[k] = e + k >= ebeg && e + k < eend ? (int)ids[e + k] : 0;
+        }
+    };
+    int sl_n[8];
+    fetch(abeg + 8 * lane < eend ? abeg + 8 * lane : abeg, sl_n);
+    for (long long base = abeg; base < eend; base += 512) {
+        const long long e = base + 8 * lane;
+        int sl[8], id[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) sl[k] = sl_n[k];
+        const bool any = e < eend;
+        if (any) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) id[k] = s2i[sl[k]];   // eight gathers in flight (a slot is below cap_f)
+        }
+        const long long en = e + 512;
+        fetch(en < eend ? en : abeg, sl_n);                    // the next step's slots travel meanwhile
+        if (!any) continue;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that every later
+            // kernel stays in bounds; the host discards the result
+            id[k] = id[k] < L.m_bound ? id[k] : L.m_bound - 1;
+            id[k] -= f0;
+            id[k] = id[k] < Mf ? id[k] : Mf - 1;
+            id[k] = id[k] < 0 ? 0 : id[k];
+        }
+        if (e >= ebeg && e + 8 <= eend) {
+            u16x8_ids t;
+#pragma unroll
+            for (int k = 0; k < 8; k++) t[k] = (unsigned short)id[k];
+            *reinterpret_cast<u16x8_ids*>(ids + e) = t;        // slot -> vertex id, in place
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) if (e + k >= ebeg && e + k < eend) ids[e + k] = (unsigned short)id[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (e + k < ebeg || e + k >= eend) continue;
+            if (Mf > 0) atomicAdd(&my[id[k]], 1u);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
+}
+
 // Scatter pass with one lane per POINT (the generic pass above has one lane per entry and ranks ~10
 // distinct vertices per 64 entries; PMC: 438 vector instructions per 64 entries).  A chunk is 64
 // consecutive points x DP1 entries.  For every distinct vertex k of the chunk the lanes that hold k
@@ -582,7 +671,8 @@ csr_count_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
 // found with DP1 ballots; their union, masked to the lower lanes, is the rank of a point among the
 // chunk's entries of k, i.e. ascending point order again.  Neighbouring points share their simplex,
 // so a chunk has ~12-20 distinct vertices for 448 entries.
-template <int DP1>
+// NARROW (LatticeDev::ids16, DP1 == 7): the rows hold frame-local ids as uint16_t.
+template <int DP1, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int mcap) {
     extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
@@ -610,11 +700,17 @@ csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int 
         const size_t gp = (size_t)frame * L.N + (valid ? p : p1 - 1);
         int lv[DP1];
         float w[DP1];
-        load_row<DP1>(L.offsets + gp * DP1, lv);
+        if constexpr (NARROW) {
+            unsigned raw[4];
+            load_ids16(L.offsets, gp, raw);
+            unpack_ids16(raw, gp, lv);
+        } else {
+            load_row<DP1>(L.offsets + gp * DP1, lv);
+        }
         load_row<DP1>(L.bary + gp * DP1, w);
 #pragma unroll
         for (int j = 0; j < DP1; j++) {
-            lv[j] -= f0;
+            if (!NARROW) lv[j] -= f0;
             lv[j] = lv[j] < Mf ? lv[j] : Mf - 1;   // overflow case (flagged elsewhere): stay in bounds
             lv[j] = lv[j] < 0 ? 0 : lv[j];
         }
@@ -759,7 +855,8 @@ void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_ent
         const long long waves = (long long)wbpf * L.n_frames;
         const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
         const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
-        if (L.d == 6) csr_scatter_kernel<7><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        if (L.d == 6 && L.ids16) csr_scatter_kernel<7, true><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        else if (L.d == 6) csr_scatter_kernel<7><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
         else if (L.d == 5) csr_scatter_kernel<6><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
         else if (L.d == 2) csr_scatter_kernel<3><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
         else csr_pass_kernel<true><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
@@ -782,7 +879,8 @@ void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_ent
         const long long waves = (long long)wbpf * L.n_frames;
         const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
         const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
-        csr_count_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        if (L.ids16) csr_count16_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
+        else csr_count_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
         const int n_groups = (mcap + 63) / 64;
         csr_total_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);
         csr_scan_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);

@@ -131,7 +131,7 @@ slice_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha,
     const int dp1 = L.d + 1;
     float acc = 0.0f;
     for (int j = 0; j < dp1; j++) {
-        const int o = L.offsets[p * dp1 + j];
+        const int o = lattice_vertex(L, p, dp1, j);
         const float bw = L.bary[p * dp1 + j];
         const float val = values[(size_t)o * C + c];
         if (SEQ) {
@@ -159,7 +159,8 @@ slice_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha,
 
 // The normaliser's slice (C == 1, seqCompute rounding, OUT_MODE 1; RECIP: OUT_MODE 3) with the d+1 offsets and weights
 // of a point fetched as two wide rows.
-template <int DP1, bool RECIP = false>
+// NARROW (LatticeDev::ids16, DP1 == 7): 16-bit ids local to the point's frame.
+template <int DP1, bool RECIP = false, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 slice_norm_kernel(LatticeDev L, const float* __restrict__ values, float alpha, float* __restrict__ out, long long n_points) {
     if (L.counters[1]) return;
@@ -167,7 +168,14 @@ slice_norm_kernel(LatticeDev L, const float* __restrict__ values, float alpha, f
     if (p >= n_points) return;
     int offs[DP1];
     float wts[DP1];
-    load_row<DP1>(L.offsets + p * DP1, offs);
+    if constexpr (NARROW) {
+        unsigned raw[4];
+        load_ids16(L.offsets, (size_t)p, raw);
+        values += L.fstart[p / L.N];
+        unpack_ids16(raw, (size_t)p, offs);
+    } else {
+        load_row<DP1>(L.offsets + p * DP1, offs);
+    }
     load_row<DP1>(L.bary + p * DP1, wts);
     float acc = 0.0f;
 #pragma unroll
@@ -185,7 +193,8 @@ void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const floa
     const float alpha = 1.0f / (1 + powf(2, (float)-L.d));  // permutohedral.cpp:571
     if (seq && out_mode == 1 && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
         const dim3 g1((unsigned)((n_points + 255) / 256)), b1(256);
-        if (L.d == 6) slice_norm_kernel<7><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        if (L.d == 6 && L.ids16) slice_norm_kernel<7, false, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        else if (L.d == 6) slice_norm_kernel<7><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         else if (L.d == 5) slice_norm_kernel<6><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         else slice_norm_kernel<3><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         RV_LAUNCHED("slice_norm_kernel");
@@ -193,7 +202,8 @@ void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const floa
     }
     if (seq && out_mode == 3 && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
         const dim3 g1((unsigned)((n_points + 255) / 256)), b1(256);
-        if (L.d == 6) slice_norm_kernel<7, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        if (L.d == 6 && L.ids16) slice_norm_kernel<7, true, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        else if (L.d == 6) slice_norm_kernel<7, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         else if (L.d == 5) slice_norm_kernel<6, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         else slice_norm_kernel<3, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
         RV_LAUNCHED("slice_norm_kernel");
@@ -266,18 +276,25 @@ void launch_softmax(const float* tmp, int C, int N, const ValueView& q, long lon
 constexpr int MF_LDS_BYTES = 24 * 1024;   // frames with more vertices than fit read `values` from L2
 constexpr int MF_PTS = 512;               // points per block (2 per thread; 256 / 1024 / 2048 / 4096 measured +0.16 / +0.05 / +0.11 / +0.17 ms per 64-frame step)
 
-// inputs of one point of the update: fetched one point ahead of their use
-template <int C, int DP1>
+// inputs of one point of the update: fetched one point ahead of their use.  NARROW (LatticeDev::ids16, DP1 == 7): the
+// ids are the four raw dwords around the point's row of 16-bit frame-local ids, unpacked where they are used
+template <int C, int DP1, bool NARROW>
 struct MfIn {
-    int offs[DP1 > 0 ? DP1 : 1];
+    int offs[NARROW ? 4 : (DP1 > 0 ? DP1 : 1)];
     float wts[DP1 > 0 ? DP1 : 1];
     float ur[C];
     float nrm;
 };
 
-template <int C, int DP1>
-__device__ __forceinline__ void mf_load(const LatticeDev& L, const ValueView& unary, int f0, size_t p, MfIn<C, DP1>& in) {
-    if (DP1 > 0) {
+template <int C, int DP1, bool NARROW>
+__device__ __forceinline__ void mf_load(const LatticeDev& L, const ValueView& unary, int f0, size_t p, MfIn<C, DP1, NARROW>& in) {
+    if constexpr (NARROW) {
+        unsigned raw[4];
+        load_ids16(L.offsets, p, raw);
+#pragma unroll
+        for (int k = 0; k < 4; k++) in.offs[k] = (int)raw[k];
+        load_row<DP1>(L.bary + p * DP1, in.wts);
+    } else if (DP1 > 0) {
         load_row<(DP1 > 0 ? DP1 : 1)>(L.offsets + p * DP1, in.offs);
         load_row<(DP1 > 0 ? DP1 : 1)>(L.bary + p * DP1, in.wts);
     }
@@ -289,7 +306,7 @@ __device__ __forceinline__ void mf_load(const LatticeDev& L, const ValueView& un
 // t = sliced, times norm when `post` (block-uniform); out = Diagonal fl(v[c] * t[c]) / Matrix sum_c' W[c][c'] t[c'] from
 // c' = 0 up, with v / W read from `compat` at compile-time offsets (uniform loads).  TERM 0 never reads compat / post,
 // TERM 1 / 2 never neg_w.
-template <bool SEQ, int C, int DP1, bool USE_LDS, int TERM>
+template <bool SEQ, int C, int DP1, bool USE_LDS, int TERM, bool NARROW>
 __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __restrict__ values, const float* tab, float alpha,
                                           float neg_w, const ValueView& unary, int negate, const ValueView& Q, int scale_out,
                                           const MfLabels& lab, int frame, int f0, int i0,
@@ -297,25 +314,33 @@ __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __re
     constexpr int CP = (C + 3) / 4 * 4;
     constexpr int PER_THREAD = MF_PTS / 256;
     const int dp1 = DP1 > 0 ? DP1 : L.d + 1;
-    MfIn<C, DP1> cur, nxt;
-    if (i0 < L.N) mf_load<C, DP1>(L, unary, f0, (size_t)frame * L.N + i0, cur);
+    MfIn<C, DP1, NARROW> cur, nxt;
+    if (i0 < L.N) mf_load<C, DP1, NARROW>(L, unary, f0, (size_t)frame * L.N + i0, cur);
 #pragma unroll
     for (int k = 0; k < PER_THREAD; k++) {   // the staged table serves MF_PTS points
         const int i = i0 + 256 * k;
         if (i >= L.N) break;
         const size_t p = (size_t)frame * L.N + i;
-        if (k + 1 < PER_THREAD && i + 256 < L.N) mf_load<C, DP1>(L, unary, f0, p + 256, nxt);   // next point's rows travel now
+        if (k + 1 < PER_THREAD && i + 256 < L.N) mf_load<C, DP1, NARROW>(L, unary, f0, p + 256, nxt);   // next point's rows travel now
         float acc[C];
 #pragma unroll
         for (int c = 0; c < C; c++) acc[c] = 0.0f;
+        int loc[7];   // NARROW: the point's frame-local ids
+        if constexpr (NARROW) {
+            unsigned raw[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) raw[k] = (unsigned)cur.offs[k];
+            unpack_ids16(raw, p, loc);
+        }
 #pragma unroll
         for (int j = 0; j < (DP1 > 0 ? DP1 : 8); j++) {
             if (DP1 == 0 && j >= dp1) break;
-            const int o = DP1 > 0 ? cur.offs[j] : L.offsets[p * dp1 + j];
+            // the vertex's row in the staged table, and its global id (the runtime-d form reads either id form)
+            const int o = NARROW ? loc[j < 7 ? j : 0] + (USE_LDS ? 0 : f0) : DP1 > 0 ? cur.offs[j] : lattice_vertex(L, (long long)p, dp1, j);
             const float bw = DP1 > 0 ? cur.wts[j] : L.bary[p * dp1 + j];
             float val[C];
             if (USE_LDS) {
-                const float* row = tab + (o - f0) * CP;
+                const float* row = tab + (NARROW ? o : o - f0) * CP;
 #pragma unroll
                 for (int c = 0; c < C; c++) val[c] = row[c];
             } else {
@@ -384,7 +409,8 @@ __device__ __forceinline__ void mf_points(const LatticeDev& L, const float* __re
 // update of ONE learned term is TERM 1 (Diagonal; Potts with a normalisation other than SYMMETRIC is Diagonal(-w, .., -w))
 // or TERM 2 (Matrix), at runtime d.  post: scale the sliced values by norm (SYMMETRIC / AFTER); scale_out: hand the
 // next splat Q * norm (SYMMETRIC / BEFORE, not the last iteration).
-template <bool SEQ, int C, int DP1, int TERM = 0>
+// NARROW: 16-bit frame-local ids (LatticeDev::ids16; DP1 == 7).
+template <bool SEQ, int C, int DP1, int TERM = 0, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 mf_update_kernel(LatticeDev L, const float* __restrict__ values, float alpha, float neg_w, ValueView unary, int negate,
                  ValueView Q, int scale_out, MfLabels lab, const float* __restrict__ compat, int post) {
@@ -403,9 +429,9 @@ mf_update_kernel(LatticeDev L, const float* __restrict__ values, float alpha, fl
             tab[r * CP + c] = values[(size_t)(f0 + r) * C + c];
         }
         __syncthreads();
-        mf_points<SEQ, C, DP1, true, TERM>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
+        mf_points<SEQ, C, DP1, true, TERM, NARROW>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
     } else {
-        mf_points<SEQ, C, DP1, false, TERM>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
+        mf_points<SEQ, C, DP1, false, TERM, NARROW>(L, values, tab, alpha, neg_w, unary, negate, Q, scale_out, lab, frame, f0, i0, compat, post);
     }
 }
 
@@ -443,7 +469,8 @@ bool launch_mf_update(const LatticeDev& L, int C, const float* values, const MfT
     return with_fused_class_count(C, [&](auto cc) {
         constexpr int CC = decltype(cc)::value;
         constexpr bool SEQ = CC <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
-        if (!term.compat && L.d == 6) mf_update_kernel<SEQ, CC, 7><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        if (!term.compat && L.d == 6 && L.ids16) mf_update_kernel<SEQ, CC, 7, 0, true><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
+        else if (!term.compat && L.d == 6) mf_update_kernel<SEQ, CC, 7><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
         else if (!term.compat) mf_update_kernel<SEQ, CC, 0><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
         else if (term.matrix) mf_update_kernel<SEQ, CC, 0, 2><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
         else mf_update_kernel<SEQ, CC, 0, 1><<<grid, block, MF_LDS_BYTES, s>>>(L, values, alpha, term.neg_w, unary, neg, Q, so, lab, term.compat, post);
@@ -534,7 +561,7 @@ term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float 
         if (live) {
             float acc = 0.0f;
             for (int j = 0; j < dp1; j++) {
-                const int o = L.offsets[p * dp1 + j];
+                const int o = lattice_vertex(L, p, dp1, j);
                 const float bw = L.bary[p * dp1 + j];
                 const float val = values[(size_t)o * C + c];
                 if (SEQ) {

@@ -26,7 +26,10 @@ struct LatticeDev {
     int* counters;               // [0] vertices M, [1] overflow flag, [2] (unused), [3] entries of the longest vertex list
     int* fstart;                 // n_frames + 1: first vertex id of each frame (ids are frame-contiguous)
     unsigned long long* vkeys;   // per vertex id: key
-    int* offsets;                // P x (d+1): slot, later vertex id
+    int* offsets;                // P x (d+1): slot, later vertex id.  ids16: the same rows as uint16_t, frame-local
+    int ids16;                   // 1: `offsets` holds 16-bit frame-local values -- slot - frame * cap_f, later vertex id -
+                                 // fstart[frame] -- in rows of d+1 without padding (frame path on the counting-sort
+                                 // path, d = 6: both are below 2^13); 0: 32-bit global values
     float* bary;                 // P x (d+1)
     int *nb1, *nb2;              // (d+1) x m_bound blur neighbours (-1 = none)
     uint2* csr_pw;               // entries sorted by vertex, ascending point index inside a vertex:
@@ -47,6 +50,22 @@ struct LatticeDev {
     int wbpf;                    // wave-blocks per frame
     float* norm;                 // per point, pairwise.cpp:55-56
 };
+
+// The kernels that are not specialised on the id form read `offsets` through these (L.ids16 is uniform).
+typedef unsigned short lattice_id16 __attribute__((may_alias));
+// entry e as stored: a global value, or with ids16 a frame-local one
+__device__ __forceinline__ int lattice_entry(const LatticeDev& L, long long e) {
+    return L.ids16 ? (int)reinterpret_cast<const lattice_id16*>(L.offsets)[e] : L.offsets[e];
+}
+__device__ __forceinline__ void lattice_entry_store(const LatticeDev& L, long long e, int v) {
+    if (L.ids16) reinterpret_cast<lattice_id16*>(L.offsets)[e] = (unsigned short)v;
+    else L.offsets[e] = v;
+}
+// global vertex id of vertex j of point p (after the count pass)
+__device__ __forceinline__ int lattice_vertex(const LatticeDev& L, long long p, int dp1, int j) {
+    const int o = lattice_entry(L, p * dp1 + j);
+    return L.ids16 ? o + L.fstart[p / L.N] : o;
+}
 
 // Band-interleaved resident schedule of the ordered splat ("resident bands").  A frame's
 // vertices are dealt to B blocks that all stay on the chip for the whole launch; a block walks ITS vertices band after

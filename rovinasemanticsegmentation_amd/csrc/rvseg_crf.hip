@@ -110,7 +110,9 @@ static bool resident_pays(int n_frames, int N, int vertices_per_frame_seen) {
     return n_frames >= 2 && (long long)n_frames * N >= 6900000ll + 4900ll * vpf;
 }
 
-static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N, int n_frames, bool safe, int vertices_per_frame_seen = 0) {
+// frame_ids: the frame path's lattice (d = 6, table partitioned by frame) may keep 16-bit frame-local ids (LatticeDev::ids16)
+static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N, int n_frames, bool safe, int vertices_per_frame_seen = 0,
+                                    bool frame_ids = false) {
     if (d < 1 || d > 7) { ctx->err = "feature dimension must be in [1,7]"; return RVSEG_ERR_INVALID_ARG; }
     if (n_frames > 1022) { ctx->err = "at most 1022 frames per chunk (lower max_batch)"; return RVSEG_ERR_INVALID_ARG; }   // 10-bit frame field of the launch-order sort key
     const int Npad = (N + 3) / 4 * 4;
@@ -129,7 +131,7 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
     RV_RES(b.slot_to_id, cap * 4);
     RV_RES(b.fstart, ((size_t)n_frames + 1) * 4);
     RV_RES(b.vkeys, m_bound * 16);
-    RV_RES(b.offsets, E * 4);
+    RV_RES(b.offsets, E * 4);   // (the 16-bit form uses half of it: a context that leaves the counting-sort path needs nothing new)
     RV_RES(b.bary, E * 4);
     RV_RES(b.nb1, m_bound * (d + 1) * 4);
     RV_RES(b.nb2, m_bound * (d + 1) * 4);
@@ -182,11 +184,14 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
     // gain nothing, so small launches keep 256 (sweep of 256 .. 4096 over 8 - 64 frames: scratch-style script in
     // DESIGN.md section 4; results are identical for every size)
     L.cs_pix = ctx->sched.csr_block > 0 ? ctx->sched.csr_block : (n_frames <= 8 ? 256 : 1024);
+    L.ids16 = 0;
     if (csr_fast_path(L)) {
         if ((st = dev_reserve(ctx, b.block_hist, csr_fast_bytes(L))) != RVSEG_OK) return st;
         b.sb.block_hist = b.block_hist.as<unsigned>();
         L.bh = b.sb.block_hist;
         L.wbpf = (N + L.cs_pix - 1) / L.cs_pix;
+        // at most 8192 slots and 4096 vertices per frame: frame-local slots and ids fit 16 bits
+        L.ids16 = frame_ids && d == 6 ? 1 : 0;
     }
     b.n_entries = E; b.n_points = P;
     b.built = false;
@@ -602,7 +607,7 @@ rvseg_status crf_frames_build_begin(rvseg_ctx* ctx, Pipeline* im, int n, hipStre
     if ((st = crf_frames_status(ctx, im, true)) != RVSEG_OK) return st;
     if (cs->lat.size() < 1) cs->lat.resize(1);
     LatticeBufs& lb = cs->lat[0];
-    if ((st = lattice_prepare(ctx, lb, 6, N, n, false, cs->frame_vertices_seen)) != RVSEG_OK) return st;
+    if ((st = lattice_prepare(ctx, lb, 6, N, n, false, cs->frame_vertices_seen, true)) != RVSEG_OK) return st;
     return lattice_clear(ctx, lb, s);
 }
 
