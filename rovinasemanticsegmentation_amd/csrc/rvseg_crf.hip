@@ -1,6 +1,5 @@
-// CRF orchestration: lattice construction, normaliser, mean-field loop; the C-ABI entry points
-// rvseg_crf_infer / rvseg_crf_infer_multi / rvseg_lattice_build / rvseg_lattice_filter and the
-// per-frame CRF stage of the frame pipeline.
+// CRF orchestration: lattice construction, normaliser, mean-field loop; the C-ABI entry points rvseg_crf_infer* /
+// rvseg_lattice_* and the CRF stages of the frame pipeline and of the cloud path.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -78,16 +77,26 @@ static int ceil_log2(unsigned long long v) {
     return b;
 }
 
-// per-frame hash capacity: params.lattice_capacity_log2 > 0 as given; 0 = 2^12; < 0 or `safe` =
-// enough for every point to own d+1 private vertices at load factor 1/2.  Every overflow seen on this
-// context has raised cap_boost by 3 (x8 slots), so a scene that does not fit is paid for once.
+// the vector of lattices grown to hold lattice k (one per pairwise term; the frame path and the clouds use lattice 0)
+static LatticeBufs& lattice_at(CrfState* cs, int k) {
+    if ((int)cs->lat.size() <= k) cs->lat.resize((size_t)k + 1);
+    return cs->lat[k];
+}
+
+// the per-frame capacity the context asks for: params.lattice_capacity_log2 > 0 as given, else 2^12 (the Segmenter
+// kernel yields ~300 vertices per synthetic 640x480 frame).  Every overflow seen on this context has raised cap_boost
+// by 3 (x8 slots), so a scene that does not fit is paid for once.
+static int configured_capacity_log2(const rvseg_ctx* ctx) {
+    const int want = ctx->params.lattice_capacity_log2 > 0 ? ctx->params.lattice_capacity_log2 : 12;
+    return want + (ctx->impl ? ctx->impl->cap_boost : 0);
+}
+
+// per-frame hash capacity: the configured one; params.lattice_capacity_log2 < 0 or `safe` = enough for every point to
+// own d+1 private vertices at load factor 1/2, which also bounds the configured one
 static int capacity_log2_per_frame(const rvseg_ctx* ctx, int Npad, int d, bool safe) {
     const int safe_log2 = ceil_log2(2ull * (unsigned long long)Npad * (d + 1));
-    int want = ctx->params.lattice_capacity_log2;
-    if (safe || want < 0) return safe_log2;
-    if (want == 0) want = 12;   // the Segmenter kernel yields ~300 vertices per synthetic 640x480 frame
-    if (ctx->impl) want += ctx->impl->cap_boost;
-    return want < safe_log2 ? want : safe_log2;
+    if (safe || ctx->params.lattice_capacity_log2 < 0) return safe_log2;
+    return std::min(configured_capacity_log2(ctx), safe_log2);
 }
 
 static bool capacity_is_worst_case(const rvseg_ctx* ctx, int N, int d) {
@@ -110,22 +119,30 @@ static bool resident_pays(int n_frames, int N, int vertices_per_frame_seen) {
     return n_frames >= 2 && (long long)n_frames * N >= 6900000ll + 4900ll * vpf;
 }
 
-// frame_ids: the frame path's lattice (d = 6, table partitioned by frame) may keep 16-bit frame-local ids (LatticeDev::ids16)
-static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N, int n_frames, bool safe, int vertices_per_frame_seen = 0,
-                                    bool frame_ids = false) {
-    if (d < 1 || d > 7) { ctx->err = "feature dimension must be in [1,7]"; return RVSEG_ERR_INVALID_ARG; }
-    if (n_frames > 1022) { ctx->err = "at most 1022 frames per chunk (lower max_batch)"; return RVSEG_ERR_INVALID_ARG; }   // 10-bit frame field of the launch-order sort key
-    const int Npad = (N + 3) / 4 * 4;
-    const int cap_f_log2 = capacity_log2_per_frame(ctx, Npad, d, safe);
-    const unsigned long long cap = (unsigned long long)n_frames << cap_f_log2;
-    if (cap >= (1ull << 31)) { ctx->err = "lattice hash capacity too large (lower max_batch or lattice_capacity_log2)"; return RVSEG_ERR_CAPACITY; }
-    const unsigned long long worst = (unsigned long long)Npad * n_frames * (d + 1);
-    const unsigned long long m_bound = std::min<unsigned long long>(cap / 2 + 2, worst);
-    const long long P = (long long)N * n_frames;
-    const long long E = P * (d + 1);
-    if (E >= (1ll << 32) || m_bound >= (1ull << 31)) { ctx->err = "too many lattice entries for 32-bit indices"; return RVSEG_ERR_CAPACITY; }
-    rvseg_status st;
-#define RV_RES(buf, bytes) if ((st = dev_reserve(ctx, buf, (size_t)(bytes))) != RVSEG_OK) return st
+// Sizes of one lattice over n_frames frames of N points, from plain integers: hash slots of all frames, bound of the
+// vertex count, points, entries = P (d+1)
+struct LatticeLimits { int Npad, cap_f_log2, key_bits; unsigned long long cap, m_bound; long long P, E; };
+
+static rvseg_status lattice_limits(int d, int N, int n_frames, int cap_f_log2, LatticeLimits& m, const char** err) {
+    if (n_frames > 1022) { *err = "at most 1022 frames per chunk (lower max_batch)"; return RVSEG_ERR_INVALID_ARG; }   // 10-bit frame field of the launch-order sort key
+    m.Npad = (N + 3) / 4 * 4;
+    m.cap_f_log2 = cap_f_log2;
+    m.cap = (unsigned long long)n_frames << cap_f_log2;
+    if (m.cap >= (1ull << 31)) { *err = "lattice hash capacity too large (lower max_batch or lattice_capacity_log2)"; return RVSEG_ERR_CAPACITY; }
+    const unsigned long long worst = (unsigned long long)m.Npad * n_frames * (d + 1);
+    m.m_bound = std::min<unsigned long long>(m.cap / 2 + 2, worst);
+    m.P = (long long)N * n_frames;
+    m.E = m.P * (d + 1);
+    if (m.E >= (1ll << 32) || m.m_bound >= (1ull << 31)) { *err = "too many lattice entries for 32-bit indices"; return RVSEG_ERR_CAPACITY; }
+    m.key_bits = std::max(1, ceil_log2(m.m_bound));
+    return RVSEG_OK;
+}
+
+#define RV_RES(buf, bytes) do { const rvseg_status st_ = dev_reserve(ctx, buf, (size_t)(bytes)); if (st_ != RVSEG_OK) return st_; } while (0)
+
+// the lattice's buffers (all but block_hist and the resident schedule's, whose sizes follow from the filled LatticeDev)
+static rvseg_status lattice_reserve(rvseg_ctx* ctx, LatticeBufs& b, const LatticeLimits& m, int d, int n_frames) {
+    const unsigned long long cap = m.cap, m_bound = m.m_bound, E = (unsigned long long)m.E;
     RV_RES(b.state, cap * 4);
     RV_RES(b.tkeys, cap * 16);
     RV_RES(b.slot_to_id, cap * 4);
@@ -138,24 +155,28 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
     RV_RES(b.csr_pw, E * 8);
     RV_RES(b.vstart, (2 * m_bound + 4) * 4);   // vstart | vend | counters: one allocation, zeroed by ONE memset per build
     RV_RES(b.vorder, m_bound * 4);
-    RV_RES(b.norm, P * 4);
-    const unsigned long long SE = std::max<unsigned long long>((unsigned long long)E, m_bound);  // also sorts the vertex order
+    RV_RES(b.norm, m.P * 4);
+    const unsigned long long SE = std::max(E, m_bound);  // also sorts the vertex order
     RV_RES(b.keys_in, SE * 4);
     RV_RES(b.keys_out, SE * 4);
     RV_RES(b.vals_in, SE * 4);
     RV_RES(b.vals_out, SE * 4);
-    const int key_bits = std::max(1, ceil_log2(m_bound));
-    const size_t temp = std::max(sort_temp_bytes(E, key_bits), sort_temp_bytes((long long)m_bound, 32));
-    RV_RES(b.sort_temp, temp);
-    const size_t stemp = scan_temp_bytes((unsigned)cap);
-    RV_RES(b.scan_temp, stemp);
-#undef RV_RES
+    b.sb.temp_bytes = std::max(sort_temp_bytes(m.E, m.key_bits), sort_temp_bytes((long long)m_bound, 32));
+    RV_RES(b.sort_temp, b.sb.temp_bytes);
+    b.sb.scan_temp_bytes = scan_temp_bytes((unsigned)cap);
+    RV_RES(b.scan_temp, b.sb.scan_temp_bytes);
+    return RVSEG_OK;
+}
+
+// LatticeDev / SortBuffers over the reserved buffers, and the CSR path: block_hist where the counting sort serves
+// frame_ids: the frame path's lattice (d = 6, table partitioned by frame) may keep 16-bit frame-local ids (LatticeDev::ids16)
+static rvseg_status lattice_fill(rvseg_ctx* ctx, LatticeBufs& b, const LatticeLimits& m, int d, int N, int n_frames, bool frame_ids) {
     LatticeDev& L = b.dev;
-    L.d = d; L.N = N; L.Npad = Npad; L.n_frames = n_frames;
-    L.cap_f_log2 = (unsigned)cap_f_log2;
-    L.cap_f_mask = (1u << cap_f_log2) - 1u;
-    L.cap_total = (unsigned)cap;
-    L.m_bound = (int)m_bound;
+    L.d = d; L.N = N; L.Npad = m.Npad; L.n_frames = n_frames;
+    L.cap_f_log2 = (unsigned)m.cap_f_log2;
+    L.cap_f_mask = (1u << m.cap_f_log2) - 1u;
+    L.cap_total = (unsigned)m.cap;
+    L.m_bound = (int)m.m_bound;
     // diagonal of E (permutohedral.cpp:177-182): float inv_std_dev; scale = 1/sqrt((i+2)(i+1)) * inv_std_dev
     const float inv_std_dev = (float)(std::sqrt(2.0 / 3.0) * (d + 1));
     for (int i = 0; i < 8; i++) L.scale[i] = i < d ? (float)(1.0 / std::sqrt((double)((i + 2) * (i + 1))) * inv_std_dev) : 0.f;
@@ -165,13 +186,13 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
     L.nb1 = b.nb1.as<int>(); L.nb2 = b.nb2.as<int>();
     L.csr_pw = b.csr_pw.as<uint2>(); L.csr_nrm = nullptr;
     b.has_csr_nrm = false;
-    L.vstart = b.vstart.as<unsigned>(); L.vend = L.vstart + m_bound; L.counters = reinterpret_cast<int*>(L.vend + m_bound);
+    L.vstart = b.vstart.as<unsigned>(); L.vend = L.vstart + m.m_bound; L.counters = reinterpret_cast<int*>(L.vend + m.m_bound);
     L.vorder = b.vorder.as<unsigned>(); L.norm = b.norm.as<float>();
     L.n_groups = n_frames >= 8 ? 8 : 1;
     b.sb.keys_in = b.keys_in.as<unsigned>(); b.sb.keys_out = b.keys_out.as<unsigned>();
     b.sb.vals_in = b.vals_in.as<unsigned>(); b.sb.vals_out = b.vals_out.as<unsigned>();
-    b.sb.temp = b.sort_temp.p; b.sb.temp_bytes = temp; b.sb.key_bits = key_bits;
-    b.sb.scan_temp = b.scan_temp.p; b.sb.scan_temp_bytes = stemp;
+    b.sb.temp = b.sort_temp.p; b.sb.key_bits = m.key_bits;   // (temp_bytes / scan_temp_bytes: lattice_reserve)
+    b.sb.scan_temp = b.scan_temp.p;
     b.sb.block_hist = nullptr;
     L.bh = nullptr; L.wbpf = 0;
     L.group_vertices = ctx->sched.group_vertices;
@@ -186,67 +207,85 @@ static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N
     L.cs_pix = ctx->sched.csr_block > 0 ? ctx->sched.csr_block : (n_frames <= 8 ? 256 : 1024);
     L.ids16 = 0;
     if (csr_fast_path(L)) {
-        if ((st = dev_reserve(ctx, b.block_hist, csr_fast_bytes(L))) != RVSEG_OK) return st;
+        RV_RES(b.block_hist, csr_fast_bytes(L));
         b.sb.block_hist = b.block_hist.as<unsigned>();
         L.bh = b.sb.block_hist;
         L.wbpf = (N + L.cs_pix - 1) / L.cs_pix;
         // at most 8192 slots and 4096 vertices per frame: frame-local slots and ids fit 16 bits
         L.ids16 = frame_ids && d == 6 ? 1 : 0;
     }
-    b.n_entries = E; b.n_points = P;
+    b.n_entries = m.E; b.n_points = m.P;
     b.built = false;
     b.cleared = false;
-    // Resident band schedule of the mean-field splat: chunks of many frames, whose splat is
-    // bound by the bytes the list-major walk re-reads.  All n_frames x B blocks have to be on the chip together.
-    b.resident_on = false;
-    {
-        const rvseg_schedule& sc = ctx->sched;
-        // Worth it where the list-major walk is bound by the bytes it re-reads rather than by its longest chain
-        // ("where it pays"): see resident_pays().  sched.splat = 2 forces it, 1 forbids it.
-        const bool wanted = sc.splat == 2 || (sc.splat == 0 && resident_pays(n_frames, N, vertices_per_frame_seen));
-        const int chunk = sc.resident_chunk == 64 ? 64 : 128;
-        const int capacity = resident_block_capacity(chunk);
-        // one block per CU measured best (the tile loop is bound by its own barrier-coupled latencies, a second block on
-        // the CU slows both): B = CUs / frames, at least 2, at most 12
-        int B = sc.resident_blocks > 0 ? sc.resident_blocks : (n_frames > 0 ? resident_cu_count() / n_frames : 0);
-        if (sc.resident_blocks <= 0) B = B < 2 ? 2 : (B > 12 ? 12 : B);
-        B = B > RES_MAXB ? RES_MAXB : B;
-        if (wanted && L.bh && d == 6 && B >= 2 && (long long)n_frames * B <= capacity &&
-            7ll * N < (1ll << 24) && (long long)L.wbpf * L.cs_pix <= 8192ll * RES_MAX_BANDS && L.cs_pix <= 4096) {   // (bands stay under 16 384 points: chunk counts fit 8 bits)
-            SplatResidentDev& R = b.resident;
-            R.B = B;
-            R.band_wb = sc.resident_band < 1 ? 1 : (sc.resident_band > 32 ? 32 : sc.resident_band);
-            R.band_wb = std::max(1, R.band_wb * 256 / L.cs_pix);   // rvseg_schedule.resident_band counts 256 points
-            R.n_bands = (L.wbpf + R.band_wb - 1) / R.band_wb;
-            while (R.n_bands > RES_MAX_BANDS) { R.band_wb *= 2; R.n_bands = (L.wbpf + R.band_wb - 1) / R.band_wb; }
-            R.window = sc.resident_window;
-            R.chunk_log2 = chunk == 128 ? 7 : 6;
-            R.cap_tiles = (unsigned)(N / 8 + 1024);
-            if (sc.resident_cap_tiles > 0 && (unsigned)sc.resident_cap_tiles < R.cap_tiles) R.cap_tiles = (unsigned)sc.resident_cap_tiles;
-            const size_t small = (16 + (size_t)n_frames * (RES_MAXB + 1) + (size_t)n_frames * RES_MAXB + 2 * (size_t)n_frames * RES_MAXB) * 4;
-            if ((st = dev_reserve(ctx, b.r_desc, (size_t)n_frames * 7 * R.cap_tiles * 4)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, b.r_vl, (size_t)n_frames * 7 * R.cap_tiles * 2)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, b.r_info, (size_t)n_frames * R.cap_tiles * 4)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, b.r_small, small)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, b.r_verts, (size_t)n_frames * RES_MAXB * RES_MAX_OWNV * 2)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, b.r_jb, (size_t)n_frames * RES_MAXB * (R.n_bands + 1) * 4)) != RVSEG_OK) return st;
-            R.tdesc = b.r_desc.as<unsigned>(); R.tvl = b.r_vl.as<unsigned short>(); R.tinfo = b.r_info.as<unsigned>();
-            unsigned* sm = b.r_small.as<unsigned>();
-            R.flags = reinterpret_cast<int*>(sm); sm += 16;
-            R.blk_tile0 = sm; sm += (size_t)n_frames * (RES_MAXB + 1);
-            R.blk_nown = sm; sm += (size_t)n_frames * RES_MAXB;
-            R.prog = sm;
-            R.blk_verts = b.r_verts.as<unsigned short>();
-            R.jb_tile = b.r_jb.as<unsigned>();
-            R.trace = nullptr;
-            if (sc.trace) {
-                if ((st = dev_reserve(ctx, b.r_trace, (size_t)n_frames * RES_MAXB * 64)) != RVSEG_OK) return st;
-                R.trace = b.r_trace.as<unsigned long long>();
-            }
-            b.resident_on = true;
-        }
-    }
     return RVSEG_OK;
+}
+
+// Resident band schedule of the mean-field splat: chunks of many frames, whose splat is
+// bound by the bytes the list-major walk re-reads.  All n_frames x B blocks have to be on the chip together.
+static rvseg_status resident_prepare(rvseg_ctx* ctx, LatticeBufs& b, int vertices_per_frame_seen) {
+    const LatticeDev& L = b.dev;
+    const int d = L.d, N = L.N, n_frames = L.n_frames;
+    const rvseg_schedule& sc = ctx->sched;
+    b.resident_on = false;
+    // Worth it where the list-major walk is bound by the bytes it re-reads rather than by its longest chain
+    // ("where it pays"): see resident_pays().  sched.splat = 2 forces it, 1 forbids it.
+    const bool wanted = sc.splat == 2 || (sc.splat == 0 && resident_pays(n_frames, N, vertices_per_frame_seen));
+    const int chunk = sc.resident_chunk == 64 ? 64 : 128;
+    const int capacity = resident_block_capacity(chunk);
+    // one block per CU measured best (the tile loop is bound by its own barrier-coupled latencies, a second block on
+    // the CU slows both): B = CUs / frames, at least 2, at most 12
+    int B = sc.resident_blocks > 0 ? sc.resident_blocks : (n_frames > 0 ? resident_cu_count() / n_frames : 0);
+    if (sc.resident_blocks <= 0) B = B < 2 ? 2 : (B > 12 ? 12 : B);
+    B = B > RES_MAXB ? RES_MAXB : B;
+    if (!(wanted && L.bh && d == 6 && B >= 2 && (long long)n_frames * B <= capacity &&
+          7ll * N < (1ll << 24) && (long long)L.wbpf * L.cs_pix <= 8192ll * RES_MAX_BANDS && L.cs_pix <= 4096)) return RVSEG_OK;   // (bands stay under 16 384 points: chunk counts fit 8 bits)
+    SplatResidentDev& R = b.resident;
+    R.B = B;
+    R.band_wb = sc.resident_band < 1 ? 1 : (sc.resident_band > 32 ? 32 : sc.resident_band);
+    R.band_wb = std::max(1, R.band_wb * 256 / L.cs_pix);   // rvseg_schedule.resident_band counts 256 points
+    R.n_bands = (L.wbpf + R.band_wb - 1) / R.band_wb;
+    while (R.n_bands > RES_MAX_BANDS) { R.band_wb *= 2; R.n_bands = (L.wbpf + R.band_wb - 1) / R.band_wb; }
+    R.window = sc.resident_window;
+    R.chunk_log2 = chunk == 128 ? 7 : 6;
+    R.cap_tiles = (unsigned)(N / 8 + 1024);
+    if (sc.resident_cap_tiles > 0 && (unsigned)sc.resident_cap_tiles < R.cap_tiles) R.cap_tiles = (unsigned)sc.resident_cap_tiles;
+    const size_t small = (16 + (size_t)n_frames * (RES_MAXB + 1) + (size_t)n_frames * RES_MAXB + 2 * (size_t)n_frames * RES_MAXB) * 4;
+    RV_RES(b.r_desc, (size_t)n_frames * 7 * R.cap_tiles * 4);
+    RV_RES(b.r_vl, (size_t)n_frames * 7 * R.cap_tiles * 2);
+    RV_RES(b.r_info, (size_t)n_frames * R.cap_tiles * 4);
+    RV_RES(b.r_small, small);
+    RV_RES(b.r_verts, (size_t)n_frames * RES_MAXB * RES_MAX_OWNV * 2);
+    RV_RES(b.r_jb, (size_t)n_frames * RES_MAXB * (R.n_bands + 1) * 4);
+    R.tdesc = b.r_desc.as<unsigned>(); R.tvl = b.r_vl.as<unsigned short>(); R.tinfo = b.r_info.as<unsigned>();
+    unsigned* sm = b.r_small.as<unsigned>();
+    R.flags = reinterpret_cast<int*>(sm); sm += 16;
+    R.blk_tile0 = sm; sm += (size_t)n_frames * (RES_MAXB + 1);
+    R.blk_nown = sm; sm += (size_t)n_frames * RES_MAXB;
+    R.prog = sm;
+    R.blk_verts = b.r_verts.as<unsigned short>();
+    R.jb_tile = b.r_jb.as<unsigned>();
+    R.trace = nullptr;
+    if (sc.trace) {
+        RV_RES(b.r_trace, (size_t)n_frames * RES_MAXB * 64);
+        R.trace = b.r_trace.as<unsigned long long>();
+    }
+    b.resident_on = true;
+    return RVSEG_OK;
+}
+#undef RV_RES
+
+// limits, buffers, LatticeDev and the splat's schedule of a lattice of n_frames x N points; `safe`: at the capacity that
+// cannot overflow.  vertices_per_frame_seen / frame_ids: the frame path's (resident_pays, LatticeDev::ids16)
+static rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N, int n_frames, bool safe, int vertices_per_frame_seen = 0,
+                                    bool frame_ids = false) {
+    if (d < 1 || d > 7) { ctx->err = "feature dimension must be in [1,7]"; return RVSEG_ERR_INVALID_ARG; }
+    LatticeLimits m;
+    const char* err = nullptr;
+    rvseg_status st = lattice_limits(d, N, n_frames, capacity_log2_per_frame(ctx, (N + 3) / 4 * 4, d, safe), m, &err);
+    if (st != RVSEG_OK) { ctx->err = err; return st; }
+    if ((st = lattice_reserve(ctx, b, m, d, n_frames)) != RVSEG_OK) return st;
+    if ((st = lattice_fill(ctx, b, m, d, N, n_frames, frame_ids)) != RVSEG_OK) return st;
+    return resident_prepare(ctx, b, vertices_per_frame_seen);
 }
 
 static rvseg_status values_reserve(rvseg_ctx* ctx, CrfState* cs, long long m_bound, int C, int slot = 0) {
@@ -353,17 +392,22 @@ static rvseg_status counters_readback(rvseg_ctx* ctx, CrfState* cs, const Lattic
     return RVSEG_OK;
 }
 
-// synchronous read of the build counters (host entry points)
+// what a read-back slot tells rvseg_last_schedule about the build cs->info describes
+static void counters_to_info(CrfState* cs, const int* h) {
+    cs->info.vertices = h[0];
+    cs->info.longest_list = h[2];
+    cs->info.planner_fallback = h[3];
+    cs->info_async = false;
+}
+
+// synchronous read of the build counters (host entry points): out = M, overflow, longest vertex list
 static rvseg_status lattice_counters(rvseg_ctx* ctx, CrfState* cs, const LatticeBufs& b, hipStream_t s, int out[3]) {
     rvseg_status st = counters_readback(ctx, cs, b, 1, s);
     if (st != RVSEG_OK) return st;
     RV_HIP(ctx, hipStreamSynchronize(s));
     const int* h = cs->h_counters.as<int>() + 4;
     out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
-    cs->info.vertices = h[0];
-    cs->info.longest_list = h[2];
-    cs->info.planner_fallback = h[3];
-    cs->info_async = false;
+    counters_to_info(cs, h);
     return RVSEG_OK;
 }
 
@@ -569,22 +613,14 @@ rvseg_status crf_frames_status(rvseg_ctx* ctx, Pipeline* im, bool wait) {
     cs->counters_pending = false;
     const int* h = cs->h_counters.as<int>();
     if (cs->pending_frames > 0 && !h[1]) cs->frame_vertices_seen = h[0] / cs->pending_frames;
-    if (cs->info_async) {   // no other lattice has been built on this context since
-        cs->info.vertices = h[0];
-        cs->info.longest_list = h[2];
-        cs->info.planner_fallback = h[3];
-        cs->info_async = false;
-    }
+    if (cs->info_async) counters_to_info(cs, h);   // no other lattice has been built on this context since
     if (h[1]) {
         const FrameGeom& g = im->geom;
         const bool was_worst = capacity_is_worst_case(ctx, g.W * g.H, 6);
         // x8 slots per step, but stop at 2^13 on the way up: the largest capacity the counting-sort CSR path serves
         // (real scenes with a deep range have ~2 000 vertices per frame; beyond it the radix-sort path takes over)
-        {
-            int base = ctx->params.lattice_capacity_log2 > 0 ? ctx->params.lattice_capacity_log2 : 12;
-            const int cur = base + im->cap_boost;
-            im->cap_boost += cur < 13 ? std::min(3, 13 - cur) : 3;
-        }
+        const int cur = configured_capacity_log2(ctx);
+        im->cap_boost += cur < 13 ? std::min(3, 13 - cur) : 3;
         ctx->err = was_worst ? "lattice hash table overflowed at its worst-case capacity (internal error)"
                              : "lattice hash table overflowed: the outputs of that call are invalid; the context has raised its "
                                "capacity (x8 slots per frame), repeat the call (or set params.lattice_capacity_log2 = -1)";
@@ -605,8 +641,7 @@ rvseg_status crf_frames_build_begin(rvseg_ctx* ctx, Pipeline* im, int n, hipStre
     // status of the previous asynchronous build (an earlier chunk of this call, or an earlier call whose
     // status nobody polled): its outputs were invalid, so this call must not pass for a clean one
     if ((st = crf_frames_status(ctx, im, true)) != RVSEG_OK) return st;
-    if (cs->lat.size() < 1) cs->lat.resize(1);
-    LatticeBufs& lb = cs->lat[0];
+    LatticeBufs& lb = lattice_at(cs, 0);
     if ((st = lattice_prepare(ctx, lb, 6, N, n, false, cs->frame_vertices_seen, true)) != RVSEG_OK) return st;
     return lattice_clear(ctx, lb, s);
 }
@@ -632,46 +667,67 @@ rvseg_status crf_frames_build(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
     return RVSEG_OK;
 }
 
+// What the mean field of one label layer reads and writes.  lab.labels == nullptr: no labels wanted; label_here: labels
+// that the fused update did not write are taken from Q (one dense N x C matrix) right behind the layer's loop
+struct LayerIo { ValueView U, Q; MfLabels lab; bool label_here; };
+
+// The mean fields of the label layers of cs->lat[0], layer l on scratch slot l & 1 and, with two streams, odd layers on
+// the second one.  `layer(l, prefix, slot)` gives the LayerIo of layer l, whose classes start at `prefix`: an inlined
+// functor, because enqueuing a layer must not allocate (see below).  *all_labelled: every layer's labels are written.
+template <class Layer>
+static rvseg_status crf_layers(rvseg_ctx* ctx, CrfState* cs, int n_layers, const int* class_counts, int N, long long n_points, float potts_w,
+                               int iterations, hipStream_t s, const Layer& layer, bool* all_labelled) {
+    const std::vector<TermPlan> plan{potts_term(potts_w)};
+    *all_labelled = true;
+    hipStream_t s2;
+    rvseg_status st = csr_nrm_before_fork(ctx, cs, n_layers, class_counts, iterations, s);
+    if (st != RVSEG_OK) return st;
+    if ((st = layer_stream_fork(ctx, cs, s, n_layers, &s2)) != RVSEG_OK) return st;
+    // With two streams the layers of the SECOND stream are enqueued first: enqueuing a layer's whole loop takes the host
+    // a few hundred microseconds, during which the other stream has nothing to run, and the reference's second layer
+    // is the one with more classes (8 and 9: the longer loop starts first)
+    for (int li = 0; li < n_layers && st == RVSEG_OK; li++) {
+        const int l = layer_enqueue_order(li, n_layers, s2 != s);
+        size_t prefix = 0;
+        for (int k = 0; k < l; k++) prefix += (size_t)class_counts[k];
+        const int C = class_counts[l], slot = l & 1;
+        hipStream_t sl = slot ? s2 : s;
+        const bool timed = slot == 0 || s2 == s;
+        const LayerIo io = layer(l, prefix, slot);
+        bool done = false;
+        st = mean_field(ctx, cs, plan, nullptr, io.U, false, C, N, n_points, iterations, io.Q, sl, io.lab.labels ? &io.lab : nullptr, &done, slot, timed);
+        if (st == RVSEG_OK && io.lab.labels && !done && io.label_here) {
+            if (timed) timer_mark(ctx, "labels", sl);
+            launch_labels(io.Q.base, (size_t)N, C, io.lab.mode, io.lab.unknown, io.lab.labels, sl);
+            done = true;
+        }
+        *all_labelled = *all_labelled && done;
+    }
+    const rvseg_status stj = layer_stream_join(ctx, cs, s, s2);   // (also behind a failed layer: the second stream rejoins)
+    return st != RVSEG_OK ? st : stj;
+}
+
 rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& f, int n, const float* d_post, float* d_marg,
                               int8_t* d_labels, hipStream_t s) {
     CrfState* cs;
-    rvseg_status st0 = crf_state(ctx, &cs);
-    if (st0 != RVSEG_OK) return st0;
-    const FrameGeom& g = im->geom;
+    rvseg_status st = crf_state(ctx, &cs);
+    if (st != RVSEG_OK) return st;
     const rvseg_params& p = ctx->params;
-    const int N = g.W * g.H;
-    rvseg_status st;
+    const int N = im->geom.W * im->geom.H;
     const size_t frame_stride = (size_t)N * f.sum_classes;
     float* marg = d_marg;
     if (!marg) {
         if ((st = dev_reserve(ctx, cs->q, frame_stride * 4 * n)) != RVSEG_OK) return st;
         marg = cs->q.as<float>();
     }
-    int prefix = 0;
-    const std::vector<TermPlan> plan{potts_term(p.dcrf_kernel_weight)};
-    bool all_labelled = true;   // the last fused update of every layer wrote its labels
-    hipStream_t s2;
-    if ((st = csr_nrm_before_fork(ctx, cs, f.n_layers, f.class_counts, p.dcrf_iterations, s)) != RVSEG_OK) return st;
-    if ((st = layer_stream_fork(ctx, cs, s, f.n_layers, &s2)) != RVSEG_OK) return st;
-    // With two streams the layers of the SECOND stream are enqueued first: enqueuing a layer's whole loop takes the host
-    // a few hundred microseconds, during which the other stream has nothing to run, and the reference's second layer
-    // is the one with more classes (8 and 9: the longer loop starts first)
-    for (int li = 0; li < f.n_layers; li++) {
-        const int l = layer_enqueue_order(li, f.n_layers, s2 != s);
-        prefix = 0;
-        for (int k = 0; k < l; k++) prefix += f.class_counts[k];
-        const int C = f.class_counts[l];
-        ValueView U{const_cast<float*>(d_post), frame_stride, (size_t)N * prefix};
-        ValueView Q{marg, frame_stride, (size_t)N * prefix};
-        // unary energy = -(log-posterior) (segmenter.cpp:642), so -U is the posterior itself
-        MfLabels lab{d_labels, p.label_mode, p.unknown_label[l], f.n_layers, l};
-        bool done = false;
-        const int slot = l & 1;
-        if ((st = mean_field(ctx, cs, plan, nullptr, U, false, C, N, (long long)N * n, p.dcrf_iterations, Q, slot ? s2 : s, d_labels ? &lab : nullptr,
-                             &done, slot, slot == 0 || s2 == s)) != RVSEG_OK) { (void)layer_stream_join(ctx, cs, s, s2); return st; }
-        all_labelled = all_labelled && done;
-    }
-    if ((st = layer_stream_join(ctx, cs, s, s2)) != RVSEG_OK) return st;
+    // a layer inside the frames' posteriors and marginals; unary energy = -(log-posterior) (segmenter.cpp:642), so -U is the posterior
+    auto layer = [&](int l, size_t prefix, int) {
+        return LayerIo{ValueView{const_cast<float*>(d_post), frame_stride, (size_t)N * prefix}, ValueView{marg, frame_stride, (size_t)N * prefix},
+                       MfLabels{d_labels, p.label_mode, p.unknown_label[l], f.n_layers, l}, false};
+    };
+    bool all_labelled;   // the last fused update of every layer wrote its labels
+    if ((st = crf_layers(ctx, cs, f.n_layers, f.class_counts, N, (long long)N * n, p.dcrf_kernel_weight, p.dcrf_iterations, s, layer,
+                         &all_labelled)) != RVSEG_OK) return st;
     if (d_labels && !all_labelled) {
         timer_mark(ctx, "labels", s);
         launch_labels_frames(marg, n, N, f, p.label_mode, p.unknown_label, d_labels, s);
@@ -679,71 +735,105 @@ rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& f
     return RVSEG_OK;
 }
 
-// Permutohedral::init on device-resident features with the overflow retry of the host entry points:
-// the counters are read back (one stream synchronisation) before the mean field is enqueued
-static rvseg_status lattice_build_retry(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb, int d, int N, const float* d_feat, hipStream_t s) {
-    rvseg_status st;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if ((st = lattice_prepare(ctx, lb, d, N, 1, attempt == 1)) != RVSEG_OK) return st;
-        FeatureSource fs{};
-        fs.mode = 0; fs.feat = d_feat;
-        if ((st = lattice_build(ctx, cs, lb, fs, s)) != RVSEG_OK) return st;
-        int cnt[3];
-        if ((st = lattice_counters(ctx, cs, lb, s, cnt)) != RVSEG_OK) return st;
-        if (!cnt[1]) return RVSEG_OK;
-    }
-    ctx->err = "lattice hash table overflow";
-    return RVSEG_ERR_CAPACITY;
+// One pairwise term's lattice input: N x d features in host or device memory, the kernel parameters that transform them
+// (pairwise.cpp:140-152; none for CONST_KERNEL or a null pointer) and the normaliser the term needs (rvseg_norm_kind)
+struct TermInput { int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; };
+
+static TermInput potts_input(int d, const float* features, bool on_host) {
+    return TermInput{d, features, on_host, RVSEG_CONST_KERNEL, nullptr, RVSEG_NORMALIZE_SYMMETRIC};
 }
 
-// The lattices of learned terms: the features (host: copied in; device: read in place), transformed by the term's kernel
-// parameters (pairwise.cpp:140-152) into context memory, then built with the normaliser the term needs.  A hash overflow
-// of any term rebuilds all of them once at the safe capacity, as rvseg_crf_infer_multi does.
-static rvseg_status build_terms(rvseg_ctx* ctx, CrfState* cs, int N, int n_terms, const rvseg_crf_term* terms, bool host_features,
-                                hipStream_t s) {
-    if ((int)cs->lat.size() < n_terms) cs->lat.resize(n_terms);
+// Permutohedral::init + normaliser of term `t` on lattice `lb` (host features are copied into cs->feat, kernel
+// parameters applied into cs->kfeat), then the counters, read back with one stream synchronisation
+static rvseg_status build_lattice(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb, int N, const TermInput& t, bool safe, hipStream_t s, int cnt[3]) {
     rvseg_status st;
+    if ((st = lattice_prepare(ctx, lb, t.d, N, 1, safe)) != RVSEG_OK) return st;
+    const float* f = t.features;
+    if (t.on_host) {
+        if ((st = dev_reserve(ctx, cs->feat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, t.features, (size_t)N * t.d * 4, hipMemcpyHostToDevice, s));
+        f = cs->feat.as<float>();
+    }
+    if (t.kernel_params && t.kernel_type != RVSEG_CONST_KERNEL) {
+        KernelParams kp{};
+        const int np = t.kernel_type == RVSEG_DIAG_KERNEL ? t.d : t.d * t.d;
+        for (int i = 0; i < np; i++) kp.p[i] = t.kernel_params[i];
+        if ((st = dev_reserve(ctx, cs->kfeat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
+        launch_kernel_params(f, N, t.d, t.kernel_type, kp, cs->kfeat.as<float>(), s);
+        f = cs->kfeat.as<float>();
+    }
+    FeatureSource fs{};
+    fs.feat = f;   // (mode 0)
+    if ((st = lattice_build(ctx, cs, lb, fs, s, t.norm)) != RVSEG_OK) return st;
+    return lattice_counters(ctx, cs, lb, s, cnt);
+}
+
+// The lattices of n terms over N points, term k on cs->lat[k], with the overflow retry of the synchronous entry points:
+// a hash overflow of any term stops the attempt, and ALL terms are rebuilt once at the safe capacity, which cannot
+// overflow.  cnt (optional): the counters of the last lattice (M, overflow, longest list).
+static rvseg_status build_lattices(rvseg_ctx* ctx, CrfState* cs, int N, int n, const TermInput* terms, hipStream_t s, int* cnt = nullptr) {
+    if (n > 0) lattice_at(cs, n - 1);
+    int c[3] = {0, 0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
-        bool overflow = false;
-        for (int k = 0; k < n_terms && !overflow; k++) {
-            const rvseg_crf_term& t = terms[k];
-            LatticeBufs& lb = cs->lat[k];
-            if ((st = lattice_prepare(ctx, lb, t.d, N, 1, attempt == 1)) != RVSEG_OK) return st;
-            const float* f = t.features;
-            if (host_features) {
-                if ((st = dev_reserve(ctx, cs->feat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
-                RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, t.features, (size_t)N * t.d * 4, hipMemcpyHostToDevice, s));
-                f = cs->feat.as<float>();
-            }
-            if (t.kernel_params && t.kernel_type != RVSEG_CONST_KERNEL) {
-                KernelParams kp{};
-                const int np = t.kernel_type == RVSEG_DIAG_KERNEL ? t.d : t.d * t.d;
-                for (int i = 0; i < np; i++) kp.p[i] = t.kernel_params[i];
-                if ((st = dev_reserve(ctx, cs->kfeat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
-                launch_kernel_params(f, N, t.d, t.kernel_type, kp, cs->kfeat.as<float>(), s);
-                f = cs->kfeat.as<float>();
-            }
-            FeatureSource fs{};
-            fs.mode = 0; fs.feat = f;
-            if ((st = lattice_build(ctx, cs, lb, fs, s, t.normalization)) != RVSEG_OK) return st;
-            int cnt[3];
-            if ((st = lattice_counters(ctx, cs, lb, s, cnt)) != RVSEG_OK) return st;
-            overflow = cnt[1] != 0;
+        c[1] = 0;
+        for (int k = 0; k < n && !c[1]; k++) {
+            rvseg_status st = build_lattice(ctx, cs, cs->lat[k], N, terms[k], attempt == 1, s, c);
+            if (st != RVSEG_OK) return st;
         }
-        if (!overflow) return RVSEG_OK;
+        if (cnt) std::memcpy(cnt, c, sizeof(c));
+        if (!c[1]) return RVSEG_OK;
     }
     ctx->err = "lattice hash table overflow";
     return RVSEG_ERR_CAPACITY;
 }
 
-// the terms' compatibilities in context memory (uploaded from CrfState::h_compat, which outlives the copy)
-static rvseg_status upload_terms(rvseg_ctx* ctx, CrfState* cs, int C, int n_terms, const rvseg_crf_term* terms,
-                                 std::vector<TermPlan>& plan, hipStream_t s) {
-    plan_terms(C, n_terms, terms, plan, cs->h_compat);
-    if (cs->h_compat.empty()) return RVSEG_OK;
-    rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
-    if (st != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(cs->compat.p, cs->h_compat.data(), cs->h_compat.size() * 4, hipMemcpyHostToDevice, s));
+// Where a point CRF's unary comes from and where its marginals and labels go.  on_host: caller host memory, staged
+// through cs->unary / cs->q / cs->labels, and the call returns with the outputs complete.  Otherwise device memory, read
+// and written in place on the caller's stream (Q or map may be null), and the call only enqueues.
+struct PointIo { bool on_host; const float* unary; bool unary_is_energy; float* Q; int8_t* map; };
+
+// DenseCRF::inference + map over the lattices cs->lat[0 .. plan.size()) (build_lattices).  Stage timing: a host call
+// shows the mean field alone (its labels follow "end"); a device call adds to what its entry has marked, labels included.
+static rvseg_status crf_points(rvseg_ctx* ctx, CrfState* cs, int N, int C, const std::vector<TermPlan>& plan, const float* d_compat,
+                               const PointIo& io, int iterations, int label_mode, int unknown_label, hipStream_t s) {
+    rvseg_status st;
+    const size_t tot = (size_t)N * C;
+    const float* u = io.unary;
+    float* q = io.Q;
+    if (io.on_host || !q) {
+        if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
+        q = cs->q.as<float>();
+    }
+    if (io.on_host) {
+        if ((st = dev_reserve(ctx, cs->unary, tot * 4)) != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, io.unary, tot * 4, hipMemcpyHostToDevice, s));
+        u = cs->unary.as<float>();
+        timer_reset(ctx);
+    }
+    const ValueView U{const_cast<float*>(u), tot, 0}, Q{q, tot, 0};
+    // a device call lets the last fused update write the labels; a host call labels the marginals it downloads
+    const MfLabels lab{io.map, label_mode, unknown_label, 1, 0};
+    bool done = false;
+    if ((st = mean_field(ctx, cs, plan, d_compat, U, io.unary_is_energy, C, N, N, iterations, Q, s, !io.on_host && io.map ? &lab : nullptr,
+                         &done)) != RVSEG_OK) return st;
+    int8_t* d_map = io.map;
+    if (io.on_host) {
+        timer_mark(ctx, "end", s);
+        RV_HIP(ctx, hipMemcpyAsync(io.Q, q, tot * 4, hipMemcpyDeviceToHost, s));
+        if (io.map && (st = dev_reserve(ctx, cs->labels, (size_t)N)) != RVSEG_OK) return st;
+        d_map = cs->labels.as<int8_t>();
+    }
+    if (io.map && !done) {
+        if (!io.on_host) timer_mark(ctx, "labels", s);
+        launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map, s);
+    }
+    if (!io.on_host) {
+        timer_mark(ctx, "end", s);
+        RV_LAUNCH_OK(ctx);
+        return RVSEG_OK;
+    }
+    if (io.map) RV_HIP(ctx, hipMemcpyAsync(io.map, d_map, (size_t)N, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
     return RVSEG_OK;
 }
 
@@ -753,38 +843,22 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
     CrfState* cs;
     rvseg_status st = crf_state(ctx, &cs);
     if (st != RVSEG_OK) return st;
-    if (cs->lat.size() < 1) cs->lat.resize(1);
     timer_mark(ctx, "lattice_build", s);
-    if ((st = lattice_build_retry(ctx, cs, cs->lat[0], 6, N, d_features, s)) != RVSEG_OK) return st;
+    const TermInput cloud = potts_input(6, d_features, false);
+    if ((st = build_lattices(ctx, cs, N, 1, &cloud, s)) != RVSEG_OK) return st;
     int cmax = 0;
     for (int l = 0; l < n_layers; l++) cmax = std::max(cmax, class_counts[l]);
     // marginals of even / odd layers in two halves of cs->q (the odd layers run on the second stream)
     if ((st = dev_reserve(ctx, cs->q, (size_t)N * cmax * 4 * 2)) != RVSEG_OK) return st;
-    hipStream_t s2;
-    const std::vector<TermPlan> plan{potts_term(potts_w)};
-    if ((st = csr_nrm_before_fork(ctx, cs, n_layers, class_counts, iterations, s)) != RVSEG_OK) return st;
-    if ((st = layer_stream_fork(ctx, cs, s, n_layers, &s2)) != RVSEG_OK) return st;
-    for (int li = 0; li < n_layers; li++) {
-        const int l = layer_enqueue_order(li, n_layers, s2 != s);
-        size_t prefix = 0;
-        for (int k = 0; k < l; k++) prefix += (size_t)class_counts[k];
-        const int C = class_counts[l];
-        const int slot = l & 1;
-        hipStream_t sl = slot ? s2 : s;
-        float* q = cs->q.as<float>() + (size_t)slot * N * cmax;
-        ValueView U{const_cast<float*>(d_unaries) + (size_t)N * prefix, (size_t)N * C, 0};
-        ValueView Q{q, (size_t)N * C, 0};
-        MfLabels lab{d_labels ? d_labels + (size_t)l * N : nullptr, label_mode, unknown[l], 1, 0};
-        bool done = false;
-        // crf.setUnaryEnergy(-unaries[l]) (segmenter.cpp:642): the accumulated posteriors ARE -energy
-        if ((st = mean_field(ctx, cs, plan, nullptr, U, false, C, N, N, iterations, Q, sl, d_labels ? &lab : nullptr, &done, slot,
-                             slot == 0 || s2 == s)) != RVSEG_OK) { (void)layer_stream_join(ctx, cs, s, s2); return st; }
-        if (d_labels && !done) {
-            if (slot == 0 || s2 == s) timer_mark(ctx, "labels", sl);
-            launch_labels(q, (size_t)N, C, label_mode, unknown[l], d_labels + (size_t)l * N, sl);
-        }
-    }
-    if ((st = layer_stream_join(ctx, cs, s, s2)) != RVSEG_OK) return st;
+    // crf.setUnaryEnergy(-unaries[l]) (segmenter.cpp:642): the accumulated posteriors ARE -energy
+    auto layer = [&](int l, size_t prefix, int slot) {
+        const size_t tot = (size_t)N * class_counts[l];
+        return LayerIo{ValueView{const_cast<float*>(d_unaries) + (size_t)N * prefix, tot, 0},
+                       ValueView{cs->q.as<float>() + (size_t)slot * N * cmax, tot, 0},
+                       MfLabels{d_labels ? d_labels + (size_t)l * N : nullptr, label_mode, unknown[l], 1, 0}, true};
+    };
+    bool all_labelled;
+    if ((st = crf_layers(ctx, cs, n_layers, class_counts, N, N, potts_w, iterations, s, layer, &all_labelled)) != RVSEG_OK) return st;
     RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
 }
@@ -809,47 +883,16 @@ rvseg_status rvseg_crf_infer_multi(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
     rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || n_kernels < 0 || n_kernels > 8 || iterations < 0 || !unary_energy || !Q_out ||
-        (n_kernels > 0 && (!ds || !features || !ws)) || label_mode < 0 || label_mode > 3) {
-        ctx->err = "bad arguments";
-        return RVSEG_ERR_INVALID_ARG;
-    }
-    hipStream_t s = ctx->stream;
-    if ((int)cs->lat.size() < n_kernels) cs->lat.resize(n_kernels);
-    for (int attempt = 0; attempt < 2; attempt++) {
-        bool overflow = false;
-        for (int k = 0; k < n_kernels && !overflow; k++) {
-            LatticeBufs& lb = cs->lat[k];
-            if ((st = lattice_prepare(ctx, lb, ds[k], N, 1, attempt == 1)) != RVSEG_OK) return st;
-            if ((st = dev_reserve(ctx, cs->feat, (size_t)N * ds[k] * 4)) != RVSEG_OK) return st;
-            RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, features[k], (size_t)N * ds[k] * 4, hipMemcpyHostToDevice, s));
-            FeatureSource fs{};
-            fs.mode = 0; fs.feat = cs->feat.as<float>();
-            if ((st = lattice_build(ctx, cs, lb, fs, s)) != RVSEG_OK) return st;
-            int cnt[3];
-            if ((st = lattice_counters(ctx, cs, lb, s, cnt)) != RVSEG_OK) return st;
-            overflow = cnt[1] != 0;
-        }
-        if (!overflow) break;
-        if (attempt == 1) { ctx->err = "lattice hash table overflow"; return RVSEG_ERR_CAPACITY; }
-    }
-    const size_t tot = (size_t)N * C;
-    if ((st = dev_reserve(ctx, cs->unary, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_energy, tot * 4, hipMemcpyHostToDevice, s));
-    ValueView U{cs->unary.as<float>(), tot, 0}, Q{cs->q.as<float>(), tot, 0};
+        (n_kernels > 0 && (!ds || !features || !ws)) || label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    TermInput in[8];
     std::vector<TermPlan> plan;
-    for (int k = 0; k < n_kernels; k++) plan.push_back(potts_term(ws[k]));
-    timer_reset(ctx);
-    if ((st = mean_field(ctx, cs, plan, nullptr, U, true, C, N, N, iterations, Q, s)) != RVSEG_OK) return st;
-    timer_mark(ctx, "end", s);
-    RV_HIP(ctx, hipMemcpyAsync(Q_out, cs->q.p, tot * 4, hipMemcpyDeviceToHost, s));
-    if (map_out) {
-        if ((st = dev_reserve(ctx, cs->labels, (size_t)N)) != RVSEG_OK) return st;
-        launch_labels(cs->q.as<float>(), (size_t)N, C, label_mode, unknown_label, cs->labels.as<int8_t>(), s);
-        RV_HIP(ctx, hipMemcpyAsync(map_out, cs->labels.p, (size_t)N, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < n_kernels; k++) {
+        in[k] = potts_input(ds[k], features[k], true);   // (a bad ds[k] is the build's to report)
+        plan.push_back(potts_term(ws[k]));
     }
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
+    if ((st = build_lattices(ctx, cs, N, n_kernels, in, ctx->stream)) != RVSEG_OK) return st;
+    return crf_points(ctx, cs, N, C, plan, nullptr, PointIo{true, unary_energy, true, Q_out, map_out}, iterations, label_mode, unknown_label,
+                      ctx->stream);
 }
 
 rvseg_status rvseg_crf_terms_check(int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms) {
@@ -864,38 +907,35 @@ rvseg_status rvseg_crf_terms_check(int32_t N, int32_t C, int32_t n_terms, const 
     return RVSEG_OK;
 }
 
+// A learned model's terms (arguments checked by the caller): their plan, their compatibilities in context memory
+// (uploaded from CrfState::h_compat, which outlives the copy; also for Potts terms, which do not read them) and their lattices
+static rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
+                                  std::vector<TermPlan>& plan, hipStream_t s) {
+    plan_terms(C, n_terms, terms, plan, cs->h_compat);
+    if (!cs->h_compat.empty()) {
+        rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
+        if (st != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemcpyAsync(cs->compat.p, cs->h_compat.data(), cs->h_compat.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    TermInput in[8];
+    for (int k = 0; k < n_terms; k++)
+        in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization};
+    return build_lattices(ctx, cs, N, n_terms, in, s);
+}
+
 rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
                                    const float* unary_energy, int32_t iterations, float* Q_out, int8_t* map_out,
                                    int32_t label_mode, int32_t unknown_label) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !unary_energy || !Q_out || label_mode < 0 ||
-        label_mode > 3) {
-        ctx->err = "bad arguments";
-        return RVSEG_ERR_INVALID_ARG;
-    }
+        label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     CrfState* cs;
     rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
-    hipStream_t s = ctx->stream;
     std::vector<TermPlan> plan;
-    if ((st = upload_terms(ctx, cs, C, n_terms, terms, plan, s)) != RVSEG_OK) return st;
-    if ((st = build_terms(ctx, cs, N, n_terms, terms, true, s)) != RVSEG_OK) return st;
-    const size_t tot = (size_t)N * C;
-    if ((st = dev_reserve(ctx, cs->unary, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, cs->q, tot * 4)) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_energy, tot * 4, hipMemcpyHostToDevice, s));
-    ValueView U{cs->unary.as<float>(), tot, 0}, Q{cs->q.as<float>(), tot, 0};
-    timer_reset(ctx);
-    if ((st = mean_field(ctx, cs, plan, cs->compat.as<float>(), U, true, C, N, N, iterations, Q, s)) != RVSEG_OK) return st;
-    timer_mark(ctx, "end", s);
-    RV_HIP(ctx, hipMemcpyAsync(Q_out, cs->q.p, tot * 4, hipMemcpyDeviceToHost, s));
-    if (map_out) {
-        if ((st = dev_reserve(ctx, cs->labels, (size_t)N)) != RVSEG_OK) return st;
-        launch_labels(cs->q.as<float>(), (size_t)N, C, label_mode, unknown_label, cs->labels.as<int8_t>(), s);
-        RV_HIP(ctx, hipMemcpyAsync(map_out, cs->labels.p, (size_t)N, hipMemcpyDeviceToHost, s));
-    }
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
+    if ((st = terms_prepare(ctx, cs, N, C, n_terms, terms, true, plan, ctx->stream)) != RVSEG_OK) return st;
+    return crf_points(ctx, cs, N, C, plan, cs->compat.as<float>(), PointIo{true, unary_energy, true, Q_out, map_out}, iterations, label_mode,
+                      unknown_label, ctx->stream);
 }
 
 rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
@@ -903,10 +943,7 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
                                           int8_t* d_map_out, int32_t label_mode, int32_t unknown_label, void* hip_stream) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !d_unary || (!d_Q_out && !d_map_out) ||
-        label_mode < 0 || label_mode > 3) {
-        ctx->err = "bad arguments";
-        return RVSEG_ERR_INVALID_ARG;
-    }
+        label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     CrfState* cs;
     rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
@@ -914,25 +951,9 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
     timer_reset(ctx);
     timer_mark(ctx, "lattice_build", s);
     std::vector<TermPlan> plan;
-    if ((st = upload_terms(ctx, cs, C, n_terms, terms, plan, s)) != RVSEG_OK) return st;
-    if ((st = build_terms(ctx, cs, N, n_terms, terms, false, s)) != RVSEG_OK) return st;
-    float* q = d_Q_out;
-    if (!q) {
-        if ((st = dev_reserve(ctx, cs->q, (size_t)N * C * 4)) != RVSEG_OK) return st;
-        q = cs->q.as<float>();
-    }
-    ValueView U{const_cast<float*>(d_unary), (size_t)N * C, 0}, Q{q, (size_t)N * C, 0};
-    MfLabels lab{d_map_out, label_mode, unknown_label, 1, 0};
-    bool done = false;
-    if ((st = mean_field(ctx, cs, plan, cs->compat.as<float>(), U, unary_is_energy != 0, C, N, N, iterations, Q, s,
-                         d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
-    if (d_map_out && !done) {
-        timer_mark(ctx, "labels", s);
-        launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map_out, s);
-    }
-    timer_mark(ctx, "end", s);
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
+    if ((st = terms_prepare(ctx, cs, N, C, n_terms, terms, false, plan, s)) != RVSEG_OK) return st;
+    return crf_points(ctx, cs, N, C, plan, cs->compat.as<float>(), PointIo{false, d_unary, unary_is_energy != 0, d_Q_out, d_map_out}, iterations,
+                      label_mode, unknown_label, s);
 }
 
 static rvseg_status logistic_args(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* L, const float* f, const float* U) {
@@ -983,32 +1004,15 @@ rvseg_status rvseg_crf_infer_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_
     rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || d < 1 || d > 7 || iterations < 0 || !d_unary || !d_features || (!d_Q_out && !d_map_out) ||
-        label_mode < 0 || label_mode > 3) {
-        ctx->err = "bad arguments";
-        return RVSEG_ERR_INVALID_ARG;
-    }
+        label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    if (cs->lat.size() < 1) cs->lat.resize(1);
     timer_reset(ctx);
     timer_mark(ctx, "lattice_build", s);
-    if ((st = lattice_build_retry(ctx, cs, cs->lat[0], d, N, d_features, s)) != RVSEG_OK) return st;
-    float* q = d_Q_out;
-    if (!q) {
-        if ((st = dev_reserve(ctx, cs->q, (size_t)N * C * 4)) != RVSEG_OK) return st;
-        q = cs->q.as<float>();
-    }
-    ValueView U{const_cast<float*>(d_unary), (size_t)N * C, 0}, Q{q, (size_t)N * C, 0};
-    MfLabels lab{d_map_out, label_mode, unknown_label, 1, 0};
-    bool done = false;
+    const TermInput in = potts_input(d, d_features, false);
+    if ((st = build_lattices(ctx, cs, N, 1, &in, s)) != RVSEG_OK) return st;
     const std::vector<TermPlan> plan{potts_term(potts_w)};
-    if ((st = mean_field(ctx, cs, plan, nullptr, U, unary_is_energy != 0, C, N, N, iterations, Q, s, d_map_out ? &lab : nullptr, &done)) != RVSEG_OK) return st;
-    if (d_map_out && !done) {
-        timer_mark(ctx, "labels", s);
-        launch_labels(q, (size_t)N, C, label_mode, unknown_label, d_map_out, s);
-    }
-    timer_mark(ctx, "end", s);
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
+    return crf_points(ctx, cs, N, C, plan, nullptr, PointIo{false, d_unary, unary_is_energy != 0, d_Q_out, d_map_out}, iterations, label_mode,
+                      unknown_label, s);
 }
 
 rvseg_status rvseg_crf_infer(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t d, const float* unary_energy,
@@ -1025,20 +1029,10 @@ rvseg_status rvseg_lattice_build(rvseg_ctx* ctx, const float* features, int32_t 
     if (st != RVSEG_OK) return st;
     if (!features || N <= 0 || !M_out) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     hipStream_t s = ctx->stream;
-    if (cs->lat.size() < 1) cs->lat.resize(1);
-    LatticeBufs& lb = cs->lat[0];
     int cnt[3] = {0, 0, 0};
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if ((st = lattice_prepare(ctx, lb, d, N, 1, attempt == 1)) != RVSEG_OK) return st;
-        if ((st = dev_reserve(ctx, cs->feat, (size_t)N * d * 4)) != RVSEG_OK) return st;
-        RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, features, (size_t)N * d * 4, hipMemcpyHostToDevice, s));
-        FeatureSource fs{};
-        fs.mode = 0; fs.feat = cs->feat.as<float>();
-        if ((st = lattice_build(ctx, cs, lb, fs, s)) != RVSEG_OK) return st;
-        if ((st = lattice_counters(ctx, cs, lb, s, cnt)) != RVSEG_OK) return st;
-        if (!cnt[1]) break;
-        if (attempt == 1) { ctx->err = "lattice hash table overflow"; return RVSEG_ERR_CAPACITY; }
-    }
+    const TermInput in = potts_input(d, features, true);
+    if ((st = build_lattices(ctx, cs, N, 1, &in, s, cnt)) != RVSEG_OK) return st;
+    const LatticeBufs& lb = cs->lat[0];
     const int M = cnt[0];
     *M_out = M;
     const size_t E = (size_t)N * (d + 1);
