@@ -12,6 +12,8 @@
 //   * The splat (kernels_splat.hip) adds a vertex's contributions in ascending point order: the sort by vertex is STABLE.
 #include <string.h>   // rocprim's texture iterator calls the host memset without including it
 
+#include <type_traits>
+
 #include <rocprim/rocprim.hpp>
 
 #include "device_math.h"
@@ -301,6 +303,22 @@ lattice_points_kernel(LatticeDev L, FeatureSource fs, int n_chunks) {
   }
 }
 
+// The one statement of which dimensions are instantiated: calls f with d as a compile-time constant.  The API entry
+// points take no other d (RVSEG_ERR_INVALID_ARG), so a LatticeDev never carries one.
+template <class F>
+static void with_dimension(int d, F&& f) {
+    switch (d) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        case 6: f(std::integral_constant<int, 6>()); break;
+        case 7: f(std::integral_constant<int, 7>()); break;
+        default: break;   // rejected at the API
+    }
+}
+
 void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStream_t s) {
     const long long total = (long long)L.Npad * L.n_frames;
     // chunks per block: as many as leave >= 1024 blocks (a single frame or a cloud is a latency case: 150 blocks of
@@ -309,19 +327,13 @@ void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStre
     while (n_chunks > 1 && (total + 255) / 256 / n_chunks < 1024) n_chunks >>= 1;
     const long long per_block = 256ll * n_chunks;
     const dim3 grid((unsigned)((total + per_block - 1) / per_block)), block(256);
-    switch (L.d) {
-        case 1: lattice_points_kernel<1><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 2: lattice_points_kernel<2><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 3: lattice_points_kernel<3><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 4: lattice_points_kernel<4><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 5: lattice_points_kernel<5><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        case 6:
-            if (L.ids16) lattice_points_kernel<6, true><<<grid, block, 0, s>>>(L, fs, n_chunks);
-            else lattice_points_kernel<6><<<grid, block, 0, s>>>(L, fs, n_chunks);
-            break;
-        case 7: lattice_points_kernel<7><<<grid, block, 0, s>>>(L, fs, n_chunks); break;
-        default: break;
-    }
+    with_dimension(L.d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        if constexpr (D == 6) {   // the only dimension with a 16-bit form
+            if (L.ids16) { lattice_points_kernel<6, true><<<grid, block, 0, s>>>(L, fs, n_chunks); return; }
+        }
+        lattice_points_kernel<D><<<grid, block, 0, s>>>(L, fs, n_chunks);
+    });
     RV_LAUNCHED("lattice_points_kernel");
 }
 
@@ -413,286 +425,186 @@ void launch_vertex_order(const LatticeDev& L, SortBuffers& sb, hipStream_t s);
 // ---------------------------------------------------------------------------------------------
 // Vertex-major ordering by a counting sort (fast path, used when a frame has at most CS_MCAP
 // vertices -- the Segmenter kernel has ~300).  The entries of a frame are cut into wave-blocks of
-// CS_PIX points; every wave walks its block in order, 64 entries at a time, and ranks equal vertex
-// ids inside the chunk with ballots, so the order inside a vertex stays ascending in the point
-// index without any comparison sort:
+// cs_pix points, one wave each; the scatter walks its block in order, 64 points at a time, and ranks
+// equal vertex ids inside the chunk with ballots, so the order inside a vertex stays ascending in
+// the point index without any comparison sort:
 //   pass 1 (count)   per wave-block histogram over the frame's vertices (LDS) + slot -> id remap
 //   scan             per frame: vertex start offsets and per-(wave-block, vertex) bases
-//   pass 2 (scatter) same walk, entries land at base + rank
+//   pass 2 (scatter) entries land at base + rank
 // ---------------------------------------------------------------------------------------------
 constexpr int CS_PIX_MIN = 256;   // points per wave-block (LatticeDev::cs_pix): 256 .. 4096, a power of two
 constexpr int CS_MCAP = 4096;   // 4 waves x 4096 counters = 64 KB of LDS at the largest fast-path capacity (2^13 slots per frame)
 
-// bh holds, per frame, a dense [wave-block][vertex] matrix with row stride M_f; the frame's matrix
-// starts at wbpf * fstart[frame] (so the whole array needs wbpf * M_total words).
-template <bool SCATTER>
-__global__ void __launch_bounds__(256)
-csr_pass_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
-    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long gwb = (long long)blockIdx.x * 4 + wave;
-    const int frame = (int)(gwb / wbpf);
-    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
-    const int wb = (int)(gwb - (long long)frame * wbpf);
-    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
-    const unsigned n_entries_total = (unsigned)((long long)L.n_frames * L.N * (L.d + 1));
-    unsigned* my = cs_cnt + (size_t)wave * mcap;
-    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
-    for (int lv = lane; lv < Mf; lv += 64) my[lv] = SCATTER ? row[lv] : 0u;
-    if (Mf == 0 && lane == 0) my[0] = 0xFFFFFFFFu;   // no vertices (overflow only): positions fail the bound check
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const int dp1 = L.d + 1;
-    const long long p0 = (long long)wb * L.cs_pix;
-    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
-    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    // software pipeline: the next chunk's loads are in flight while the current chunk is ranked
-    auto fetch = [&](long long e, int& id, float& wgt) {
-        id = 0; wgt = 0.f;
-        if (e < eend) {
-            // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that
-            // every later kernel stays in bounds; the host discards the result
-            // (ids16: the stored values are local to the frame's slot region / id range)
-            if (!SCATTER) { id = L.slot_to_id[lattice_entry(L, e) + (L.ids16 ? frame << L.cap_f_log2 : 0)]; id = id < L.m_bound ? id : L.m_bound - 1; }
-            else { id = lattice_entry(L, e) + (L.ids16 ? f0 : 0); wgt = L.bary[e]; }
-        }
-    };
-    int id_n; float w_n;
-    fetch(ebeg + lane, id_n, w_n);
-    for (long long base = ebeg; base < eend; base += 64) {
-        const long long e = base + lane;
-        const bool valid = e < eend;
-        const int id = id_n;
-        const float wgt = w_n;
-        fetch(e + 64, id_n, w_n);
-        int lv = valid ? id - f0 : -1;
-        if (lv >= Mf) lv = Mf - 1;                   // overflow case (flagged elsewhere): stay in bounds
-        if (valid && lv < 0) lv = 0;
-        if (!SCATTER && valid) lattice_entry_store(L, e, L.ids16 ? lv : id);    // slot -> vertex id, in place
-        if (!SCATTER) {
-            // counting needs no order: LDS atomics (same-address lanes serialise in hardware, still an
-            // order of magnitude cheaper than ranking the chunk with ballots)
-            if (valid) atomicAdd(&my[lv], 1u);
-            continue;
-        }
-        bool pending = valid;
-        // distinct vertex ids of a chunk touch distinct counters, so the loop needs no ordering
-        // inside a chunk; one fence per chunk orders the counters between chunks
-        for (;;) {
-            const unsigned long long todo = __ballot(pending);
-            if (!todo) break;
-            const int leader = __ffsll((long long)todo) - 1;
-            const int k = __shfl(lv, leader, 64);
-            const bool same = pending && lv == k;
-            const unsigned long long m = __ballot(same);
-            const unsigned c = (unsigned)__popcll(m);
-            if (SCATTER) {
-                const unsigned b = my[k];
-                if (same) {
-                    const unsigned pos = b + (unsigned)__popcll(m & lt);
-                    if (pos < n_entries_total) {
-                        L.csr_pw[pos] = make_uint2((unsigned)(e / dp1), __float_as_uint(wgt));   // one 8-byte store
-                    }
-                }
-                if (lane == leader) my[k] = b + c;
-            } else {
-                if (lane == leader) my[k] = my[k] + c;
-            }
-            pending = pending && !same;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (!SCATTER) {
-        for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
-    }
+// Launch shape of the count and scatter passes: one wave per wave-block, four to a block, each with a row of mcap
+// counters in LDS (mcap = the vertices a frame can have at this capacity).  The device side is CsWaveBlock.
+struct CsLaunch {
+    int mcap, wbpf;   // wbpf: wave-blocks per frame
+    dim3 grid, block;
+    size_t lds;
+};
+static CsLaunch cs_launch(const LatticeDev& L) {
+    CsLaunch c;
+    c.mcap = (int)((L.cap_f_mask + 1) / 2);
+    c.wbpf = (L.N + L.cs_pix - 1) / L.cs_pix;
+    c.grid = dim3((unsigned)(((long long)c.wbpf * L.n_frames + 3) / 4));
+    c.block = dim3(256);
+    c.lds = (size_t)4 * c.mcap * sizeof(unsigned);
+    return c;
 }
 
-// Count pass, four entries per lane.  The generic pass above walks a wave-block 64 entries at a time with two DEPENDENT
-// loads per step (slot, then slot -> vertex id): PMC showed its waves waiting 91 % of their cycles.  Counting needs no
-// order, so a lane takes four consecutive entries at once -- one 16-byte load, four id gathers in flight together, one
-// 16-byte store of the remapped ids -- and a wave-block is done in 7 steps instead of 28.
+// {first vertex id f0, vertex count Mf} of a frame as the counting sort sees them (the clamps only matter after a
+// flagged hash overflow; they keep every access in bounds)
+__device__ __forceinline__ int2 cs_frame_vertices(const LatticeDev& L, int frame, int mcap) {
+    const int2 fr = lattice_frame_range(L, frame, L.m_bound);
+    return make_int2(fr.x, fr.y - fr.x < mcap ? fr.y - fr.x : mcap);
+}
+
+// What a wave of the count / scatter pass works on.  bh holds, per frame, a dense [wave-block][vertex] matrix with row
+// stride Mf; the frame's matrix starts at wbpf * fstart[frame] (so the whole array needs wbpf * M_total words).
+struct CsWaveBlock {
+    bool outside;           // past the last frame (the grid is rounded up to 4 waves): the whole wave leaves
+    int lane, frame, wb;
+    int f0, Mf;             // the frame's first vertex id and its vertices
+    long long p0, p1;       // the wave-block's points [p0, p1) of the frame ...
+    long long ebeg, eend;   // ... and their entries, counted over all frames
+    unsigned* my;           // this wave's counters in LDS: [Mf]
+    size_t row;             // this wave-block's row of bh: bh[row + vertex]
+};
+__device__ __forceinline__ CsWaveBlock cs_wave_block(const LatticeDev& L, int wbpf, int mcap) {
+    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
+    CsWaveBlock B{};
+    const int wave = threadIdx.x >> 6;
+    const long long gwb = (long long)blockIdx.x * 4 + wave;
+    B.lane = threadIdx.x & 63;
+    B.frame = (int)(gwb / wbpf);
+    B.outside = B.frame >= L.n_frames;
+    if (B.outside) return B;
+    B.wb = (int)(gwb - (long long)B.frame * wbpf);
+    const int2 fv = cs_frame_vertices(L, B.frame, mcap);
+    B.f0 = fv.x;
+    B.Mf = fv.y;
+    B.p0 = (long long)B.wb * L.cs_pix;
+    B.p1 = B.p0 + L.cs_pix < L.N ? B.p0 + L.cs_pix : L.N;
+    B.ebeg = ((long long)B.frame * L.N + B.p0) * (L.d + 1);
+    B.eend = ((long long)B.frame * L.N + B.p1) * (L.d + 1);
+    B.my = cs_cnt + (size_t)wave * mcap;
+    B.row = (size_t)wbpf * B.f0 + (size_t)B.wb * B.Mf;
+    return B;
+}
+
+// a unit of the count pass: W consecutive ids in one 16-byte access
+__device__ __forceinline__ void load_unit(const int* p, int (&v)[4]) { load_row<4>(p, v); }
+__device__ __forceinline__ void store_unit(int* p, const int (&v)[4]) { store_row<4>(p, v); }
+__device__ __forceinline__ void load_unit(const u16_ids* p, int (&v)[8]) {
+    const u16x8_ids t = *reinterpret_cast<const u16x8_ids*>(p);
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = t[k];
+}
+__device__ __forceinline__ void store_unit(u16_ids* p, const int (&v)[8]) {
+    u16x8_ids t;
+#pragma unroll
+    for (int k = 0; k < 8; k++) t[k] = (unsigned short)v[k];
+    *reinterpret_cast<u16x8_ids*>(p) = t;
+}
+
+// Count pass, a unit of W entries per lane and step.  Walking a wave-block one entry per lane means two DEPENDENT loads
+// per step (slot, then slot -> vertex id): PMC showed such waves waiting 91 % of their cycles.  Counting needs no order, so
+// a lane takes W consecutive entries at once -- one 16-byte load, W id gathers in flight together, one 16-byte store of the
+// remapped ids -- and adds into the counters with LDS atomics (same-address lanes serialise in hardware, still an order
+// of magnitude cheaper than ranking with ballots).
+//   32-bit global ids: W = 4, units start at the wave-block's first entry (4-byte aligned accesses).
+//   NARROW (LatticeDev::ids16), 16-bit frame-local values: W = 8, and a wave-block walks the ALIGNED 16-byte units that
+//   hold its entries, although a frame's first entry (frame * N * (d+1)) need not be a multiple of eight.  The slot -> id
+//   gather adds the frame's region base, and the stored id is local to the frame's id range, clamped like the counter index.
+// A unit that lies wholly inside the wave-block is one wide load and one wide store; the others -- the tail, and with
+// NARROW the unit shared with the neighbouring frame (a wave-block has a multiple of 256 points, so only there) -- are
+// read and written element by element, each wave its own entries.
+template <bool NARROW>
 __global__ void __launch_bounds__(256)
 csr_count_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
-    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long gwb = (long long)blockIdx.x * 4 + wave;
-    const int frame = (int)(gwb / wbpf);
-    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
-    const int wb = (int)(gwb - (long long)frame * wbpf);
-    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
-    unsigned* my = cs_cnt + (size_t)wave * mcap;
-    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    constexpr int W = NARROW ? 8 : 4;
+    typedef typename std::conditional<NARROW, u16_ids, int>::type id_t;
+    const CsWaveBlock B = cs_wave_block(L, wbpf, mcap);
+    if (B.outside) return;   // no block-wide barrier below
+    const int lane = B.lane, f0 = B.f0, Mf = B.Mf;
+    const long long ebeg = B.ebeg, eend = B.eend;
+    unsigned* my = B.my;
     for (int lv = lane; lv < Mf; lv += 64) my[lv] = 0u;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const int dp1 = L.d + 1;
-    const long long p0 = (long long)wb * L.cs_pix;
-    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
-    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
-    auto fetch = [&](long long e, int (&sl)[4]) {   // slots of entries e .. e + 3 (clamped into the wave-block)
-        if (e + 4 <= eend) {
-            load_row<4>(L.offsets + e, sl);
+    const long long ubeg = NARROW ? ebeg & ~7ll : ebeg;   // first unit; every unit [e, e + W) below has e + W > ebeg
+    id_t* ids = reinterpret_cast<id_t*>(L.offsets);
+    const int* s2i = L.slot_to_id + (NARROW ? (size_t)B.frame << L.cap_f_log2 : (size_t)0);   // NARROW: a slot is below cap_f
+    auto mine = [&](long long e) { return (!NARROW || e >= ebeg) && e < eend; };          // entry e is this wave-block's
+    auto whole = [&](long long e) { return (!NARROW || e >= ebeg) && e + W <= eend; };    // and so is all of unit e
+    auto fetch = [&](long long e, int (&sl)[W]) {   // slots of the unit at e; 0 outside the wave-block
+        if (whole(e)) {
+            load_unit(ids + e, sl);
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; k++) sl[k] = e + k < eend ? L.offsets[e + k] : 0;
+            for (int k = 0; k < W; k++) sl[k] = mine(e + k) ? (int)ids[e + k] : 0;
         }
     };
-    int sl_n[4];
-    fetch(ebeg + 4 * lane < eend ? ebeg + 4 * lane : ebeg, sl_n);
-    for (long long base = ebeg; base < eend; base += 256) {
-        const long long e = base + 4 * lane;
-        int sl[4], id[4];
+    int sl_n[W];
+    fetch(ubeg + W * lane < eend ? ubeg + W * lane : ubeg, sl_n);
+    for (long long base = ubeg; base < eend; base += 64 * W) {
+        const long long e = base + W * lane;
+        int sl[W], id[W], lv[W];
 #pragma unroll
-        for (int k = 0; k < 4; k++) sl[k] = sl_n[k];
+        for (int k = 0; k < W; k++) sl[k] = sl_n[k];
         const bool any = e < eend;
         if (any) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) id[k] = L.slot_to_id[sl[k]];   // four gathers in flight
+            for (int k = 0; k < W; k++) id[k] = s2i[sl[k]];   // W gathers in flight
         }
-        const long long en = e + 256;
-        fetch(en < eend ? en : ebeg, sl_n);                             // the next step's slots travel meanwhile
+        const long long en = e + 64 * W;
+        fetch(en < eend ? en : ubeg, sl_n);                    // the next step's slots travel meanwhile
         if (!any) continue;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < W; k++) {
             // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that every later
             // kernel stays in bounds; the host discards the result
             id[k] = id[k] < L.m_bound ? id[k] : L.m_bound - 1;
+            lv[k] = id[k] - f0;
+            lv[k] = lv[k] < Mf ? lv[k] : Mf - 1;
+            lv[k] = lv[k] < 0 ? 0 : lv[k];
         }
-        if (e + 4 <= eend) {
-            store_row<4>(L.offsets + e, id);                            // slot -> vertex id, in place
+        const int (&out)[W] = NARROW ? lv : id;                // slot -> vertex id, in place
+        if (whole(e)) {
+            store_unit(ids + e, out);
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; k++) if (e + k < eend) L.offsets[e + k] = id[k];
+            for (int k = 0; k < W; k++) if (mine(e + k)) ids[e + k] = (id_t)out[k];
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (e + k >= eend) continue;
-            int lv = id[k] - f0;
-            lv = lv < Mf ? lv : Mf - 1;   // overflow case (flagged elsewhere): stay in bounds
-            lv = lv < 0 ? 0 : lv;
-            if (Mf > 0) atomicAdd(&my[lv], 1u);
+        for (int k = 0; k < W; k++) {
+            if (mine(e + k) && Mf > 0) atomicAdd(&my[lv[k]], 1u);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    unsigned* row = bh + B.row;
     for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
 }
 
-// The count pass over 16-bit frame-local values (LatticeDev::ids16): eight entries per lane and step.  A wave-block walks
-// the 16-byte units of the id array that hold its entries, so a unit is always aligned although a frame's first entry
-// (frame * N * (d+1)) need not be a multiple of eight.  A unit that lies wholly inside the wave-block is one 16-byte load
-// and one 16-byte store; the unit a wave-block shares with its neighbour (only at a frame boundary: a wave-block has a
-// multiple of 256 points) is read and written element by element, each wave its own entries.  The slot -> id gather adds the
-// frame's region base, the stored id is local to the frame's id range, with the same clamps as the counters.
-__global__ void __launch_bounds__(256)
-csr_count16_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
-    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long gwb = (long long)blockIdx.x * 4 + wave;
-    const int frame = (int)(gwb / wbpf);
-    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
-    const int wb = (int)(gwb - (long long)frame * wbpf);
-    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
-    unsigned* my = cs_cnt + (size_t)wave * mcap;
-    unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
-    for (int lv = lane; lv < Mf; lv += 64) my[lv] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const int dp1 = L.d + 1;
-    const long long p0 = (long long)wb * L.cs_pix;
-    const long long p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
-    const long long ebeg = ((long long)frame * L.N + p0) * dp1, eend = ((long long)frame * L.N + p1) * dp1;
-    const long long abeg = ebeg & ~7ll;    // first unit; every unit [e, e + 8) below has e + 8 > ebeg
-    u16_ids* ids = reinterpret_cast<u16_ids*>(L.offsets);
-    const int* s2i = L.slot_to_id + ((size_t)frame << L.cap_f_log2);
-    auto fetch = [&](long long e, int (&sl)[8]) {   // slots of the unit at e; 0 outside the wave-block
-        if (e >= ebeg && e + 8 <= eend) {
-            const u16x8_ids t = *reinterpret_cast<const u16x8_ids*>(ids + e);
-#pragma unroll
-            for (int k = 0; k < 8; k++) sl[k] = t[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) sl[k] = e + k >= ebeg && e + k < eend ? (int)ids[e + k] : 0;
-        }
-    };
-    int sl_n[8];
-    fetch(abeg + 8 * lane < eend ? abeg + 8 * lane : abeg, sl_n);
-    for (long long base = abeg; base < eend; base += 512) {
-        const long long e = base + 8 * lane;
-        int sl[8], id[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) sl[k] = sl_n[k];
-        const bool any = e < eend;
-        if (any) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) id[k] = s2i[sl[k]];   // eight gathers in flight (a slot is below cap_f)
-        }
-        const long long en = e + 512;
-        fetch(en < eend ? en : abeg, sl_n);                    // the next step's slots travel meanwhile
-        if (!any) continue;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            // ids beyond the per-vertex arrays only occur after a (flagged) hash overflow: clamp so that every later
-            // kernel stays in bounds; the host discards the result
-            id[k] = id[k] < L.m_bound ? id[k] : L.m_bound - 1;
-            id[k] -= f0;
-            id[k] = id[k] < Mf ? id[k] : Mf - 1;
-            id[k] = id[k] < 0 ? 0 : id[k];
-        }
-        if (e >= ebeg && e + 8 <= eend) {
-            u16x8_ids t;
-#pragma unroll
-            for (int k = 0; k < 8; k++) t[k] = (unsigned short)id[k];
-            *reinterpret_cast<u16x8_ids*>(ids + e) = t;        // slot -> vertex id, in place
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) if (e + k >= ebeg && e + k < eend) ids[e + k] = (unsigned short)id[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (e + k < ebeg || e + k >= eend) continue;
-            if (Mf > 0) atomicAdd(&my[id[k]], 1u);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    for (int lv = lane; lv < Mf; lv += 64) row[lv] = my[lv];
-}
-
-// Scatter pass with one lane per POINT (the generic pass above has one lane per entry and ranks ~10
-// distinct vertices per 64 entries; PMC: 438 vector instructions per 64 entries).  A chunk is 64
-// consecutive points x DP1 entries.  For every distinct vertex k of the chunk the lanes that hold k
-// -- in any of their DP1 slots, at most one per lane since a point's vertices are distinct -- are
-// found with DP1 ballots; their union, masked to the lower lanes, is the rank of a point among the
-// chunk's entries of k, i.e. ascending point order again.  Neighbouring points share their simplex,
-// so a chunk has ~12-20 distinct vertices for 448 entries.
+// Scatter pass with one lane per POINT.  A chunk is 64 consecutive points x DP1 entries.  For every distinct vertex k
+// of the chunk the lanes that hold k -- in any of their DP1 slots, at most one per lane since a point's vertices are
+// distinct -- are found with DP1 ballots; their union, masked to the lower lanes, is the rank of a point among the
+// chunk's entries of k, i.e. ascending point order again.  Neighbouring points share their simplex, so a chunk has
+// ~12-20 distinct vertices for 448 entries.  (One lane per ENTRY ranks ~10 distinct vertices per 64 entries; PMC: 438
+// vector instructions per 64 entries.)
 // NARROW (LatticeDev::ids16, DP1 == 7): the rows hold frame-local ids as uint16_t.
 template <int DP1, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int mcap) {
-    extern __shared__ unsigned cs_cnt[];   // [4 waves][mcap]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long gwb = (long long)blockIdx.x * 4 + wave;
-    const int frame = (int)(gwb / wbpf);
-    if (frame >= L.n_frames) return;       // whole wave; no block-wide barrier below
-    const int wb = (int)(gwb - (long long)frame * wbpf);
-    // (clamps only matter after a flagged hash overflow; they keep every access in bounds)
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const CsWaveBlock B = cs_wave_block(L, wbpf, mcap);
+    if (B.outside) return;   // no block-wide barrier below
+    const int lane = B.lane, frame = B.frame, f0 = B.f0, Mf = B.Mf;
     const unsigned n_entries_total = (unsigned)((long long)L.n_frames * L.N * DP1);
-    unsigned* my = cs_cnt + (size_t)wave * mcap;
-    const unsigned* row = bh + (size_t)wbpf * f0 + (size_t)wb * Mf;
+    unsigned* my = B.my;
+    const unsigned* row = bh + B.row;
     for (int lv = lane; lv < Mf; lv += 64) my[lv] = row[lv];
     if (Mf == 0 && lane == 0) my[0] = 0xFFFFFFFFu;   // no vertices (overflow only): positions fail the bound check
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const int p0 = wb * L.cs_pix;
-    const int p1 = p0 + L.cs_pix < L.N ? p0 + L.cs_pix : L.N;
+    const int p0 = (int)B.p0, p1 = (int)B.p1;
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     for (int pc = p0; pc < p1; pc += 64) {
         const int p = pc + lane;
@@ -745,6 +657,61 @@ csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int 
     }
 }
 
+// Scatter pass with one lane per ENTRY, for d = 1, 3, 4 and 7 (clouds only, 32-bit ids): csr_scatter_kernel is
+// instantiated for d = 2, 5 and 6 alone, and nobody has timed it against this kernel at the other dimensions.  A wave
+// walks its block 64 entries at a time and ranks equal vertex ids inside the chunk with ballots, so the order inside a
+// vertex is ascending in the point index here too.
+__global__ void __launch_bounds__(256)
+csr_scatter_entries_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int mcap) {
+    const CsWaveBlock B = cs_wave_block(L, wbpf, mcap);
+    if (B.outside) return;   // no block-wide barrier below
+    const int lane = B.lane, f0 = B.f0, Mf = B.Mf, dp1 = L.d + 1;
+    const long long ebeg = B.ebeg, eend = B.eend;
+    const unsigned n_entries_total = (unsigned)((long long)L.n_frames * L.N * dp1);
+    unsigned* my = B.my;
+    const unsigned* row = bh + B.row;
+    for (int lv = lane; lv < Mf; lv += 64) my[lv] = row[lv];
+    if (Mf == 0 && lane == 0) my[0] = 0xFFFFFFFFu;   // no vertices (overflow only): positions fail the bound check
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    // software pipeline: the next chunk's loads are in flight while the current chunk is ranked
+    auto fetch = [&](long long e, int& id, float& wgt) {
+        id = 0; wgt = 0.f;
+        if (e < eend) { id = L.offsets[e]; wgt = L.bary[e]; }
+    };
+    int id_n; float w_n;
+    fetch(ebeg + lane, id_n, w_n);
+    for (long long base = ebeg; base < eend; base += 64) {
+        const long long e = base + lane;
+        const bool valid = e < eend;
+        const int id = id_n;
+        const float wgt = w_n;
+        fetch(e + 64, id_n, w_n);
+        int lv = valid ? id - f0 : -1;
+        if (lv >= Mf) lv = Mf - 1;                   // overflow case (flagged elsewhere): stay in bounds
+        if (valid && lv < 0) lv = 0;
+        bool pending = valid;
+        // distinct vertex ids of a chunk touch distinct counters, so the loop needs no ordering
+        // inside a chunk; one fence per chunk orders the counters between chunks
+        for (;;) {
+            const unsigned long long todo = __ballot(pending);
+            if (!todo) break;
+            const int leader = __ffsll((long long)todo) - 1;
+            const int k = __shfl(lv, leader, 64);
+            const bool same = pending && lv == k;
+            const unsigned long long m = __ballot(same);
+            const unsigned b = my[k];
+            if (same) {
+                const unsigned pos = b + (unsigned)__popcll(m & lt);
+                if (pos < n_entries_total) L.csr_pw[pos] = make_uint2((unsigned)(e / dp1), __float_as_uint(wgt));   // one 8-byte store
+            }
+            if (lane == leader) my[k] = b + (unsigned)__popcll(m);
+            pending = pending && !same;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+}
+
 // per frame: bh[wb][lv] (counts) -> absolute base of (wave-block, vertex) in the csr arrays; vstart / vend per vertex.
 // Two launches over (frame, group of 64 vertices) blocks of 1024 threads = 16 wave-block segments x 64 vertices: the
 // first adds up the columns (per segment and whole), the second turns them into running bases.  The only thing a group
@@ -758,9 +725,8 @@ __global__ void __launch_bounds__(1024)
 csr_total_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap, int n_groups) {
     __shared__ unsigned sseg[CS_SEGS][64];
     const int frame = blockIdx.x / n_groups, grp = blockIdx.x - frame * n_groups;
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const int2 fv = cs_frame_vertices(L, frame, mcap);
+    const int f0 = fv.x, Mf = fv.y;
     const int lv0 = grp * 64;
     if (lv0 >= Mf) return;                   // whole block
     const int lvl = threadIdx.x & 63, seg = threadIdx.x >> 6;
@@ -789,9 +755,8 @@ csr_scan_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap, int
     __shared__ unsigned red[16];
     __shared__ unsigned vbase[64];
     const int frame = blockIdx.x / n_groups, grp = blockIdx.x - frame * n_groups;
-    const int f0 = L.fstart[frame] < L.m_bound ? L.fstart[frame] : L.m_bound;
-    const int f1 = L.fstart[frame + 1] < L.m_bound ? L.fstart[frame + 1] : L.m_bound;
-    const int Mf = f1 - f0 < mcap ? f1 - f0 : mcap;
+    const int2 fv = cs_frame_vertices(L, frame, mcap);
+    const int f0 = fv.x, Mf = fv.y;
     const int lv0 = grp * 64;
     if (lv0 >= Mf) return;                   // whole block
     const int lvl = threadIdx.x & 63, seg = threadIdx.x >> 6;
@@ -839,30 +804,32 @@ csr_scan_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap, int
 
 bool csr_fast_path(const LatticeDev& L) { return ((L.cap_f_mask + 1) / 2) <= (unsigned)CS_MCAP; }
 size_t csr_fast_bytes(const LatticeDev& L) {
-    const size_t wbpf = ((size_t)L.N + L.cs_pix - 1) / L.cs_pix;
+    const size_t wbpf = (size_t)cs_launch(L).wbpf;
     // the [wave-block][vertex] matrices of all frames, then per vertex its column total and CS_SEGS segment sums
     return (wbpf * ((size_t)L.m_bound + 64) + (size_t)L.m_bound * (1 + CS_SEGS)) * sizeof(unsigned);
 }
 
-// phase 0: everything; 1: everything but the scatter of the counting-sort path (vertex numbering, neighbours, counts,
-// list bounds, launch order: all the splat planner needs); 2: that scatter.  (The radix-sort path does it all in 0 / 1.)
-void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_entries, hipStream_t s, int phase) {
-    const bool fast = csr_fast_path(L) && sb.block_hist;
-    if (phase == 2) {
-        if (!fast) return;
-        const int mcap = (int)((L.cap_f_mask + 1) / 2);
-        const int wbpf = (L.N + L.cs_pix - 1) / L.cs_pix;
-        const long long waves = (long long)wbpf * L.n_frames;
-        const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-        const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
-        if (L.d == 6 && L.ids16) csr_scatter_kernel<7, true><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        else if (L.d == 6) csr_scatter_kernel<7><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        else if (L.d == 5) csr_scatter_kernel<6><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        else if (L.d == 2) csr_scatter_kernel<3><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        else csr_pass_kernel<true><<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        RV_LAUNCHED("csr_scatter_kernel");
-        return;
-    }
+// The scatter of the counting-sort path, the last step of its CSR build (nothing to do on the radix-sort path).
+void launch_csr_scatter(const LatticeDev& L, SortBuffers& sb, hipStream_t s) {
+    if (!(csr_fast_path(L) && sb.block_hist)) return;
+    const CsLaunch c = cs_launch(L);
+    with_dimension(L.d, [&](auto dim) {
+        constexpr int DP1 = decltype(dim)::value + 1;
+        if constexpr (DP1 == 7) {   // the only dimension with a 16-bit form
+            if (L.ids16) { csr_scatter_kernel<7, true><<<c.grid, c.block, c.lds, s>>>(L, sb.block_hist, c.wbpf, c.mcap); return; }
+        }
+        if constexpr (DP1 == 3 || DP1 == 6 || DP1 == 7)   // d = 2, 5, 6: the only instantiations of the per-point scatter
+            csr_scatter_kernel<DP1><<<c.grid, c.block, c.lds, s>>>(L, sb.block_hist, c.wbpf, c.mcap);
+        else
+            csr_scatter_entries_kernel<<<c.grid, c.block, c.lds, s>>>(L, sb.block_hist, c.wbpf, c.mcap);
+    });
+    RV_LAUNCHED("csr_scatter_kernel");
+}
+
+// Vertex numbering, neighbours, the CSR and the splat's launch order.  defer_scatter: everything but the scatter of the
+// counting-sort path -- counts, list bounds and launch order are all the splat planner needs; the caller launches
+// launch_csr_scatter beside it.  (The radix-sort path has no separate scatter and does it all here.)
+void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_entries, hipStream_t s, bool defer_scatter) {
     const unsigned cap = L.cap_total;
     {
         size_t temp = sb.scan_temp_bytes;
@@ -873,19 +840,15 @@ void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_ent
     const long long nb_threads = (long long)L.m_bound * (L.d + 1);
     lattice_neighbours_kernel<<<dim3((unsigned)((nb_threads + 255) / 256)), dim3(256), 0, s>>>(L);
     RV_LAUNCHED("lattice_compact_kernel / lattice_neighbours_kernel");
-    if (fast) {
-        const int mcap = (int)((L.cap_f_mask + 1) / 2);
-        const int wbpf = (L.N + L.cs_pix - 1) / L.cs_pix;
-        const long long waves = (long long)wbpf * L.n_frames;
-        const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-        const size_t lds = (size_t)4 * mcap * sizeof(unsigned);
-        if (L.ids16) csr_count16_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        else csr_count_kernel<<<grid, block, lds, s>>>(L, sb.block_hist, wbpf, mcap);
-        const int n_groups = (mcap + 63) / 64;
-        csr_total_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);
-        csr_scan_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, wbpf, mcap, n_groups);
+    if (csr_fast_path(L) && sb.block_hist) {
+        const CsLaunch c = cs_launch(L);
+        if (L.ids16) csr_count_kernel<true><<<c.grid, c.block, c.lds, s>>>(L, sb.block_hist, c.wbpf, c.mcap);
+        else csr_count_kernel<false><<<c.grid, c.block, c.lds, s>>>(L, sb.block_hist, c.wbpf, c.mcap);
+        const int n_groups = (c.mcap + 63) / 64;
+        csr_total_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, c.wbpf, c.mcap, n_groups);
+        csr_scan_kernel<<<dim3((unsigned)(L.n_frames * n_groups)), dim3(1024), 0, s>>>(L, sb.block_hist, c.wbpf, c.mcap, n_groups);
         RV_LAUNCHED("csr_count_kernel / csr_total_kernel / csr_scan_kernel");
-        if (phase == 0) launch_lattice_finish(L, sb, n_entries, s, 2);
+        if (!defer_scatter) launch_csr_scatter(L, sb, s);
     } else {
         lattice_remap_kernel<<<dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s>>>(L, sb.keys_in, sb.vals_in, n_entries);
         // stable radix sort by vertex id: equal keys keep ascending entry (= point) order

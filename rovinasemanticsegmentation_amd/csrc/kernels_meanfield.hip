@@ -49,8 +49,8 @@ blur_frames_kernel(LatticeDev L, int C, int reverse, float* __restrict__ a, floa
     if (L.counters[1]) return;
     const int frame = blockIdx.x;
     const int M = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    const int f0 = L.fstart[frame] < M ? L.fstart[frame] : M, f1 = L.fstart[frame + 1] < M ? L.fstart[frame + 1] : M;
-    const int n = (f1 - f0) * C;
+    const int2 fr = lattice_frame_range(L, frame, M);
+    const int f0 = fr.x, n = (fr.y - fr.x) * C;
     const bool lds = n <= BLUR_LDS_FLOATS;
     float* ga = a + (size_t)f0 * C;
     float* gb = b + (size_t)f0 * C;

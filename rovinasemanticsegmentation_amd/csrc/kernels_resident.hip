@@ -39,9 +39,8 @@ resident_plan_kernel(LatticeDev L, SplatResidentDev R, int heavy_cap) {
     if (L.counters[1]) return;
     const int frame = blockIdx.x;
     const int Mtot = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    const int f0 = L.fstart[frame] < Mtot ? L.fstart[frame] : Mtot;
-    const int f1 = L.fstart[frame + 1] < Mtot ? L.fstart[frame + 1] : Mtot;
-    const int Mf = f1 - f0, nb = R.n_bands, B = R.B;
+    const int2 fr = lattice_frame_range(L, frame, Mtot);
+    const int f0 = fr.x, Mf = fr.y - fr.x, nb = R.n_bands, B = R.B;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned clog = (unsigned)R.chunk_log2, cmask = (1u << clog) - 1u;   // entries per chunk: 64 or 128
     unsigned* T = plan_lds;                                               // [B][nb]: greedy: (sum of chunks) << 8 | longest; then tiles, then their scan
@@ -205,9 +204,8 @@ resident_fill_kernel(LatticeDev L, SplatResidentDev R) {
     if (idx >= B * nb) return;
     const int j = idx / nb, b = idx - j * nb;
     const int Mtot = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    const int f0 = L.fstart[frame] < Mtot ? L.fstart[frame] : Mtot;
-    const int f1 = L.fstart[frame + 1] < Mtot ? L.fstart[frame + 1] : Mtot;
-    const int Mf = f1 - f0;
+    const int2 fr = lattice_frame_range(L, frame, Mtot);
+    const int f0 = fr.x, Mf = fr.y - fr.x;
     const unsigned* jb = R.jb_tile + ((size_t)frame * RES_MAXB + j) * (nb + 1);
     const unsigned t0 = jb[b], T = jb[b + 1] - t0;
     if (!T) return;
@@ -312,7 +310,7 @@ splat_resident_kernel(LatticeDev L, SplatResidentDev R, ValueView srcv, float* _
     const unsigned j = jj % B, frame = (jj / B) * NG + x;
     if (frame >= (unsigned)L.n_frames) return;
     const int Mtot = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    const int f0 = L.fstart[frame] < Mtot ? L.fstart[frame] : Mtot;
+    const int f0 = lattice_frame_range(L, (int)frame, Mtot).x;
     const unsigned tb = R.blk_tile0[(size_t)frame * (RES_MAXB + 1) + j], te = R.blk_tile0[(size_t)frame * (RES_MAXB + 1) + j + 1];
     const unsigned n_t = te - tb;
     const unsigned n_own = R.blk_nown[(size_t)frame * RES_MAXB + j];

@@ -145,9 +145,9 @@ __device__ __forceinline__ NormItem norm_item(const LatticeDev& L, unsigned item
     it.r = j / nfg;
     it.frame = g + (j - it.r * nfg) * (unsigned)L.n_groups;
     const int Mtot = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    it.fs0 = L.fstart[it.frame] < Mtot ? L.fstart[it.frame] : Mtot;
-    const int fs1 = L.fstart[it.frame + 1] < Mtot ? L.fstart[it.frame + 1] : Mtot;
-    it.n_vert = (unsigned)(fs1 - it.fs0);
+    const int2 fr = lattice_frame_range(L, (int)it.frame, Mtot);
+    it.fs0 = fr.x;
+    it.n_vert = (unsigned)(fr.y - fr.x);
     it.ok = true;
     return it;
 }

@@ -51,20 +51,19 @@ struct LatticeDev {
     float* norm;                 // per point, pairwise.cpp:55-56
 };
 
-// The kernels that are not specialised on the id form read `offsets` through these (L.ids16 is uniform).
+// Vertex ids [x, y) of a frame, each clamped to `bound`: the per-vertex arrays' capacity or the vertices that exist.  (The
+// clamp only binds after a flagged hash overflow; it keeps every access in bounds.)
+__device__ __forceinline__ int2 lattice_frame_range(const LatticeDev& L, int frame, int bound) {
+    const int f0 = L.fstart[frame], f1 = L.fstart[frame + 1];
+    return make_int2(f0 < bound ? f0 : bound, f1 < bound ? f1 : bound);
+}
+
+// The kernels that are not specialised on the id form read `offsets` through this (L.ids16 is uniform).
 typedef unsigned short lattice_id16 __attribute__((may_alias));
-// entry e as stored: a global value, or with ids16 a frame-local one
-__device__ __forceinline__ int lattice_entry(const LatticeDev& L, long long e) {
-    return L.ids16 ? (int)reinterpret_cast<const lattice_id16*>(L.offsets)[e] : L.offsets[e];
-}
-__device__ __forceinline__ void lattice_entry_store(const LatticeDev& L, long long e, int v) {
-    if (L.ids16) reinterpret_cast<lattice_id16*>(L.offsets)[e] = (unsigned short)v;
-    else L.offsets[e] = v;
-}
-// global vertex id of vertex j of point p (after the count pass)
+// global vertex id of vertex j of point p (after the count pass); stored as such, or with ids16 local to the frame
 __device__ __forceinline__ int lattice_vertex(const LatticeDev& L, long long p, int dp1, int j) {
-    const int o = lattice_entry(L, p * dp1 + j);
-    return L.ids16 ? o + L.fstart[p / L.N] : o;
+    const long long e = p * dp1 + j;
+    return L.ids16 ? (int)reinterpret_cast<const lattice_id16*>(L.offsets)[e] + L.fstart[p / L.N] : L.offsets[e];
 }
 
 // Band-interleaved resident schedule of the ordered splat ("resident bands").  A frame's
@@ -132,7 +131,9 @@ struct SortBuffers {
 
 void launch_fill_int(int* p, int v, long long n, hipStream_t s);
 void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStream_t s);
-void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_entries, hipStream_t s, int phase = 0);
+// defer_scatter: leaves the counting-sort path's scatter to a later launch_csr_scatter (which the radix-sort path ignores)
+void launch_lattice_finish(const LatticeDev& L, SortBuffers& sb, long long n_entries, hipStream_t s, bool defer_scatter);
+void launch_csr_scatter(const LatticeDev& L, SortBuffers& sb, hipStream_t s);
 size_t sort_temp_bytes(long long n_entries, int key_bits);
 size_t scan_temp_bytes(unsigned cap);
 bool csr_fast_path(const LatticeDev& L);

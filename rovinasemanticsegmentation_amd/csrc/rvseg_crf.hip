@@ -338,7 +338,7 @@ static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, 
     tr("points");
     // the splat's band schedule needs the lists' bounds (count / scan) and the launch order, not the lists themselves: it
     // is planned beside the scatter and the normaliser
-    launch_lattice_finish(L, b.sb, b.n_entries, s, b.resident_on ? 1 : 0);
+    launch_lattice_finish(L, b.sb, b.n_entries, s, /*defer_scatter=*/b.resident_on);
     tr("finish");
     rvseg_status st;
     bool plan_forked = false;
@@ -351,7 +351,7 @@ static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, 
         RV_HIP(ctx, hipEventRecord(cs->layer_join, cs->layer_stream));
         plan_forked = true;
         tr("resident plan");
-        launch_lattice_finish(L, b.sb, b.n_entries, s, 2);   // the scatter (counting-sort path)
+        launch_csr_scatter(L, b.sb, s);
     }
     st = values_reserve(ctx, cs, L.m_bound, 1);
     if (st != RVSEG_OK) { if (plan_forked) (void)hipStreamWaitEvent(s, cs->layer_join, 0); return st; }

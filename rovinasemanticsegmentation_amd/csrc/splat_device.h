@@ -122,9 +122,8 @@ __device__ __forceinline__ void splat_group_item(const LatticeDev& L, const Valu
     if (nfg == 0) return;
     const unsigned r = j / nfg, frame = g + (j - r * nfg) * (unsigned)L.n_groups;
     const int Mtot = L.counters[0] < L.m_bound ? L.counters[0] : L.m_bound;
-    const int fs0 = L.fstart[frame] < Mtot ? L.fstart[frame] : Mtot;
-    const int fs1 = L.fstart[frame + 1] < Mtot ? L.fstart[frame + 1] : Mtot;
-    const unsigned n_vert = (unsigned)(fs1 - fs0), gstart = (unsigned)fs0;
+    const int2 fr = lattice_frame_range(L, (int)frame, Mtot);
+    const unsigned n_vert = (unsigned)(fr.y - fr.x), gstart = (unsigned)fr.x;
     if (r * G >= n_vert) return;
     const bool contig = FAST || (src.frame_stride == (size_t)L.N * (size_t)C && src.layer_off == 0);
     const int pw = wave < AW ? wave : wave - 1;   // producer index of this wave (unused by the adder)

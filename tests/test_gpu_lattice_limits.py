@@ -363,8 +363,8 @@ def test_lattice_points_key_set_smooth_then_saturated(gpu_ctx_factory, oracle):
 # ---- I. the generic counting-sort kernel at its largest capacity --------------------------------------------------------
 @pytest.mark.parametrize("d,spread", [(3, 12.0), (4, 6.0), (7, 1.9)])
 def test_generic_counting_sort_at_its_largest_capacity(gpu_ctx_factory, oracle, d, spread):
-    """Clouds with 2 049 - 4 096 vertices and 2^13 slots: the counting-sort CSR at mcap = 4 096 for dimensions without a
-    dedicated instantiation (csr_pass_kernel<true>).  Structure, filter and a 3-iteration CRF against the oracle."""
+    """Clouds with 2 049 - 4 096 vertices and 2^13 slots: the counting-sort CSR at mcap = 4 096 for dimensions whose
+    scatter goes entry by entry (csr_scatter_entries_kernel).  Structure, filter and a 3-iteration CRF against the oracle."""
     N = 30000
     rng = np.random.default_rng(d * 31 + N)
     F = (rng.random((N, d)) * spread - spread / 3).astype(np.float32)
