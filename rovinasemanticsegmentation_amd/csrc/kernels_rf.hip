@@ -97,14 +97,17 @@ void launch_forest_eval(const DeviceForest& f, const float* d_X, int P, int D, f
 }  // namespace rvseg
 
 // =============================================================================================
-// Frame path: fused per-point feature vector + forest traversal over the stride grid
+// Frame path: per-point feature vector + forest traversal over the stride grid
 // (replaces FeatureExtractor::extract + the per-point multiClassLogPosterior loop,
 // include/feature_extractor.h:125-197 and src/segmenter.cpp:351-376).
 //
-// A wavefront owns 16 consecutive sample points.  Their 363-byte Lab patch vectors are built
-// directly in LDS (the reference materialises P x 366 floats on the heap; here features never
-// touch HBM), then the 64 lanes become (point, tree) pairs and walk the breadth-first node array,
-// fetching one 16-byte node per level from HBM/L2 and the tested feature byte from LDS.
+// A wavefront owns 16 consecutive sample points.  Two kernels share the per-point state and the
+// patch resize below:
+//   rf_frames_lazy_kernel  the frame path: the 64 lanes are (point, tree) pairs that walk the
+//                          breadth-first node array and compute a patch value when a node asks for
+//                          it; features never touch HBM
+//   feature_dump_kernel    the parity / training entry points: every patch value of every point,
+//                          built in LDS and written out as the reference's P x D float matrix
 // =============================================================================================
 namespace rvseg {
 
@@ -118,56 +121,132 @@ struct ClassMap {
     int cl[64];          // class index inside the layer
 };
 
+// per-point state (mask rule feature_extractor.h:60; half size :139-140)
+struct PointState {
+    bool valid;
+    int half, x, y, frame, p;   // ROI half size, pixel, frame and index inside the frame's stride grid
+    float depth_m, height, nrm;
+};
+
+__device__ __forceinline__ PointState point_state(const FrameGeom& g, int pid, int n_points_total,
+                                                  const uint16_t* __restrict__ depth_all, const float4* __restrict__ cloud_all,
+                                                  const float* __restrict__ nfeat_all) {
+    PointState s{false, 0, 0, 0, 0, 0, 0.f, 0.f, 0.f};
+    if (pid < n_points_total) {
+        const int per_frame = g.lw * g.lh;
+        s.frame = pid / per_frame;
+        s.p = pid - s.frame * per_frame;
+        const int ly = s.p / g.lw, lx = s.p - ly * g.lw;
+        s.y = ly * g.stride; s.x = lx * g.stride;
+        const size_t pix = (size_t)s.frame * g.W * g.H + (size_t)s.y * g.W + s.x;
+        const float dv = (float)depth_all[pix];
+        s.valid = dv >= g.dmin_mm && dv <= g.dmax_mm;
+        s.depth_m = dv / 1000.0f;
+        if (s.valid) {
+            s.half = (int)((double)g.patch_size / (2.0 * (double)s.depth_m));
+            if (g.pos_height >= 0) s.height = cloud_all[pix].z;
+            if (g.pos_normal >= 0) s.nrm = nfeat_all[pid];
+        }
+    }
+    return s;
+}
+
+// ---- one value of the r x r x 3 patch vector: cv::resize(ROI -> r x r) of 8-bit data in 11-bit fixed point
+//      (feature_extractor.h:142).  A cell's two records name its 2 x 2 taps inside the ROI and their weights.
+struct ResizeTaps { int sx0, sx1, sy0, sy1, ia0, ia1, ib0, ib1; };
+
+// the only place that knows the 8-byte ResizeRec layout: {first tap, weight of it, weight of the second, second tap}
+__device__ __forceinline__ ResizeTaps resize_taps(const ResizeRow* row, int dy, int dx) {
+    const uint2 xr = *reinterpret_cast<const uint2*>(&row->x[dx]);
+    const uint2 yr = *reinterpret_cast<const uint2*>(&row->y[dy]);
+    ResizeTaps t;
+    t.sx0 = (int)(short)(xr.x & 0xffffu); t.ia0 = (int)(short)(xr.x >> 16);
+    t.ia1 = (int)(short)(xr.y & 0xffffu); t.sx1 = (int)(short)(xr.y >> 16);
+    t.sy0 = (int)(short)(yr.x & 0xffffu); t.ib0 = (int)(short)(yr.x >> 16);
+    t.ib1 = (int)(short)(yr.y & 0xffffu); t.sy1 = (int)(short)(yr.y >> 16);
+    return t;
+}
+
+// one channel of the packed Lab taps {row 0: p00 p01, row 1: p10 p11}
+__device__ __forceinline__ int resize_blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, const ResizeTaps& t, int channel) {
+    const int sh = 8 * channel;
+    const int r0 = (int)((p00 >> sh) & 255u) * t.ia0 + (int)((p01 >> sh) & 255u) * t.ia1;
+    const int r1 = (int)((p10 >> sh) & 255u) * t.ia0 + (int)((p11 >> sh) & 255u) * t.ia1;
+    const int v = (((t.ib0 * (r0 >> 4)) >> 16) + ((t.ib1 * (r1 >> 4)) >> 16) + 2) >> 2;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
 __device__ __forceinline__ int reflect_idx(int p, int len) {  // BORDER_REFLECT: fedcba|abcdefgh|hgfedcb
     return p < 0 ? -p - 1 : (p >= len ? 2 * len - p - 1 : p);
 }
 
-template <bool DUMP>
+typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x4_p __attribute__((ext_vector_type(4), aligned(8)));
+
+// The taps of a ROI at (x0, y0) that may leave the image: mirrored border.  The two taps of a row are at most one pixel
+// apart (also across the mirror): one 8-byte load per row and a pick.  Returns {p00, p01, p10, p11}.
+__device__ __forceinline__ uint4 taps_mirrored(const uint32_t* __restrict__ lab, int W, int H, int x0, int y0, const ResizeTaps& t) {
+    const int rx0 = reflect_idx(x0 + t.sx0, W), rx1 = reflect_idx(x0 + t.sx1, W);
+    const int ry0 = reflect_idx(y0 + t.sy0, H), ry1 = reflect_idx(y0 + t.sy1, H);
+    int xb = rx0 < rx1 ? rx0 : rx1;
+    xb = xb < W - 1 ? xb : W - 2;
+    const u32x2_u q0 = *reinterpret_cast<const u32x2_u*>(lab + (ry0 * W + xb));
+    const u32x2_u q1 = *reinterpret_cast<const u32x2_u*>(lab + (ry1 * W + xb));
+    return make_uint4(rx0 == xb ? q0.x : q0.y, rx1 == xb ? q0.x : q0.y, rx0 == xb ? q1.x : q1.y, rx1 == xb ? q1.x : q1.y);
+}
+
+__device__ __forceinline__ int patch_value_mirrored(const uint32_t* __restrict__ lab, int W, int H, int x0, int y0,
+                                                    const ResizeTaps& t, int channel) {
+    const uint4 q = taps_mirrored(lab, W, H, x0, y0, t);
+    return resize_blend(q.x, q.y, q.z, q.w, t, channel);
+}
+
+// The ROI lies strictly inside the image (lab_base = y0 * W + x0; its last column is not the image's): the taps are at
+// (y0 + sy, x0 + sx) directly and a record's second row / column is the first one or its neighbour (pipeline_init:
+// ofs1 = ofs or ofs + 1).  PMC: the lazy kernel is VALU bound (64 % of the issue cycles, 83 vector instructions per tree
+// level); the four reflections and the pair selection were ~30 of them.
+__device__ __forceinline__ int patch_value_inside(const uint32_t* __restrict__ lab, int lab_base, int W, const ResizeTaps& t, int channel) {
+    const bool two = t.sx1 != t.sx0;
+    const u32x2_u q0 = *reinterpret_cast<const u32x2_u*>(lab + (lab_base + t.sy0 * W + t.sx0));
+    const u32x2_u q1 = *reinterpret_cast<const u32x2_u*>(lab + (lab_base + t.sy1 * W + t.sx0));
+    return resize_blend(q0.x, two ? q0.y : q0.x, q1.x, two ? q1.y : q1.x, t, channel);
+}
+
+// the same from the row-pair image: one 16-byte load {top(x), bottom(x), top(x + 1), bottom(x + 1)}
+__device__ __forceinline__ int patch_value_inside2(const uint32_t* __restrict__ lab2, int lab_base, int W, const ResizeTaps& t, int channel) {
+    const bool two = t.sx1 != t.sx0, below = t.sy1 != t.sy0;
+    const u32x4_p q = *reinterpret_cast<const u32x4_p*>(lab2 + 2 * (lab_base + t.sy0 * W + t.sx0));
+    return resize_blend(q.x, two ? q.z : q.x, below ? q.y : q.x, below ? (two ? q.w : q.y) : (two ? q.z : q.x), t, channel);
+}
+
+// ---------------------------------------------------------------------------------------------
+// feature_dump_kernel: the materialised feature vectors of rvseg_extract_features and
+// rvseg_forest_train_frames.  The 363-byte Lab patch vectors of a wave's 16 points are built in LDS,
+// 64 cells at a time, then written out as floats with the scalar features behind them.
+// ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK)
-rf_frames_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ nodes, const int32_t* __restrict__ roots,
-                 const float* __restrict__ hist, int n_trees, const ResizeRow* __restrict__ rt,
-                 const uint32_t* __restrict__ lab_all, const uint16_t* __restrict__ depth_all,
-                 const float4* __restrict__ cloud_all, const float* __restrict__ nfeat_all,
-                 float* __restrict__ low_all, float* __restrict__ dump_all, uint8_t* __restrict__ valid_all,
-                 int n_points_total, int fb_stride) {
+feature_dump_kernel(FrameGeom g, const ResizeRow* __restrict__ rt, const uint32_t* __restrict__ lab_all,
+                    const uint16_t* __restrict__ depth_all, const float4* __restrict__ cloud_all,
+                    const float* __restrict__ nfeat_all, float* __restrict__ dump_all, uint8_t* __restrict__ valid_all,
+                    int n_points_total, int fb_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // per wave: PPW x fb_stride bytes of patch features, then PPW x 8 ints of per-point state
     unsigned char* fb = smem + (size_t)wave * (PPW * fb_stride + PPW * 32);
     int* pst = reinterpret_cast<int*>(fb + PPW * fb_stride);  // [PPW][8]: valid,half,x,y,depth_f,height_f,normal_f,frame
-    const int per_frame = g.lw * g.lh;
     const int base = (blockIdx.x * WAVES_PER_BLOCK + wave) * PPW;
     const int W = g.W, H = g.H;
 
-    // ---- phase A: per-point state (mask rule feature_extractor.h:60; half size :139-140)
     if (lane < PPW) {
-        const int pid = base + lane;
-        int valid = 0, half = 0, x = 0, y = 0, frame = 0;
-        float depth_m = 0.f, height = 0.f, nrm = 0.f;
-        if (pid < n_points_total) {
-            frame = pid / per_frame;
-            const int p = pid - frame * per_frame;
-            const int ly = p / g.lw, lx = p - ly * g.lw;
-            y = ly * g.stride; x = lx * g.stride;
-            const size_t pix = (size_t)frame * W * H + (size_t)y * W + x;
-            const uint16_t d = depth_all[pix];
-            const float dv = (float)d;
-            valid = (dv >= g.dmin_mm && dv <= g.dmax_mm) ? 1 : 0;
-            depth_m = dv / 1000.0f;
-            if (valid) {
-                half = (int)((double)g.patch_size / (2.0 * (double)depth_m));
-                if (g.pos_height >= 0) height = cloud_all[pix].z;
-                if (g.pos_normal >= 0) nrm = nfeat_all[pid];
-            }
-        }
+        const PointState ps = point_state(g, base + lane, n_points_total, depth_all, cloud_all, nfeat_all);
         int* s = pst + lane * 8;
-        s[0] = valid; s[1] = half; s[2] = x; s[3] = y;
-        s[4] = __float_as_int(depth_m); s[5] = __float_as_int(height); s[6] = __float_as_int(nrm); s[7] = frame;
+        s[0] = ps.valid; s[1] = ps.half; s[2] = ps.x; s[3] = ps.y;
+        s[4] = __float_as_int(ps.depth_m); s[5] = __float_as_int(ps.height); s[6] = __float_as_int(ps.nrm); s[7] = ps.frame;
     }
     __builtin_amdgcn_wave_barrier();
     __syncthreads();
 
-    // ---- phase B: Lab patch, cv::resize(ROI -> r x r) in 11-bit fixed point (feature_extractor.h:142)
+    // the Lab patch: lane = cell, the three channels from one tap quad
     if (g.n_patch > 0) {
         const int rr = g.r * g.r;
         for (int k0 = 0; k0 < rr; k0 += 64) {
@@ -176,119 +255,38 @@ rf_frames_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ nodes,
             for (int pt = 0; pt < PPW; pt++) {
                 const int* s = pst + pt * 8;
                 if (!s[0] || k >= rr) continue;
-                const int half = s[1], size = 2 * half + 1;
-                const int x0 = s[2] - half, y0 = s[3] - half;
-                // one 8-byte record per axis: {source index, weight of it, weight of the next}
-                const uint2 xr = *reinterpret_cast<const uint2*>(&rt[half].x[dx]);
-                const uint2 yr = *reinterpret_cast<const uint2*>(&rt[half].y[dy]);
-                const int sx0 = (int)(short)(xr.x & 0xffffu), ia0 = (int)(short)(xr.x >> 16), ia1 = (int)(short)(xr.y & 0xffffu);
-                const int ib0 = (int)(short)(yr.x >> 16), ib1 = (int)(short)(yr.y & 0xffffu);
-                const int sx1 = (int)(short)(xr.y >> 16);
-                const int sy0 = (int)(short)(yr.x & 0xffffu), sy1 = (int)(short)(yr.y >> 16);
-                (void)size;
-                const int rx0 = reflect_idx(x0 + sx0, W), rx1 = reflect_idx(x0 + sx1, W);
-                const int ry0 = reflect_idx(y0 + sy0, H), ry1 = reflect_idx(y0 + sy1, H);
-                const uint32_t* lab = lab_all + (size_t)s[7] * W * H;
-                // the two taps of a row are always at most one pixel apart (also across the mirrored
-                // border): fetch them with one 8-byte load and pick
-                int xb = rx0 < rx1 ? rx0 : rx1;
-                xb = xb < W - 1 ? xb : W - 2;
-                typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
-                const u32x2_u q0 = *reinterpret_cast<const u32x2_u*>(lab + (size_t)ry0 * W + xb);
-                const u32x2_u q1 = *reinterpret_cast<const u32x2_u*>(lab + (size_t)ry1 * W + xb);
-                const uint32_t p00 = rx0 == xb ? q0.x : q0.y, p01 = rx1 == xb ? q0.x : q0.y;
-                const uint32_t p10 = rx0 == xb ? q1.x : q1.y, p11 = rx1 == xb ? q1.x : q1.y;
+                const int half = s[1];
+                const ResizeTaps t = resize_taps(rt + half, dy, dx);
+                const uint4 q = taps_mirrored(lab_all + (size_t)s[7] * W * H, W, H, s[2] - half, s[3] - half, t);
                 unsigned char* dst = fb + pt * fb_stride + k * 3;
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const int sh = 8 * c;
-                    const int r0 = (int)((p00 >> sh) & 255u) * ia0 + (int)((p01 >> sh) & 255u) * ia1;
-                    const int r1 = (int)((p10 >> sh) & 255u) * ia0 + (int)((p11 >> sh) & 255u) * ia1;
-                    int v = (((ib0 * (r0 >> 4)) >> 16) + ((ib1 * (r1 >> 4)) >> 16) + 2) >> 2;
-                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-                    dst[c] = (unsigned char)v;
-                }
+                for (int c = 0; c < 3; c++) dst[c] = (unsigned char)resize_blend(q.x, q.y, q.z, q.w, t, c);
             }
         }
     }
     __syncthreads();
 
-    if (DUMP) {
-        for (int pt = 0; pt < PPW; pt++) {
-            const int pid = base + pt;
-            if (pid >= n_points_total) break;
-            const int* s = pst + pt * 8;
-            if (lane == 0) valid_all[pid] = (uint8_t)s[0];
-            float* d = dump_all + (size_t)pid * g.D;
-            for (int k = lane; k < g.n_patch; k += 64) d[k] = s[0] ? (float)fb[pt * fb_stride + k] : 0.f;
-            if (lane == 0) {
-                if (g.pos_depth >= 0) d[g.pos_depth] = __int_as_float(s[4]);
-                if (g.pos_height >= 0) d[g.pos_height] = __int_as_float(s[5]);
-                if (g.pos_normal >= 0) d[g.pos_normal] = __int_as_float(s[6]);
-            }
-        }
-        return;
-    }
-
-    // ---- phase C: lanes = (point, tree); findLeafNode (classifier.cpp:97-117)
-    const int pt = lane >> 2, sub = lane & 3;
-    const int* s = pst + pt * 8;
-    const bool valid = s[0] != 0;
-    const unsigned char* myfb = fb + pt * fb_stride;
-    int leaf_rows[16];
-    int n_mine = 0;
-    const int4* np = reinterpret_cast<const int4*>(nodes);
-    for (int t = sub; t < n_trees; t += 4) {
-        int row = 0;
-        if (valid) {
-            int4 nd = np[roots[t]];
-            while (nd.z != 0) {
-                const int f = nd.x;
-                float v;
-                if (f < g.n_patch) v = (float)myfb[f];
-                else v = __int_as_float(f == g.pos_depth ? s[4] : (f == g.pos_height ? s[5] : s[6]));
-                nd = np[(v < __int_as_float(nd.y)) ? nd.z : nd.z + 1];
-            }
-            row = nd.w;
-        }
-#pragma unroll
-        for (int q = 0; q < 16; q++) if (q == n_mine) leaf_rows[q] = row;
-        n_mine++;
-    }
-
-    // ---- phase D: tree-order accumulation (classifier.cpp:193-206) and scatter into the low-res
-    //      image at (y/stride, x/stride) (segmenter.cpp:369-375); invalid cells get the fill value
-    const int lane_base = lane & ~3;
-    const int pid = base + pt;
-    const int frame = s[7];
-    const int p = pid - frame * per_frame;
-    for (int c0 = 0; c0 < cm.S; c0 += 4) {
-        const int c = c0 + sub;
-        float acc = 0.f;
-        for (int t = 0; t < n_trees; t++) {
-            const int slot = t >> 2;
-            int row = 0;
-#pragma unroll
-            for (int q = 0; q < 16; q++) if (q == slot) row = leaf_rows[q];
-            row = __shfl(row, lane_base + (t & 3), 64);
-            if (c < cm.S && valid) {
-                const float h = hist[(size_t)row * cm.S + c];
-                acc = (t == 0) ? h : acc + h;
-            }
-        }
-        if (pid < n_points_total && c < cm.S) {
-            float* low = low_all + (size_t)frame * per_frame * cm.S;
-            low[cm.layer_base[c] + (size_t)p * cm.layer_C[c] + cm.cl[c]] = valid ? acc : g.fill;
+    for (int pt = 0; pt < PPW; pt++) {
+        const int pid = base + pt;
+        if (pid >= n_points_total) break;
+        const int* s = pst + pt * 8;
+        if (lane == 0) valid_all[pid] = (uint8_t)s[0];
+        float* d = dump_all + (size_t)pid * g.D;
+        for (int k = lane; k < g.n_patch; k += 64) d[k] = s[0] ? (float)fb[pt * fb_stride + k] : 0.f;
+        if (lane == 0) {
+            if (g.pos_depth >= 0) d[g.pos_depth] = __int_as_float(s[4]);
+            if (g.pos_height >= 0) d[g.pos_height] = __int_as_float(s[5]);
+            if (g.pos_normal >= 0) d[g.pos_normal] = __int_as_float(s[6]);
         }
     }
 }
 
 // =============================================================================================
-// Frame path, on-demand features (the default).  PMC on the kernel above: vector-ALU bound, and 85 %
-// of it is phase B, which resizes all 121 x 3 patch values of every point although a walk through
-// T trees of depth <= 31 tests only ~20 per tree.  Here the lanes are (point, tree) pairs from the
-// start and a patch value is computed when a node asks for it: one channel of one cv::resize cell
-// = 2 LDS weight records + two 8-byte tap loads + ~25 integer ops -- the same arithmetic as phase B.
+// The frame path, on-demand features.  PMC on a kernel that, like the dump kernel above, resized all
+// 121 x 3 patch values of every point before the walk: vector-ALU bound, 85 % of it in the resize,
+// although a walk through T trees of depth <= 31 tests only ~20 values per tree.  Here the lanes are
+// (point, tree) pairs from the start and a patch value is computed when a node asks for it: one
+// channel of one cv::resize cell = 2 LDS weight records + two 8-byte tap loads + ~25 integer ops.
 // A node's two children are adjacent, so both are fetched together with the taps of the node's
 // own test: still one memory round trip per level.
 // COMPACT (round 3; PMC of the 16-byte-node version: texture addresser 92 % busy, 4 vector-memory instructions per
@@ -321,108 +319,26 @@ rf_frames_lazy_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ n
     const int pt = lane >> 2, sub = lane & 3;
     const int pid = base + pt;
 
-    // per-point state (mask rule feature_extractor.h:60; half size :139-140), once per lane
-    bool valid = false;
-    int half = 0, x = 0, y = 0, frame = 0;
-    float depth_m = 0.f, height = 0.f, nrm = 0.f;
-    if (pid < n_points_total) {
-        frame = pid / per_frame;
-        const int p = pid - frame * per_frame;
-        const int ly = p / g.lw, lx = p - ly * g.lw;
-        y = ly * g.stride; x = lx * g.stride;
-        const size_t pix = (size_t)frame * W * H + (size_t)y * W + x;
-        const float dv = (float)depth_all[pix];
-        valid = dv >= g.dmin_mm && dv <= g.dmax_mm;
-        depth_m = dv / 1000.0f;
-        if (valid) {
-            half = (int)((double)g.patch_size / (2.0 * (double)depth_m));
-            if (g.pos_height >= 0) height = cloud_all[pix].z;
-            if (g.pos_normal >= 0) nrm = nfeat_all[pid];
-        }
-    }
-    const int size = 2 * half + 1, x0 = x - half, y0 = y - half;
-    const uint32_t* lab = lab_all + (size_t)frame * W * H;
-    const ResizeRow* myrt = rtl + (valid ? half : 0);
-    typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
-
-    // one value of the r x r x 3 patch vector: cv::resize(ROI -> r x r) in 11-bit fixed point
-    // (feature_extractor.h:142), exactly phase B of the kernel above for cell k, channel c
-    auto patch_value = [&](int packed) -> float {   // packed = channel << 16 | dy << 8 | dx (upload_forest)
-        const int c = packed >> 16, dy = (packed >> 8) & 255, dx = packed & 255;
-        const uint2 xr = *reinterpret_cast<const uint2*>(&myrt->x[dx]);
-        const uint2 yr = *reinterpret_cast<const uint2*>(&myrt->y[dy]);
-        const int sx0 = (int)(short)(xr.x & 0xffffu), ia0 = (int)(short)(xr.x >> 16), ia1 = (int)(short)(xr.y & 0xffffu);
-        const int ib0 = (int)(short)(yr.x >> 16), ib1 = (int)(short)(yr.y & 0xffffu);
-        const int sx1 = (int)(short)(xr.y >> 16);
-        const int sy0 = (int)(short)(yr.x & 0xffffu), sy1 = (int)(short)(yr.y >> 16);
-        const int rx0 = reflect_idx(x0 + sx0, W), rx1 = reflect_idx(x0 + sx1, W);
-        const int ry0 = reflect_idx(y0 + sy0, H), ry1 = reflect_idx(y0 + sy1, H);
-        int xb = rx0 < rx1 ? rx0 : rx1;
-        xb = xb < W - 1 ? xb : W - 2;
-        const u32x2_u q0 = *reinterpret_cast<const u32x2_u*>(lab + (size_t)ry0 * W + xb);
-        const u32x2_u q1 = *reinterpret_cast<const u32x2_u*>(lab + (size_t)ry1 * W + xb);
-        const uint32_t p00 = rx0 == xb ? q0.x : q0.y, p01 = rx1 == xb ? q0.x : q0.y;
-        const uint32_t p10 = rx0 == xb ? q1.x : q1.y, p11 = rx1 == xb ? q1.x : q1.y;
-        const int sh = 8 * c;
-        const int r0 = (int)((p00 >> sh) & 255u) * ia0 + (int)((p01 >> sh) & 255u) * ia1;
-        const int r1 = (int)((p10 >> sh) & 255u) * ia0 + (int)((p11 >> sh) & 255u) * ia1;
-        int v = (((ib0 * (r0 >> 4)) >> 16) + ((ib1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        return (float)v;
-    };
-    // The same value when the ROI of every point of the wave lies strictly inside the image (no mirrored border: all
-    // but a ~25-pixel frame of the sample points at the bench's depths): the taps are at (y0 + sy, x0 + sx) directly and
-    // the second column is the first one's right neighbour or itself.  PMC: this kernel is VALU bound (64 % of the
-    // issue cycles, 83 vector instructions per tree level); the four reflections and the pair selection were ~30 of them.
+    const PointState ps = point_state(g, pid, n_points_total, depth_all, cloud_all, nfeat_all);   // once per lane
+    const bool valid = ps.valid;
+    const int size = 2 * ps.half + 1, x0 = ps.x - ps.half, y0 = ps.y - ps.half;
+    const uint32_t* lab = lab_all + (size_t)ps.frame * W * H;
+    const uint32_t* lab2 = COMPACT ? lab2_all + 2 * (size_t)ps.frame * W * H : nullptr;
+    const ResizeRow* myrt = rtl + (valid ? ps.half : 0);
     const int lab_base = y0 * W + x0;
-    auto patch_value_inside = [&](int packed) -> float {
-        const int c = packed >> 16, dy = (packed >> 8) & 255, dx = packed & 255;
-        const uint2 xr = *reinterpret_cast<const uint2*>(&myrt->x[dx]);
-        const uint2 yr = *reinterpret_cast<const uint2*>(&myrt->y[dy]);
-        const int sx0 = (int)(short)(xr.x & 0xffffu), ia0 = (int)(short)(xr.x >> 16), ia1 = (int)(short)(xr.y & 0xffffu);
-        const int ib0 = (int)(short)(yr.x >> 16), ib1 = (int)(short)(yr.y & 0xffffu);
-        const bool two = (int)(short)(xr.y >> 16) != sx0;
-        const int sy0 = (int)(short)(yr.x & 0xffffu), sy1 = (int)(short)(yr.y >> 16);
-        const u32x2_u q0 = *reinterpret_cast<const u32x2_u*>(lab + (lab_base + sy0 * W + sx0));
-        const u32x2_u q1 = *reinterpret_cast<const u32x2_u*>(lab + (lab_base + sy1 * W + sx0));
-        const int sh = 8 * c;
-        const int a00 = (int)((q0.x >> sh) & 255u), a01 = (int)(((two ? q0.y : q0.x) >> sh) & 255u);
-        const int a10 = (int)((q1.x >> sh) & 255u), a11 = (int)(((two ? q1.y : q1.x) >> sh) & 255u);
-        const int r0 = a00 * ia0 + a01 * ia1;
-        const int r1 = a10 * ia0 + a11 * ia1;
-        int v = (((ib0 * (r0 >> 4)) >> 16) + ((ib1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        return (float)v;
-    };
-    // the same value from the row-pair image: one 16-byte load {top(x), bottom(x), top(x + 1), bottom(x + 1)}; a record's
-    // second row / column is the first one or its neighbour (pipeline_init: ofs1 = ofs or ofs + 1)
-    typedef uint32_t u32x4_p __attribute__((ext_vector_type(4), aligned(8)));
-    const uint32_t* lab2 = COMPACT ? lab2_all + 2 * (size_t)frame * W * H : nullptr;
-    auto patch_value_inside2 = [&](unsigned cell) -> float {   // cell = channel << 8 | dy << 4 | dx
-        const int c = (int)(cell >> 8) & 3, dy = (int)(cell >> 4) & 15, dx = (int)cell & 15;
-        const uint2 xr = *reinterpret_cast<const uint2*>(&myrt->x[dx]);
-        const uint2 yr = *reinterpret_cast<const uint2*>(&myrt->y[dy]);
-        const int sx0 = (int)(short)(xr.x & 0xffffu), ia0 = (int)(short)(xr.x >> 16), ia1 = (int)(short)(xr.y & 0xffffu);
-        const int ib0 = (int)(short)(yr.x >> 16), ib1 = (int)(short)(yr.y & 0xffffu);
-        const bool two = (int)(short)(xr.y >> 16) != sx0;
-        const int sy0 = (int)(short)(yr.x & 0xffffu);
-        const bool below = (int)(short)(yr.y >> 16) != sy0;
-        const u32x4_p q = *reinterpret_cast<const u32x4_p*>(lab2 + 2 * (lab_base + sy0 * W + sx0));
-        const int sh = 8 * c;
-        const uint32_t t0 = q.x, b0 = below ? q.y : q.x, t1 = two ? q.z : q.x, b1 = below ? (two ? q.w : q.y) : (two ? q.z : q.x);
-        const int a00 = (int)((t0 >> sh) & 255u), a01 = (int)((t1 >> sh) & 255u);
-        const int a10 = (int)((b0 >> sh) & 255u), a11 = (int)((b1 >> sh) & 255u);
-        const int r0 = a00 * ia0 + a01 * ia1;
-        const int r1 = a10 * ia0 + a11 * ia1;
-        int v = (((ib0 * (r0 >> 4)) >> 16) + ((ib1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        return (float)v;
-    };
-    // strictly inside: the 8-byte tap load at column x0 + sx0 <= x0 + size - 1 must not be the image's last column
+    // strictly inside: the 8-byte tap load at column x0 + sx0 <= x0 + size - 1 must not be the image's last column.
+    // The fast fetchers run when that holds for every point of the wave (all but a ~25-pixel frame of the sample points
+    // at the bench's depths)
     const bool roi_inside = x0 >= 0 && y0 >= 0 && x0 + size < W && y0 + size <= H;
     const bool wave_inside = __ballot(valid && !roi_inside) == 0ull;
+    auto patch_value = [&](int channel, int dy, int dx) -> float {
+        const ResizeTaps t = resize_taps(myrt, dy, dx);
+        if (!wave_inside) return (float)patch_value_mirrored(lab, W, H, x0, y0, t, channel);
+        return (float)(COMPACT ? patch_value_inside2(lab2, lab_base, W, t, channel) : patch_value_inside(lab, lab_base, W, t, channel));
+    };
 
     // lanes = (point, tree); findLeafNode (classifier.cpp:97-117)
+    static_assert(kMaxTrees <= 64, "leaf_rows[16] x 4 lanes per point");
     int leaf_rows[16];
     int n_mine = 0;
     const int4* np = reinterpret_cast<const int4*>(nodes);
@@ -434,10 +350,10 @@ rf_frames_lazy_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ n
             while ((nd.y & 0xFFFFFu) != 0u) {
                 // both children in one load, in flight while the node's own test is evaluated
                 const u32x4_p ch = *reinterpret_cast<const u32x4_p*>(nodes8 + 2 * (size_t)(nd.y & 0xFFFFFu));
-                const unsigned kind = nd.y >> 30, cell = (nd.y >> 20) & 0x3FFu;
+                const unsigned kind = nd.y >> 30;   // then channel << 8 | dy << 4 | dx in 10 bits (upload_forest)
                 float v;
-                if (kind == 0u) v = wave_inside ? patch_value_inside2(cell) : patch_value((int)(((cell >> 8) & 3u) << 16 | ((cell >> 4) & 15u) << 8 | (cell & 15u)));
-                else v = kind == 1u ? depth_m : (kind == 2u ? height : nrm);
+                if (kind == 0u) v = patch_value((int)(nd.y >> 28) & 3, (int)(nd.y >> 24) & 15, (int)(nd.y >> 20) & 15);
+                else v = kind == 1u ? ps.depth_m : (kind == 2u ? ps.height : ps.nrm);
                 const bool go_left = v < __uint_as_float(nd.x);
                 nd = go_left ? make_uint2(ch.x, ch.y) : make_uint2(ch.z, ch.w);
             }
@@ -449,8 +365,8 @@ rf_frames_lazy_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ n
                 const int4 c0 = np[nd.z], c1 = np[nd.z + 1];
                 const int f = nd.x;
                 float v;
-                if (f < g.n_patch) v = wave_inside ? patch_value_inside(nd.w) : patch_value(nd.w);
-                else v = f == g.pos_depth ? depth_m : (f == g.pos_height ? height : nrm);
+                if (f < g.n_patch) v = patch_value(nd.w >> 16, (nd.w >> 8) & 255, nd.w & 255);   // channel << 16 | dy << 8 | dx
+                else v = f == g.pos_depth ? ps.depth_m : (f == g.pos_height ? ps.height : ps.nrm);
                 nd = (v < __int_as_float(nd.y)) ? c0 : c1;
             }
             row = nd.w;
@@ -463,7 +379,6 @@ rf_frames_lazy_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ n
     // tree-order accumulation (classifier.cpp:193-206) and scatter into the low-res image at
     // (y/stride, x/stride) (segmenter.cpp:369-375); invalid cells get the fill value
     const int lane_base = lane & ~3;
-    const int p = pid - frame * per_frame;
     for (int c0 = 0; c0 < cm.S; c0 += 4) {
         const int c = c0 + sub;
         const int cc = c < cm.S ? c : cm.S - 1;
@@ -488,19 +403,23 @@ rf_frames_lazy_kernel(FrameGeom g, ClassMap cm, const DeviceNode* __restrict__ n
             }
         }
         if (pid < n_points_total && c < cm.S) {
-            float* low = low_all + (size_t)frame * per_frame * cm.S;
-            low[cm.layer_base[c] + (size_t)p * cm.layer_C[c] + cm.cl[c]] = valid ? acc : g.fill;
+            float* low = low_all + (size_t)ps.frame * per_frame * cm.S;
+            low[cm.layer_base[c] + (size_t)ps.p * cm.layer_C[c] + cm.cl[c]] = valid ? acc : g.fill;
         }
     }
 }
 
-static bool n_trees_ok(int n_trees) { return n_trees >= 1 && n_trees <= 64; }   // leaf_rows[16] x 4 lanes per point
+bool rf_frames_wants_lab2(const DeviceForest& f) { return f.nodes8.p != nullptr; }
 
-bool rf_frames_wants_lab2(const DeviceForest& f) { return f.nodes8.p != nullptr && n_trees_ok(f.n_trees); }
+// one block = WAVES_PER_BLOCK waves of PPW points, in both kernels
+static dim3 point_grid(int total) {
+    const int pts_per_block = PPW * WAVES_PER_BLOCK;
+    return dim3((unsigned)((total + pts_per_block - 1) / pts_per_block));
+}
 
 void launch_rf_frames(const FrameGeom& g, const DeviceForest& f, const ResizeRow* d_rt, const uint32_t* d_lab,
-                      const uint16_t* d_depth, const float4* d_cloud, const float* d_nfeat, float* d_low,
-                      float* d_dump, uint8_t* d_valid, int n, hipStream_t s, const uint2* d_lab2) {
+                      const uint16_t* d_depth, const float4* d_cloud, const float* d_nfeat, float* d_low, int n,
+                      hipStream_t s, const uint2* d_lab2) {
     ClassMap cm{};
     cm.S = f.sum_classes;
     cm.n_layers = f.n_layers;
@@ -515,31 +434,27 @@ void launch_rf_frames(const FrameGeom& g, const DeviceForest& f, const ResizeRow
         prefix += f.class_counts[l];
     }
     const int total = per_frame * n;
+    const size_t rt_bytes = (size_t)g.rt_rows * sizeof(ResizeRow);
+    const int in_lds = g.n_patch > 0 && rt_bytes <= 40 * 1024 ? 1 : 0;   // else the records come through L1
+    if (d_lab2 && rf_frames_wants_lab2(f))
+        rf_frames_lazy_kernel<true><<<point_grid(total), dim3(256), in_lds ? rt_bytes : 0, s>>>(
+            g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(), f.n_trees, d_rt, in_lds, d_lab, d_depth,
+            d_cloud, d_nfeat, d_low, total, f.nodes8.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_lab2));
+    else
+        rf_frames_lazy_kernel<false><<<point_grid(total), dim3(256), in_lds ? rt_bytes : 0, s>>>(
+            g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(), f.n_trees, d_rt, in_lds, d_lab, d_depth,
+            d_cloud, d_nfeat, d_low, total, nullptr, nullptr);
+    RV_LAUNCHED("rf_frames_lazy_kernel");
+}
+
+void launch_feature_dump(const FrameGeom& g, const ResizeRow* d_rt, const uint32_t* d_lab, const uint16_t* d_depth,
+                         const float4* d_cloud, const float* d_nfeat, float* d_dump, uint8_t* d_valid, int n, hipStream_t s) {
+    const int total = g.lw * g.lh * n;
     const int fb_stride = ((g.n_patch + 3) / 4) * 4 + 4;
     const size_t smem = (size_t)WAVES_PER_BLOCK * (PPW * fb_stride + PPW * 32);
-    const int pts_per_block = PPW * WAVES_PER_BLOCK;
-    const dim3 grid((unsigned)((total + pts_per_block - 1) / pts_per_block)), block(64 * WAVES_PER_BLOCK);
-    if (!d_dump && n_trees_ok(f.n_trees)) {
-        const size_t rt_bytes = (size_t)g.rt_rows * sizeof(ResizeRow);
-        const int in_lds = g.n_patch > 0 && rt_bytes <= 40 * 1024 ? 1 : 0;   // else the records come through L1
-        if (d_lab2 && rf_frames_wants_lab2(f))
-            rf_frames_lazy_kernel<true><<<grid, dim3(256), in_lds ? rt_bytes : 0, s>>>(
-                g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(), f.n_trees, d_rt, in_lds, d_lab, d_depth,
-                d_cloud, d_nfeat, d_low, total, f.nodes8.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_lab2));
-        else
-            rf_frames_lazy_kernel<false><<<grid, dim3(256), in_lds ? rt_bytes : 0, s>>>(
-                g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(), f.n_trees, d_rt, in_lds, d_lab, d_depth,
-                d_cloud, d_nfeat, d_low, total, nullptr, nullptr);
-        RV_LAUNCHED("rf_frames_lazy_kernel");
-        return;
-    }
-    if (d_dump)
-        rf_frames_kernel<true><<<grid, block, smem, s>>>(g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(),
-                                                         f.n_trees, d_rt, d_lab, d_depth, d_cloud, d_nfeat, d_low, d_dump, d_valid, total, fb_stride);
-    else
-        rf_frames_kernel<false><<<grid, block, smem, s>>>(g, cm, f.nodes.as<DeviceNode>(), f.roots.as<int32_t>(), f.hist.as<float>(),
-                                                          f.n_trees, d_rt, d_lab, d_depth, d_cloud, d_nfeat, d_low, d_dump, d_valid, total, fb_stride);
-    RV_LAUNCHED("rf_frames_kernel");
+    feature_dump_kernel<<<point_grid(total), dim3(64 * WAVES_PER_BLOCK), smem, s>>>(g, d_rt, d_lab, d_depth, d_cloud, d_nfeat, d_dump,
+                                                                                  d_valid, total, fb_stride);
+    RV_LAUNCHED("feature_dump_kernel");
 }
 
 // =============================================================================================

@@ -50,16 +50,20 @@ void launch_normal_feature(const FrameGeom& g, const float4* d_cloud, const uint
                            int n, hipStream_t s);
 
 // ---- kernels_rf.hip --------------------------------------------------------------------------
-// Fused per-point feature vector (LDS) + forest traversal over the stride grid of n frames.
+// The frame path: per-point features computed on demand + forest traversal over the stride grid of n frames.
 //   d_low   : n x (lh*lw*S) low-resolution log-posteriors, layers concatenated per frame, each
 //             [ly][lx][class]; invalid-depth cells receive g.fill
-//   d_dump  : optional n x (lh*lw) x D materialised feature vectors (parity API only)
-//   d_valid : optional n x (lh*lw) mask bytes
+//   d_lab2  : the row-pair Lab image of launch_prep, when rf_frames_wants_lab2(f)
 void launch_rf_frames(const FrameGeom& g, const DeviceForest& f, const ResizeRow* d_rt, const uint32_t* d_lab,
-                      const uint16_t* d_depth, const float4* d_cloud, const float* d_nfeat, float* d_low,
-                      float* d_dump, uint8_t* d_valid, int n, hipStream_t s, const uint2* d_lab2 = nullptr);
+                      const uint16_t* d_depth, const float4* d_cloud, const float* d_nfeat, float* d_low, int n,
+                      hipStream_t s, const uint2* d_lab2 = nullptr);
 // true when the frame kernel can use the row-pair Lab image (8-byte nodes exist for this model)
 bool rf_frames_wants_lab2(const DeviceForest& f);
+// The same features materialised (rvseg_extract_features, rvseg_forest_train_frames); needs no model.
+//   d_dump  : n x (lh*lw) x D feature vectors, zero patch values at invalid-depth points
+//   d_valid : n x (lh*lw) mask bytes
+void launch_feature_dump(const FrameGeom& g, const ResizeRow* d_rt, const uint32_t* d_lab, const uint16_t* d_depth,
+                         const float4* d_cloud, const float* d_nfeat, float* d_dump, uint8_t* d_valid, int n, hipStream_t s);
 // cv::resize to full resolution + pack [layer][y][x][class] (segmenter.cpp:380-431)
 void launch_upsample_pack(const FrameGeom& g, const LayerLayout& f, const UpsampleTables& t,
                           const float* d_low, float* d_post, int n, hipStream_t s);

@@ -54,6 +54,10 @@ Pipeline* pipeline_of(rvseg_ctx* ctx);
 rvseg_status pipeline_init(rvseg_ctx* ctx);
 // stages the per-frame A = R*Kinv, t of n calibrations (21 floats each) and enqueues their copy to im->calibA
 rvseg_status upload_calib(rvseg_ctx* ctx, Pipeline* im, const float* calib, int n, hipStream_t s);
+// One frame's feature vectors, materialised: reserves the working buffers and enqueues prep, the normal feature and the
+// dump kernel on s.  The frame is in im->in_rgb / im->in_depth and its calibration uploaded (upload_calib); the result
+// is im->dump (lh*lw x D floats, stride-grid order) and im->valid (lh*lw mask bytes).
+rvseg_status dump_frame_features(rvseg_ctx* ctx, Pipeline* im, hipStream_t s);
 void timer_reset(rvseg_ctx* ctx);
 void timer_mark(rvseg_ctx* ctx, const char* name, hipStream_t s);
 

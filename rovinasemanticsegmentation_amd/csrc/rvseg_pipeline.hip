@@ -145,6 +145,28 @@ rvseg_status upload_calib(rvseg_ctx* ctx, Pipeline* im, const float* calib, int 
     return RVSEG_OK;
 }
 
+// ---- the materialised feature vectors of one frame (rvseg_extract_features, rvseg_forest_train_frames) -----------
+rvseg_status dump_frame_features(rvseg_ctx* ctx, Pipeline* im, hipStream_t s) {
+    const FrameGeom& g = im->geom;
+    const size_t npix = (size_t)g.W * g.H;
+    const int P = g.lw * g.lh;
+    const bool normal = ctx->params.feature_normal;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, im->lab, npix * 4)) != RVSEG_OK || (st = dev_reserve(ctx, im->cloud, npix * 16)) != RVSEG_OK ||
+        (st = dev_reserve(ctx, im->rect, npix)) != RVSEG_OK || (st = dev_reserve(ctx, im->change, npix)) != RVSEG_OK ||
+        (st = dev_reserve(ctx, im->nfeat, (size_t)P * 4)) != RVSEG_OK || (st = dev_reserve(ctx, im->dump, (size_t)P * g.D * 4)) != RVSEG_OK ||
+        (st = dev_reserve(ctx, im->valid, (size_t)P)) != RVSEG_OK) return st;
+    launch_prep(g, ctx->lab, im->in_rgb.as<uint8_t>(), im->in_depth.as<uint16_t>(), im->calibA.as<float>(), im->lab.as<uint32_t>(),
+                im->cloud.as<float4>(), normal ? im->change.as<uint8_t>() : nullptr, 1, s);
+    if (normal) {
+        launch_window_map(g, im->cloud.as<float4>(), im->change.as<uint8_t>(), im->rect.as<uint8_t>(), 1, s);
+        launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), 1, s);
+    }
+    launch_feature_dump(g, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), im->in_depth.as<uint16_t>(), im->cloud.as<float4>(),
+                        im->nfeat.as<float>(), im->dump.as<float>(), im->valid.as<uint8_t>(), 1, s);
+    return RVSEG_OK;
+}
+
 // ---- stage timing ----------------------------------------------------------------------------
 void timer_reset(rvseg_ctx* ctx) {
     ctx->timer.names.clear();
@@ -244,7 +266,7 @@ static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t
     }
     timer_mark(ctx, "rf_frames", s);
     launch_rf_frames(g, f, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), d_depth, im->cloud.as<float4>(),
-                     im->nfeat.as<float>(), im->low.as<float>(), nullptr, nullptr, n, s, use_lab2 ? im->lab2.as<uint2>() : nullptr);
+                     im->nfeat.as<float>(), im->low.as<float>(), n, s, use_lab2 ? im->lab2.as<uint2>() : nullptr);
     timer_mark(ctx, "upsample_pack", s);
     launch_upsample_pack(g, f, im->up, im->low.as<float>(), post, n, s);
     if (p.use_dense_crf) {
@@ -578,31 +600,15 @@ rvseg_status rvseg_extract_features(rvseg_ctx* ctx, const uint8_t* rgb, const ui
     if (st != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
     const FrameGeom& g = im->geom;
-    const rvseg_params& p = ctx->params;
     const size_t npix = (size_t)g.W * g.H;
     const int P = g.lw * g.lh;
     hipStream_t s = ctx->stream;
     if ((st = dev_reserve(ctx, im->in_rgb, npix * 3)) != RVSEG_OK) return st;
     if ((st = dev_reserve(ctx, im->in_depth, npix * 2)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->lab, npix * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->cloud, npix * 16)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->rect, npix)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->change, npix)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->nfeat, (size_t)P * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->dump, (size_t)P * g.D * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, im->valid, (size_t)P)) != RVSEG_OK) return st;
     RV_HIP(ctx, hipMemcpyAsync(im->in_rgb.p, rgb, npix * 3, hipMemcpyHostToDevice, s));
     RV_HIP(ctx, hipMemcpyAsync(im->in_depth.p, depth_mm, npix * 2, hipMemcpyHostToDevice, s));
     if ((st = upload_calib(ctx, im, calib, 1, s)) != RVSEG_OK) return st;
-    launch_prep(g, ctx->lab, im->in_rgb.as<uint8_t>(), im->in_depth.as<uint16_t>(), im->calibA.as<float>(),
-                im->lab.as<uint32_t>(), im->cloud.as<float4>(), p.feature_normal ? im->change.as<uint8_t>() : nullptr, 1, s);
-    if (p.feature_normal) {
-        launch_window_map(g, im->cloud.as<float4>(), im->change.as<uint8_t>(), im->rect.as<uint8_t>(), 1, s);
-        launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), 1, s);
-    }
-    // the dump variant never touches the forest; a context without a model can still extract
-    launch_rf_frames(g, ctx->forest, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), im->in_depth.as<uint16_t>(),
-                     im->cloud.as<float4>(), im->nfeat.as<float>(), nullptr, im->dump.as<float>(), im->valid.as<uint8_t>(), 1, s);
+    if ((st = dump_frame_features(ctx, im, s)) != RVSEG_OK) return st;
     RV_LAUNCH_OK(ctx);
     std::vector<float> dump((size_t)P * g.D);
     std::vector<uint8_t> valid((size_t)P);

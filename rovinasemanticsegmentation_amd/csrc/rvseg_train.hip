@@ -835,7 +835,6 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
     if (st != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
     const FrameGeom& g = im->geom;
-    const rvseg_params& p = ctx->params;
     if ((st = check_train_args(ctx, n_layers, class_counts, tp, g.D)) != RVSEG_OK) return st;
     const size_t npix = (size_t)g.W * g.H;
     const int Pg = g.lw * g.lh;
@@ -862,11 +861,7 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
     void* dScan = A.alloc<uint8_t>(ctx, scan_bytes, &ok);
     if (!ok) return RVSEG_ERR_HIP;
     RV_HIP(ctx, hipMemcpyAsync(T.d_nb_index, T.nb_index.data(), (size_t)g.D * 4, hipMemcpyHostToDevice, s));
-    if ((st = dev_reserve(ctx, im->in_rgb, npix * 3)) != RVSEG_OK || (st = dev_reserve(ctx, im->in_depth, npix * 2)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, im->lab, npix * 4)) != RVSEG_OK || (st = dev_reserve(ctx, im->cloud, npix * 16)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, im->rect, npix)) != RVSEG_OK || (st = dev_reserve(ctx, im->change, npix)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, im->nfeat, (size_t)Pg * 4)) != RVSEG_OK || (st = dev_reserve(ctx, im->dump, (size_t)Pg * g.D * 4)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, im->valid, (size_t)Pg)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, im->in_rgb, npix * 3)) != RVSEG_OK || (st = dev_reserve(ctx, im->in_depth, npix * 2)) != RVSEG_OK) return st;
     std::vector<uint8_t> h_rgb(npix * 3);
     std::vector<uint16_t> h_depth(npix);
     std::vector<int8_t> h_lab((size_t)n_layers * npix);
@@ -895,14 +890,7 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
             RV_HIP(ctx, hipMemcpyAsync(im->in_depth.p, h_depth.data(), npix * 2, hipMemcpyHostToDevice, s));
             RV_HIP(ctx, hipMemcpyAsync(dLabels, h_lab.data(), h_lab.size(), hipMemcpyHostToDevice, s));
             if ((st = upload_calib(ctx, im, calib + (size_t)fr * 21, 1, s)) != RVSEG_OK) return st;
-            launch_prep(g, ctx->lab, im->in_rgb.as<uint8_t>(), im->in_depth.as<uint16_t>(), im->calibA.as<float>(), im->lab.as<uint32_t>(),
-                        im->cloud.as<float4>(), p.feature_normal ? im->change.as<uint8_t>() : nullptr, 1, s);
-            if (p.feature_normal) {
-                launch_window_map(g, im->cloud.as<float4>(), im->change.as<uint8_t>(), im->rect.as<uint8_t>(), 1, s);
-                launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), 1, s);
-            }
-            launch_rf_frames(g, ctx->forest, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), im->in_depth.as<uint16_t>(),
-                             im->cloud.as<float4>(), im->nfeat.as<float>(), nullptr, im->dump.as<float>(), im->valid.as<uint8_t>(), 1, s);
+            if ((st = dump_frame_features(ctx, im, s)) != RVSEG_OK) return st;
             train_frame_flags_kernel<<<dim3((unsigned)((Pg + 255) / 256)), dim3(256), 0, s>>>(g, im->valid.as<uint8_t>(), dLabels, n_layers, dFlags);
             size_t sb = scan_bytes;
             RV_HIP(ctx, rocprim::exclusive_scan(dScan, sb, dFlags, dOffs, 0, (size_t)Pg, rocprim::plus<int>(), s));

@@ -174,13 +174,59 @@ def test_forest_eval_with_2_20_nodes(gpu_ctx_factory, oracle, frame1, big3):
 @pytest.mark.parametrize("r", [3, 4])
 def test_wave_inside_at_its_boundary(gpu_ctx_factory, oracle, big3, big4, r, model):
     """Single valid points decide per wave whether patch_value_inside2 / patch_value_inside (16-byte model) or the
-    reflecting patch_value runs.  `dense` is a 32-tree forest in which every point tests 160 cells (8-byte nodes)."""
+    reflecting patch_value_mirrored runs.  `dense` is a 32-tree forest in which every point tests 160 cells (8-byte nodes)."""
     rgb, depth, pts = fc.wave_inside_frames(r)
     blob = fc.patch_forest(r, r)[1] if model == "dense" else (big3 if r == 3 else big4)[model][1]
     assert fc.split_features(blob) == set(range(fc.layout(r)[4]))
     kw = dict(fc.FRAME_KW, patch_size_reduce=r)
     counts, info = frames_equal_oracle(gpu_ctx_factory, oracle, kw, blob, rgb, depth, synthetic.make_calib(64, 48), model)
     assert sum(counts) == len(pts)
+
+
+@pytest.fixture(scope="module")
+def resize_sharers(big3):
+    """The wave_inside frames and the two models of test_one_resize_in_three_kernels: 32 trees that split on every
+    feature of r = 3 (8-byte nodes), and the same trees with the 2^20 + 1-node tree appended (16-byte nodes)."""
+    rgb, depth, pts = fc.wave_inside_frames(3)
+    trees = fc.patch_forest(3, 3)[0]
+    wide = trees + big3["wide_plus_one_split"][0]
+    return rgb, depth, pts, {"8-byte": fc.write_forest(trees, [2]), "16-byte": fc.write_forest(wide, [2])}
+
+
+@pytest.mark.parametrize("nodes", ["8-byte", "16-byte"])
+def test_one_resize_in_three_kernels(gpu_ctx_factory, oracle, resize_sharers, nodes):
+    """The lazy walk with 8-byte nodes (row-pair taps), the lazy walk with 16-byte nodes (8-byte pair taps) and the dump
+    kernel (mirrored taps, all cells) share resize_taps / resize_blend: the posteriors of segment_frames must equal, bit
+    for bit at every valid point, forest_eval over the vectors extract_features returns, scattered to their (x, y) --
+    for each node format over its own model, and the vectors themselves the oracle's.  At stride 1 the up-sampler
+    multiplies by weights 1 and 0; that this is the identity on these finite values is checked here on the CPU with the
+    oracle's resize_linear, so the comparison is of the full-resolution posteriors."""
+    rgb, depth, pts, blobs = resize_sharers
+    W, H, S = 64, 48, 2
+    calib = synthetic.make_calib(W, H)
+    p = oracle.default_params(**fc.FRAME_KW)
+    ctx = gpu_ctx_factory(max_batch=len(rgb), **fc.FRAME_KW)
+    try:
+        ctx.forest_load(blobs[nodes])
+        assert (ctx.forest_info()["n_nodes"] >= fc.NODES8_LIMIT) == (nodes == "16-byte")
+        post = ctx.segment_frames(rgb, depth, calib, want_labels=False)["posteriors"]
+        seen = 0
+        for i in range(len(rgb)):
+            X, xv, yv = ctx.extract_features(rgb[i], depth[i], calib)
+            wantX, wx, wy = oracle.extract(p, rgb[i], depth[i], calib)
+            assert np.array_equal(xv, wx) and np.array_equal(yv, wy)
+            same(X, wantX, "features of frame %d" % i)
+            assert sorted(zip(xv.tolist(), yv.tolist())) == sorted((x, y) for f, x, y, half, inside in pts if f == i)
+            low = np.full((H, W, S), p.fill_value, np.float32)
+            low[yv, xv] = ctx.forest_eval(X)
+            assert np.isfinite(low).all()
+            same(oracle.resize_linear(low, W, H), low, "the up-sampler at stride 1 is not the identity")
+            got = np.asarray(post[i], np.float32).reshape(H, W, S)
+            same(got[yv, xv], low[yv, xv], "%s walk against the dump kernel + forest_eval, frame %d" % (nodes, i))
+            seen += len(xv)
+        assert seen == len(pts) and {inside for *_, inside in pts} == {True, False}
+    finally:
+        ctx.close()
 
 
 # ---- 7. resize table in LDS and through L1 ----------------------------------------------------------------------------
