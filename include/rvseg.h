@@ -418,6 +418,61 @@ rvseg_status rvseg_process_map_device(rvseg_ctx *ctx, int32_t n_images, const in
                                       const float *d_cloud_rgb, int8_t *d_labels_out, float *d_unaries_out,
                                       void *hip_stream);
 
+/* ---- the projector: index images from poses (src/segmenter.cpp:234-240, 576-578) -----------------------------
+ * _projector.project(zbuffer, index_image, m_multi->transform().inverse(), *cloud), set up by initializeProjector
+ * from the cameras' intrinsics, the image size, depth_min and depth_max.  fps_mapper::MultiProjector is not in the
+ * reference tree, so the projection is a BUILD-OWNED definition (parity with fps_mapper is unpinned):
+ *
+ * Inputs: a cloud of N points, xyz fp32 in the map frame.  For each of the n_images sub-images (one camera of one
+ * node, in the order the fusion uses), one projection matrix P: 3x4, fp32, row-major, mapping the map frame to
+ * homogeneous pixels, K * [R | t] of that view.  W, H, depth_min, depth_max are the context's (rvseg_params;
+ * setImageSize / setMinDistance / setMaxDistance, :237-240).  depth_min must be > 0, otherwise the call returns
+ * RVSEG_ERR_INVALID_ARG.
+ *
+ * Per point i and image m, all in fp32, every product and sum rounded separately (no FMA):
+ *     px = ((P00*x + P01*y) + P02*z) + P03      (same shape for py with row 1, w with row 2)
+ *     keep only if  w >= depth_min && w <= depth_max     (NaN fails both tests: skipped)
+ *     u = px / w ; v = py / w                    (IEEE division)
+ *     cu = rintf(u) ; cv = rintf(v)              (nearest, ties to even)
+ *     keep only if  cu >= 0 && cu < W && cv >= 0 && cv < H   (tested on the floats, then converted; -0.0 is
+ *                                                             column / row 0)
+ * A pixel's winner is the kept point with the smallest w.  Among equal w, the smallest index wins.  This is exactly
+ * what the sequential loop "if (z < zbuffer(r,c)) { zbuffer = z; index = i; }" over ascending i produces, so the
+ * result does not depend on any execution order.
+ *
+ * Outputs: index (int32, n_images x H x W) holds the winner, or -1 where no point lands -- the convention the
+ * fusion reads (:601-607).  The optional zbuffer (fp32, same shape) holds the winner's w, or +inf where no point
+ * lands.
+ *
+ * The same call limit as the fusion applies: n_images * W * H < 2^32 - 1.  N == 0 or n_images == 0 is not an error
+ * (the output is all -1).  `proj` is HOST memory (n_images x 12 floats) in both entries; it is consumed before the
+ * call returns. */
+/* (segmenter.cpp:234-240, 576-578) device buffers, work enqueued on hip_stream, no synchronisation, no allocation per
+ * call once the context's key image has grown (at most 32 x W x H x 8 bytes: larger calls run in groups of 32 images) */
+rvseg_status rvseg_project_cloud_device(rvseg_ctx *ctx, int32_t n_images, const float *proj, int32_t N,
+                                        const float *d_cloud_xyz, int32_t *d_index_out, float *d_zbuffer_out,
+                                        void *hip_stream);
+/* (segmenter.cpp:234-240, 576-578) host buffers, staged through context memory, synchronous; zbuffer_out may be NULL */
+rvseg_status rvseg_project_cloud(rvseg_ctx *ctx, int32_t n_images, const float *proj, int32_t N,
+                                 const float *cloud_xyz, int32_t *index_out, float *zbuffer_out);
+/* (segmenter.cpp:234-240, 576-578, then :561-682) rvseg_process_map_device with the index images produced in context
+ * memory by the projector instead of passed in: the same fusion, CRF and labels through the same internal function.
+ * d_cloud_xyz is needed with or without use_dense_crf.  d_index_out (optional, n_images x H x W int32) receives
+ * the index images. */
+rvseg_status rvseg_process_map_poses_device(rvseg_ctx *ctx, int32_t n_images, const float *proj,
+                                            const float *d_posteriors, int32_t cloud_size, const float *d_cloud_xyz,
+                                            const float *d_cloud_rgb, int8_t *d_labels_out, float *d_unaries_out,
+                                            int32_t *d_index_out, void *hip_stream);
+/* (segmenter.cpp:234-240, 576-578) Host only, no context: P = K * [R_c^T | -R_c^T t_c] * T^-1 for one camera
+ * (calib_R_t: the extrinsic camera -> base link, R row-major then t, floats 9..20 of a calibration) and one node pose
+ * T (base link -> map, 3x4 row-major [R_n | t_n], rotation assumed orthonormal, so T^-1 = [R_n^T | -R_n^T t_n]).
+ * Computed in double in this order, every dot product summed left to right ((a0*b0 + a1*b1) + a2*b2):
+ *     A = R_c^T * R_n^T ;  b = R_n^T * t_n ;  c = R_c^T * (b + t_c)  (so the view is [A | -c]) ;
+ *     P[r][j] = K[r] . A[:, j]  (j < 3) ;  P[r][3] = -(K[r] . c) ;  each of the 12 values rounded to fp32 once.
+ * A convenience: the projector's contract starts at P. */
+rvseg_status rvseg_projection_matrix(const float K[9], const float calib_R_t[12], const float node_pose[12],
+                                     float P_out[12]);
+
 /* One of the label rules above over a host matrix of N points x C classes (class-contiguous); the
  * no-CRF branch of processMapFromQueue applies RVSEG_LABEL_NOCRF to the fused unaries
  * (src/segmenter.cpp:660-681). */

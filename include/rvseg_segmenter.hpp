@@ -54,6 +54,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -146,10 +147,13 @@ struct LocalMapSegmentationResponse {
 };
 
 // One fps_mapper::MultiImageMapNode of a local map as the fusion loop needs it (segmenter.cpp:571-621).  The projector is
-// external to the reference (fps_mapper::MultiProjector::project, :578), so the caller hands over its result.
+// external to the reference (fps_mapper::MultiProjector::project, :578): the caller either hands over its result
+// (index_image) or the node's pose, from which the library's own projector (include/rvseg.h, a build-owned definition)
+// makes the index images of every camera (Segmenter::setCameraMatrices).
 struct LocalMapNode {
     std::vector<int> subimage_seqs;        // m_multi->subimageSeqs(): the depth sequence number of every camera's sub-image
     std::vector<int32_t> index_image;      // IndexImage, cameras stacked row-wise: (n_cameras * H) x W, < 0 = no cloud point (:601-604)
+    std::vector<float> pose;               // m_multi->transform(): base link -> map, 3 x 4 row-major (12 floats); empty = not given
 };
 // One fps_mapper::LocalMap: its id, nodes and cloud (xyz in the map frame, rgb in [0, 1]; :560, :629-637)
 struct LocalMap {
@@ -301,6 +305,12 @@ public:
         result_queues_.assign((size_t)n_cameras, {});
     }
     int cameraCount() const { return (int)image_queues_.size(); }
+    // initializeProjector's intrinsics (segmenter.cpp:234-240): one K (3 x 3 row-major) per camera of setCameras, for the
+    // nodes that arrive with a pose instead of an index image
+    void setCameraMatrices(const float* K) {
+        std::lock_guard<std::mutex> g(frame_mtx_);
+        camera_K_.assign(K, K + image_queues_.size() * 9);
+    }
 
     // onNewNode for one camera's sub-image (segmenter.cpp:271-284): the frames are copied (the reference holds cv::Mat
     // references) and pushed with their depth sequence number.
@@ -390,6 +400,8 @@ public:
         const size_t per = (size_t)total_labels_ * npix;
         std::vector<int32_t> index_images;
         std::vector<float> posteriors;
+        std::vector<float> projections;      // of the sub-images whose node has a pose and no index image ...
+        std::vector<int> projected_slots;    // ... and their places in index_images
         int n_images = 0;
         for (const LocalMapNode& nd : lmap.nodes) {
             for (size_t i = 0; i < nd.subimage_seqs.size() && i < result_queues_.size(); i++) {
@@ -397,9 +409,18 @@ public:
                 std::deque<std::pair<int, std::vector<float>>>& q = result_queues_[i];
                 while (!q.empty() && q.front().first < nd.subimage_seqs[i]) q.pop_front();   // "Drop skipped maps", :589-592
                 if (!q.empty() && q.front().first == nd.subimage_seqs[i]) {
-                    if (nd.index_image.size() < (i + 1) * npix) throw std::runtime_error("index image smaller than n_cameras * H x W");
-                    index_images.insert(index_images.end(), nd.index_image.begin() + (std::ptrdiff_t)(i * npix),
-                                        nd.index_image.begin() + (std::ptrdiff_t)((i + 1) * npix));   // rows y + i*_camera_h, :601
+                    if (nd.index_image.empty() && nd.pose.size() == 12 && camera_K_.size() >= (i + 1) * 9) {   // the projector's job, :576-578
+                        float P[12];
+                        if (rvseg_projection_matrix(camera_K_.data() + i * 9, camera_calib_.data() + i * 21 + 9, nd.pose.data(), P) != RVSEG_OK)
+                            throw std::runtime_error("rvseg_projection_matrix failed");
+                        projections.insert(projections.end(), P, P + 12);
+                        projected_slots.push_back(n_images);
+                        index_images.insert(index_images.end(), npix, -1);
+                    } else {
+                        if (nd.index_image.size() < (i + 1) * npix) throw std::runtime_error("index image smaller than n_cameras * H x W");
+                        index_images.insert(index_images.end(), nd.index_image.begin() + (std::ptrdiff_t)(i * npix),
+                                            nd.index_image.begin() + (std::ptrdiff_t)((i + 1) * npix));   // rows y + i*_camera_h, :601
+                    }
                     posteriors.insert(posteriors.end(), q.front().second.begin(), q.front().second.end());
                     q.pop_front();
                     n_images++;
@@ -409,6 +430,11 @@ public:
             }
         }
         if (posteriors.size() != (size_t)n_images * per) throw std::runtime_error("result queue entry of the wrong size");
+        if (!projected_slots.empty()) {   // the queue layer works on host buffers like its neighbours; processMapPosesDevice stays in HBM
+            const std::vector<int32_t> made = projectCloud((int)projected_slots.size(), projections.data(), lmap.cloud_size, lmap.cloud_xyz.data());
+            for (size_t k = 0; k < projected_slots.size(); k++)
+                std::memcpy(index_images.data() + (size_t)projected_slots[k] * npix, made.data() + k * npix, npix * sizeof(int32_t));
+        }
         processMap(lmap.id, n_images, index_images.data(), posteriors.data(), lmap.cloud_size, lmap.cloud_xyz.data(), lmap.cloud_rgb.data());
         return true;
     }
@@ -573,6 +599,28 @@ public:
                                        d_labels_out, nullptr, hip_stream), mc);
     }
 
+    // The projector (segmenter.cpp:234-240, 576-578; the definition is include/rvseg.h's): one 3 x 4 projection matrix per
+    // sub-image (rvseg_projection_matrix), cloud_xyz in the map frame.  Returns n_images x H x W indices, -1 = no point;
+    // zbuffer (optional) receives the winners' depths, +inf = no point.
+    std::vector<int32_t> projectCloud(int n_images, const float* projections, size_t cloud_size, const float* cloud_xyz,
+                                      std::vector<float>* zbuffer = nullptr) {
+        const size_t n = (size_t)(n_images > 0 ? n_images : 0) * (size_t)conf_.width * conf_.height;
+        std::vector<int32_t> index(n, -1);
+        if (zbuffer) zbuffer->assign(n, std::numeric_limits<float>::infinity());
+        rvseg_ctx* mc = map_ctx();
+        check(rvseg_project_cloud(mc, n_images, projections, (int32_t)cloud_size, cloud_xyz, index.data(), zbuffer ? zbuffer->data() : nullptr), mc);
+        return index;
+    }
+
+    // processMapDevice with the index images made in HBM by the projector from one projection matrix per sub-image
+    // (host array, n_images x 12); d_index_out (optional) receives them.
+    void processMapPosesDevice(int n_images, const float* projections, const float* d_posteriors, size_t cloud_size, const float* d_cloud_xyz,
+                               const float* d_cloud_rgb, int8_t* d_labels_out, int32_t* d_index_out, void* hip_stream) {
+        rvseg_ctx* mc = map_ctx();
+        check(rvseg_process_map_poses_device(mc, n_images, projections, d_posteriors, (int32_t)cloud_size, d_cloud_xyz, d_cloud_rgb,
+                                             d_labels_out, nullptr, d_index_out, hip_stream), mc);
+    }
+
     // "Save data for the service based on the map id" (segmenter.cpp:711-713)
     void storeMapResult(int32_t local_map_id, const std::vector<std::vector<unsigned char>>& result_labels) { store_.store(local_map_id, result_labels); }
 
@@ -626,6 +674,7 @@ public:
         rvseg_params p;
         rvseg_params_default(&p);
         p.width = conf_.width; p.height = conf_.height;
+        p.depth_min = conf_.depth_min; p.depth_max = conf_.depth_max;   // the projector's setMinDistance / setMaxDistance (:239-240)
         p.use_dense_crf = conf_.use_dense_crf ? 1 : 0;
         p.dcrf_xyz_kernel = conf_.dcrf_xyz_kernel; p.dcrf_rgb_kernel = conf_.dcrf_rgb_kernel;
         p.dcrf_kernel_weight = conf_.dcrf_kernel_weight; p.dcrf_iterations = conf_.dcrf_iterations;
@@ -684,6 +733,7 @@ private:
     mutable std::mutex frame_mtx_;            // _frame_mtx: image and result queues
     std::mutex cloud_processing_mtx_;         // _cloud_processing_mtx: the local-map queue
     std::vector<float> camera_calib_;         // 21 floats per camera
+    std::vector<float> camera_K_;             // 9 floats per camera (setCameraMatrices), or empty
     std::vector<std::deque<QueuedFrame>> image_queues_;                               // _image_queues
     std::vector<std::deque<std::pair<int, std::vector<float>>>> result_queues_;      // _result_queues
     std::deque<LocalMap> local_map_queue_;                                            // _local_map_queue

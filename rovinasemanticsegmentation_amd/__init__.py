@@ -6,6 +6,7 @@ runtime.  There is no CPU fallback: without the built library the import of `_ca
 without a GPU `Context()` raises.
 """
 from . import _capi as capi  # noqa: F401
+from ._capi import projection_matrix  # noqa: F401
 from .segmenter import (Context, DenseCRF, Evaluator, FeatureExtractor, LocalMapStore, RandomForest,  # noqa: F401
                         RgbLabelConversion, Segmenter, PottsCompatibility, DiagonalCompatibility, MatrixCompatibility,
                         CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL, NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER,
@@ -15,4 +16,4 @@ from . import synthetic  # noqa: F401
 __all__ = ["capi", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
            "RgbLabelConversion", "Evaluator", "PottsCompatibility", "DiagonalCompatibility", "MatrixCompatibility",
            "CONST_KERNEL", "DIAG_KERNEL", "FULL_KERNEL", "NO_NORMALIZATION", "NORMALIZE_BEFORE", "NORMALIZE_AFTER",
-           "NORMALIZE_SYMMETRIC"]
+           "NORMALIZE_SYMMETRIC", "projection_matrix"]

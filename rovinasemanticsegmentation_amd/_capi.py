@@ -46,6 +46,7 @@ SYMBOLS = [
     "rvseg_crf_logistic_unary", "rvseg_crf_logistic_unary_device",
     "rvseg_rectify_depth", "rvseg_rectify_depth_device", "rvseg_external_layers_set",
     "rvseg_segment_external", "rvseg_segment_external_device",
+    "rvseg_project_cloud", "rvseg_project_cloud_device", "rvseg_process_map_poses_device", "rvseg_projection_matrix",
 ]
 
 
@@ -195,6 +196,10 @@ def lib():
     L.rvseg_external_layers_set.argtypes = [vp, i32, vp]
     L.rvseg_segment_external.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp]
     L.rvseg_segment_external_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.rvseg_project_cloud.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.rvseg_project_cloud_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
+    L.rvseg_process_map_poses_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rvseg_projection_matrix.argtypes = [vp, vp, vp, vp]
     # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
     L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
     L.rvseg_debug_live_resources.restype = None
@@ -263,6 +268,25 @@ def crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im):
     assert im.size == W * H * 3
     out = np.empty((W * H, 5), np.float32)
     st = lib().rvseg_crf_features_bilateral(W, H, sx, sy, sr, sg, sb, im.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    return out
+
+
+def projection_matrix(K, calib, pose):
+    """rvseg_projection_matrix (host only): K (3 x 3), calib (the 21 floats of a calibration, or its last 12: R row-major
+    then t, camera -> base link), pose (3 x 4, base link -> map) -> P (3 x 4 float32) of rvseg_project_cloud."""
+    import numpy as np
+    K = np.ascontiguousarray(K, np.float32).reshape(9)
+    calib = np.ascontiguousarray(calib, np.float32).reshape(-1)
+    if calib.size == 21:
+        calib = np.ascontiguousarray(calib[9:])
+    pose = np.ascontiguousarray(pose, np.float32).reshape(-1)
+    if calib.size != 12 or pose.size != 12:
+        raise ValueError("calib: 21 or 12 floats, pose: 12 floats")
+    out = np.empty((3, 4), np.float32)
+    st = lib().rvseg_projection_matrix(K.ctypes.data_as(C.c_void_p), calib.ctypes.data_as(C.c_void_p), pose.ctypes.data_as(C.c_void_p),
+                                       out.ctypes.data_as(C.c_void_p))
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return out

@@ -78,19 +78,9 @@ cloud_features_kernel(const float* __restrict__ xyz, const float* __restrict__ r
     for (int k = 0; k < 3; k++) { f[k] = xyz[i * 3 + k] * kx; f[3 + k] = rgb[i * 3 + k] * kc; }
 }
 
-// buffers of the fusion, owned by the context (no allocation per call once they have grown)
-struct FusionState {
-    DevBuf kin, kout, vin, vout, temp, start, end, bad;
-    DevBuf idx, post, un;          // staging of the host entry point
-    DevBuf map_un, map_feat, map_q, map_lab;   // intermediates of rvseg_process_map_device
-    PinnedBuf h_bad;               // int: pinned copy of the "index beyond cloud_size" flag
-    Event bad_ev;
-    bool bad_pending = false;
-};
-
 // the context's fusion state, created by the first call: the pinned flag and its event first, so that a failure leaves
 // nothing behind and the next call tries again
-static rvseg_status fusion_state(rvseg_ctx* ctx, FusionState** out) {
+rvseg_status fusion_state(rvseg_ctx* ctx, FusionState** out) {
     Pipeline* im = pipeline_of(ctx);
     if (!im->fusion) {
         PinnedBuf h;
@@ -283,34 +273,47 @@ extern "C" rvseg_status rvseg_label_values_device(rvseg_ctx* ctx, const float* d
 // processMapFromQueue for one local map with every buffer in HBM (src/segmenter.cpp:561-682): fusion of
 // the frames' label distributions, then per layer the cloud DenseCRF + thresholded argmax (:628-658)
 // or the no-CRF rule (:660-681).  Intermediates (unaries, 6-D features, marginals) belong to the context.
-extern "C" rvseg_status rvseg_process_map_device(rvseg_ctx* ctx, int32_t n_images, const int32_t* d_index_images,
-                                                 const float* d_posteriors, int32_t cloud_size, const float* d_cloud_xyz,
-                                                 const float* d_cloud_rgb, int8_t* d_labels_out, float* d_unaries_out, void* hip_stream) {
+// The index images are the caller's (d_index_images), or -- with proj, the host array of n_images projection matrices --
+// the projector's (:576-578), written to d_index_out or to context memory.
+static rvseg_status process_map(rvseg_ctx* ctx, int32_t n_images, const float* proj, const int32_t* d_index_images, int32_t* d_index_out,
+                                const float* d_posteriors, int32_t cloud_size, const float* d_cloud_xyz, const float* d_cloud_rgb,
+                                int8_t* d_labels_out, float* d_unaries_out, void* hip_stream) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     if (!ctx->forest_loaded) { ctx->err = "no forest loaded (the layer / class layout comes from the model)"; return RVSEG_ERR_NO_FOREST; }
-    if (n_images < 0 || cloud_size < 0 || !d_labels_out || (n_images > 0 && (!d_index_images || !d_posteriors)) ||
+    if (n_images < 0 || cloud_size < 0 || !d_labels_out || (n_images > 0 && ((!proj && !d_index_images) || !d_posteriors)) ||
         (ctx->params.use_dense_crf && cloud_size > 0 && (!d_cloud_xyz || !d_cloud_rgb))) {
         ctx->err = "bad arguments";
         return RVSEG_ERR_INVALID_ARG;
     }
-    if (cloud_size == 0) return RVSEG_OK;
+    rvseg_status st;
+    if (proj && (st = project_check(ctx, n_images, proj, cloud_size, d_cloud_xyz, proj)) != RVSEG_OK) return st;
+    if (cloud_size == 0 && !(proj && d_index_out)) return RVSEG_OK;
     const DeviceForest& f = ctx->forest;
     FusionLayers fl;
-    rvseg_status st = fusion_layers(ctx, f.n_layers, f.class_counts, fl);
-    if (st != RVSEG_OK) return st;
+    if ((st = fusion_layers(ctx, f.n_layers, f.class_counts, fl)) != RVSEG_OK) return st;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     FusionState* fs;
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
     if ((st = fusion_status(ctx, im, true)) != RVSEG_OK) return st;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    timer_reset(ctx);
+    if (proj) {
+        if (!d_index_out) {
+            if ((st = dev_reserve(ctx, fs->proj_idx, (size_t)n_images * ctx->params.width * ctx->params.height * 4 + 4)) != RVSEG_OK) return st;
+            d_index_out = fs->proj_idx.as<int32_t>();
+        }
+        timer_mark(ctx, "project", s);
+        if ((st = project_enqueue(ctx, fs, n_images, proj, cloud_size, d_cloud_xyz, d_index_out, nullptr, s)) != RVSEG_OK) return st;
+        d_index_images = d_index_out;
+        if (cloud_size == 0) { timer_mark(ctx, "end", s); return RVSEG_OK; }
+    }
     const int S = f.sum_classes;
     float* un = d_unaries_out;
     if (!un) {
         if ((st = dev_reserve(ctx, fs->map_un, (size_t)cloud_size * S * 4)) != RVSEG_OK) return st;
         un = fs->map_un.as<float>();
     }
-    timer_reset(ctx);
     timer_mark(ctx, "fusion", s);
     if ((st = fuse_device(ctx, fs, fl, n_images, d_index_images, d_posteriors, cloud_size, un, s)) != RVSEG_OK) return st;
     const rvseg_params& p = ctx->params;
@@ -332,6 +335,24 @@ extern "C" rvseg_status rvseg_process_map_device(rvseg_ctx* ctx, int32_t n_image
     }
     timer_mark(ctx, "end", s);
     return RVSEG_OK;
+}
+
+extern "C" rvseg_status rvseg_process_map_device(rvseg_ctx* ctx, int32_t n_images, const int32_t* d_index_images,
+                                                 const float* d_posteriors, int32_t cloud_size, const float* d_cloud_xyz,
+                                                 const float* d_cloud_rgb, int8_t* d_labels_out, float* d_unaries_out, void* hip_stream) {
+    return process_map(ctx, n_images, nullptr, d_index_images, nullptr, d_posteriors, cloud_size, d_cloud_xyz, d_cloud_rgb, d_labels_out,
+                       d_unaries_out, hip_stream);
+}
+
+// the same with the index images made by the projector from one projection matrix per sub-image (:234-240, 576-578)
+extern "C" rvseg_status rvseg_process_map_poses_device(rvseg_ctx* ctx, int32_t n_images, const float* proj, const float* d_posteriors,
+                                                       int32_t cloud_size, const float* d_cloud_xyz, const float* d_cloud_rgb,
+                                                       int8_t* d_labels_out, float* d_unaries_out, int32_t* d_index_out, void* hip_stream) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (n_images > 0 && !proj) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    static const float none[12] = {};   // n_images == 0: no matrix is read
+    return process_map(ctx, n_images, proj ? proj : none, nullptr, d_index_out, d_posteriors, cloud_size, d_cloud_xyz, d_cloud_rgb, d_labels_out,
+                       d_unaries_out, hip_stream);
 }
 
 // The label rules on host matrices (the no-CRF branch of processMapFromQueue labels the fused

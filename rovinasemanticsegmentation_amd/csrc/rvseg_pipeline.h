@@ -6,7 +6,20 @@
 namespace rvseg {
 
 struct CrfState;     // rvseg_crf.hip
-struct FusionState;  // rvseg_fusion.hip
+
+// buffers of the fusion and of the projector that feeds it, owned by the context (no allocation per call once they have
+// grown); created by fusion_state, deleted by fusion_state_free (rvseg_fusion.hip)
+struct FusionState {
+    DevBuf kin, kout, vin, vout, temp, start, end, bad;
+    DevBuf idx, post, un;          // staging of the host entry point
+    DevBuf map_un, map_feat, map_q, map_lab;   // intermediates of rvseg_process_map_device
+    // projector (rvseg_project.hip): the key image of one launch group (at most 32 images x W x H uint64), the index
+    // images of rvseg_process_map_poses_device, and the staging of rvseg_project_cloud (cloud in, index + z-buffer out)
+    DevBuf proj_keys, proj_idx, proj_xyz, proj_stage_idx, proj_stage_z;
+    PinnedBuf h_bad;               // int: pinned copy of the "index beyond cloud_size" flag
+    Event bad_ev;
+    bool bad_pending = false;
+};
 
 // Host-buffer entry point (rvseg_segment_frames): two slots of pinned staging + device in/out
 // buffers, so that the H2D copy of chunk k+1 and the D2H copy of chunk k-1 run under the compute of
@@ -76,8 +89,15 @@ rvseg_status segment_host(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames
                           const float* calib, float* posteriors_out, float* marginals_out, int8_t* labels_out);
 
 // rvseg_fusion.hip
+rvseg_status fusion_state(rvseg_ctx* ctx, FusionState** out);   // the context's fusion state, created by the first call
 void fusion_state_free(Pipeline* im);
 rvseg_status fusion_status(rvseg_ctx* ctx, Pipeline* im, bool wait);   // like crf_frames_status, for the index-range flag
+
+// rvseg_project.hip: the projector of include/rvseg.h on device buffers, enqueued on s in launch groups of at most 32
+// images.  proj: host, n_images x 12.  d_zbuffer may be null.  Arguments are checked by the callers (project_check).
+rvseg_status project_check(rvseg_ctx* ctx, int32_t n_images, const float* proj, int32_t N, const void* xyz, const void* index_out);
+rvseg_status project_enqueue(rvseg_ctx* ctx, FusionState* fs, int32_t n_images, const float* proj, int32_t N, const float* d_xyz,
+                             int32_t* d_index, float* d_zbuffer, hipStream_t s);
 
 // rvseg_crf.hip
 void crf_state_free(Pipeline* im);

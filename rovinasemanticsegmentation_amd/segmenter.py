@@ -393,6 +393,42 @@ class Context:
             C.c_void_p(d_cloud_xyz or None), C.c_void_p(d_cloud_rgb or None), C.c_void_p(d_labels),
             C.c_void_p(d_unaries or None), C.c_void_p(stream or None)))
 
+    # ---- projector: index images from poses (src/segmenter.cpp:234-240, 576-578) --------------------------
+    @staticmethod
+    def _projections(projections):
+        P = np.ascontiguousarray(projections, np.float32)
+        if P.size % 12:
+            raise ValueError("projections: n_images x 3 x 4 floats")
+        return P.reshape(-1, 12)
+
+    def project_cloud(self, projections, cloud_xyz, want_zbuffer=True):
+        """rvseg_project_cloud: projections (n, 3, 4) float32 (map frame -> homogeneous pixels), cloud_xyz (N, 3).
+        Returns (index (n, H, W) int32 with -1 = no point, zbuffer (n, H, W) float32 with +inf = no point, or None)."""
+        p = self.params
+        P = self._projections(projections)
+        xyz = np.ascontiguousarray(cloud_xyz, np.float32).reshape(-1, 3)
+        n = P.shape[0]
+        idx = np.full((n, p.height, p.width), -1, np.int32)
+        z = np.full((n, p.height, p.width), np.inf, np.float32) if want_zbuffer else None
+        capi.check(self.h, self.L.rvseg_project_cloud(self.h, n, _ptr(P), xyz.shape[0], _ptr(xyz), _ptr(idx), _ptr(z)))
+        return idx, z
+
+    def project_cloud_device(self, projections, N, d_cloud_xyz, d_index, d_zbuffer=0, stream=0):
+        """rvseg_project_cloud_device: integer device addresses (the matrices stay a host array), enqueues only."""
+        P = self._projections(projections)
+        capi.check(self.h, self.L.rvseg_project_cloud_device(self.h, P.shape[0], _ptr(P), N, C.c_void_p(d_cloud_xyz or None),
+                                                             C.c_void_p(d_index or None), C.c_void_p(d_zbuffer or None),
+                                                             C.c_void_p(stream or None)))
+
+    def process_map_poses_device(self, projections, d_posteriors, cloud_size, d_cloud_xyz, d_cloud_rgb, d_labels, d_unaries=0,
+                                 d_index=0, stream=0):
+        """rvseg_process_map_poses_device: process_map_device with the index images made by the projector."""
+        P = self._projections(projections)
+        capi.check(self.h, self.L.rvseg_process_map_poses_device(
+            self.h, P.shape[0], _ptr(P), C.c_void_p(d_posteriors or None), cloud_size, C.c_void_p(d_cloud_xyz or None),
+            C.c_void_p(d_cloud_rgb or None), C.c_void_p(d_labels or None), C.c_void_p(d_unaries or None), C.c_void_p(d_index or None),
+            C.c_void_p(stream or None)))
+
     def crf_infer_device(self, N, Cn, d, d_unary, unary_is_energy, d_features, potts_w, iterations, d_Q=0, d_map=0,
                          label_mode=capi.LABEL_ARGMAX, unknown_label=0, stream=0):
         capi.check(self.h, self.L.rvseg_crf_infer_device(
@@ -863,12 +899,19 @@ class Segmenter:
         "depth": (n, H, W, 3) float32 (TYPE_32FC3, the rectified xyz image; NaN outside 0.5 .. 15 m, :472)}."""
         return {"rgb": np.ascontiguousarray(color, np.uint8), "depth": self.ctx.rectify_depth(depth, calib, 0.5, 15.0)}
 
-    def processMap(self, index_images, posteriors, cloud_xyz, cloud_rgb, unknown_labels=None, local_map_id=None):
+    def processMap(self, index_images=None, posteriors=None, cloud_xyz=None, cloud_rgb=None, unknown_labels=None, local_map_id=None,
+                   projections=None):
         """The body of processMapFromQueue for one local map (src/segmenter.cpp:561-682): fuse the frames'
         label distributions into per-point unaries through the index images, then per layer either the
         cloud DenseCRF with the thresholded argmax (:628-658) or the no-CRF rule (:660-681).
         cloud_rgb is in [0, 1] like fps_mapper's cloud (:698-700).  With local_map_id the labels are kept
-        for the services (:711-713).  Returns (result_labels, unaries)."""
+        for the services (:711-713).  Returns (result_labels, unaries).
+        projections=P (n_images x 3 x 4) instead of index_images=: the projector makes the index images from one
+        projection matrix per sub-image (:576-578; Context.project_cloud)."""
+        if (index_images is None) == (projections is None):
+            raise RuntimeError("processMap takes either index_images or projections")
+        if posteriors is None or cloud_xyz is None or cloud_rgb is None:
+            raise RuntimeError("processMap needs posteriors, cloud_xyz and cloud_rgb")
         p = self.ctx.params
         cc = self.layer_class_counts
         # the layout comes from the context's model: none (a refused load raises ERR_NO_FOREST here) or another one
@@ -877,6 +920,8 @@ class Segmenter:
         cloud_xyz = np.ascontiguousarray(cloud_xyz, np.float32)
         cloud_rgb = np.ascontiguousarray(cloud_rgb, np.float32)
         n_pts = cloud_xyz.shape[0]
+        if projections is not None:
+            index_images = self.ctx.project_cloud(projections, cloud_xyz, want_zbuffer=False)[0]
         flat = self.ctx.fuse_posteriors(index_images, posteriors, cc, n_pts)
         offs = np.cumsum([0] + [c * n_pts for c in cc])
         unaries = [flat[offs[l]:offs[l + 1]].reshape(n_pts, cc[l]) for l in range(len(cc))]
