@@ -397,7 +397,6 @@ rvseg_status accumulate_device(rvseg_ctx* ctx, int32_t n, const int8_t* d_pred, 
 using namespace rvseg;
 
 // NULL = the context's own stream, as for every other _device entry point
-static hipStream_t device_stream(rvseg_ctx* ctx, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : ctx->stream; }
 
 extern "C" {
 
@@ -434,13 +433,13 @@ rvseg_status rvseg_color_coding_set(rvseg_ctx* ctx, int32_t layer, int32_t n, co
 rvseg_status rvseg_labels_from_rgb_device(rvseg_ctx* ctx, int32_t layer, int32_t n_images, const uint8_t* d_rgb, int8_t* d_labels,
                                           void* hip_stream) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    return convert_device(ctx, false, layer, n_images, d_rgb, d_labels, device_stream(ctx, hip_stream));
+    return convert_device(ctx, false, layer, n_images, d_rgb, d_labels, stream_of(ctx, hip_stream));
 }
 
 rvseg_status rvseg_labels_to_rgb_device(rvseg_ctx* ctx, int32_t layer, int32_t n_images, const int8_t* d_labels, uint8_t* d_rgb,
                                         void* hip_stream) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    return convert_device(ctx, true, layer, n_images, d_labels, d_rgb, device_stream(ctx, hip_stream));
+    return convert_device(ctx, true, layer, n_images, d_labels, d_rgb, stream_of(ctx, hip_stream));
 }
 
 // host variants: staged through the context's stream, max_batch images per round trip
@@ -489,7 +488,7 @@ rvseg_status rvseg_eval_reset(rvseg_ctx* ctx) {
 rvseg_status rvseg_eval_accumulate_device(rvseg_ctx* ctx, int32_t n_frames, const int8_t* d_pred, const void* d_gt, int32_t gt_format,
                                           void* hip_stream) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    return accumulate_device(ctx, n_frames, d_pred, d_gt, gt_format, device_stream(ctx, hip_stream));
+    return accumulate_device(ctx, n_frames, d_pred, d_gt, gt_format, stream_of(ctx, hip_stream));
 }
 
 rvseg_status rvseg_eval_accumulate(rvseg_ctx* ctx, int32_t n_frames, const int8_t* pred, const void* gt, int32_t gt_format) {

@@ -100,7 +100,7 @@ rvseg_status rvseg_gather_frames(rvseg_ctx* ctx, const void* d_local, size_t byt
     if (bytes_per_rank == 0) return RVSEG_OK;
     Rccl& r = rccl();
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = rvseg::stream_of(ctx, hip_stream);
     const int rc = r.Gather(d_local, d_recv, bytes_per_rank, /*ncclInt8*/ 0, root, ctx->comm, s);
     if (rc != 0) return rccl_fail(ctx, "ncclGather", rc);
     return RVSEG_OK;

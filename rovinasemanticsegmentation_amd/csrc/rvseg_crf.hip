@@ -947,7 +947,7 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
     CrfState* cs;
     rvseg_status st = crf_enter(ctx, &cs);
     if (st != RVSEG_OK) return st;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     timer_mark(ctx, "lattice_build", s);
     std::vector<TermPlan> plan;
@@ -987,7 +987,7 @@ rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx* ctx, int32_t N, int32_t 
     if (st != RVSEG_OK) return st;
     CrfState* cs;
     if ((st = crf_enter(ctx, &cs)) != RVSEG_OK) return st;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
     // L is caller memory that may be gone once this returns: its copy is complete before the call returns
     RV_HIP(ctx, hipMemcpyAsync(cs->lmat.p, L, (size_t)C * K * 4, hipMemcpyHostToDevice, s));
@@ -1005,7 +1005,7 @@ rvseg_status rvseg_crf_infer_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || d < 1 || d > 7 || iterations < 0 || !d_unary || !d_features || (!d_Q_out && !d_map_out) ||
         label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     timer_mark(ctx, "lattice_build", s);
     const TermInput in = potts_input(d, d_features, false);

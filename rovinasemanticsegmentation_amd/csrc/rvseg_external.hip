@@ -112,7 +112,7 @@ rvseg_status rvseg_rectify_depth_device(rvseg_ctx* ctx, int32_t n_frames, const 
     if (n_frames == 0) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     Pipeline* im = pipeline_of(ctx);   // the calibration ring only: no frame tables, so no stride rule applies here
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     rvseg_status st = upload_calib(ctx, im, calib, n_frames, s);
     if (st != RVSEG_OK) return st;
     launch_rectify_depth(ctx->params.width, ctx->params.height, n_frames, depth_min, depth_max, d_depth_mm, im->calibA.as<float>(),

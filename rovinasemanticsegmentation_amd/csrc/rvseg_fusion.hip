@@ -198,7 +198,7 @@ extern "C" rvseg_status rvseg_fuse_posteriors_device(rvseg_ctx* ctx, int32_t n_i
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
     if ((st = fusion_status(ctx, im, true)) != RVSEG_OK) return st;   // an unpolled failure of the previous fusion
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     timer_mark(ctx, "fusion", s);
     st = fuse_device(ctx, fs, fl, n_images, d_index_images, d_posteriors, cloud_size, d_unaries_out, s);
@@ -248,7 +248,7 @@ extern "C" rvseg_status rvseg_cloud_features_device(rvseg_ctx* ctx, int32_t N, c
     if (N < 0 || (N > 0 && (!d_xyz || !d_rgb || !d_features_out))) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     if (N == 0) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     cloud_features_kernel<<<dim3((unsigned)(((long long)N + 255) / 256)), dim3(256), 0, s>>>(d_xyz, d_rgb, ctx->params.dcrf_xyz_kernel,
                                                                                              ctx->params.dcrf_rgb_kernel, d_features_out, N);
     RV_LAUNCH_OK(ctx);
@@ -264,7 +264,7 @@ extern "C" rvseg_status rvseg_label_values_device(rvseg_ctx* ctx, const float* d
     }
     if (N == 0) return RVSEG_OK;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     launch_labels(d_values, (size_t)N, C, label_mode, unknown_label, d_labels_out, s);
     RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
@@ -296,7 +296,7 @@ static rvseg_status process_map(rvseg_ctx* ctx, int32_t n_images, const float* p
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
     if ((st = fusion_status(ctx, im, true)) != RVSEG_OK) return st;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     if (proj) {
         if (!d_index_out) {

@@ -158,6 +158,9 @@ rvseg_status dev_alloc(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 // grow-only allocation: reallocates when the buffer is too small
 rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 
+// the stream of a device entry point: the caller's, or the context's own when the caller passes none
+inline hipStream_t stream_of(const rvseg_ctx* ctx, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : ctx->stream; }
+
 // ---- kernels_eval.hip: frees the scoring state (waits for its pending work first) -----------------------------
 void eval_destroy(rvseg_ctx* ctx);
 

@@ -21,15 +21,15 @@ struct FusionState {
     bool bad_pending = false;
 };
 
-// Host-buffer entry point (rvseg_segment_frames): two slots of pinned staging + device in/out
-// buffers, so that the H2D copy of chunk k+1 and the D2H copy of chunk k-1 run under the compute of
-// chunk k (three streams: in, compute, out).
+// Host-buffer entry point (rvseg_segment_frames, rvseg_segment_external): two slots of pinned staging + device buffers
+// per staged channel, so that the H2D copy of chunk k+1 and the D2H copy of chunk k-1 run under the compute of chunk k
+// (three streams: in, compute, out).  A channel is one array that crosses the bus -- three inputs (dist: the external
+// provider's distributions), three outputs; a call reserves only the channels it uses, and no pinned staging for a
+// channel whose caller buffer is page-locked (segment_host).
 struct HostStage {
     static constexpr int SLOTS = 2;
-    PinnedBuf h_rgb[SLOTS], h_depth[SLOTS], h_post[SLOTS], h_marg[SLOTS], h_lab[SLOTS];
-    DevBuf d_rgb[SLOTS], d_depth[SLOTS], d_post[SLOTS], d_marg[SLOTS], d_lab[SLOTS];
-    PinnedBuf h_dist[SLOTS];   // the third input of the external provider's path (rvseg_segment_external)
-    DevBuf d_dist[SLOTS];
+    struct Channel { PinnedBuf h[SLOTS]; DevBuf d[SLOTS]; };
+    Channel rgb, depth, dist, post, marg, lab;
     Stream s_in, s_out;   // created together with the six events (stage_init): s_in set = all of them exist
     Event ev_in[SLOTS], ev_done[SLOTS], ev_out[SLOTS];
 };
@@ -40,7 +40,7 @@ struct Pipeline {
     DevBuf resize_rows;
     UpsampleTables up;
     // per-chunk device buffers (grow-only, sized for up to max_batch frames)
-    DevBuf calibA, lab, lab2, cloud, change, rect, nfeat, low, post, marg, labels, in_rgb, in_depth, dump, valid;
+    DevBuf calibA, lab, lab2, cloud, change, rect, nfeat, low, post, in_rgb, in_depth, dump, valid;
     // pinned staging for the per-frame A = R*Kinv, t.  The device entry point returns without
     // synchronising, so a slot may only be rewritten once the copy that read it has run: a small ring,
     // each slot guarded by an event recorded behind its H2D copy
@@ -57,7 +57,7 @@ struct Pipeline {
     bool bare = false;  // created by a CRF entry point: frame tables not initialised yet
     // the lattice build depends only on the cloud and the colours, not on the forest: it runs on a
     // side stream beside feature extraction + forest evaluation (fork after prep, join before inference)
-    // (created together with timer.side0 / side1 by run_chunk: side set = all of them exist)
+    // (created together with timer.side0 / side1 by side_init: side set = all of them exist)
     Stream side;
     Event ev_fork, ev_join, ev_entry;   // ev_entry: everything before this chunk on the caller's stream
 };

@@ -187,135 +187,143 @@ void timer_mark(rvseg_ctx* ctx, const char* name, hipStream_t s) {
 }
 
 // ---- the frame path for one chunk of at most max_batch frames ----------------------------------
-static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t* d_rgb, const uint16_t* d_depth,
-                              const float* d_calibA, float* d_post, float* d_marg, int8_t* d_labels, hipStream_t s) {
+// element counts per frame of the arrays both drivers chunk: pixels, classes over all layers (of the forest, or of the
+// external provider's layout), layers, and floats of the provider's distributions
+struct FrameSizes { size_t npix, S, L, dist; };
+static FrameSizes frame_sizes(const rvseg_ctx* ctx, const FrameGeom& g, const ExternalInput* ext) {
+    const LayerLayout& lay = ext ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
+    const size_t npix = (size_t)g.W * g.H, S = (size_t)lay.sum_classes;
+    return {npix, S, (size_t)lay.n_layers, ext ? S * (ext->dist_stride > 1 ? (size_t)g.lw * g.lh : npix) : 0};
+}
+
+// the device pointers of one chunk
+struct ChunkIo {
+    const uint8_t* rgb; const uint16_t* depth; const float* calibA;
+    const float* dist; int dist_stride;   // the external provider's distributions; null: features + forest make the posteriors
+    float *post, *marg; int8_t* labels;   // outputs, each optional (post: forest only)
+};
+
+// the build stream and what orders and times it, created by the first chunk that forks the lattice build
+static rvseg_status side_init(rvseg_ctx* ctx, Pipeline* im) {
+    if (im->side) return RVSEG_OK;
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    // priority of the build stream.  Round 1 (build = the longer branch) measured the highest priority ahead,
+    // 13.85 vs 13.98 ms per step; since the feature branch is the longer one (5.2 vs 3.6 ms) the lowest is, by
+    // a little: 13.31 / 13.33 vs 13.37 / 13.42 ms (rvseg_schedule.build_priority_high restores the old choice;
+    // it is read when the stream is created, i.e. before the first frame call of the context)
+    Stream side;
+    Event fork, join, entry, side0, side1;
+    RV_HIP(ctx, stream_create(side, hipStreamNonBlocking, ctx->sched.build_priority_high ? prio_hi : prio_lo));
+    RV_HIP(ctx, event_create(fork, hipEventDisableTiming));
+    RV_HIP(ctx, event_create(join, hipEventDisableTiming));
+    RV_HIP(ctx, event_create(entry, hipEventDisableTiming));
+    RV_HIP(ctx, event_create(side0, hipEventDefault));
+    RV_HIP(ctx, event_create(side1, hipEventDefault));
+    im->ev_fork = std::move(fork);   // all six exist: hand them over
+    im->ev_join = std::move(join);
+    im->ev_entry = std::move(entry);
+    ctx->timer.side0 = std::move(side0);
+    ctx->timer.side1 = std::move(side1);
+    im->side = std::move(side);
+    return RVSEG_OK;
+}
+
+static rvseg_status run_chunk(rvseg_ctx* ctx, Pipeline* im, int n, const ChunkIo& io, hipStream_t s) {
     const FrameGeom& g = im->geom;
     const rvseg_params& p = ctx->params;
-    const DeviceForest& f = ctx->forest;
     const size_t npix = (size_t)g.W * g.H;
+    const LayerLayout& lay = io.dist ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
     rvseg_status st;
-    const bool need_cloud = p.feature_height || p.feature_normal || p.use_dense_crf;
-    if (p.feature_color_patch && (st = dev_reserve(ctx, im->lab, npix * 4 * n)) != RVSEG_OK) return st;
-    const bool use_lab2 = p.feature_color_patch && rf_frames_wants_lab2(f);
-    if (use_lab2 && (st = dev_reserve(ctx, im->lab2, npix * 8 * n + 16)) != RVSEG_OK) return st;
-    if (need_cloud && (st = dev_reserve(ctx, im->cloud, npix * 16 * n)) != RVSEG_OK) return st;
-    if (p.feature_normal) {
-        if ((st = dev_reserve(ctx, im->rect, npix * n)) != RVSEG_OK) return st;
-        if ((st = dev_reserve(ctx, im->change, npix * n)) != RVSEG_OK) return st;
-        if ((st = dev_reserve(ctx, im->nfeat, (size_t)g.lw * g.lh * 4 * n)) != RVSEG_OK) return st;
-    }
-    if ((st = dev_reserve(ctx, im->low, (size_t)g.lw * g.lh * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
-    float* post = d_post;
-    if (!post) {
-        if ((st = dev_reserve(ctx, im->post, npix * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
-        post = im->post.as<float>();
-    }
-    const bool fork_build = p.use_dense_crf && ctx->sched.overlap_build;
-    if (fork_build) {
-        // the build stream first: table and list heads of the new lattice are cleared while prep_kernel runs.  The
-        // lattice's previous user (the last chunk's mean field, a cloud CRF on this context) ran on the caller's
-        // stream: ev_entry, recorded there before anything of this chunk, orders the memsets behind it.
-        if (!im->side) {
-            int prio_lo = 0, prio_hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            // priority of the build stream.  Round 1 (build = the longer branch) measured the highest priority ahead,
-            // 13.85 vs 13.98 ms per step; since the feature branch is the longer one (5.2 vs 3.6 ms) the lowest is, by
-            // a little: 13.31 / 13.33 vs 13.37 / 13.42 ms (rvseg_schedule.build_priority_high restores the old choice;
-            // it is read when the stream is created, i.e. before the first frame call of the context)
-            Stream side;
-            Event fork, join, entry, side0, side1;
-            RV_HIP(ctx, stream_create(side, hipStreamNonBlocking, ctx->sched.build_priority_high ? prio_hi : prio_lo));
-            RV_HIP(ctx, event_create(fork, hipEventDisableTiming));
-            RV_HIP(ctx, event_create(join, hipEventDisableTiming));
-            RV_HIP(ctx, event_create(entry, hipEventDisableTiming));
-            RV_HIP(ctx, event_create(side0, hipEventDefault));
-            RV_HIP(ctx, event_create(side1, hipEventDefault));
-            im->side = std::move(side);
-            im->ev_fork = std::move(fork);
-            im->ev_join = std::move(join);
-            im->ev_entry = std::move(entry);
-            ctx->timer.side0 = std::move(side0);
-            ctx->timer.side1 = std::move(side1);
+    const float* post;     // the chunk's posteriors, n x S x H x W: each provider's block leaves them here
+    bool forked = false;   // the lattice build is already running on the side stream
+    if (io.dist) {
+        // ---- an external provider: its distributions are the posteriors (segmenter.cpp:445-514).  No Lab image, no
+        // change map, no features, no forest.  There is nothing for the lattice build to hide under, so it runs on the
+        // caller's stream without the fork.
+        post = io.dist;   // full resolution: the wire layout is the posterior layout
+        if (io.dist_stride > 1) {
+            // the wire layout at low resolution is the up-sampler's `low` layout ([layer][ly][lx][class] per frame): no repack
+            if ((st = dev_reserve(ctx, im->post, npix * lay.sum_classes * 4 * n)) != RVSEG_OK) return st;
+            timer_mark(ctx, "upsample_pack", s);
+            launch_upsample_pack(g, lay, im->up, io.dist, im->post.as<float>(), n, s);
+            post = im->post.as<float>();
         }
-        RV_HIP(ctx, hipEventRecord(im->ev_entry, s));
-        RV_HIP(ctx, hipStreamWaitEvent(im->side, im->ev_entry, 0));
-        if ((st = crf_frames_build_begin(ctx, im, n, im->side)) != RVSEG_OK) return st;
+        if (p.use_dense_crf) {
+            if ((st = dev_reserve(ctx, im->cloud, npix * 16 * n)) != RVSEG_OK) return st;
+            timer_mark(ctx, "prep", s);
+            launch_prep(g, ctx->lab, io.rgb, io.depth, io.calibA, nullptr, im->cloud.as<float4>(), nullptr, n, s);
+        }
+    } else {
+        // ---- features + forest
+        const DeviceForest& f = ctx->forest;
+        const bool need_cloud = p.feature_height || p.feature_normal || p.use_dense_crf;
+        if (p.feature_color_patch && (st = dev_reserve(ctx, im->lab, npix * 4 * n)) != RVSEG_OK) return st;
+        const bool use_lab2 = p.feature_color_patch && rf_frames_wants_lab2(f);
+        if (use_lab2 && (st = dev_reserve(ctx, im->lab2, npix * 8 * n + 16)) != RVSEG_OK) return st;
+        if (need_cloud && (st = dev_reserve(ctx, im->cloud, npix * 16 * n)) != RVSEG_OK) return st;
+        if (p.feature_normal) {
+            if ((st = dev_reserve(ctx, im->rect, npix * n)) != RVSEG_OK) return st;
+            if ((st = dev_reserve(ctx, im->change, npix * n)) != RVSEG_OK) return st;
+            if ((st = dev_reserve(ctx, im->nfeat, (size_t)g.lw * g.lh * 4 * n)) != RVSEG_OK) return st;
+        }
+        if ((st = dev_reserve(ctx, im->low, (size_t)g.lw * g.lh * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
+        float* out = io.post;
+        if (!out) {
+            if ((st = dev_reserve(ctx, im->post, npix * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
+            out = im->post.as<float>();
+        }
+        const bool fork_build = p.use_dense_crf && ctx->sched.overlap_build;
+        if (fork_build) {
+            // the build stream first: table and list heads of the new lattice are cleared while prep_kernel runs.  The
+            // lattice's previous user (the last chunk's mean field, a cloud CRF on this context) ran on the caller's
+            // stream: ev_entry, recorded there before anything of this chunk, orders the memsets behind it.
+            if ((st = side_init(ctx, im)) != RVSEG_OK) return st;
+            RV_HIP(ctx, hipEventRecord(im->ev_entry, s));
+            RV_HIP(ctx, hipStreamWaitEvent(im->side, im->ev_entry, 0));
+            if ((st = crf_frames_build_begin(ctx, im, n, im->side)) != RVSEG_OK) return st;
+        }
+        timer_mark(ctx, "prep", s);
+        launch_prep(g, ctx->lab, io.rgb, io.depth, io.calibA, p.feature_color_patch ? im->lab.as<uint32_t>() : nullptr,
+                    need_cloud ? im->cloud.as<float4>() : nullptr, p.feature_normal ? im->change.as<uint8_t>() : nullptr, n, s,
+                    use_lab2 ? im->lab2.as<uint2>() : nullptr);
+        if (fork_build) {
+            // fork: the lattice build runs on the side stream while this stream extracts features and walks the forest
+            RV_HIP(ctx, hipEventRecord(im->ev_fork, s));
+            RV_HIP(ctx, hipStreamWaitEvent(im->side, im->ev_fork, 0));
+            RV_HIP(ctx, hipEventRecord(ctx->timer.side0, im->side));
+            if ((st = crf_frames_build(ctx, im, n, io.rgb, im->side)) != RVSEG_OK) { (void)hipStreamSynchronize(im->side); return st; }
+            RV_HIP(ctx, hipEventRecord(ctx->timer.side1, im->side));
+            RV_HIP(ctx, hipEventRecord(im->ev_join, im->side));
+            ctx->timer.side_name = "lattice_build";
+            ctx->timer.side_used = true;
+            forked = true;
+        }
+        if (p.feature_normal) {
+            timer_mark(ctx, "window_map", s);
+            launch_window_map(g, im->cloud.as<float4>(), im->change.as<uint8_t>(), im->rect.as<uint8_t>(), n, s);
+            timer_mark(ctx, "normal_feature", s);
+            launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), n, s);
+        }
+        timer_mark(ctx, "rf_frames", s);
+        launch_rf_frames(g, f, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), io.depth, im->cloud.as<float4>(),
+                         im->nfeat.as<float>(), im->low.as<float>(), n, s, use_lab2 ? im->lab2.as<uint2>() : nullptr);
+        timer_mark(ctx, "upsample_pack", s);
+        launch_upsample_pack(g, f, im->up, im->low.as<float>(), out, n, s);
+        post = out;
     }
-    timer_mark(ctx, "prep", s);
-    launch_prep(g, ctx->lab, d_rgb, d_depth, d_calibA, p.feature_color_patch ? im->lab.as<uint32_t>() : nullptr,
-                need_cloud ? im->cloud.as<float4>() : nullptr, p.feature_normal ? im->change.as<uint8_t>() : nullptr, n, s,
-                use_lab2 ? im->lab2.as<uint2>() : nullptr);
-    bool forked = false;
-    if (fork_build) {
-        // fork: the lattice build runs on the side stream while this stream extracts features and walks the forest
-        RV_HIP(ctx, hipEventRecord(im->ev_fork, s));
-        RV_HIP(ctx, hipStreamWaitEvent(im->side, im->ev_fork, 0));
-        RV_HIP(ctx, hipEventRecord(ctx->timer.side0, im->side));
-        if ((st = crf_frames_build(ctx, im, n, d_rgb, im->side)) != RVSEG_OK) { (void)hipStreamSynchronize(im->side); return st; }
-        RV_HIP(ctx, hipEventRecord(ctx->timer.side1, im->side));
-        RV_HIP(ctx, hipEventRecord(im->ev_join, im->side));
-        ctx->timer.side_name = "lattice_build";
-        ctx->timer.side_used = true;
-        forked = true;
-    }
-    if (p.feature_normal) {
-        timer_mark(ctx, "window_map", s);
-        launch_window_map(g, im->cloud.as<float4>(), im->change.as<uint8_t>(), im->rect.as<uint8_t>(), n, s);
-        timer_mark(ctx, "normal_feature", s);
-        launch_normal_feature(g, im->cloud.as<float4>(), im->rect.as<uint8_t>(), im->nfeat.as<float>(), n, s);
-    }
-    timer_mark(ctx, "rf_frames", s);
-    launch_rf_frames(g, f, im->resize_rows.as<ResizeRow>(), im->lab.as<uint32_t>(), d_depth, im->cloud.as<float4>(),
-                     im->nfeat.as<float>(), im->low.as<float>(), n, s, use_lab2 ? im->lab2.as<uint2>() : nullptr);
-    timer_mark(ctx, "upsample_pack", s);
-    launch_upsample_pack(g, f, im->up, im->low.as<float>(), post, n, s);
+    // ---- both providers: the frame CRF on the posteriors, or their labels
     if (p.use_dense_crf) {
         if (forked) {
             RV_HIP(ctx, hipStreamWaitEvent(s, im->ev_join, 0));   // join
         } else {
             timer_mark(ctx, "lattice_build", s);
-            if ((st = crf_frames_build(ctx, im, n, d_rgb, s)) != RVSEG_OK) return st;
+            if ((st = crf_frames_build(ctx, im, n, io.rgb, s)) != RVSEG_OK) return st;
         }
-        st = crf_frames_infer(ctx, im, f, n, post, d_marg, d_labels, s);
-        if (st != RVSEG_OK) return st;
-    } else if (d_labels) {
+        if ((st = crf_frames_infer(ctx, im, lay, n, post, io.marg, io.labels, s)) != RVSEG_OK) return st;
+    } else if (io.labels) {
         timer_mark(ctx, "labels", s);
-        launch_labels_frames(post, n, (int)npix, f, p.label_mode, p.unknown_label, d_labels, s);
-    }
-    timer_mark(ctx, "end", s);
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// ---- the same for an external provider: its distributions are the posteriors (segmenter.cpp:445-514) -------------
-// No Lab image, no change map, no features, no forest.  There is nothing for the lattice build to hide under, so it runs
-// on the caller's stream without the fork.
-static rvseg_status run_chunk_external(rvseg_ctx* ctx, Pipeline* im, int n, const uint8_t* d_rgb, const uint16_t* d_depth,
-                                       const float* d_calibA, const float* d_dist, int dist_stride, float* d_marg,
-                                       int8_t* d_labels, hipStream_t s) {
-    const FrameGeom& g = im->geom;
-    const rvseg_params& p = ctx->params;
-    const LayerLayout& f = ctx->external;
-    const size_t npix = (size_t)g.W * g.H;
-    rvseg_status st;
-    const float* post = d_dist;   // full resolution: the wire layout is the posterior layout
-    if (dist_stride > 1) {
-        // the wire layout at low resolution is the up-sampler's `low` layout ([layer][ly][lx][class] per frame): no repack
-        if ((st = dev_reserve(ctx, im->post, npix * f.sum_classes * 4 * n)) != RVSEG_OK) return st;
-        timer_mark(ctx, "upsample_pack", s);
-        launch_upsample_pack(g, f, im->up, d_dist, im->post.as<float>(), n, s);
-        post = im->post.as<float>();
-    }
-    if (p.use_dense_crf) {
-        if ((st = dev_reserve(ctx, im->cloud, npix * 16 * n)) != RVSEG_OK) return st;
-        timer_mark(ctx, "prep", s);
-        launch_prep(g, ctx->lab, d_rgb, d_depth, d_calibA, nullptr, im->cloud.as<float4>(), nullptr, n, s);
-        timer_mark(ctx, "lattice_build", s);
-        if ((st = crf_frames_build(ctx, im, n, d_rgb, s)) != RVSEG_OK) return st;
-        if ((st = crf_frames_infer(ctx, im, f, n, post, d_marg, d_labels, s)) != RVSEG_OK) return st;
-    } else if (d_labels) {
-        timer_mark(ctx, "labels", s);
-        launch_labels_frames(post, n, (int)npix, f, p.label_mode, p.unknown_label, d_labels, s);
+        launch_labels_frames(post, n, (int)npix, lay, p.label_mode, p.unknown_label, io.labels, s);
     }
     timer_mark(ctx, "end", s);
     RV_LAUNCH_OK(ctx);
@@ -328,24 +336,18 @@ rvseg_status segment_device(rvseg_ctx* ctx, const ExternalInput* ext, int n_fram
     rvseg_status st = pipeline_init(ctx);
     if (st != RVSEG_OK) return st;
     Pipeline* im = ctx->impl;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     if ((st = upload_calib(ctx, im, calib, n_frames, s)) != RVSEG_OK) return st;
-    const FrameGeom& g = im->geom;
-    const size_t npix = (size_t)g.W * g.H;
-    const LayerLayout& lay = ext ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
-    const size_t S = (size_t)lay.sum_classes, L = (size_t)lay.n_layers;
-    const size_t dist_frame = ext ? S * (ext->dist_stride > 1 ? (size_t)g.lw * g.lh : npix) : 0;
+    const FrameSizes z = frame_sizes(ctx, im->geom, ext);
+    auto from = [](auto* p, size_t off) { return p ? p + off : nullptr; };   // an optional array, `off` elements in
     for (int start = 0; start < n_frames; start += ctx->params.max_batch) {
         const int n = std::min(ctx->params.max_batch, n_frames - start);
-        const uint8_t* c_rgb = d_rgb + (size_t)start * npix * 3;
-        const uint16_t* c_depth = d_depth_mm + (size_t)start * npix;
-        const float* c_calib = im->calibA.as<float>() + (size_t)start * 12;
-        float* c_marg = d_marginals_out ? d_marginals_out + (size_t)start * npix * S : nullptr;
-        int8_t* c_lab = d_labels_out ? d_labels_out + (size_t)start * npix * L : nullptr;
-        if (ext) st = run_chunk_external(ctx, im, n, c_rgb, c_depth, c_calib, ext->dist + (size_t)start * dist_frame, ext->dist_stride, c_marg, c_lab, s);
-        else st = run_chunk(ctx, im, n, c_rgb, c_depth, c_calib, d_posteriors_out ? d_posteriors_out + (size_t)start * npix * S : nullptr, c_marg, c_lab, s);
-        if (st != RVSEG_OK) return st;
+        const size_t px = (size_t)start * z.npix;
+        const ChunkIo io{d_rgb + px * 3, d_depth_mm + px, im->calibA.as<float>() + (size_t)start * 12,
+                         ext ? ext->dist + (size_t)start * z.dist : nullptr, ext ? ext->dist_stride : 0,
+                         from(d_posteriors_out, px * z.S), from(d_marginals_out, px * z.S), from(d_labels_out, px * z.L)};
+        if ((st = run_chunk(ctx, im, n, io, s)) != RVSEG_OK) return st;
     }
     return RVSEG_OK;
 }
@@ -431,6 +433,18 @@ rvseg_status stage_init(rvseg_ctx* ctx, HostStage& hs) {
     return RVSEG_OK;
 }
 
+// one staged channel of one call
+struct Staged {
+    HostStage::Channel* ch;
+    char* host;           // the caller's array
+    size_t frame_bytes;
+    bool out;             // direction: false = host -> device on s_in, true = device -> host on s_out
+    bool pinned;          // the caller's memory is page-locked: the copy engines reach it directly, no staging copy
+    char* caller(size_t frame) const { return host + frame * frame_bytes; }
+    // host end of the DMA of the chunk that starts at `frame`
+    void* dma(int slot, size_t frame) const { return pinned ? (void*)caller(frame) : ch->h[slot].p; }
+};
+
 }  // namespace
 
 rvseg_status rvseg::segment_host(rvseg_ctx* ctx, const ExternalInput* ext, int n_frames, const uint8_t* rgb, const uint16_t* depth_mm,
@@ -441,119 +455,103 @@ rvseg_status rvseg::segment_host(rvseg_ctx* ctx, const ExternalInput* ext, int n
     Pipeline* im = ctx->impl;
     HostStage& hs = im->stage;
     if ((st = stage_init(ctx, hs)) != RVSEG_OK) return st;
-    const FrameGeom& g = im->geom;
-    const size_t npix = (size_t)g.W * g.H;
-    const LayerLayout& lay = ext ? ctx->external : static_cast<const LayerLayout&>(ctx->forest);
-    const size_t S = (size_t)lay.sum_classes, L = (size_t)lay.n_layers;
-    // the external provider's distributions: a third input, staged like the other two
-    const size_t dist_frame = ext ? S * (ext->dist_stride > 1 ? (size_t)g.lw * g.lh : npix) : 0;
-    const bool dist_pinned = ext && is_pinned_host(ext->dist);
-    const bool want_marg = marginals_out && ctx->params.use_dense_crf;
-    // page-locked caller buffers are read / written by the copy engines directly (no staging copy on the host):
-    // the 11 MB of marginals per frame otherwise cross the host memory twice, which bounds the call at ~10 GB/s
-    const bool in_pinned = is_pinned_host(rgb) && is_pinned_host(depth_mm);
-    const bool post_pinned = is_pinned_host(posteriors_out), marg_pinned = want_marg && is_pinned_host(marginals_out),
-               lab_pinned = is_pinned_host(labels_out);
+    const FrameSizes z = frame_sizes(ctx, im->geom, ext);
     hipStream_t s = ctx->stream;
+    // The channels of this call, inputs first (the order of the copies on s_in and on s_out).  Page-locked caller
+    // buffers are read / written by the copy engines directly (no staging copy on the host): the 11 MB of marginals per
+    // frame otherwise cross the host memory twice, which bounds the call at ~10 GB/s
+    std::vector<Staged> act;
+    auto stage = [&](HostStage::Channel& ch, const void* host, size_t frame_bytes, bool out, bool pinned) {
+        if (host) act.push_back({&ch, (char*)host, frame_bytes, out, pinned});
+    };
+    const bool in_pinned = is_pinned_host(rgb) && is_pinned_host(depth_mm);
+    const size_t post_bytes = z.npix * z.S * 4;
+    stage(hs.rgb, rgb, z.npix * 3, false, in_pinned);
+    stage(hs.depth, depth_mm, z.npix * 2, false, in_pinned);
+    if (ext) stage(hs.dist, ext->dist, z.dist * 4, false, is_pinned_host(ext->dist));
+    stage(hs.post, posteriors_out, post_bytes, true, is_pinned_host(posteriors_out));
+    const bool want_marg = marginals_out && ctx->params.use_dense_crf;
+    if (want_marg) stage(hs.marg, marginals_out, post_bytes, true, is_pinned_host(marginals_out));
+    stage(hs.lab, labels_out, z.npix * z.L, true, is_pinned_host(labels_out));
     // chunk size: at most max_batch, and small enough that a call has a few chunks to overlap
     const int chunk = std::max(1, std::min(ctx->params.max_batch, std::max(8, (n_frames + 3) / 4)));
     const int n_chunks = (n_frames + chunk - 1) / chunk;
     auto chunk_n = [&](int c) { return std::min(chunk, n_frames - c * chunk); };
 
-    // copies the outputs of chunk c from its pinned slot into the caller's buffers (after its D2H has run)
-    auto retire = [&](int c) -> rvseg_status {
+    // steps 1-4 of chunk c: stage its inputs, copy them in, compute, copy the outputs back.  RVSEG_ERR_CAPACITY: the
+    // lattice build of chunk c - 1 (or of an earlier call nobody polled) overflowed its hash table -- its status is read
+    // at the start of this chunk's build, and nothing of chunk c has been enqueued past the feature branch
+    auto enqueue_chunk = [&](int c) -> rvseg_status {
         const int slot = c % HostStage::SLOTS, n = chunk_n(c);
         const size_t start = (size_t)c * chunk;
-        RV_HIP(ctx, hipEventSynchronize(hs.ev_out[slot]));
-        if (posteriors_out && !post_pinned) host_copy(posteriors_out + start * npix * S, hs.h_post[slot].p, npix * S * 4 * n);
-        if (want_marg && !marg_pinned) host_copy(marginals_out + start * npix * S, hs.h_marg[slot].p, npix * S * 4 * n);
-        if (labels_out && !lab_pinned) host_copy(labels_out + start * npix * L, hs.h_lab[slot].p, npix * L * n);
-        return RVSEG_OK;
-    };
-    auto drain = [&]() { (void)hipStreamSynchronize(hs.s_in); (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(hs.s_out); };
-
-    int retries = 0;
-    for (int c = 0; c <= n_chunks; c++) {
-        if (c == n_chunks) {
-            // all chunks are enqueued: the status of the last build is the only one nobody has looked at yet
-            RV_HIP(ctx, hipStreamSynchronize(s));
-            st = ctx->params.use_dense_crf ? crf_frames_status(ctx, im, true) : RVSEG_OK;
-            if (st == RVSEG_ERR_CAPACITY && retries++ < 16) { drain(); c = n_chunks - 2; continue; }   // redo the last chunk
-            if (st != RVSEG_OK) { drain(); return st; }
-            if ((st = retire(n_chunks - 1)) != RVSEG_OK) { drain(); return st; }
-            break;
-        }
-        const int slot = c % HostStage::SLOTS, n = chunk_n(c);
-        const size_t start = (size_t)c * chunk;
+        rvseg_status st;
         // staging + device buffers of this slot (grow only; the slot's previous chunk c - 2 has been retired)
-        if ((!in_pinned && ((st = hs.h_rgb[slot].reserve(ctx, npix * 3 * n)) != RVSEG_OK ||
-                            (st = hs.h_depth[slot].reserve(ctx, npix * 2 * n)) != RVSEG_OK)) ||
-            (st = dev_reserve(ctx, hs.d_rgb[slot], npix * 3 * n)) != RVSEG_OK ||
-            (st = dev_reserve(ctx, hs.d_depth[slot], npix * 2 * n)) != RVSEG_OK) { drain(); return st; }
-        if (ext && ((!dist_pinned && (st = hs.h_dist[slot].reserve(ctx, dist_frame * 4 * n)) != RVSEG_OK) ||
-                    (st = dev_reserve(ctx, hs.d_dist[slot], dist_frame * 4 * n)) != RVSEG_OK)) { drain(); return st; }
-        const bool need_post_dev = posteriors_out != nullptr;
-        if (need_post_dev && ((!post_pinned && (st = hs.h_post[slot].reserve(ctx, npix * S * 4 * n)) != RVSEG_OK) ||
-                              (st = dev_reserve(ctx, hs.d_post[slot], npix * S * 4 * n)) != RVSEG_OK)) { drain(); return st; }
-        if (want_marg && ((!marg_pinned && (st = hs.h_marg[slot].reserve(ctx, npix * S * 4 * n)) != RVSEG_OK) ||
-                          (st = dev_reserve(ctx, hs.d_marg[slot], npix * S * 4 * n)) != RVSEG_OK)) { drain(); return st; }
-        if (labels_out && ((!lab_pinned && (st = hs.h_lab[slot].reserve(ctx, npix * L * n)) != RVSEG_OK) ||
-                           (st = dev_reserve(ctx, hs.d_lab[slot], npix * L * n)) != RVSEG_OK)) { drain(); return st; }
+        for (const Staged& u : act)
+            if ((!u.pinned && (st = u.ch->h[slot].reserve(ctx, u.frame_bytes * n)) != RVSEG_OK) ||
+                (st = dev_reserve(ctx, u.ch->d[slot], u.frame_bytes * n)) != RVSEG_OK) return st;
         // 1. caller's pageable buffers -> pinned (host threads; the GPU is busy with chunk c - 1 meanwhile)
-        const void* src_rgb = rgb + start * npix * 3;
-        const void* src_depth = depth_mm + start * npix;
-        if (!in_pinned) {
-            host_copy(hs.h_rgb[slot].p, src_rgb, npix * 3 * n);
-            host_copy(hs.h_depth[slot].p, src_depth, npix * 2 * n);
-            src_rgb = hs.h_rgb[slot].p;
-            src_depth = hs.h_depth[slot].p;
-        }
-        const void* src_dist = ext ? ext->dist + start * dist_frame : nullptr;
-        if (ext && !dist_pinned) {
-            host_copy(hs.h_dist[slot].p, src_dist, dist_frame * 4 * n);
-            src_dist = hs.h_dist[slot].p;
-        }
+        for (const Staged& u : act)
+            if (!u.out && !u.pinned) host_copy(u.ch->h[slot].p, u.caller(start), u.frame_bytes * n);
         // 2. H2D on the input stream, after the compute of chunk c - 2 (the last reader of these device buffers)
         if (c >= HostStage::SLOTS) RV_HIP(ctx, hipStreamWaitEvent(hs.s_in, hs.ev_done[slot], 0));
-        RV_HIP(ctx, hipMemcpyAsync(hs.d_rgb[slot].p, src_rgb, npix * 3 * n, hipMemcpyHostToDevice, hs.s_in));
-        RV_HIP(ctx, hipMemcpyAsync(hs.d_depth[slot].p, src_depth, npix * 2 * n, hipMemcpyHostToDevice, hs.s_in));
-        if (ext) RV_HIP(ctx, hipMemcpyAsync(hs.d_dist[slot].p, src_dist, dist_frame * 4 * n, hipMemcpyHostToDevice, hs.s_in));
+        for (const Staged& u : act)
+            if (!u.out) RV_HIP(ctx, hipMemcpyAsync(u.ch->d[slot].p, u.dma(slot, start), u.frame_bytes * n, hipMemcpyHostToDevice, hs.s_in));
         RV_HIP(ctx, hipEventRecord(hs.ev_in[slot], hs.s_in));
         // 3. compute: after its inputs arrived and after the D2H of chunk c - 2 released the output buffers
         RV_HIP(ctx, hipStreamWaitEvent(s, hs.ev_in[slot], 0));
         if (c >= HostStage::SLOTS) RV_HIP(ctx, hipStreamWaitEvent(s, hs.ev_out[slot], 0));
         timer_reset(ctx);
-        if ((st = upload_calib(ctx, im, calib + start * 21, n, s)) != RVSEG_OK) { drain(); return st; }
-        if (ext)
-            st = run_chunk_external(ctx, im, n, hs.d_rgb[slot].as<uint8_t>(), hs.d_depth[slot].as<uint16_t>(), im->calibA.as<float>(),
-                                    hs.d_dist[slot].as<float>(), ext->dist_stride, want_marg ? hs.d_marg[slot].as<float>() : nullptr,
-                                    labels_out ? hs.d_lab[slot].as<int8_t>() : nullptr, s);
-        else
-            st = run_chunk(ctx, im, n, hs.d_rgb[slot].as<uint8_t>(), hs.d_depth[slot].as<uint16_t>(), im->calibA.as<float>(),
-                           need_post_dev ? hs.d_post[slot].as<float>() : nullptr, want_marg ? hs.d_marg[slot].as<float>() : nullptr,
-                           labels_out ? hs.d_lab[slot].as<int8_t>() : nullptr, s);
-        if (st == RVSEG_ERR_CAPACITY && retries++ < 16) {
-            // the lattice build of chunk c - 1 overflowed its hash table (its status is read at the start of this
-            // chunk's build): nothing of chunk c has been enqueued past the feature branch.  The context has raised
-            // its capacity; take the two chunks again.
-            drain();
-            c = std::max(0, c - 1) - 1;
-            continue;
-        }
-        if (st != RVSEG_OK) { drain(); return st; }
+        if ((st = upload_calib(ctx, im, calib + start * 21, n, s)) != RVSEG_OK) return st;
+        const ChunkIo io{hs.rgb.d[slot].as<uint8_t>(), hs.depth.d[slot].as<uint16_t>(), im->calibA.as<float>(),
+                         ext ? hs.dist.d[slot].as<float>() : nullptr, ext ? ext->dist_stride : 0,
+                         posteriors_out ? hs.post.d[slot].as<float>() : nullptr, want_marg ? hs.marg.d[slot].as<float>() : nullptr,
+                         labels_out ? hs.lab.d[slot].as<int8_t>() : nullptr};
+        if ((st = run_chunk(ctx, im, n, io, s)) != RVSEG_OK) return st;
         RV_HIP(ctx, hipEventRecord(hs.ev_done[slot], s));
         // 4. D2H on the output stream
         RV_HIP(ctx, hipStreamWaitEvent(hs.s_out, hs.ev_done[slot], 0));
-        if (posteriors_out) RV_HIP(ctx, hipMemcpyAsync(post_pinned ? (void*)(posteriors_out + start * npix * S) : hs.h_post[slot].p, hs.d_post[slot].p,
-                                                       npix * S * 4 * n, hipMemcpyDeviceToHost, hs.s_out));
-        if (want_marg) RV_HIP(ctx, hipMemcpyAsync(marg_pinned ? (void*)(marginals_out + start * npix * S) : hs.h_marg[slot].p, hs.d_marg[slot].p,
-                                                  npix * S * 4 * n, hipMemcpyDeviceToHost, hs.s_out));
-        if (labels_out) RV_HIP(ctx, hipMemcpyAsync(lab_pinned ? (void*)(labels_out + start * npix * L) : hs.h_lab[slot].p, hs.d_lab[slot].p,
-                                                   npix * L * n, hipMemcpyDeviceToHost, hs.s_out));
+        for (const Staged& u : act)
+            if (u.out) RV_HIP(ctx, hipMemcpyAsync(u.dma(slot, start), u.ch->d[slot].p, u.frame_bytes * n, hipMemcpyDeviceToHost, hs.s_out));
         RV_HIP(ctx, hipEventRecord(hs.ev_out[slot], hs.s_out));
-        // 5. hand chunk c - 1 to the caller while chunk c runs (its build status was checked by run_chunk above)
-        if (c >= 1 && (st = retire(c - 1)) != RVSEG_OK) { drain(); return st; }
-    }
+        return RVSEG_OK;
+    };
+    // copies the outputs of chunk c from its pinned slot into the caller's buffers (after its D2H has run).  Taking a
+    // chunk twice, as after a retry, copies the same bytes again
+    auto retire = [&](int c) -> rvseg_status {
+        const int slot = c % HostStage::SLOTS, n = chunk_n(c);
+        RV_HIP(ctx, hipEventSynchronize(hs.ev_out[slot]));
+        for (const Staged& u : act)
+            if (u.out && !u.pinned) host_copy(u.caller((size_t)c * chunk), u.ch->h[slot].p, u.frame_bytes * n);
+        return RVSEG_OK;
+    };
+    auto drain = [&]() { (void)hipStreamSynchronize(hs.s_in); (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(hs.s_out); };
+    auto fail = [&](rvseg_status e) { drain(); return e; };
+
+    int next = 0, retries = 0;   // next: the chunk to enqueue; every chunk before next - 1 has been retired
+    // Capacity overflow reported for the build of chunk k (the context has raised its capacity): drain, and enqueue
+    // again from k.  False when st is another status, or the budget of 16 retries per call is spent.
+    auto redo_from = [&](rvseg_status st, int k) {
+        if (st != RVSEG_ERR_CAPACITY || retries++ >= 16) return false;
+        drain();
+        next = k;
+        return true;
+    };
+    // the status of the last build is the only one nobody has looked at once all chunks are enqueued
+    auto last_build = [&]() -> rvseg_status {
+        RV_HIP(ctx, hipStreamSynchronize(s));
+        return ctx->params.use_dense_crf ? crf_frames_status(ctx, im, true) : RVSEG_OK;
+    };
+    do {
+        while (next < n_chunks) {
+            st = enqueue_chunk(next);   // reports the build of chunk next - 1
+            if (redo_from(st, std::max(0, next - 1))) continue;
+            if (st != RVSEG_OK) return fail(st);
+            // hand chunk next - 1 to the caller while chunk next runs
+            if (next >= 1 && (st = retire(next - 1)) != RVSEG_OK) return fail(st);
+            next++;
+        }
+    } while (redo_from(st = last_build(), n_chunks - 1));
+    if (st != RVSEG_OK || (st = retire(n_chunks - 1)) != RVSEG_OK) return fail(st);
     return RVSEG_OK;
 }
 

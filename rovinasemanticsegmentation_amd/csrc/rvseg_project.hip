@@ -110,7 +110,7 @@ extern "C" rvseg_status rvseg_project_cloud_device(rvseg_ctx* ctx, int32_t n_ima
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     FusionState* fs;
     if ((st = fusion_state(ctx, &fs)) != RVSEG_OK) return st;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
     timer_mark(ctx, "project", s);
     st = project_enqueue(ctx, fs, n_images, proj, N, d_cloud_xyz, d_index_out, d_zbuffer_out, s);

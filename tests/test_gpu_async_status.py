@@ -39,6 +39,93 @@ def test_host_entry_recovers_from_hash_overflow(gpu_ctx_factory, oracle):
     assert np.array_equal(out2["marginals"][0], out["marginals"][0])
 
 
+# ---- the two-slot ring of the host entry past both slots, with retries ---------------------------------------------------
+RING = dict(width=W, height=H, use_dense_crf=1, dcrf_iterations=2, label_mode=1, max_batch=1, lattice_capacity_log2=4)
+OUTPUTS = ("posteriors", "marginals", "labels")
+
+
+def _ring_pageable_and_pinned(gpu_ctx_factory, blob, rgb, depth, calib):
+    """One segment_frames call with pageable numpy buffers and one, on a fresh context, with page-locked ones (out=):
+    5 frames with max_batch = 1 are 5 chunks on slots 0, 1, 0, 1, 0.  Returns the two results."""
+    n = rgb.shape[0]
+    ctx = gpu_ctx_factory(**RING)
+    ctx.forest_load(blob)
+    pageable = ctx.segment_frames(rgb, depth, calib)
+    assert ctx.last_schedule()["capacity_log2"] > 4, "no overflow, so no retry"
+    ctx = gpu_ctx_factory(**RING)
+    ctx.forest_load(blob)
+    bufs = ctx.host_buffers(n)
+    try:
+        bufs["rgb"][:] = rgb
+        bufs["depth"][:] = depth
+        for k in OUTPUTS:
+            bufs[k].fill(0)
+        ctx.segment_frames(bufs["rgb"], bufs["depth"], calib, out=bufs)
+        pinned = {k: bufs[k].copy() for k in OUTPUTS}
+    finally:
+        ctx.release_host_buffers(bufs)
+    assert ctx.last_schedule()["capacity_log2"] > 4
+    return pageable, pinned
+
+
+def _assert_ring_equals_oracle(oracle, blob, rgb, depth, calib, pageable, pinned):
+    forest = oracle.Forest(blob)
+    p = oracle.default_params(width=W, height=H, dcrf_iterations=2)
+    for i in range(rgb.shape[0]):
+        post, marg, lab = oracle.segment_frame(p, forest, 1, rgb[i], depth[i], calib, label_mode=1, unknown=[7, 8])
+        for out in (pageable, pinned):
+            assert np.array_equal(out["posteriors"][i], post), i
+            assert np.array_equal(out["marginals"][i], marg), i
+            assert np.array_equal(out["labels"][i].ravel(), lab), i
+    for k in OUTPUTS:
+        assert pageable[k].tobytes() == pinned[k].tobytes(), k
+
+
+def test_host_ring_past_both_slots_with_retries(gpu_ctx_factory, oracle):
+    """Every frame's lattice (~190 vertices) overflows 2^4 and then 2^7 slots: the first retries take chunks 0 and 1
+    again, and chunks 2, 3 and 4 then reuse slots whose events were last recorded before a drain."""
+    blob, rgb, depth, calib = _case(5)
+    pageable, pinned = _ring_pageable_and_pinned(gpu_ctx_factory, blob, rgb, depth, calib)
+    _assert_ring_equals_oracle(oracle, blob, rgb, depth, calib, pageable, pinned)
+
+
+def test_host_ring_overflow_first_reported_at_a_reused_slot(gpu_ctx_factory, oracle):
+    """Overflow reported late: a frame of one colour without any valid depth has 7 lattice vertices (one simplex), which
+    fit 2^4 slots at load factor 1/2.  Two of them lead, so chunks 0 and 1 are clean and retired; chunk 2 (slot 0 again)
+    is the first to overflow, reported while chunk 3 is enqueued: chunks 2 and 3 are taken again after the drain and wait
+    for ev_done / ev_out of their slots' earlier chunks.  A clean chunk follows the retries."""
+    blob, rgb, depth, calib = _case(5)
+    rgb, depth = rgb.copy(), depth.copy()
+    for i in (0, 1, 4):
+        rgb[i] = 128
+        depth[i] = 0
+    p = oracle.default_params(width=W, height=H, dcrf_iterations=2)
+    vertices = [oracle.Lattice(oracle.frame_crf_features(p, rgb[i], oracle.cloud(p, depth[i], calib))).M for i in range(5)]
+    fits = [m <= (1 << 4) // 2 for m in vertices]
+    assert fits == [True, True, False, False, True], vertices
+    pageable, pinned = _ring_pageable_and_pinned(gpu_ctx_factory, blob, rgb, depth, calib)
+    _assert_ring_equals_oracle(oracle, blob, rgb, depth, calib, pageable, pinned)
+
+
+def test_external_host_ring_past_both_slots_with_retries(gpu_ctx_factory):
+    """The same ring with the distributions as third staged input: 5 chunks of one frame at 2^4 slots against a context
+    whose 2^12 slots never overflow (that path is pinned to the oracle by test_gpu_external.py)."""
+    import external_cases as X
+    n, layers, unknown = 5, (8, 9), (7, 8)
+    rgb, depth = X.frames(n, W, H)
+    cal = X.calibs(n, W, H)
+    dist = X.log_softmax_distributions(11, n, layers, H, W)
+    kw = dict(width=W, height=H, use_dense_crf=1, dcrf_iterations=2, label_mode=X.LABEL_CRF, max_batch=1, unknown_label=unknown)
+    outs = {}
+    for cap in (4, 12):
+        ctx = gpu_ctx_factory(lattice_capacity_log2=cap, **kw)
+        ctx.external_layers_set(layers)
+        outs[cap] = ctx.segment_external(rgb, depth, cal, dist, dist_stride=1)
+        assert (ctx.last_schedule()["capacity_log2"] > 4) if cap == 4 else (ctx.last_schedule()["capacity_log2"] == 12)
+    assert outs[4]["marginals"].tobytes() == outs[12]["marginals"].tobytes()
+    assert outs[4]["labels"].tobytes() == outs[12]["labels"].tobytes()
+
+
 def test_device_entry_reports_overflow_through_poll_status(gpu_ctx_factory, oracle):
     torch = pytest.importorskip("torch")
     import rovinasemanticsegmentation_amd as rv
