@@ -354,6 +354,56 @@ rvseg_status rvseg_crf_logistic_unary(rvseg_ctx *ctx, int32_t N, int32_t C, int3
 rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *L,
                                              const float *d_f, float *d_U_out, void *hip_stream);
 
+/* ---- A kept DenseCRF model: stepwise inference, energies, KL divergence (densecrf.h:77-94, densecrf.cpp:141-235).
+ *      rvseg_crf_model_set builds the model of rvseg_crf_infer_terms once -- lattices, normalisers, compatibilities, the
+ *      overflow retry -- and copies the unary into context memory; when it returns, the caller's feature and unary buffers
+ *      are no longer referenced.  The model is the state of the context (no handle): it lives until ANY call builds a
+ *      lattice on the same context (rvseg_crf_infer*, rvseg_lattice_build, the frame and local-map calls, another
+ *      rvseg_crf_model_set).  A model call without a live model returns RVSEG_ERR_INVALID_ARG and rvseg_last_error names
+ *      the call that replaced it.  Host entries take host pointers and synchronise; _device entries take device pointers
+ *      and enqueue on hip_stream (NULL = the context's stream) -- except rvseg_crf_model_set_device, which waits for each
+ *      lattice build like rvseg_crf_infer_terms_device.  Q, out: N x C point-major.
+ *
+ *      Definitions (fp32 with the library's pinned orders unless stated):
+ *        start   Q = expAndNormalize(-U)                                             (startInference, :178-186)
+ *        step    tmp = -U; per term in order tmp -= apply_k(Q); Q = expAndNormalize(tmp)   (stepInference, :187-201)
+ *                start + k steps == rvseg_crf_infer_terms(iterations = k), bit for bit
+ *        apply   pairwise_[term]->apply(out, Q): normalisation scale, lattice filter, compatibility; nothing subtracted
+ *        energy  unary_out[i] = U[i][l_i];  pairwise_out[i] = -0.5f * apply_term(onehot(l))[i][l_i];  a label < 0 or >= C
+ *                gives a zero one-hot row and 0 in both outputs (:149,:172-175);  term == -1: the terms' energies added in
+ *                fp32 from 0.0f, term ascending (:159-162)
+ *        kl      parts[0] = sum q log(max(q, 1e-20f)), parts[1] = sum U q, parts[2 + k] = sum q apply_k(Q): every product,
+ *                the log and every add in double from the fp32 q, U and apply values; KL = the parts added in that order.
+ *                Reduced in a fixed order without atomics: the same input gives the same 64 bits on every call, but the
+ *                order is the device's -- against a host sum the parts agree to ~N C 2^-53 of the sum of their absolute
+ *                element terms.  The reference takes `log` and its fp32 products from libm / Eigen: unpinned, like the rest
+ *                of DenseCRF.
+ *        trace   inference from the start; kl_out[it] = the KL sum of Q after the start (it = 0) and after iteration it, the
+ *                same bits rvseg_crf_model_kl gives for that Q.  Written on the device, read back once at the end. */
+rvseg_status rvseg_crf_model_set(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term *terms,
+                                 const float *unary, int32_t unary_is_energy);
+rvseg_status rvseg_crf_model_set_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term *terms,
+                                        const float *d_unary, int32_t unary_is_energy, void *hip_stream);
+rvseg_status rvseg_crf_model_start(rvseg_ctx *ctx, float *Q_out);
+rvseg_status rvseg_crf_model_start_device(rvseg_ctx *ctx, float *d_Q_out, void *hip_stream);
+/* The caller need not have produced Q with this library. */
+rvseg_status rvseg_crf_model_step(rvseg_ctx *ctx, float *Q_inout, int32_t n_steps);
+rvseg_status rvseg_crf_model_step_device(rvseg_ctx *ctx, float *d_Q_inout, int32_t n_steps, void *hip_stream);
+rvseg_status rvseg_crf_model_apply(rvseg_ctx *ctx, int32_t term, const float *Q_in, float *out);
+rvseg_status rvseg_crf_model_apply_device(rvseg_ctx *ctx, int32_t term, const float *d_Q_in, float *d_out, void *hip_stream);
+/* labels: N int8 (the map_out of an inference fits).  unary_out / pairwise_out: N floats each, either may be NULL. */
+rvseg_status rvseg_crf_model_energy(rvseg_ctx *ctx, const int8_t *labels, int32_t term, float *unary_out, float *pairwise_out);
+rvseg_status rvseg_crf_model_energy_device(rvseg_ctx *ctx, const int8_t *d_labels, int32_t term, float *d_unary_out,
+                                           float *d_pairwise_out, void *hip_stream);
+/* parts: 2 + n_terms doubles (entropy, unary, one per term). */
+rvseg_status rvseg_crf_model_kl(rvseg_ctx *ctx, const float *Q, double *parts);
+rvseg_status rvseg_crf_model_kl_device(rvseg_ctx *ctx, const float *d_Q, double *d_parts, void *hip_stream);
+/* kl_out: iterations + 1 doubles.  map_out (optional): labels of the final Q under label_mode / unknown_label. */
+rvseg_status rvseg_crf_model_trace(rvseg_ctx *ctx, int32_t iterations, float *Q_out, int8_t *map_out, int32_t label_mode,
+                                   int32_t unknown_label, double *kl_out);
+rvseg_status rvseg_crf_model_trace_device(rvseg_ctx *ctx, int32_t iterations, float *d_Q_out, int8_t *d_map_out, int32_t label_mode,
+                                          int32_t unknown_label, double *d_kl_out, void *hip_stream);
+
 /* ---- lattice introspection for parity tests: Permutohedral::init + compute
  *      (densecrf permutohedral.cpp:140-321,596-603).  offsets_out / bary_out: N x (d+1);
  *      keys_out: capacity M_cap x d int16; vertex numbering is arbitrary (results do not depend on

@@ -782,6 +782,17 @@ struct MatrixCompatibility : LabelCompatibility {
     }
 };
 
+// Which DenseCRF object set the model a context keeps (rvseg_crf_model_*): the context has one model and no handle for it,
+// so two objects that share a context take turns.  set: record `owner` (nullptr: nobody).
+inline const void* crf_model_owner(rvseg_ctx* ctx, bool set = false, const void* owner = nullptr) {
+    static std::mutex mtx;
+    static std::map<rvseg_ctx*, const void*> owners;
+    std::lock_guard<std::mutex> lock(mtx);
+    if (set) owners[ctx] = owner;
+    const auto it = owners.find(ctx);
+    return it == owners.end() ? nullptr : it->second;
+}
+
 // DenseCRF (densecrf.h:36-121) over feature matrices the caller builds: N points, M labels.  addPairwiseEnergy with a bare
 // weight is PottsCompatibility; a model of bare weights with NORMALIZE_SYMMETRIC and no kernel parameters runs through
 // rvseg_crf_infer_multi as before, every other model (learned compatibilities, normalisations, kernel parameters, a
@@ -789,9 +800,11 @@ struct MatrixCompatibility : LabelCompatibility {
 class DenseCRF {
 public:
     DenseCRF(rvseg_ctx* ctx, int N, int M) : ctx_(ctx), N_(N), M_(M) {}
-    void setUnaryEnergy(const float* unary /* N x M */) { unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
+    ~DenseCRF() { if (crf_model_owner(ctx_) == this) crf_model_owner(ctx_, true, nullptr); }
+    void setUnaryEnergy(const float* unary /* N x M */) { model_set_ = false; unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
     // LogisticUnaryEnergy (unary.cpp:44-63): L M x K row-major, f N x K point-major
     void setUnaryEnergy(const float* L, const float* f, int K) {
+        model_set_ = false;
         K_ = K;
         logistic_L_.assign(L, L + (size_t)M_ * K);
         logistic_f_.assign(f, f + (size_t)N_ * K);
@@ -815,6 +828,7 @@ public:
     void setUnaryParameters(const std::vector<float>& v) {
         if (logistic_f_.empty()) return;
         check(v.size() == logistic_L_.size());
+        model_set_ = false;
         for (int k = 0; k < K_; k++)
             for (int m = 0; m < M_; m++) logistic_L_[(size_t)m * K_ + k] = v[(size_t)k * M_ + m];
     }
@@ -824,6 +838,7 @@ public:
         return r;
     }
     void setLabelCompatibilityParameters(const std::vector<float>& v) {
+        model_set_ = false;
         size_t i = 0;
         for (auto& t : terms_) {
             const size_t n = t.compat.parameters().size();
@@ -840,6 +855,7 @@ public:
         return r;
     }
     void setKernelParameters(const std::vector<float>& v) {   // pairwise.cpp:140-152
+        model_set_ = false;
         size_t i = 0;
         for (auto& t : terms_) {
             const size_t n = kernelParams(t).size();
@@ -855,13 +871,7 @@ public:
     std::vector<float> inference(int n_iterations, std::vector<int8_t>* map_out = nullptr) {
         const size_t N = (size_t)N_;
         std::vector<float> U;
-        if (!logistic_f_.empty()) {
-            U.resize(N * M_);
-            status(rvseg_crf_logistic_unary(ctx_, N_, M_, K_, logistic_L_.data(), logistic_f_.data(), U.data()));
-        } else if (unary_.empty()) {
-            U.assign(N * M_, 0.f);
-        }
-        const float* u = unary_.empty() ? U.data() : unary_.data();
+        const float* u = unaryEnergyMatrix(U);
         std::vector<float> Q(N * M_);
         if (map_out) map_out->resize(N);
         int8_t* mp = map_out ? map_out->data() : nullptr;
@@ -876,14 +886,7 @@ public:
                                          Q.data(), mp, RVSEG_LABEL_ARGMAX, 0));
             return Q;
         }
-        std::vector<rvseg_crf_term> tt;
-        for (const auto& t : terms_) {
-            rvseg_crf_term r{};
-            r.d = t.d; r.compat = t.compat.kind; r.kernel_type = t.kernel_type; r.normalization = t.normalization;
-            r.features = t.f.data(); r.compat_params = t.compat.params.data();
-            r.kernel_params = t.kp.empty() ? nullptr : t.kp.data();
-            tt.push_back(r);
-        }
+        const std::vector<rvseg_crf_term> tt = termRecords();
         status(rvseg_crf_infer_terms(ctx_, (int32_t)N, M_, (int32_t)tt.size(), tt.data(), u, n_iterations, Q.data(), mp,
                                      RVSEG_LABEL_ARGMAX, 0));
         return Q;
@@ -892,6 +895,54 @@ public:
         std::vector<int8_t> m;
         inference(n_iterations, &m);
         return m;
+    }
+    // ---- stepwise inference, energies and KL divergence (densecrf.h:77-94) on a model the context keeps
+    // (rvseg_crf_model_*): set by the first of these calls, again after any add* / set* call, and again when the context
+    // reports that another call replaced it.  Q: N x M point-major.
+    std::vector<float> startInference() {   // densecrf.cpp:178-186
+        std::vector<float> Q((size_t)N_ * M_);
+        onModel([&] { return rvseg_crf_model_start(ctx_, Q.data()); });
+        return Q;
+    }
+    void stepInference(std::vector<float>& Q, int n_steps = 1) {   // densecrf.cpp:187-201
+        check(Q.size() == (size_t)N_ * M_);
+        onModel([&] { return rvseg_crf_model_step(ctx_, Q.data(), n_steps); });
+    }
+    std::vector<int8_t> currentMap(const std::vector<float>& Q) {   // densecrf.cpp:202-211
+        check(Q.size() == (size_t)N_ * M_);
+        std::vector<int8_t> m((size_t)N_);
+        status(rvseg_label_values(ctx_, Q.data(), N_, M_, RVSEG_LABEL_ARGMAX, 0, m.data()));
+        return m;
+    }
+    std::vector<float> unaryEnergy(const std::vector<int8_t>& l) {   // densecrf.cpp:141-153
+        check(l.size() == (size_t)N_);
+        std::vector<float> r((size_t)N_);
+        onModel([&] { return rvseg_crf_model_energy(ctx_, l.data(), -1, r.data(), nullptr); });
+        return r;
+    }
+    std::vector<float> pairwiseEnergy(const std::vector<int8_t>& l, int term = -1) {   // densecrf.cpp:154-177
+        check(l.size() == (size_t)N_);
+        std::vector<float> r((size_t)N_);
+        onModel([&] { return rvseg_crf_model_energy(ctx_, l.data(), term, nullptr, r.data()); });
+        return r;
+    }
+    // densecrf.cpp:214-235; parts (optional): entropy, unary, one per term -- the value returned is their sum in that order
+    double klDivergence(const std::vector<float>& Q, std::vector<double>* parts = nullptr) {
+        check(Q.size() == (size_t)N_ * M_);
+        std::vector<double> p(2 + terms_.size());
+        onModel([&] { return rvseg_crf_model_kl(ctx_, Q.data(), p.data()); });
+        double kl = 0;
+        for (double v : p) kl += v;
+        if (parts) *parts = p;
+        return kl;
+    }
+    // inference(n) with the KL divergence after the start and after every iteration (kl: n + 1 values)
+    std::vector<float> inferenceTrace(int n_iterations, std::vector<double>& kl, std::vector<int8_t>* map_out = nullptr) {
+        std::vector<float> Q((size_t)N_ * M_);
+        kl.assign((size_t)n_iterations + 1, 0.0);
+        if (map_out) map_out->resize((size_t)N_);
+        onModel([&] { return rvseg_crf_model_trace(ctx_, n_iterations, Q.data(), map_out ? map_out->data() : nullptr, RVSEG_LABEL_ARGMAX, 0, kl.data()); });
+        return Q;
     }
 protected:
     struct Term {
@@ -906,6 +957,7 @@ protected:
         const size_t want = c.kind == RVSEG_COMPAT_POTTS ? 1 : c.kind == RVSEG_COMPAT_DIAGONAL ? (size_t)M_ : (size_t)M_ * M_;
         if (c.params.size() != want || (c.kind == RVSEG_COMPAT_MATRIX && c.M != M_))
             throw std::runtime_error("label compatibility does not match the class count");
+        model_set_ = false;
         Term t;
         t.f.assign(features, features + (size_t)N_ * d);
         t.d = d; t.compat = c; t.kernel_type = kernel_type; t.normalization = normalization; t.bare = bare;
@@ -919,6 +971,47 @@ protected:
         return p;
     }
     static void check(bool ok) { if (!ok) throw std::runtime_error("bad parameter vector"); }
+    // the unary energy as N x M values: the constant one, the logistic one computed on the GPU into U, or zeros in U
+    const float* unaryEnergyMatrix(std::vector<float>& U) {
+        const size_t N = (size_t)N_;
+        if (!logistic_f_.empty()) {
+            U.resize(N * M_);
+            status(rvseg_crf_logistic_unary(ctx_, N_, M_, K_, logistic_L_.data(), logistic_f_.data(), U.data()));
+        } else if (unary_.empty()) {
+            U.assign(N * M_, 0.f);
+        }
+        return unary_.empty() ? U.data() : unary_.data();
+    }
+    std::vector<rvseg_crf_term> termRecords() const {
+        std::vector<rvseg_crf_term> tt;
+        for (const auto& t : terms_) {
+            rvseg_crf_term r{};
+            r.d = t.d; r.compat = t.compat.kind; r.kernel_type = t.kernel_type; r.normalization = t.normalization;
+            r.features = t.f.data(); r.compat_params = t.compat.params.data();
+            r.kernel_params = t.kp.empty() ? nullptr : t.kp.data();
+            tt.push_back(r);
+        }
+        return tt;
+    }
+    // runs a model call, (re)setting the context's model first when this object changed or another call replaced it
+    template <class F>
+    void onModel(F&& call) {
+        for (int attempt = 0;; attempt++) {
+            if (!model_set_ || crf_model_owner(ctx_) != this) {
+                std::vector<float> U;
+                const float* u = unaryEnergyMatrix(U);
+                const std::vector<rvseg_crf_term> tt = termRecords();
+                status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), u, 1));
+                model_set_ = true;
+                crf_model_owner(ctx_, true, this);
+            }
+            const rvseg_status st = call();
+            const bool replaced = st == RVSEG_ERR_INVALID_ARG && std::string(rvseg_last_error(ctx_)).find("DenseCRF model") != std::string::npos;
+            if (!replaced || attempt) { status(st); return; }
+            model_set_ = false;
+        }
+    }
+    bool model_set_ = false;
     void status(rvseg_status st) {
         if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
     }

@@ -47,6 +47,10 @@ SYMBOLS = [
     "rvseg_rectify_depth", "rvseg_rectify_depth_device", "rvseg_external_layers_set",
     "rvseg_segment_external", "rvseg_segment_external_device",
     "rvseg_project_cloud", "rvseg_project_cloud_device", "rvseg_process_map_poses_device", "rvseg_projection_matrix",
+    "rvseg_crf_model_set", "rvseg_crf_model_set_device", "rvseg_crf_model_start", "rvseg_crf_model_start_device",
+    "rvseg_crf_model_step", "rvseg_crf_model_step_device", "rvseg_crf_model_apply", "rvseg_crf_model_apply_device",
+    "rvseg_crf_model_energy", "rvseg_crf_model_energy_device", "rvseg_crf_model_kl", "rvseg_crf_model_kl_device",
+    "rvseg_crf_model_trace", "rvseg_crf_model_trace_device",
 ]
 
 
@@ -191,6 +195,20 @@ def lib():
     L.rvseg_crf_infer_terms_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, i32, vp, vp, i32, i32, vp]
     L.rvseg_crf_logistic_unary.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.rvseg_crf_logistic_unary_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.rvseg_crf_model_set.argtypes = [vp, i32, i32, i32, TP, vp, i32]
+    L.rvseg_crf_model_set_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, vp]
+    L.rvseg_crf_model_start.argtypes = [vp, vp]
+    L.rvseg_crf_model_start_device.argtypes = [vp, vp, vp]
+    L.rvseg_crf_model_step.argtypes = [vp, vp, i32]
+    L.rvseg_crf_model_step_device.argtypes = [vp, vp, i32, vp]
+    L.rvseg_crf_model_apply.argtypes = [vp, i32, vp, vp]
+    L.rvseg_crf_model_apply_device.argtypes = [vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_energy.argtypes = [vp, vp, i32, vp, vp]
+    L.rvseg_crf_model_energy_device.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_kl.argtypes = [vp, vp, vp]
+    L.rvseg_crf_model_kl_device.argtypes = [vp, vp, vp, vp]
+    L.rvseg_crf_model_trace.argtypes = [vp, i32, vp, vp, i32, i32, vp]
+    L.rvseg_crf_model_trace_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp]
     L.rvseg_rectify_depth.argtypes = [vp, i32, vp, vp, f32, f32, vp]
     L.rvseg_rectify_depth_device.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp]
     L.rvseg_external_layers_set.argtypes = [vp, i32, vp]

@@ -9,6 +9,7 @@
 
 #include "device_math.h"
 #include "rvseg_crf.h"
+#include "term_device.h"
 
 namespace rvseg {
 
@@ -128,22 +129,7 @@ slice_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha,
     if (gid >= n_points * C) return;
     const long long p = gid / C;
     const int c = (int)(gid - p * C);
-    const int dp1 = L.d + 1;
-    float acc = 0.0f;
-    for (int j = 0; j < dp1; j++) {
-        const int o = lattice_vertex(L, p, dp1, j);
-        const float bw = L.bary[p * dp1 + j];
-        const float val = values[(size_t)o * C + c];
-        if (SEQ) {
-            const float t = bw * val;
-            const float u = t * alpha;
-            acc += u;
-        } else {
-            const float w = bw * alpha;
-            const float prod = w * val;
-            acc += prod;
-        }
-    }
+    const float acc = term_slice<SEQ>(L, C, values, alpha, p, c);
     if (OUT_MODE == 0) {
         out[gid] = acc;
     } else if (OUT_MODE == 1) {
@@ -534,14 +520,14 @@ void launch_fill_int(int* p, int v, long long n, hipStream_t s) {
 //   t      = sliced (permutohedral.cpp:574-584 / :515-524), times norm[p] when `post` (DenseKernel::filter, pairwise.cpp:77-79)
 //   out[c] = Diagonal: fl(v[c] * t[c])      (labelcompatibility.cpp:66; Potts(w) is Diagonal(-w, .., -w), :47)
 //            Matrix:   sum_c' W[c][c'] * t[c'], from c' = 0 up, separately rounded (:85; W symmetric, :79)
-//   tmp[p][c] -= out[c]                      (densecrf.cpp:126)
+//   tmp[p][c] -= out[c]                      (densecrf.cpp:126); ASSIGN: tmp[p][c] = out[c] (DenseKernel::apply alone)
 // A block stages the compatibility once (C x C floats at most: 16 KB) and walks groups of PB = 256 / C points; thread
 // (lp, c) slices class c of point lp.  A Matrix needs all C sliced values of a point: they meet in an LDS row.  W is
 // read as W[c'][c] (= W[c][c'], symmetric), so the lanes of a wave read consecutive LDS banks.
 // ---------------------------------------------------------------------------------------------
 constexpr int TERM_THREADS = 256;
 
-template <bool SEQ>
+template <bool SEQ, bool ASSIGN>
 __global__ void __launch_bounds__(TERM_THREADS)
 term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float alpha, int post, int matrix,
                    const float* __restrict__ compat, float* __restrict__ tmp, long long n_points) {
@@ -553,27 +539,12 @@ term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float 
     __syncthreads();
     const int PB = TERM_THREADS / C;
     const int lp = threadIdx.x / C, c = threadIdx.x - lp * C;
-    const int dp1 = L.d + 1;
     for (long long p0 = (long long)blockIdx.x * PB; p0 < n_points; p0 += (long long)gridDim.x * PB) {   // block-uniform
         const long long p = p0 + lp;
         const bool live = lp < PB && p < n_points;
         float t = 0.0f;
         if (live) {
-            float acc = 0.0f;
-            for (int j = 0; j < dp1; j++) {
-                const int o = lattice_vertex(L, p, dp1, j);
-                const float bw = L.bary[p * dp1 + j];
-                const float val = values[(size_t)o * C + c];
-                if (SEQ) {
-                    const float q = bw * val;
-                    const float u = q * alpha;
-                    acc += u;
-                } else {
-                    const float w = bw * alpha;
-                    const float prod = w * val;
-                    acc += prod;
-                }
-            }
+            const float acc = term_slice<SEQ>(L, C, values, alpha, p, c);
             t = post ? acc * L.norm[p] : acc;
         }
         if (matrix) {
@@ -581,33 +552,25 @@ term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float 
             __syncthreads();
         }
         if (live) {
-            float out;
-            if (matrix) {
-                const float* r = rows + lp * C;
-                out = wt[c] * r[0];
-                for (int k = 1; k < C; k++) {
-                    const float m = wt[k * C + c] * r[k];
-                    out = out + m;
-                }
-            } else {
-                out = wt[c] * t;
-            }
+            const float out = term_compat(matrix != 0, wt, rows + lp * C, C, c, t);
             const size_t g = (size_t)p * C + c;
-            tmp[g] = tmp[g] - out;
+            tmp[g] = ASSIGN ? out : tmp[g] - out;
         }
         if (matrix) __syncthreads();   // the row is rewritten by the next group
     }
 }
 
 void launch_term_update(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
-                        float* tmp, long long n_points, hipStream_t s) {
+                        float* tmp, long long n_points, hipStream_t s, bool assign) {
     const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
     const int PB = TERM_THREADS / C;
     long long blocks = (n_points + PB - 1) / PB;
     if (blocks > 4096) blocks = 4096;   // each block loads the compatibility once
     const dim3 grid((unsigned)blocks), block(TERM_THREADS);
-    if (seq) term_update_kernel<true><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, tmp, n_points);
-    else term_update_kernel<false><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, tmp, n_points);
+#define RV_TERM(SEQ, ASSIGN) term_update_kernel<SEQ, ASSIGN><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, tmp, n_points)
+    if (seq) { if (assign) RV_TERM(true, true); else RV_TERM(true, false); }
+    else { if (assign) RV_TERM(false, true); else RV_TERM(false, false); }
+#undef RV_TERM
     RV_LAUNCHED("term_update_kernel");
 }
 

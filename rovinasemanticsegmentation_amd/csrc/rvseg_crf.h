@@ -183,13 +183,32 @@ bool launch_softmax_unary(const ValueView& unary, bool negate, int C, int N, con
                           const float* scale, hipStream_t s);
 void launch_softmax(const float* tmp, int C, int N, const ValueView& q, long long n_points, hipStream_t s);
 // one general pairwise term: slice, optional post-scale by L.norm, Diagonal (compat: C floats) or symmetric Matrix (C x C)
-// compatibility, tmp -= result
+// compatibility, tmp -= result (assign: tmp = result, the term's apply on its own)
 void launch_term_update(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
-                        float* tmp, long long n_points, hipStream_t s);
+                        float* tmp, long long n_points, hipStream_t s, bool assign = false);
 // kernel parameters of a term: kind 1 DIAG (d values), 2 FULL (d x d column-major)
 struct KernelParams { float p[49]; };
 void launch_kernel_params(const float* f, int N, int d, int kind, const KernelParams& kp, float* out, hipStream_t s);
 // U (N x C) = f (N x K) times L^T (L: C x K row-major, device)
 void launch_logistic_unary(const float* Lm, const float* f, int N, int C, int K, float* U, hipStream_t s);
+
+
+// ---- kernels_crf_model.hip: energies and KL divergence of a kept model -----------------------------------------------
+// rows[i][c] = 1.0f where c == labels[i], else 0 (a label outside [0, C) gives a zero row: densecrf.cpp:165-169)
+void launch_onehot(const int8_t* labels, long long n, int C, float* rows, hipStream_t s);
+// v = fl(scale * rows[i][labels[i]]), 0 for a label outside [0, C); out[i] = v, or fl(out[i] + v) when accumulate
+void launch_label_gather(const float* rows, const int8_t* labels, long long n, int C, float scale, bool accumulate, float* out, hipStream_t s);
+// The KL passes share one thread layout (256 / C points per block step) and one grid: kl_blocks(C, n) blocks, each of
+// which leaves ONE double per part in partials[part * KL_MAX_BLOCKS + block].
+constexpr int KL_MAX_BLOCKS = 512;
+constexpr int KL_FINAL_THREADS = 256;
+int kl_blocks(int C, long long n_points);
+// parts 0 (entropy, q log max(q, 1e-20f)) and 1 (unary, U q; U = unary_is_energy ? unary : -unary)
+void launch_kl_unary(const float* unary, bool unary_is_energy, const float* Q, int C, long long n_points, double* partials, hipStream_t s);
+// one pairwise part: sum q * a with a the fp32 value of the term's apply, sliced from the term's blurred `values`
+void launch_kl_term(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
+                    const float* Q, long long n_points, double* partial, hipStream_t s);
+// adds each part's partials, index ascending; parts_out (n_parts) / sum_out (1, the parts added in order) may be null
+void launch_kl_final(const double* partials, int n_blocks, int n_parts, double* parts_out, double* sum_out, hipStream_t s);
 
 }  // namespace rvseg

@@ -24,8 +24,33 @@ struct LatticeBufs {
     bool has_csr_nrm = false;   // per-entry normaliser (multi-kernel inference only)
 };
 
+// One pairwise term as the mean field runs it.  Potts, and a Diagonal whose entries are all equal, are the same term
+// (Potts(w) == Diagonal(-w, .., -w) bit for bit).
+struct TermPlan {
+    int norm = RVSEG_NORMALIZE_SYMMETRIC;
+    bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
+    float w = 0.f;
+    bool matrix = false;
+    size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
+};
+
+// The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
+// CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
+struct CrfModel {
+    bool valid = false;
+    int N = 0, C = 0;
+    bool unary_is_energy = true;
+    std::vector<TermPlan> plan;
+    std::string replaced_by;   // the entry whose lattice build ended the model
+    DevBuf unary;              // N x C, as the caller passed it
+    // staging of the host entries and scratch of the energies / the KL passes (never the mean field's tmp)
+    DevBuf q, rows, onehot, labels, vec, partials, kl;
+};
+
 struct CrfState {
     std::vector<LatticeBufs> lat;  // one per pairwise kernel
+    CrfModel model;                // rvseg_crf_model_*
+    const char* entry = "";        // the C-ABI entry at work (crf_enter; the frame and cloud paths name themselves): CrfModel::replaced_by
     // two slots of mean-field scratch: a second label layer's mean field runs beside the first on its own stream
     struct { DevBuf val_a, val_b, tmp, qn; } scratch[2];
     DevBuf q, unary, feat, labels;
@@ -320,11 +345,18 @@ static rvseg_status lattice_clear(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s)
     return RVSEG_OK;
 }
 
+static void model_replaced(CrfState* cs) {
+    if (!cs->model.valid) return;
+    cs->model.valid = false;
+    cs->model.replaced_by = cs->entry;
+}
+
 // norm_kind: the normaliser the term needs (rvseg_norm_kind): SYMMETRIC 1/sqrt(n + 1e-20), BEFORE / AFTER 1/(n + 1e-20),
 // NONE none at all (pairwise.cpp:40-56; the mean norm NO_NORMALIZATION computes is never read in inference)
 static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s,
                                   int norm_kind = RVSEG_NORMALIZE_SYMMETRIC) {
     const LatticeDev& L = b.dev;
+    model_replaced(cs);   // a kept model (rvseg_crf_model_*) ends with any lattice build on its context
     if (!b.cleared) { rvseg_status stc = lattice_clear(ctx, b, s); if (stc != RVSEG_OK) return stc; }
     b.cleared = false;
     const bool trace = ctx->sched.trace >= 2;
@@ -431,21 +463,108 @@ static rvseg_status csr_nrm_before_fork(rvseg_ctx* ctx, CrfState* cs, int n_laye
     return RVSEG_OK;
 }
 
-// One pairwise term as the mean field runs it.  Potts, and a Diagonal whose entries are all equal, are the same term
-// (Potts(w) == Diagonal(-w, .., -w) bit for bit).
-struct TermPlan {
-    int norm = RVSEG_NORMALIZE_SYMMETRIC;
-    bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
-    float w = 0.f;
-    bool matrix = false;
-    size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
-};
-
 // the Potts term of the Segmenter and of rvseg_crf_infer[_multi|_device] (pairwise.cpp:173-178): needs no compatibility table
 static TermPlan potts_term(float w) {
     TermPlan t;
     t.w = w;
     return t;
+}
+
+// DenseKernel::filter (pairwise.cpp:63-80): the input scaled by the normaliser (SYMMETRIC / BEFORE), the output (SYMMETRIC / AFTER)
+static bool term_pre(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_BEFORE; }
+static bool term_post(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_AFTER; }
+
+// What one mean field reads and where it runs: the terms (term k on cs->lat[k]) with their compatibilities d_compat (may
+// be null when every term is uniform with NORMALIZE_SYMMETRIC), the unary, the shape, the stream and the scratch slot
+// (0 / 1; two layers may run side by side on two streams); timed: record stage marks (only one of two concurrent loops
+// may: the marks are a sequence on ONE stream)
+struct MfRun {
+    const std::vector<TermPlan>& plan;
+    const float* d_compat;
+    ValueView unary;
+    bool unary_is_energy;
+    int C, N;
+    long long n_points;
+    hipStream_t s;
+    int slot;
+    bool timed;
+};
+
+// the scratch of the general loop: tmp and the lattice values of the largest term
+static rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
+    rvseg_status st = dev_reserve(ctx, cs->scratch[r.slot].tmp, (size_t)r.n_points * r.C * 4);
+    if (st != RVSEG_OK) return st;
+    long long mb = 0;
+    for (size_t k = 0; k < r.plan.size(); k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
+    return values_reserve(ctx, cs, mb, r.C, r.slot);
+}
+
+// the general loop scales by the normaliser inside the splat: per-entry copy of norm
+static rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
+    for (size_t k = 0; k < r.plan.size(); k++) {
+        rvseg_status st;
+        if (term_pre(r.plan[k]) && (st = ensure_csr_nrm(ctx, cs->lat[k], r.s)) != RVSEG_OK) return st;
+    }
+    return RVSEG_OK;
+}
+
+// Q = expAndNormalize(-U) (densecrf.cpp:120, :178-186) of the general loop (needs mf_scratch)
+static void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q) {
+    float* tmp = cs->scratch[r.slot].tmp.as<float>();
+    if (r.timed) timer_mark(ctx, "softmax", r.s);
+    if (!launch_softmax_unary(r.unary, r.unary_is_energy, r.C, r.N, Q, r.n_points, nullptr, r.s)) {
+        launch_neg_unary(r.unary, r.unary_is_energy, r.C, r.N, tmp, r.n_points, r.s);
+        launch_softmax(tmp, r.C, r.N, Q, r.n_points, r.s);
+    }
+}
+
+// Where a traced step leaves the KL divergence of the Q it starts from: the term passes read the splat and blur the step
+// needs anyway.  partials: [2 + n_terms][KL_MAX_BLOCKS] doubles.
+struct KlTap { double* partials; };
+
+// The entropy and unary parts, and -- when the caller has no blurred values at hand (tap of a step: it has) -- the
+// pairwise parts of Q through a splat and blur of their own.  Q: one dense N x C matrix.
+static void kl_unary_parts(rvseg_ctx* ctx, const MfRun& r, const float* Q, const KlTap& tap) {
+    if (r.timed) timer_mark(ctx, "kl", r.s);
+    launch_kl_unary(r.unary.base, r.unary_is_energy, Q, r.C, r.n_points, tap.partials, r.s);
+}
+static void kl_term_part(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* blurred, const float* Q, const KlTap& tap) {
+    if (r.timed) timer_mark(ctx, "kl", r.s);
+    const TermPlan& t = r.plan[k];
+    launch_kl_term(cs->lat[k].dev, r.C, r.C <= 2, blurred, term_post(t), t.matrix, r.d_compat + t.off, Q, r.n_points,
+                   tap.partials + (size_t)(2 + k) * KL_MAX_BLOCKS, r.s);
+}
+
+// One iteration of the general loop (densecrf.cpp:122-128, stepInference :187-201): tmp = -U, per term splat, blur and
+// slice + compatibility folded into tmp, then Q = expAndNormalize(tmp).  Needs mf_scratch and mf_entry_norms.
+// tap (optional): the KL parts of the incoming Q (a dense N x C matrix then).
+static void mf_step(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q, const KlTap* tap = nullptr) {
+    auto& sc = cs->scratch[r.slot];
+    float* tmp = sc.tmp.as<float>();
+    const int C = r.C, N = r.N;
+    hipStream_t s = r.s;
+    const bool seq = C <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
+    auto mark = [&](const char* name) { if (r.timed) timer_mark(ctx, name, s); };
+    mark("softmax");
+    launch_neg_unary(r.unary, r.unary_is_energy, C, N, tmp, r.n_points, s);
+    if (tap) kl_unary_parts(ctx, r, Q.base, *tap);
+    for (int k = 0; k < (int)r.plan.size(); k++) {
+        const LatticeBufs& b = cs->lat[k];
+        const TermPlan& t = r.plan[k];
+        mark("splat");
+        launch_splat(b.dev, Q, C, term_pre(t) ? 1 : 0, sc.val_a.as<float>(), s, false, b.resident_on ? &b.resident : nullptr, r.slot);
+        mark("blur");
+        float* blurred = launch_blur(b.dev, C, seq, false, sc.val_a.as<float>(), sc.val_b.as<float>(), s);
+        if (tap) kl_term_part(ctx, cs, r, k, blurred, Q.base, *tap);
+        // DenseKernel::filter's output scale + the compatibility folded into tmp (pairwise.cpp:77-80, labelcompatibility.cpp:47-85);
+        // which kernel: DESIGN.md section 4, "Learned models"
+        mark("slice");
+        if (t.uniform && term_post(t)) launch_slice(b.dev, C, seq, 2, blurred, -t.w, tmp, r.n_points, s);
+        else launch_term_update(b.dev, C, seq, blurred, term_post(t), t.matrix, r.d_compat + t.off, tmp, r.n_points, s);
+    }
+    mark("softmax");
+    // expAndNormalize(tmp1) with the row in registers where C has an instantiation (same operations, same bits)
+    if (!launch_softmax_unary(ValueView{tmp, (size_t)N * C, 0}, false, C, N, Q, r.n_points, nullptr, s)) launch_softmax(tmp, C, N, Q, r.n_points, s);
 }
 
 // DenseCRF::inference (densecrf.cpp:115-131) over the terms of `plan`, term k on cs->lat[k]; d_compat: the device copy of
@@ -460,16 +579,12 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<T
     if (labels_done) *labels_done = false;
     rvseg_status st;
     const int n_terms = (int)plan.size();
-    DevBuf &b_tmp = cs->scratch[slot].tmp, &b_qn = cs->scratch[slot].qn, &b_va = cs->scratch[slot].val_a, &b_vb = cs->scratch[slot].val_b;
+    DevBuf &b_qn = cs->scratch[slot].qn, &b_va = cs->scratch[slot].val_a, &b_vb = cs->scratch[slot].val_b;
     auto mark = [&](const char* name) { if (timed) timer_mark(ctx, name, s); };
-    // DenseKernel::filter (pairwise.cpp:63-80): the input scaled by the normaliser (SYMMETRIC / BEFORE), the output (SYMMETRIC / AFTER)
-    auto pre = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_BEFORE; };
-    auto post = [&](int k) { return plan[k].norm == RVSEG_NORMALIZE_SYMMETRIC || plan[k].norm == RVSEG_NORMALIZE_AFTER; };
-    if ((st = dev_reserve(ctx, b_tmp, (size_t)n_points * C * 4)) != RVSEG_OK) return st;
-    long long mb = 0;
-    for (int k = 0; k < n_terms; k++) mb = std::max<long long>(mb, cs->lat[k].dev.m_bound);
-    if ((st = values_reserve(ctx, cs, mb, C, slot)) != RVSEG_OK) return st;
-    float* tmp = b_tmp.as<float>();
+    auto pre = [&](int k) { return term_pre(plan[k]); };
+    auto post = [&](int k) { return term_post(plan[k]); };
+    const MfRun run{plan, d_compat, unary, unary_is_energy, C, N, n_points, s, slot, timed};
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
     const bool seq = C <= 2;   // Permutohedral::compute dispatch, permutohedral.cpp:600-603
     if (n_terms == 1 && iterations > 0 && mf_fused_supported(C)) {
         // Single term with a fused instantiation: splat, blur, then one fused slice + update + softmax pass.  When the
@@ -505,34 +620,9 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<T
         return RVSEG_OK;
     }
     // The general loop: several terms, or a class count without a fused update.
-    mark("softmax");
-    if (!launch_softmax_unary(unary, unary_is_energy, C, N, Q, n_points, nullptr, s)) {
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
-        launch_softmax(tmp, C, N, Q, n_points, s);
-    }
-    // it scales by the normaliser inside the splat: per-entry copy of norm
-    for (int k = 0; k < n_terms; k++)
-        if (pre(k) && (st = ensure_csr_nrm(ctx, cs->lat[k], s)) != RVSEG_OK) return st;
-    for (int it = 0; it < iterations; it++) {
-        mark("softmax");
-        launch_neg_unary(unary, unary_is_energy, C, N, tmp, n_points, s);
-        for (int k = 0; k < n_terms; k++) {
-            const LatticeBufs& b = cs->lat[k];
-            const TermPlan& t = plan[k];
-            mark("splat");
-            launch_splat(b.dev, Q, C, pre(k) ? 1 : 0, b_va.as<float>(), s, false, b.resident_on ? &b.resident : nullptr, slot);
-            mark("blur");
-            float* blurred = launch_blur(b.dev, C, seq, false, b_va.as<float>(), b_vb.as<float>(), s);
-            // DenseKernel::filter's output scale + the compatibility folded into tmp (pairwise.cpp:77-80, labelcompatibility.cpp:47-85);
-            // which kernel: DESIGN.md section 4, "Learned models"
-            mark("slice");
-            if (t.uniform && post(k)) launch_slice(b.dev, C, seq, 2, blurred, -t.w, tmp, n_points, s);
-            else launch_term_update(b.dev, C, seq, blurred, post(k), t.matrix, d_compat + t.off, tmp, n_points, s);
-        }
-        mark("softmax");
-        // expAndNormalize(tmp1) with the row in registers where C has an instantiation (same operations, same bits)
-        if (!launch_softmax_unary(ValueView{tmp, (size_t)N * C, 0}, false, C, N, Q, n_points, nullptr, s)) launch_softmax(tmp, C, N, Q, n_points, s);
-    }
+    mf_start(ctx, cs, run, Q);
+    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
+    for (int it = 0; it < iterations; it++) mf_step(ctx, cs, run, Q);
     RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
 }
@@ -641,6 +731,7 @@ rvseg_status crf_frames_build_begin(rvseg_ctx* ctx, Pipeline* im, int n, hipStre
     // status of the previous asynchronous build (an earlier chunk of this call, or an earlier call whose
     // status nobody polled): its outputs were invalid, so this call must not pass for a clean one
     if ((st = crf_frames_status(ctx, im, true)) != RVSEG_OK) return st;
+    cs->entry = "a frame segmentation call (rvseg_segment_frames / rvseg_segment_external)";
     LatticeBufs& lb = lattice_at(cs, 0);
     if ((st = lattice_prepare(ctx, lb, 6, N, n, false, cs->frame_vertices_seen, true)) != RVSEG_OK) return st;
     return lattice_clear(ctx, lb, s);
@@ -843,6 +934,7 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
     CrfState* cs;
     rvseg_status st = crf_state(ctx, &cs);
     if (st != RVSEG_OK) return st;
+    cs->entry = "a local-map call (rvseg_process_map_device / rvseg_process_map_poses_device)";
     timer_mark(ctx, "lattice_build", s);
     const TermInput cloud = potts_input(6, d_features, false);
     if ((st = build_lattices(ctx, cs, N, 1, &cloud, s)) != RVSEG_OK) return st;
@@ -868,10 +960,13 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
 using namespace rvseg;
 
 // entry of the C-ABI CRF calls: selects the device; they do not need the frame tables (a bare pipeline will do)
-static rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out) {
+// (`entry`: its name, which a kept model that it replaces reports)
+static rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    return crf_state(ctx, cs_out);
+    const rvseg_status st = crf_state(ctx, cs_out);
+    if (st == RVSEG_OK) (*cs_out)->entry = entry;
+    return st;
 }
 
 extern "C" {
@@ -880,7 +975,7 @@ rvseg_status rvseg_crf_infer_multi(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
                                    const float* const* features, const float* ws, const float* unary_energy,
                                    int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label) {
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || n_kernels < 0 || n_kernels > 8 || iterations < 0 || !unary_energy || !Q_out ||
         (n_kernels > 0 && (!ds || !features || !ws)) || label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
@@ -930,7 +1025,7 @@ rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t
     if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !unary_energy || !Q_out || label_mode < 0 ||
         label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     std::vector<TermPlan> plan;
     if ((st = terms_prepare(ctx, cs, N, C, n_terms, terms, true, plan, ctx->stream)) != RVSEG_OK) return st;
@@ -945,7 +1040,7 @@ rvseg_status rvseg_crf_infer_terms_device(rvseg_ctx* ctx, int32_t N, int32_t C, 
     if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || iterations < 0 || !d_unary || (!d_Q_out && !d_map_out) ||
         label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     hipStream_t s = stream_of(ctx, hip_stream);
     timer_reset(ctx);
@@ -966,7 +1061,7 @@ rvseg_status rvseg_crf_logistic_unary(rvseg_ctx* ctx, int32_t N, int32_t C, int3
     rvseg_status st = logistic_args(ctx, N, C, K, L, f, U_out);
     if (st != RVSEG_OK) return st;
     CrfState* cs;
-    if ((st = crf_enter(ctx, &cs)) != RVSEG_OK) return st;
+    if ((st = crf_enter(ctx, &cs, __func__)) != RVSEG_OK) return st;
     hipStream_t s = ctx->stream;
     if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
     if ((st = dev_reserve(ctx, cs->feat, (size_t)N * K * 4)) != RVSEG_OK) return st;
@@ -986,7 +1081,7 @@ rvseg_status rvseg_crf_logistic_unary_device(rvseg_ctx* ctx, int32_t N, int32_t 
     rvseg_status st = logistic_args(ctx, N, C, K, L, d_f, d_U_out);
     if (st != RVSEG_OK) return st;
     CrfState* cs;
-    if ((st = crf_enter(ctx, &cs)) != RVSEG_OK) return st;
+    if ((st = crf_enter(ctx, &cs, __func__)) != RVSEG_OK) return st;
     hipStream_t s = stream_of(ctx, hip_stream);
     if ((st = dev_reserve(ctx, cs->lmat, (size_t)C * K * 4)) != RVSEG_OK) return st;
     // L is caller memory that may be gone once this returns: its copy is complete before the call returns
@@ -1001,7 +1096,7 @@ rvseg_status rvseg_crf_infer_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_
                                     const float* d_features, float potts_w, int32_t iterations, float* d_Q_out, int8_t* d_map_out,
                                     int32_t label_mode, int32_t unknown_label, void* hip_stream) {
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     if (N <= 0 || C <= 0 || C > 64 || d < 1 || d > 7 || iterations < 0 || !d_unary || !d_features || (!d_Q_out && !d_map_out) ||
         label_mode < 0 || label_mode > 3) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
@@ -1025,7 +1120,7 @@ rvseg_status rvseg_crf_infer(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t d, co
 rvseg_status rvseg_lattice_build(rvseg_ctx* ctx, const float* features, int32_t N, int32_t d, int32_t* offsets_out,
                                  float* bary_out, int16_t* keys_out, int32_t keys_capacity, int32_t* M_out) {
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     if (!features || N <= 0 || !M_out) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
     hipStream_t s = ctx->stream;
@@ -1052,7 +1147,7 @@ rvseg_status rvseg_lattice_build(rvseg_ctx* ctx, const float* features, int32_t 
 rvseg_status rvseg_lattice_neighbours(rvseg_ctx* ctx, int32_t* n1_out, int32_t* n2_out, uint32_t* csr_point,
                                       uint32_t* vstart, uint32_t* vend) {
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     if (cs->lat.empty() || !cs->lat[0].built || cs->lat[0].dev.n_frames != 1) { ctx->err = "no lattice built on this context"; return RVSEG_ERR_INVALID_ARG; }
     LatticeBufs& lb = cs->lat[0];
@@ -1106,7 +1201,7 @@ rvseg_status rvseg_last_schedule(rvseg_ctx* ctx, rvseg_schedule_info* out) {
 
 rvseg_status rvseg_lattice_filter(rvseg_ctx* ctx, const float* in, int32_t C, float* out) {
     CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs);
+    rvseg_status st = crf_enter(ctx, &cs, __func__);
     if (st != RVSEG_OK) return st;
     if (cs->lat.empty() || !cs->lat[0].built || cs->lat[0].dev.n_frames != 1) { ctx->err = "no lattice built on this context"; return RVSEG_ERR_INVALID_ARG; }
     if (!in || !out || C <= 0 || C > 64) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
@@ -1129,5 +1224,359 @@ rvseg_status rvseg_lattice_filter(rvseg_ctx* ctx, const float* in, int32_t C, fl
     RV_HIP(ctx, hipStreamSynchronize(s));
     return RVSEG_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// A kept DenseCRF model (rvseg_crf_model_*): the state of the context, valid until its next lattice build.  Each call
+// has one body on device pointers (model_*_on); the host entry stages through CrfModel's buffers and synchronises, the
+// _device entry enqueues on the caller's stream.
+// ---------------------------------------------------------------------------------------------
+static rvseg_status model_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    rvseg_status st = crf_enter(ctx, cs_out, entry);
+    if (st != RVSEG_OK) return st;
+    const CrfModel& m = (*cs_out)->model;
+    if (!m.valid) {
+        ctx->err = m.replaced_by.empty() ? std::string("no DenseCRF model on this context (rvseg_crf_model_set has not succeeded)")
+                                         : "the DenseCRF model of this context was replaced by " + m.replaced_by + ": call rvseg_crf_model_set again";
+        return RVSEG_ERR_INVALID_ARG;
+    }
+    return RVSEG_OK;
+}
+
+static MfRun model_run(CrfState* cs, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    return MfRun{m.plan, cs->compat.as<float>(), ValueView{m.unary.as<float>(), (size_t)m.N * m.C, 0}, m.unary_is_energy, m.C, m.N, m.N, s, 0, timed};
+}
+
+static ValueView model_view(const CrfModel& m, const float* q) { return ValueView{const_cast<float*>(q), (size_t)m.N * m.C, 0}; }
+
+static rvseg_status model_set_on(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
+                                 int32_t unary_is_energy, bool on_host, void* hip_stream, const char* entry) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || !unary) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    CrfState* cs;
+    rvseg_status st = crf_enter(ctx, &cs, entry);
+    if (st != RVSEG_OK) return st;
+    hipStream_t s = on_host ? (hipStream_t)ctx->stream : stream_of(ctx, hip_stream);
+    CrfModel& m = cs->model;
+    model_replaced(cs);   // (also a model of no terms, which builds no lattice; a failure below leaves no model)
+    m.replaced_by = entry;
+    const size_t tot = (size_t)N * C;
+    if ((st = dev_reserve(ctx, m.unary, tot * 4)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, tot * 4, on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if ((st = terms_prepare(ctx, cs, N, C, n_terms, terms, on_host, m.plan, s)) != RVSEG_OK) return st;
+    // every lattice build has waited for the stream; a model without terms waits here: the caller's buffers are free
+    if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(s));
+    m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
+    m.valid = true;
+    return RVSEG_OK;
+}
+
+static rvseg_status model_start_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, hipStream_t s, bool timed) {
+    const MfRun run = model_run(cs, s, timed);
+    rvseg_status st = mf_scratch(ctx, cs, run);
+    if (st != RVSEG_OK) return st;
+    mf_start(ctx, cs, run, model_view(cs->model, d_Q));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+static rvseg_status model_step_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, int n_steps, hipStream_t s, bool timed) {
+    const MfRun run = model_run(cs, s, timed);
+    rvseg_status st;
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
+    for (int it = 0; it < n_steps; it++) mf_step(ctx, cs, run, model_view(cs->model, d_Q));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// pairwise_[term]->apply(out, Q) (pairwise.cpp:63-80 + the compatibility): needs mf_scratch
+static rvseg_status model_apply_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, float* d_out) {
+    LatticeBufs& b = cs->lat[k];
+    const TermPlan& t = r.plan[k];
+    rvseg_status st;
+    if (term_pre(t) && (st = ensure_csr_nrm(ctx, b, r.s)) != RVSEG_OK) return st;
+    auto& sc = cs->scratch[r.slot];
+    const bool seq = r.C <= 2;
+    launch_splat(b.dev, model_view(cs->model, d_in), r.C, term_pre(t) ? 1 : 0, sc.val_a.as<float>(), r.s);
+    float* blurred = launch_blur(b.dev, r.C, seq, false, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+    launch_term_update(b.dev, r.C, seq, blurred, term_post(t), t.matrix, r.d_compat + t.off, d_out, r.n_points, r.s, true);
+    return RVSEG_OK;
+}
+
+static rvseg_status model_term_arg(rvseg_ctx* ctx, const CrfModel& m, int term, int lowest) {
+    if (term >= lowest && term < (int)m.plan.size()) return RVSEG_OK;
+    ctx->err = "no such term in the DenseCRF model";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+static rvseg_status model_apply_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_in, float* d_out, hipStream_t s) {
+    const MfRun run = model_run(cs, s, false);
+    rvseg_status st;
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+    if ((st = model_apply_term(ctx, cs, run, term, d_in, d_out)) != RVSEG_OK) return st;
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// DenseCRF::unaryEnergy / pairwiseEnergy (densecrf.cpp:141-177); term == -1: the terms' energies added in fp32 from 0.0f, ascending
+static rvseg_status model_energy_on(rvseg_ctx* ctx, CrfState* cs, const int8_t* d_labels, int term, float* d_unary_out, float* d_pairwise_out,
+                                    hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    rvseg_status st;
+    if (d_unary_out) launch_label_gather(m.unary.as<float>(), d_labels, m.N, m.C, m.unary_is_energy ? 1.0f : -1.0f, false, d_unary_out, s);
+    if (d_pairwise_out) {
+        const size_t tot = (size_t)m.N * m.C;
+        if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+        if ((st = dev_reserve(ctx, m.onehot, tot * 4)) != RVSEG_OK) return st;
+        if ((st = dev_reserve(ctx, m.rows, tot * 4)) != RVSEG_OK) return st;
+        if (term < 0) RV_HIP(ctx, hipMemsetAsync(d_pairwise_out, 0, (size_t)m.N * 4, s));
+        launch_onehot(d_labels, m.N, m.C, m.onehot.as<float>(), s);
+        for (int k = term < 0 ? 0 : term; k < (term < 0 ? (int)m.plan.size() : term + 1); k++) {
+            if ((st = model_apply_term(ctx, cs, run, k, m.onehot.as<float>(), m.rows.as<float>())) != RVSEG_OK) return st;
+            launch_label_gather(m.rows.as<float>(), d_labels, m.N, m.C, -0.5f, term < 0, d_pairwise_out, s);
+        }
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// the KL parts of a Q nobody is about to step: a splat and blur per term of their own.  Needs mf_scratch, mf_entry_norms
+// and CrfModel::partials.
+static void model_kl_parts(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const float* d_Q, const KlTap& tap) {
+    auto& sc = cs->scratch[r.slot];
+    kl_unary_parts(ctx, r, d_Q, tap);
+    for (int k = 0; k < (int)r.plan.size(); k++) {
+        const LatticeBufs& b = cs->lat[k];
+        if (r.timed) timer_mark(ctx, "splat", r.s);
+        launch_splat(b.dev, model_view(cs->model, d_Q), r.C, term_pre(r.plan[k]) ? 1 : 0, sc.val_a.as<float>(), r.s);
+        if (r.timed) timer_mark(ctx, "blur", r.s);
+        float* blurred = launch_blur(b.dev, r.C, r.C <= 2, false, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+        kl_term_part(ctx, cs, r, k, blurred, d_Q, tap);
+    }
+}
+
+static rvseg_status model_kl_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& run) {
+    rvseg_status st;
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
+    return dev_reserve(ctx, cs->model.partials, (size_t)10 * KL_MAX_BLOCKS * sizeof(double));
+}
+
+static rvseg_status model_kl_on(rvseg_ctx* ctx, CrfState* cs, const float* d_Q, double* d_parts, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, timed);
+    rvseg_status st = model_kl_scratch(ctx, cs, run);
+    if (st != RVSEG_OK) return st;
+    const KlTap tap{m.partials.as<double>()};
+    model_kl_parts(ctx, cs, run, d_Q, tap);
+    launch_kl_final(tap.partials, kl_blocks(m.C, m.N), 2 + (int)m.plan.size(), d_parts, nullptr, s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// inference from the start with the KL divergence after the start and after every iteration: d_kl[0 .. iterations].  The
+// KL of the Q an iteration starts from rides on that iteration's splat and blur (KlTap); only the last Q pays for a filter.
+static rvseg_status model_trace_on(rvseg_ctx* ctx, CrfState* cs, int iterations, float* d_Q, int8_t* d_map, int label_mode, int unknown_label,
+                                   double* d_kl, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, timed);
+    rvseg_status st = model_kl_scratch(ctx, cs, run);
+    if (st != RVSEG_OK) return st;
+    const KlTap tap{m.partials.as<double>()};
+    const int blocks = kl_blocks(m.C, m.N), parts = 2 + (int)m.plan.size();
+    const ValueView Q = model_view(m, d_Q);
+    mf_start(ctx, cs, run, Q);
+    for (int it = 0; it < iterations; it++) {
+        mf_step(ctx, cs, run, Q, &tap);
+        launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + it, s);
+    }
+    model_kl_parts(ctx, cs, run, d_Q, tap);
+    launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + iterations, s);
+    if (d_map) {
+        if (timed) timer_mark(ctx, "labels", s);
+        launch_labels(d_Q, (size_t)m.N, m.C, label_mode, unknown_label, d_map, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+#define RV_TRY(call) do { const rvseg_status st_ = (call); if (st_ != RVSEG_OK) return st_; } while (0)
+#define RV_MODEL_ARGS(ok) do { if (!(ok)) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; } } while (0)
+
+rvseg_status rvseg_crf_model_set(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
+                                 int32_t unary_is_energy) {
+    return model_set_on(ctx, N, C, n_terms, terms, unary, unary_is_energy, true, nullptr, __func__);
+}
+
+rvseg_status rvseg_crf_model_set_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
+                                        const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
+    return model_set_on(ctx, N, C, n_terms, terms, d_unary, unary_is_energy, false, hip_stream, __func__);
+}
+
+rvseg_status rvseg_crf_model_start(rvseg_ctx* ctx, float* Q_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(Q_out);
+    CrfModel& m = cs->model;
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(model_start_on(ctx, cs, m.q.as<float>(), ctx->stream, false));
+    RV_HIP(ctx, hipMemcpyAsync(Q_out, m.q.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_start_device(rvseg_ctx* ctx, float* d_Q_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_Q_out);
+    hipStream_t s = stream_of(ctx, hip_stream);
+    timer_reset(ctx);
+    RV_TRY(model_start_on(ctx, cs, d_Q_out, s, true));
+    timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_step(rvseg_ctx* ctx, float* Q_inout, int32_t n_steps) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(Q_inout && n_steps >= 0);
+    CrfModel& m = cs->model;
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q_inout, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RV_TRY(model_step_on(ctx, cs, m.q.as<float>(), n_steps, ctx->stream, false));
+    RV_HIP(ctx, hipMemcpyAsync(Q_inout, m.q.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_step_device(rvseg_ctx* ctx, float* d_Q_inout, int32_t n_steps, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_Q_inout && n_steps >= 0);
+    hipStream_t s = stream_of(ctx, hip_stream);
+    timer_reset(ctx);
+    RV_TRY(model_step_on(ctx, cs, d_Q_inout, n_steps, s, true));
+    timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_apply(rvseg_ctx* ctx, int32_t term, const float* Q_in, float* out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(Q_in && out);
+    CrfModel& m = cs->model;
+    RV_TRY(model_term_arg(ctx, m, term, 0));
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(dev_reserve(ctx, m.rows, bytes));
+    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q_in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RV_TRY(model_apply_on(ctx, cs, term, m.q.as<float>(), m.rows.as<float>(), ctx->stream));
+    RV_HIP(ctx, hipMemcpyAsync(out, m.rows.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_apply_device(rvseg_ctx* ctx, int32_t term, const float* d_Q_in, float* d_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_Q_in && d_out);
+    RV_TRY(model_term_arg(ctx, cs->model, term, 0));
+    return model_apply_on(ctx, cs, term, d_Q_in, d_out, stream_of(ctx, hip_stream));
+}
+
+rvseg_status rvseg_crf_model_energy(rvseg_ctx* ctx, const int8_t* labels, int32_t term, float* unary_out, float* pairwise_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(labels && (unary_out || pairwise_out));
+    CrfModel& m = cs->model;
+    if (pairwise_out) RV_TRY(model_term_arg(ctx, m, term, -1));
+    hipStream_t s = ctx->stream;
+    const size_t N = (size_t)m.N;
+    RV_TRY(dev_reserve(ctx, m.labels, N));
+    RV_TRY(dev_reserve(ctx, m.vec, 2 * N * 4));
+    RV_HIP(ctx, hipMemcpyAsync(m.labels.p, labels, N, hipMemcpyHostToDevice, s));
+    float* d_u = m.vec.as<float>();
+    float* d_p = d_u + N;
+    RV_TRY(model_energy_on(ctx, cs, m.labels.as<int8_t>(), term, unary_out ? d_u : nullptr, pairwise_out ? d_p : nullptr, s));
+    if (unary_out) RV_HIP(ctx, hipMemcpyAsync(unary_out, d_u, N * 4, hipMemcpyDeviceToHost, s));
+    if (pairwise_out) RV_HIP(ctx, hipMemcpyAsync(pairwise_out, d_p, N * 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_energy_device(rvseg_ctx* ctx, const int8_t* d_labels, int32_t term, float* d_unary_out, float* d_pairwise_out,
+                                           void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_labels && (d_unary_out || d_pairwise_out));
+    if (d_pairwise_out) RV_TRY(model_term_arg(ctx, cs->model, term, -1));
+    return model_energy_on(ctx, cs, d_labels, term, d_unary_out, d_pairwise_out, stream_of(ctx, hip_stream));
+}
+
+rvseg_status rvseg_crf_model_kl(rvseg_ctx* ctx, const float* Q, double* parts) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(Q && parts);
+    CrfModel& m = cs->model;
+    hipStream_t s = ctx->stream;
+    const size_t bytes = (size_t)m.N * m.C * 4, n_parts = 2 + m.plan.size();
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(dev_reserve(ctx, m.kl, n_parts * sizeof(double)));
+    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q, bytes, hipMemcpyHostToDevice, s));
+    RV_TRY(model_kl_on(ctx, cs, m.q.as<float>(), m.kl.as<double>(), s, false));
+    RV_HIP(ctx, hipMemcpyAsync(parts, m.kl.p, n_parts * sizeof(double), hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_kl_device(rvseg_ctx* ctx, const float* d_Q, double* d_parts, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_Q && d_parts);
+    hipStream_t s = stream_of(ctx, hip_stream);
+    timer_reset(ctx);
+    RV_TRY(model_kl_on(ctx, cs, d_Q, d_parts, s, true));
+    timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_trace(rvseg_ctx* ctx, int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label,
+                                   double* kl_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(iterations >= 0 && Q_out && kl_out && label_mode >= 0 && label_mode <= 3);
+    CrfModel& m = cs->model;
+    hipStream_t s = ctx->stream;
+    const size_t N = (size_t)m.N, bytes = N * m.C * 4, n_kl = (size_t)iterations + 1;
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(dev_reserve(ctx, m.kl, n_kl * sizeof(double)));
+    if (map_out) RV_TRY(dev_reserve(ctx, m.labels, N));
+    RV_TRY(model_trace_on(ctx, cs, iterations, m.q.as<float>(), map_out ? m.labels.as<int8_t>() : nullptr, label_mode, unknown_label,
+                          m.kl.as<double>(), s, false));
+    RV_HIP(ctx, hipMemcpyAsync(Q_out, m.q.p, bytes, hipMemcpyDeviceToHost, s));
+    if (map_out) RV_HIP(ctx, hipMemcpyAsync(map_out, m.labels.p, N, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipMemcpyAsync(kl_out, m.kl.p, n_kl * sizeof(double), hipMemcpyDeviceToHost, s));   // the one read-back
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_trace_device(rvseg_ctx* ctx, int32_t iterations, float* d_Q_out, int8_t* d_map_out, int32_t label_mode,
+                                          int32_t unknown_label, double* d_kl_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(iterations >= 0 && d_Q_out && d_kl_out && label_mode >= 0 && label_mode <= 3);
+    hipStream_t s = stream_of(ctx, hip_stream);
+    timer_reset(ctx);
+    RV_TRY(model_trace_on(ctx, cs, iterations, d_Q_out, d_map_out, label_mode, unknown_label, d_kl_out, s, true));
+    timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+#undef RV_TRY
+#undef RV_MODEL_ARGS
 
 }  // extern "C"

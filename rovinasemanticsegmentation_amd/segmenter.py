@@ -372,6 +372,79 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_logistic_unary_device(self.h, N, Cn, K, _ptr(Lm), C.c_void_p(d_f), C.c_void_p(d_U),
                                                                   C.c_void_p(stream or None)))
 
+    # ---- a kept DenseCRF model (rvseg_crf_model_*): the state of this context until its next lattice build ----
+    def crf_model_set(self, unary, terms, unary_is_energy=True):
+        """rvseg_crf_model_set: terms as for crf_infer_terms; the arrays are free once this returns."""
+        U = np.ascontiguousarray(unary, np.float32)
+        N, Cn = U.shape
+        arr, keep = _crf_terms(terms, Cn, N)
+        capi.check(self.h, self.L.rvseg_crf_model_set(self.h, N, Cn, len(terms), arr, _ptr(U), 1 if unary_is_energy else 0))
+        del keep
+        self._crf_model_shape = (N, Cn, len(terms))
+
+    def crf_model_set_device(self, N, Cn, terms, d_unary, unary_is_energy=True, stream=0):
+        arr, keep = _crf_terms(terms, Cn, N, device=True)
+        capi.check(self.h, self.L.rvseg_crf_model_set_device(self.h, N, Cn, len(terms), arr, C.c_void_p(d_unary), 1 if unary_is_energy else 0,
+                                                             C.c_void_p(stream or None)))
+        del keep
+        self._crf_model_shape = (N, Cn, len(terms))
+
+    def crf_model_start(self):
+        N, Cn, _ = self._crf_model_shape
+        Q = np.empty((N, Cn), np.float32)
+        capi.check(self.h, self.L.rvseg_crf_model_start(self.h, _ptr(Q)))
+        return Q
+
+    def crf_model_step(self, Q, n_steps=1):
+        """n_steps of stepInference on a copy of Q (any N x C matrix), which is returned."""
+        N, Cn, _ = self._crf_model_shape
+        Q = np.array(Q, np.float32, order="C")
+        assert Q.shape == (N, Cn)
+        capi.check(self.h, self.L.rvseg_crf_model_step(self.h, _ptr(Q), n_steps))
+        return Q
+
+    def crf_model_apply(self, term, Q):
+        N, Cn, _ = self._crf_model_shape
+        Q = np.ascontiguousarray(Q, np.float32)
+        assert Q.shape == (N, Cn)
+        out = np.empty_like(Q)
+        capi.check(self.h, self.L.rvseg_crf_model_apply(self.h, term, _ptr(Q), _ptr(out)))
+        return out
+
+    def crf_model_energy(self, labels, term=-1, unary=True, pairwise=True):
+        """(unary energy, pairwise energy) per point of a labelling (int8, N); a part not asked for is None."""
+        N = self._crf_model_shape[0]
+        lab = np.ascontiguousarray(labels, np.int8)
+        assert lab.shape == (N,)
+        u = np.empty(N, np.float32) if unary else None
+        p = np.empty(N, np.float32) if pairwise else None
+        capi.check(self.h, self.L.rvseg_crf_model_energy(self.h, _ptr(lab), term, _ptr(u), _ptr(p)))
+        return u, p
+
+    def crf_model_kl(self, Q):
+        """The parts of the KL divergence: entropy, unary, one per term (float64); their sum in that order is the KL."""
+        N, Cn, n_terms = self._crf_model_shape
+        Q = np.ascontiguousarray(Q, np.float32)
+        assert Q.shape == (N, Cn)
+        parts = np.empty(2 + n_terms, np.float64)
+        capi.check(self.h, self.L.rvseg_crf_model_kl(self.h, _ptr(Q), _ptr(parts)))
+        return parts
+
+    def crf_model_trace(self, iterations, label_mode=capi.LABEL_ARGMAX, unknown_label=0):
+        """Inference from the start: (Q, map, kl) with kl[it] the KL divergence after the start and after every iteration."""
+        N, Cn, _ = self._crf_model_shape
+        Q = np.empty((N, Cn), np.float32)
+        mp = np.empty(N, np.int8)
+        kl = np.empty(iterations + 1, np.float64)
+        capi.check(self.h, self.L.rvseg_crf_model_trace(self.h, iterations, _ptr(Q), _ptr(mp), label_mode, unknown_label, _ptr(kl)))
+        return Q, mp, kl
+
+    def crf_model_call_device(self, name, *args, stream=0):
+        """rvseg_crf_model_<name>_device with integer device addresses / integers as in rvseg.h, the stream last; enqueues only."""
+        fn = getattr(self.L, "rvseg_crf_model_%s_device" % name)
+        conv = [C.c_void_p(a or None) if t is C.c_void_p else a for a, t in zip(args, fn.argtypes[1:])]
+        capi.check(self.h, fn(self.h, *conv, C.c_void_p(stream or None)))
+
     # ---- local-map fusion -------------------------------------------------------------------
     def fuse_posteriors(self, index_images, posteriors, class_counts, cloud_size):
         p = self.params
@@ -709,6 +782,7 @@ class DenseCRF:
         self.kernels = []
 
     def setUnaryEnergy(self, unary, f=None):  # densecrf.cpp:85-91; unary is N x M energy (= -log-posterior)
+        self._touch()
         if f is not None:   # setUnaryEnergy(L, f): LogisticUnaryEnergy, unary.cpp:44-52 (L: M x K, f: N x K point-major)
             L = np.array(unary, np.float32)
             f = np.ascontiguousarray(f, np.float32)
@@ -722,6 +796,7 @@ class DenseCRF:
     def addPairwiseEnergy(self, features, function, kernel_type=DIAG_KERNEL, normalization=NORMALIZE_SYMMETRIC):  # densecrf.cpp:54-60
         features = np.ascontiguousarray(features, np.float32)
         assert features.shape[0] == self.N  # assert(features.cols() == N_), densecrf.cpp:55
+        self._touch()
         if not hasattr(function, "kind"):
             function = float(function)   # a bare weight: PottsCompatibility(w)
         self.kernels.append([features, function, int(kernel_type), int(normalization), None])
@@ -740,6 +815,7 @@ class DenseCRF:
         return np.ascontiguousarray(self.logistic[0].T).reshape(-1)
 
     def setUnaryParameters(self, v):   # unary.cpp:58-63
+        self._touch()
         if self.logistic is None:
             return
         L, f = self.logistic
@@ -751,6 +827,7 @@ class DenseCRF:
         return np.concatenate([np.zeros(0, np.float32)] + [_compat(k[1]).parameters() for k in self.kernels]).astype(np.float32)
 
     def setLabelCompatibilityParameters(self, v):
+        self._touch()
         v = np.asarray(v, np.float32)
         i = 0
         for k in self.kernels:
@@ -772,6 +849,7 @@ class DenseCRF:
         return np.concatenate([np.zeros(0, np.float32)] + [self._kernel_parameters(k) for k in self.kernels]).astype(np.float32)
 
     def setKernelParameters(self, v):   # pairwise.cpp:140-152: DIAG d values, FULL d x d column-major, CONST none
+        self._touch()
         v = np.asarray(v, np.float32)
         i = 0
         for k in self.kernels:
@@ -800,6 +878,54 @@ class DenseCRF:
 
     def map(self, n_iterations):  # densecrf.cpp:132-137
         return self.inference(n_iterations, capi.LABEL_ARGMAX)[1]
+
+    # ---- stepwise inference, energies, KL divergence (densecrf.h:77-94) on a model the context keeps ----
+    def _touch(self):
+        self._model_key = None
+
+    def _with_model(self, call):
+        """Runs call() on this CRF's model: set lazily, again after any add* / set*Parameters, and again when the context
+        reports that another call replaced it."""
+        key = getattr(self, "_model_key", None)
+        for attempt in range(2):
+            if key is None or getattr(self.ctx, "_crf_model_owner", None) is not key:
+                key = self._model_key = object()
+                self.ctx.crf_model_set(self._unary_energy(), [tuple(k) for k in self.kernels])
+                self.ctx._crf_model_owner = key
+            try:
+                return call()
+            except capi.RvsegError as e:
+                if attempt or e.status != capi.ERR_INVALID_ARG or "DenseCRF model" not in str(e):
+                    raise
+                key = None
+
+    def startInference(self):  # densecrf.cpp:178-186
+        return self._with_model(self.ctx.crf_model_start)
+
+    def stepInference(self, Q, n_steps=1):  # densecrf.cpp:187-201; returns the stepped copy
+        return self._with_model(lambda: self.ctx.crf_model_step(Q, n_steps))
+
+    def currentMap(self, Q):  # densecrf.cpp:202-211
+        return self.ctx.label_values(np.ascontiguousarray(Q, np.float32), capi.LABEL_ARGMAX)
+
+    def unaryEnergy(self, l):  # densecrf.cpp:141-153
+        return self._with_model(lambda: self.ctx.crf_model_energy(l, -1, True, False))[0]
+
+    def pairwiseEnergy(self, l, term=-1):  # densecrf.cpp:154-177
+        return self._with_model(lambda: self.ctx.crf_model_energy(l, term, False, True))[1]
+
+    def klDivergence(self, Q, parts=False):  # densecrf.cpp:214-235; parts: (kl, [entropy, unary, term 0, ...])
+        p = self._with_model(lambda: self.ctx.crf_model_kl(Q))
+        kl = 0.0
+        for v in p:
+            kl += float(v)
+        return (kl, p) if parts else kl
+
+    def inference_trace(self, n_iterations):
+        """(Q, kl): inference(n) and the KL divergence after the start and after every iteration."""
+        Q, _, kl = self._with_model(lambda: self.ctx.crf_model_trace(n_iterations))
+        return Q, kl
+
 
 
 class LocalMapStore:
