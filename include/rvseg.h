@@ -404,6 +404,90 @@ rvseg_status rvseg_crf_model_trace(rvseg_ctx *ctx, int32_t iterations, float *Q_
 rvseg_status rvseg_crf_model_trace_device(rvseg_ctx *ctx, int32_t iterations, float *d_Q_out, int8_t *d_map_out, int32_t label_mode,
                                           int32_t unknown_label, double *d_kl_out, void *hip_stream);
 
+/* ---- Learning on the kept model: the objectives of objective.cpp:35-108 and the mean-field gradient of DenseCRF::gradient
+ *      (densecrf.cpp:238-297) with respect to the unary energy and the label-compatibility parameters.  No gradient of the
+ *      kernel parameters (Permutohedral::gradient needs the per-point rank, which the lattice here does not keep) and no
+ *      optimiser: the caller hands (value, gradient) to its own.  Same conventions as the model calls above (host entries
+ *      synchronise, _device entries enqueue on hip_stream, a stale model is RVSEG_ERR_INVALID_ARG).
+ *
+ *      Definitions (fp32 with the library's pinned orders unless stated):
+ *        apply_transpose   pairwise_[term]->applyTranspose(out, in) (pairwise.cpp:179-183, :63-80 with transpose = true): the
+ *                input scaled by norm for SYMMETRIC and AFTER, the lattice filter with the blur axes in reverse order
+ *                (d .. 0), the output scaled by norm for SYMMETRIC and BEFORE, then the compatibility as in apply (a Matrix's
+ *                W^T is W bit for bit: W is stored symmetrised)
+ *        objective   a gt[i] outside 0 .. C-1 skips point i; d_mul_Q is N x C, 0.0f where nothing is written
+ *                LOGLIKELIHOOD  QQ = max(q + robust, 1e-20f) in fp32, q = Q[i][gt_i];  d_mul_Q[i][gt_i] = (q / QQ) / (float)N,
+ *                               two fp32 divisions;  value = sum of log((double)QQ) / N, each term in double
+ *                HAMMING        t = fl(class_weight[gt_i] * q);  d_mul_Q[i][gt_i] = t;  value = sum of (double)t
+ *                IOU            in[l] = sum of (double)Q[i][l] over gt_i == l;  un[l] = 1e-20 + sum over valid i of
+ *                               (gt_i == l ? 1 : (double)Q[i][l]);  d_mul_Q[i][l] = (float)(q / (un[l] * C)) for l == gt_i,
+ *                               else (float)((-q * in[l]) / ((un[l] * un[l]) * C)), in double from q = (double)Q[i][l];
+ *                               value = (sum over l ascending of in[l] / un[l]) / C
+ *                Every double sum is reduced in a fixed order without atomics, like the KL parts: the same input gives the
+ *                same 64 bits on every call; the order is the device's own.
+ *        backward   from d_mul_Q and the Q[0 .. n] of a forward pass (densecrf.cpp:258-296), with
+ *                sumAndNormalize(x, q): per point s = x[0] + x[1] + .. ascending, out[c] = fl(s * q[c]) - x[c]:
+ *                  b = sumAndNormalize(d_mul_Q, Q[n]);  unary_grad = b
+ *                  for it = n-1 .. 0:  [compat_grad, see below, from this b and Q[it]]
+ *                                      tmp1 = 0.0f; per term in order tmp1 += apply_transpose_k(b)
+ *                                      b = sumAndNormalize(fl(tmp1 * Q[it]), Q[it]);  unary_grad += b
+ *                unary_grad (N x C) is d value / d U.  compat_grad: doubles, the terms concatenated in the layout of
+ *                labelCompatibilityParameters() (POTTS 1, DIAGONAL C, MATRIX C (C + 1) / 2 values: the upper triangle row by
+ *                row).  Per it and term, with F = the term's kernel apply of Q[it] (normalisation and filter, no
+ *                compatibility, pairwise.cpp:190-195) in fp32:  POTTS -sum b F;  DIAGONAL per class c, sum over i of
+ *                b[i][c] F[i][c];  MATRIX g = b^T F packed as g(i,j) + (i != j ? g(j,i) : 0) for j >= i
+ *                (labelcompatibility.cpp:57-61, :76-78, :101-108).  Products and sums in double from the fp32 b and F, fixed
+ *                order; accumulated over it (n-1 .. 0) in double.
+ *        gradient   the forward pass keeping Q[0 .. n] in context memory (the bits of start + n steps), then objective and
+ *                backward: the three-call composition bit for bit.  iterations == 0 gives the unary gradient alone
+ *                (compat_grad all 0).
+ *        set_compat / set_unary   replace a term's compatibility parameters (as rvseg_crf_term.compat_params; the kind
+ *                stays) or the unary of the live model without a lattice build; later calls equal a fresh
+ *                rvseg_crf_model_set with the new values bit for bit.
+ *        logistic_gradient   LogisticUnaryEnergy::gradient (unary.cpp:64-68): out[k*C + m] = sum over i of
+ *                (double)g[i][m] (double)f[i][k], column-major like unaryParameters(); g: N x C (a unary_grad), f: N x K,
+ *                out: C K doubles.  Fixed order.  Needs a context, not a model. */
+typedef enum rvseg_objective_kind {
+    RVSEG_OBJECTIVE_LOGLIKELIHOOD = 0,
+    RVSEG_OBJECTIVE_HAMMING = 1,
+    RVSEG_OBJECTIVE_IOU = 2
+} rvseg_objective_kind;
+typedef struct rvseg_crf_objective {
+    int32_t kind;                /* rvseg_objective_kind */
+    const int16_t *gt;           /* N labels (VectorXs); host memory for the host entries, device memory for _device */
+    float robust;                /* LOGLIKELIHOOD only */
+    const float *class_weight;   /* HAMMING only: C weights, host / device memory like gt */
+} rvseg_crf_objective;
+/* Host-only validation (no context, no GPU): kind in range, gt non-NULL, class_weight non-NULL for HAMMING, robust finite.
+ * Every entry that takes an objective calls it first. */
+rvseg_status rvseg_crf_objective_check(const rvseg_crf_objective *obj);
+rvseg_status rvseg_crf_model_apply_transpose(rvseg_ctx *ctx, int32_t term, const float *in, float *out);
+rvseg_status rvseg_crf_model_apply_transpose_device(rvseg_ctx *ctx, int32_t term, const float *d_in, float *d_out, void *hip_stream);
+/* value_out: 1 double; d_mul_Q_out: N x C */
+rvseg_status rvseg_crf_model_objective(rvseg_ctx *ctx, const rvseg_crf_objective *obj, const float *Q, double *value_out,
+                                       float *d_mul_Q_out);
+rvseg_status rvseg_crf_model_objective_device(rvseg_ctx *ctx, const rvseg_crf_objective *obj, const float *d_Q, double *d_value_out,
+                                              float *d_d_mul_Q_out, void *hip_stream);
+/* Q_all: (iterations + 1) x N x C, Q[0 .. n] as the forward pass produced them.  unary_grad_out (N x C floats) or
+ * compat_grad_out (doubles, one per compatibility parameter) may be NULL. */
+rvseg_status rvseg_crf_model_backward(rvseg_ctx *ctx, int32_t iterations, const float *Q_all, const float *d_mul_Q,
+                                      float *unary_grad_out, double *compat_grad_out);
+rvseg_status rvseg_crf_model_backward_device(rvseg_ctx *ctx, int32_t iterations, const float *d_Q_all, const float *d_d_mul_Q,
+                                             float *d_unary_grad_out, double *d_compat_grad_out, void *hip_stream);
+/* value_out: 1 double.  unary_grad_out, compat_grad_out and Q_out (N x C, Q[n]) may be NULL. */
+rvseg_status rvseg_crf_model_gradient(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj, double *value_out,
+                                      float *unary_grad_out, double *compat_grad_out, float *Q_out);
+rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj, double *d_value_out,
+                                             float *d_unary_grad_out, double *d_compat_grad_out, float *d_Q_out, void *hip_stream);
+/* params: host memory, consumed before the call returns (it waits for the context's stream). */
+rvseg_status rvseg_crf_model_set_compat(rvseg_ctx *ctx, int32_t term, const float *params);
+rvseg_status rvseg_crf_model_set_unary(rvseg_ctx *ctx, const float *unary, int32_t unary_is_energy);
+rvseg_status rvseg_crf_model_set_unary_device(rvseg_ctx *ctx, const float *d_unary, int32_t unary_is_energy, void *hip_stream);
+rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *unary_grad, const float *f,
+                                         double *out);
+rvseg_status rvseg_crf_logistic_gradient_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *d_unary_grad,
+                                                const float *d_f, double *d_out, void *hip_stream);
+
 /* ---- lattice introspection for parity tests: Permutohedral::init + compute
  *      (densecrf permutohedral.cpp:140-321,596-603).  offsets_out / bary_out: N x (d+1);
  *      keys_out: capacity M_cap x d int16; vertex numbering is arbitrary (results do not depend on

@@ -782,6 +782,26 @@ struct MatrixCompatibility : LabelCompatibility {
     }
 };
 
+// Learning objectives (objective.h) over ground-truth labels gt (N values; a label outside 0 .. M-1 skips its point).
+// Hamming takes the class weights themselves (M values); the reference's Hamming(gt, class_weight_pow) constructor
+// (objective.cpp:51-63) is a few host lines the caller keeps.
+struct ObjectiveFunction {
+    int32_t kind = RVSEG_OBJECTIVE_LOGLIKELIHOOD;
+    std::vector<int16_t> gt;
+    float robust = 0.f;
+    std::vector<float> class_weight;
+    rvseg_crf_objective record() const { return rvseg_crf_objective{kind, gt.data(), robust, class_weight.empty() ? nullptr : class_weight.data()}; }
+};
+struct LogLikelihood : ObjectiveFunction {
+    explicit LogLikelihood(std::vector<int16_t> g, float robust_ = 0.f) { kind = RVSEG_OBJECTIVE_LOGLIKELIHOOD; gt = std::move(g); robust = robust_; }
+};
+struct Hamming : ObjectiveFunction {
+    Hamming(std::vector<int16_t> g, std::vector<float> weights) { kind = RVSEG_OBJECTIVE_HAMMING; gt = std::move(g); class_weight = std::move(weights); }
+};
+struct IntersectionOverUnion : ObjectiveFunction {
+    explicit IntersectionOverUnion(std::vector<int16_t> g) { kind = RVSEG_OBJECTIVE_IOU; gt = std::move(g); }
+};
+
 // Which DenseCRF object set the model a context keeps (rvseg_crf_model_*): the context has one model and no handle for it,
 // so two objects that share a context take turns.  set: record `owner` (nullptr: nobody).
 inline const void* crf_model_owner(rvseg_ctx* ctx, bool set = false, const void* owner = nullptr) {
@@ -943,6 +963,37 @@ public:
         if (map_out) map_out->resize((size_t)N_);
         onModel([&] { return rvseg_crf_model_trace(ctx_, n_iterations, Q.data(), map_out ? map_out->data() : nullptr, RVSEG_LABEL_ARGMAX, 0, kl.data()); });
         return Q;
+    }
+    // ---- learning (densecrf.cpp:238-297) on the kept model.  No kernel-parameter gradient and no optimiser.
+    std::vector<float> applyTranspose(int term, const std::vector<float>& in) {   // pairwise.cpp:179-183
+        check(in.size() == (size_t)N_ * M_);
+        std::vector<float> out((size_t)N_ * M_);
+        onModel([&] { return rvseg_crf_model_apply_transpose(ctx_, term, in.data(), out.data()); });
+        return out;
+    }
+    // DenseCRF::gradient: the objective's value; unary_grad (optional) the gradient of unaryParameters() (empty without a
+    // logistic unary), lbl_cmp_grad (optional) that of labelCompatibilityParameters(), both rounded to fp32 from the
+    // library's doubles; unary_energy_grad (optional): d value / d U, N x M
+    double gradient(int n_iterations, const ObjectiveFunction& objective, std::vector<float>* unary_grad, std::vector<float>* lbl_cmp_grad,
+                    std::vector<float>* unary_energy_grad = nullptr) {
+        check(objective.gt.size() == (size_t)N_ && (objective.kind != RVSEG_OBJECTIVE_HAMMING || objective.class_weight.size() == (size_t)M_));
+        const rvseg_crf_objective rec = objective.record();
+        double value = 0;
+        std::vector<float> ug((size_t)N_ * M_);
+        std::vector<double> cg(labelCompatibilityParameters().size() + 1);
+        const bool want_ug = unary_grad || unary_energy_grad;
+        onModel([&] { return rvseg_crf_model_gradient(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, lbl_cmp_grad ? cg.data() : nullptr, nullptr); });
+        if (lbl_cmp_grad) lbl_cmp_grad->assign(cg.begin(), cg.end() - 1);
+        if (unary_grad) {
+            unary_grad->clear();
+            if (!logistic_f_.empty()) {
+                std::vector<double> lg((size_t)M_ * K_);
+                status(rvseg_crf_logistic_gradient(ctx_, N_, M_, K_, ug.data(), logistic_f_.data(), lg.data()));
+                unary_grad->assign(lg.begin(), lg.end());
+            }
+        }
+        if (unary_energy_grad) *unary_energy_grad = std::move(ug);
+        return value;
     }
 protected:
     struct Term {

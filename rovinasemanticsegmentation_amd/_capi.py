@@ -20,6 +20,7 @@ GT_LABELS, GT_RGB = range(2)
 NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER, NORMALIZE_SYMMETRIC = range(4)
 CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL = range(3)
 COMPAT_POTTS, COMPAT_DIAGONAL, COMPAT_MATRIX = range(3)
+OBJECTIVE_LOGLIKELIHOOD, OBJECTIVE_HAMMING, OBJECTIVE_IOU = range(3)   # rvseg_objective_kind
 
 # every symbol include/rvseg.h declares
 SYMBOLS = [
@@ -51,6 +52,10 @@ SYMBOLS = [
     "rvseg_crf_model_step", "rvseg_crf_model_step_device", "rvseg_crf_model_apply", "rvseg_crf_model_apply_device",
     "rvseg_crf_model_energy", "rvseg_crf_model_energy_device", "rvseg_crf_model_kl", "rvseg_crf_model_kl_device",
     "rvseg_crf_model_trace", "rvseg_crf_model_trace_device",
+    "rvseg_crf_objective_check", "rvseg_crf_model_apply_transpose", "rvseg_crf_model_apply_transpose_device",
+    "rvseg_crf_model_objective", "rvseg_crf_model_objective_device", "rvseg_crf_model_backward", "rvseg_crf_model_backward_device",
+    "rvseg_crf_model_gradient", "rvseg_crf_model_gradient_device", "rvseg_crf_model_set_compat", "rvseg_crf_model_set_unary",
+    "rvseg_crf_model_set_unary_device", "rvseg_crf_logistic_gradient", "rvseg_crf_logistic_gradient_device",
 ]
 
 
@@ -97,6 +102,11 @@ class RvsegCrfTerm(C.Structure):
         ("d", C.c_int32), ("compat", C.c_int32), ("kernel_type", C.c_int32), ("normalization", C.c_int32),
         ("features", C.c_void_p), ("compat_params", C.c_void_p), ("kernel_params", C.c_void_p),
     ]
+
+
+class RvsegCrfObjective(C.Structure):
+    """rvseg_crf_objective: a learning objective of a kept DenseCRF model."""
+    _fields_ = [("kind", C.c_int32), ("gt", C.c_void_p), ("robust", C.c_float), ("class_weight", C.c_void_p)]
 
 
 SPLAT_NAMES = {0: "none", 1: "list-major", 2: "resident"}
@@ -209,6 +219,21 @@ def lib():
     L.rvseg_crf_model_kl_device.argtypes = [vp, vp, vp, vp]
     L.rvseg_crf_model_trace.argtypes = [vp, i32, vp, vp, i32, i32, vp]
     L.rvseg_crf_model_trace_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp]
+    OP = C.POINTER(RvsegCrfObjective)
+    L.rvseg_crf_objective_check.argtypes = [OP]
+    L.rvseg_crf_model_apply_transpose.argtypes = [vp, i32, vp, vp]
+    L.rvseg_crf_model_apply_transpose_device.argtypes = [vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_objective.argtypes = [vp, OP, vp, vp, vp]
+    L.rvseg_crf_model_objective_device.argtypes = [vp, OP, vp, vp, vp, vp]
+    L.rvseg_crf_model_backward.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rvseg_crf_model_backward_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_gradient.argtypes = [vp, i32, OP, vp, vp, vp, vp]
+    L.rvseg_crf_model_gradient_device.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_set_compat.argtypes = [vp, i32, vp]
+    L.rvseg_crf_model_set_unary.argtypes = [vp, vp, i32]
+    L.rvseg_crf_model_set_unary_device.argtypes = [vp, vp, i32, vp]
+    L.rvseg_crf_logistic_gradient.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.rvseg_crf_logistic_gradient_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.rvseg_rectify_depth.argtypes = [vp, i32, vp, vp, f32, f32, vp]
     L.rvseg_rectify_depth_device.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp]
     L.rvseg_external_layers_set.argtypes = [vp, i32, vp]
@@ -322,6 +347,11 @@ def crf_terms_check(N, Cn, terms):
     """Host-only validation of rvseg_crf_term records (no GPU): returns the status."""
     arr = (RvsegCrfTerm * max(1, len(terms)))(*terms)
     return lib().rvseg_crf_terms_check(N, Cn, len(terms), arr)
+
+
+def crf_objective_check(obj):
+    """Host-only validation of an rvseg_crf_objective (no GPU): returns the status.  obj: RvsegCrfObjective or None."""
+    return lib().rvseg_crf_objective_check(C.byref(obj) if obj is not None else None)
 
 
 def eval_scores_from_counts(counts):

@@ -47,33 +47,10 @@ void launch_label_gather(const float* rows, const int8_t* labels, long long n, i
 // KL passes.  Thread (lp, c) of a block serves class c of point p0 + lp, PB = 256 / C points per step, like the term
 // update whose device functions it shares.
 // ---------------------------------------------------------------------------------------------
-constexpr int KL_THREADS = 256;
-
 int kl_blocks(int C, long long n_points) {
     const int PB = KL_THREADS / C;
     const long long blocks = (n_points + PB - 1) / PB;
     return (int)(blocks > KL_MAX_BLOCKS ? KL_MAX_BLOCKS : blocks);
-}
-
-// the 64 lanes of a wave, in the fixed order of the xor butterfly (every lane ends with the same sum)
-__device__ __forceinline__ double kl_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-// block sum of one double per thread into *out (thread 0 writes): waves 0..3 added in order
-__device__ __forceinline__ void kl_block_sum(double v, double* sh /* 4 */, double* out) {
-    const double w = kl_wave_sum(v);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();   // sh may still be read by the previous part's thread 0
-    if ((threadIdx.x & 63) == 0) sh[wave] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = sh[0];
-        for (int k = 1; k < KL_THREADS / 64; k++) r = r + sh[k];
-        *out = r;
-    }
 }
 
 __global__ void __launch_bounds__(KL_THREADS)

@@ -211,4 +211,21 @@ void launch_kl_term(const LatticeDev& L, int C, bool seq, const float* values, b
 // adds each part's partials, index ascending; parts_out (n_parts) / sum_out (1, the parts added in order) may be null
 void launch_kl_final(const double* partials, int n_blocks, int n_parts, double* parts_out, double* sum_out, hipStream_t s);
 
+
+// ---- kernels_crf_learn.hip: objectives, backward pass and parameter gradients of a kept model ------------------------------
+// doubles of scratch the learning reductions of C classes need at most (partials of one launch)
+size_t learn_partials_doubles(int C);
+// rvseg_crf_objective on device pointers: d_mul_Q (N x C, zero where nothing is written) and *value; stats: 128 doubles (IoU)
+void launch_objective(int kind, const int16_t* gt, float robust, const float* class_weight, const float* Q, int C, long long n_points,
+                      float* d_mul_Q, double* partials, double* stats, double* value, hipStream_t s);
+// b = sumAndNormalize(mul ? fl(in * q) : in, q); ug (may be null): ug_mode 1 ug = b, 2 ug += b
+void launch_sum_normalize(const float* in, bool mul, const float* q, int C, long long n_points, float* b, float* ug, int ug_mode, hipStream_t s);
+// acc = (first ? 0.0f : acc) + t
+void launch_add_rows(bool first, const float* t, float* acc, long long total, hipStream_t s);
+// out (the term's slots of compat_grad) += the gradient of one term from b and the blurred `values` of its kernel apply
+void launch_compat_grad(const LatticeDev& L, int C, bool seq, const float* values, bool post, int compat, const float* b, long long n_points,
+                        double* partials, double* out, hipStream_t s);
+// out[k * C + m] = sum_i g[i][m] f[i][k]; partials: learn_partials_doubles(64)
+void launch_logistic_gradient(const float* g, const float* f, long long n_points, int C, int K, double* partials, double* out, hipStream_t s);
+
 }  // namespace rvseg

@@ -32,6 +32,7 @@ struct TermPlan {
     float w = 0.f;
     bool matrix = false;
     size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
+    int compat = RVSEG_COMPAT_POTTS;   // rvseg_compat_kind: the layout of the term's parameters and of their gradient
 };
 
 // The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
@@ -45,6 +46,10 @@ struct CrfModel {
     DevBuf unary;              // N x C, as the caller passed it
     // staging of the host entries and scratch of the energies / the KL passes (never the mean field's tmp)
     DevBuf q, rows, onehot, labels, vec, partials, kl;
+    // learning (rvseg_crf_model_objective / _backward / _gradient): Q[0 .. n] of a forward pass, d_mul_Q, the backward
+    // pass's b, tmp1 and tmp2, and the staging of the host entries (gradients, ground truth, class weights)
+    DevBuf qs, dq, bgrad, tsum, tapp, ug, cg, gt, cw;
+    DevBuf stats;              // 128 doubles of IoU sums + the objective's value
 };
 
 struct CrfState {
@@ -56,6 +61,7 @@ struct CrfState {
     DevBuf q, unary, feat, labels;
     // learned-model terms (rvseg_crf_infer_terms*): compatibilities of all terms, transformed features, logistic L
     DevBuf compat, kfeat, lmat;
+    DevBuf learn_partials, lgrad;   // partials of the learning reductions; staging of rvseg_crf_logistic_gradient's result
     std::vector<float> h_compat;   // host copy of `compat` (the source of its asynchronous upload)
     Stream layer_stream;   // the second layer's stream; created together with its two events (second_stream)
     Event layer_fork, layer_join;
@@ -629,6 +635,31 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<T
 
 // PottsCompatibility / DiagonalCompatibility / MatrixCompatibility (labelcompatibility.cpp:38-100) as diagonals and
 // symmetric matrices: W = 0.5 * (m + m^T) elementwise in fp32 when the term is created (:79)
+static void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */) {
+    tp.compat = compat;
+    tp.uniform = true;
+    tp.matrix = false;
+    tp.w = 0.f;
+    if (compat == RVSEG_COMPAT_MATRIX) {
+        tp.uniform = false;
+        tp.matrix = true;
+        for (int i = 0; i < C; i++)
+            for (int j = 0; j < C; j++) {
+                const float sum = params[(size_t)i * C + j] + params[(size_t)j * C + i];
+                hc[(size_t)i * C + j] = 0.5f * sum;
+            }
+    } else if (compat == RVSEG_COMPAT_DIAGONAL) {
+        for (int c = 0; c < C; c++) {
+            hc[c] = params[c];
+            if (!(params[c] == params[0] && std::signbit(params[c]) == std::signbit(params[0]))) tp.uniform = false;
+        }
+        tp.w = -params[0];
+    } else {
+        tp.w = params[0];
+        for (int c = 0; c < C; c++) hc[c] = -tp.w;
+    }
+}
+
 static void plan_terms(int C, int n_terms, const rvseg_crf_term* terms, std::vector<TermPlan>& plan, std::vector<float>& hc) {
     plan.assign((size_t)n_terms, TermPlan{});
     hc.clear();
@@ -637,25 +668,8 @@ static void plan_terms(int C, int n_terms, const rvseg_crf_term* terms, std::vec
         TermPlan& tp = plan[k];
         tp.norm = t.normalization;
         tp.off = hc.size();
-        if (t.compat == RVSEG_COMPAT_MATRIX) {
-            tp.uniform = false;
-            tp.matrix = true;
-            for (int i = 0; i < C; i++)
-                for (int j = 0; j < C; j++) {
-                    const float sum = t.compat_params[(size_t)i * C + j] + t.compat_params[(size_t)j * C + i];
-                    hc.push_back(0.5f * sum);
-                }
-        } else if (t.compat == RVSEG_COMPAT_DIAGONAL) {
-            for (int c = 0; c < C; c++) {
-                hc.push_back(t.compat_params[c]);
-                if (!(t.compat_params[c] == t.compat_params[0] && std::signbit(t.compat_params[c]) == std::signbit(t.compat_params[0])))
-                    tp.uniform = false;
-            }
-            tp.w = -t.compat_params[0];
-        } else {
-            tp.w = t.compat_params[0];
-            for (int c = 0; c < C; c++) hc.push_back(-tp.w);
-        }
+        hc.resize(hc.size() + (t.compat == RVSEG_COMPAT_MATRIX ? (size_t)C * C : (size_t)C));
+        plan_compat(C, t.compat, t.compat_params, tp, hc.data() + tp.off);
     }
 }
 
@@ -1291,17 +1305,30 @@ static rvseg_status model_step_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, int 
     return RVSEG_OK;
 }
 
-// pairwise_[term]->apply(out, Q) (pairwise.cpp:63-80 + the compatibility): needs mf_scratch
-static rvseg_status model_apply_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, float* d_out) {
+// DenseKernel::filter (pairwise.cpp:63-80) up to its blur: the input scaled where the normalisation says so, splat, blur
+// (transpose: the axes in reverse order).  *post: whether the sliced output is scaled.  Needs mf_scratch.
+static rvseg_status model_filter_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, bool transpose, float** blurred,
+                                      bool* post) {
     LatticeBufs& b = cs->lat[k];
     const TermPlan& t = r.plan[k];
+    const bool pre = transpose ? term_post(t) : term_pre(t);
+    *post = transpose ? term_pre(t) : term_post(t);
     rvseg_status st;
-    if (term_pre(t) && (st = ensure_csr_nrm(ctx, b, r.s)) != RVSEG_OK) return st;
+    if (pre && (st = ensure_csr_nrm(ctx, b, r.s)) != RVSEG_OK) return st;
     auto& sc = cs->scratch[r.slot];
-    const bool seq = r.C <= 2;
-    launch_splat(b.dev, model_view(cs->model, d_in), r.C, term_pre(t) ? 1 : 0, sc.val_a.as<float>(), r.s);
-    float* blurred = launch_blur(b.dev, r.C, seq, false, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
-    launch_term_update(b.dev, r.C, seq, blurred, term_post(t), t.matrix, r.d_compat + t.off, d_out, r.n_points, r.s, true);
+    launch_splat(b.dev, model_view(cs->model, d_in), r.C, pre ? 1 : 0, sc.val_a.as<float>(), r.s);
+    *blurred = launch_blur(b.dev, r.C, r.C <= 2, transpose, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+    return RVSEG_OK;
+}
+
+// pairwise_[term]->apply(out, Q) / applyTranspose (pairwise.cpp:173-183: the filter + the compatibility): needs mf_scratch
+static rvseg_status model_apply_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, float* d_out, bool transpose = false) {
+    const TermPlan& t = r.plan[k];
+    float* blurred;
+    bool post;
+    const rvseg_status st = model_filter_term(ctx, cs, r, k, d_in, transpose, &blurred, &post);
+    if (st != RVSEG_OK) return st;
+    launch_term_update(cs->lat[k].dev, r.C, r.C <= 2, blurred, post, t.matrix, r.d_compat + t.off, d_out, r.n_points, r.s, true);
     return RVSEG_OK;
 }
 
@@ -1311,11 +1338,11 @@ static rvseg_status model_term_arg(rvseg_ctx* ctx, const CrfModel& m, int term, 
     return RVSEG_ERR_INVALID_ARG;
 }
 
-static rvseg_status model_apply_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_in, float* d_out, hipStream_t s) {
+static rvseg_status model_apply_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_in, float* d_out, hipStream_t s, bool transpose = false) {
     const MfRun run = model_run(cs, s, false);
     rvseg_status st;
     if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = model_apply_term(ctx, cs, run, term, d_in, d_out)) != RVSEG_OK) return st;
+    if ((st = model_apply_term(ctx, cs, run, term, d_in, d_out, transpose)) != RVSEG_OK) return st;
     RV_LAUNCH_OK(ctx);
     return RVSEG_OK;
 }
@@ -1400,6 +1427,111 @@ static rvseg_status model_trace_on(rvseg_ctx* ctx, CrfState* cs, int iterations,
         launch_labels(d_Q, (size_t)m.N, m.C, label_mode, unknown_label, d_map, s);
     }
     RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Learning on the kept model (include/rvseg.h, "Learning on the kept model"): objective, backward pass, gradient.
+// ---------------------------------------------------------------------------------------------
+static size_t model_compat_params(const CrfModel& m, int upto = -1) {
+    size_t n = 0;
+    const int end = upto < 0 ? (int)m.plan.size() : upto;
+    for (int k = 0; k < end; k++) {
+        const int kind = m.plan[k].compat;
+        n += kind == RVSEG_COMPAT_MATRIX ? (size_t)m.C * (m.C + 1) / 2 : kind == RVSEG_COMPAT_DIAGONAL ? (size_t)m.C : 1;
+    }
+    return n;
+}
+
+static rvseg_status objective_arg(rvseg_ctx* ctx, const rvseg_crf_objective* obj) {
+    if (rvseg_crf_objective_check(obj) == RVSEG_OK) return RVSEG_OK;
+    ctx->err = "bad objective (rvseg_crf_objective_check: kind, gt, class_weight for HAMMING, finite robust)";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+// obj: device pointers
+static rvseg_status model_objective_on(rvseg_ctx* ctx, CrfState* cs, const rvseg_crf_objective& obj, const float* d_Q, double* d_value,
+                                       float* d_dq, hipStream_t s) {
+    CrfModel& m = cs->model;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double))) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.stats, 129 * sizeof(double))) != RVSEG_OK) return st;
+    launch_objective(obj.kind, obj.gt, obj.robust, obj.class_weight, d_Q, m.C, m.N, d_dq, cs->learn_partials.as<double>(), m.stats.as<double>(),
+                     d_value, s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// densecrf.cpp:258-296 from d_mul_Q and Q[0 .. n]; d_ug / d_cg may be null
+static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const float* d_Qall, const float* d_dq, float* d_ug,
+                                      double* d_cg, hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    const size_t tot = (size_t)m.N * m.C;
+    const int n_terms = (int)m.plan.size();
+    rvseg_status st;
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.bgrad, tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.tsum, tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.tapp, tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double))) != RVSEG_OK) return st;
+    float *b = m.bgrad.as<float>(), *tsum = m.tsum.as<float>(), *tapp = m.tapp.as<float>();
+    launch_sum_normalize(d_dq, false, d_Qall + (size_t)iterations * tot, m.C, m.N, b, d_ug, 1, s);
+    if (d_cg && model_compat_params(m)) RV_HIP(ctx, hipMemsetAsync(d_cg, 0, model_compat_params(m) * sizeof(double), s));
+    for (int it = iterations - 1; it >= 0; it--) {
+        const float* Qit = d_Qall + (size_t)it * tot;
+        if (n_terms == 0) RV_HIP(ctx, hipMemsetAsync(tsum, 0, tot * 4, s));   // tmp1.fill(0), :270
+        for (int k = 0; k < n_terms; k++) {
+            if (d_cg) {   // pairwise_[k]->gradient(b, Q[it]) (pairwise.cpp:190-195)
+                float* blurred;
+                bool post;
+                if ((st = model_filter_term(ctx, cs, run, k, Qit, false, &blurred, &post)) != RVSEG_OK) return st;
+                launch_compat_grad(cs->lat[k].dev, m.C, m.C <= 2, blurred, post, m.plan[k].compat, b, m.N, cs->learn_partials.as<double>(),
+                                   d_cg + model_compat_params(m, k), s);
+            }
+            if ((st = model_apply_term(ctx, cs, run, k, b, tapp, true)) != RVSEG_OK) return st;
+            launch_add_rows(k == 0, tapp, tsum, (long long)tot, s);
+        }
+        launch_sum_normalize(tsum, true, Qit, m.C, m.N, b, d_ug, 2, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// the forward pass of DenseCRF::gradient (:240-253) keeping Q[0 .. n] in CrfModel::qs, then objective and backward
+static rvseg_status model_gradient_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const rvseg_crf_objective& obj, double* d_value, float* d_ug,
+                                      double* d_cg, float* d_Q_out, hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    const size_t tot = (size_t)m.N * m.C;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, m.qs, ((size_t)iterations + 1) * tot * 4)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.dq, tot * 4)) != RVSEG_OK) return st;
+    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
+    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
+    float* qs = m.qs.as<float>();
+    mf_start(ctx, cs, run, model_view(m, qs));
+    for (int it = 0; it < iterations; it++) {
+        float* next = qs + (size_t)(it + 1) * tot;
+        RV_HIP(ctx, hipMemcpyAsync(next, qs + (size_t)it * tot, tot * 4, hipMemcpyDeviceToDevice, s));
+        mf_step(ctx, cs, run, model_view(m, next));
+    }
+    RV_LAUNCH_OK(ctx);
+    const float* Qn = qs + (size_t)iterations * tot;
+    if ((st = model_objective_on(ctx, cs, obj, Qn, d_value, m.dq.as<float>(), s)) != RVSEG_OK) return st;
+    if ((st = model_backward_on(ctx, cs, iterations, qs, m.dq.as<float>(), d_ug, d_cg, s)) != RVSEG_OK) return st;
+    if (d_Q_out) RV_HIP(ctx, hipMemcpyAsync(d_Q_out, Qn, tot * 4, hipMemcpyDeviceToDevice, s));
+    return RVSEG_OK;
+}
+
+// the objective of a host entry with gt and class_weight staged in context memory
+static rvseg_status model_objective_stage(rvseg_ctx* ctx, CrfModel& m, const rvseg_crf_objective* obj, rvseg_crf_objective* dev, hipStream_t s) {
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, m.gt, (size_t)m.N * sizeof(int16_t))) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, m.cw, (size_t)m.C * 4)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(m.gt.p, obj->gt, (size_t)m.N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    if (obj->kind == RVSEG_OBJECTIVE_HAMMING) RV_HIP(ctx, hipMemcpyAsync(m.cw.p, obj->class_weight, (size_t)m.C * 4, hipMemcpyHostToDevice, s));
+    *dev = rvseg_crf_objective{obj->kind, m.gt.as<int16_t>(), obj->robust, m.cw.as<float>()};
     return RVSEG_OK;
 }
 
@@ -1574,6 +1706,204 @@ rvseg_status rvseg_crf_model_trace_device(rvseg_ctx* ctx, int32_t iterations, fl
     timer_reset(ctx);
     RV_TRY(model_trace_on(ctx, cs, iterations, d_Q_out, d_map_out, label_mode, unknown_label, d_kl_out, s, true));
     timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+rvseg_status rvseg_crf_objective_check(const rvseg_crf_objective* obj) {
+    if (!obj || obj->kind < RVSEG_OBJECTIVE_LOGLIKELIHOOD || obj->kind > RVSEG_OBJECTIVE_IOU || !obj->gt) return RVSEG_ERR_INVALID_ARG;
+    if (obj->kind == RVSEG_OBJECTIVE_HAMMING && !obj->class_weight) return RVSEG_ERR_INVALID_ARG;
+    if (!std::isfinite(obj->robust)) return RVSEG_ERR_INVALID_ARG;
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_apply_transpose(rvseg_ctx* ctx, int32_t term, const float* in, float* out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(in && out);
+    CrfModel& m = cs->model;
+    RV_TRY(model_term_arg(ctx, m, term, 0));
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(dev_reserve(ctx, m.rows, bytes));
+    RV_HIP(ctx, hipMemcpyAsync(m.q.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RV_TRY(model_apply_on(ctx, cs, term, m.q.as<float>(), m.rows.as<float>(), ctx->stream, true));
+    RV_HIP(ctx, hipMemcpyAsync(out, m.rows.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_apply_transpose_device(rvseg_ctx* ctx, int32_t term, const float* d_in, float* d_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_in && d_out);
+    RV_TRY(model_term_arg(ctx, cs->model, term, 0));
+    return model_apply_on(ctx, cs, term, d_in, d_out, stream_of(ctx, hip_stream), true);
+}
+
+rvseg_status rvseg_crf_model_objective(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* Q, double* value_out, float* d_mul_Q_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_TRY(objective_arg(ctx, obj));
+    RV_MODEL_ARGS(Q && value_out && d_mul_Q_out);
+    CrfModel& m = cs->model;
+    hipStream_t s = ctx->stream;
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    rvseg_crf_objective dev;
+    RV_TRY(model_objective_stage(ctx, m, obj, &dev, s));
+    RV_TRY(dev_reserve(ctx, m.q, bytes));
+    RV_TRY(dev_reserve(ctx, m.dq, bytes));
+    RV_TRY(dev_reserve(ctx, m.stats, 129 * sizeof(double)));
+    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q, bytes, hipMemcpyHostToDevice, s));
+    RV_TRY(model_objective_on(ctx, cs, dev, m.q.as<float>(), m.stats.as<double>() + 128, m.dq.as<float>(), s));
+    RV_HIP(ctx, hipMemcpyAsync(value_out, m.stats.as<double>() + 128, sizeof(double), hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipMemcpyAsync(d_mul_Q_out, m.dq.p, bytes, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_objective_device(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* d_Q, double* d_value_out,
+                                              float* d_d_mul_Q_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_TRY(objective_arg(ctx, obj));
+    RV_MODEL_ARGS(d_Q && d_value_out && d_d_mul_Q_out);
+    return model_objective_on(ctx, cs, *obj, d_Q, d_value_out, d_d_mul_Q_out, stream_of(ctx, hip_stream));
+}
+
+// downloads of the gradients a host entry staged in CrfModel::ug / cg
+static rvseg_status model_gradients_home(rvseg_ctx* ctx, CrfModel& m, float* unary_grad_out, double* compat_grad_out, hipStream_t s) {
+    if (unary_grad_out) RV_HIP(ctx, hipMemcpyAsync(unary_grad_out, m.ug.p, (size_t)m.N * m.C * 4, hipMemcpyDeviceToHost, s));
+    const size_t n_cg = model_compat_params(m);
+    if (compat_grad_out && n_cg) RV_HIP(ctx, hipMemcpyAsync(compat_grad_out, m.cg.p, n_cg * sizeof(double), hipMemcpyDeviceToHost, s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_backward(rvseg_ctx* ctx, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
+                                      double* compat_grad_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(iterations >= 0 && Q_all && d_mul_Q);
+    CrfModel& m = cs->model;
+    hipStream_t s = ctx->stream;
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    RV_TRY(dev_reserve(ctx, m.qs, ((size_t)iterations + 1) * bytes));
+    RV_TRY(dev_reserve(ctx, m.dq, bytes));
+    if (unary_grad_out) RV_TRY(dev_reserve(ctx, m.ug, bytes));
+    if (compat_grad_out) RV_TRY(dev_reserve(ctx, m.cg, std::max<size_t>(1, model_compat_params(m)) * sizeof(double)));
+    RV_HIP(ctx, hipMemcpyAsync(m.qs.p, Q_all, ((size_t)iterations + 1) * bytes, hipMemcpyHostToDevice, s));
+    RV_HIP(ctx, hipMemcpyAsync(m.dq.p, d_mul_Q, bytes, hipMemcpyHostToDevice, s));
+    RV_TRY(model_backward_on(ctx, cs, iterations, m.qs.as<float>(), m.dq.as<float>(), unary_grad_out ? m.ug.as<float>() : nullptr,
+                             compat_grad_out ? m.cg.as<double>() : nullptr, s));
+    RV_TRY(model_gradients_home(ctx, m, unary_grad_out, compat_grad_out, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_backward_device(rvseg_ctx* ctx, int32_t iterations, const float* d_Q_all, const float* d_d_mul_Q,
+                                             float* d_unary_grad_out, double* d_compat_grad_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(iterations >= 0 && d_Q_all && d_d_mul_Q);
+    return model_backward_on(ctx, cs, iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out, stream_of(ctx, hip_stream));
+}
+
+rvseg_status rvseg_crf_model_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
+                                      float* unary_grad_out, double* compat_grad_out, float* Q_out) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_TRY(objective_arg(ctx, obj));
+    RV_MODEL_ARGS(iterations >= 0 && value_out);
+    CrfModel& m = cs->model;
+    hipStream_t s = ctx->stream;
+    const size_t bytes = (size_t)m.N * m.C * 4;
+    rvseg_crf_objective dev;
+    RV_TRY(model_objective_stage(ctx, m, obj, &dev, s));
+    RV_TRY(dev_reserve(ctx, m.stats, 129 * sizeof(double)));
+    if (unary_grad_out) RV_TRY(dev_reserve(ctx, m.ug, bytes));
+    if (compat_grad_out) RV_TRY(dev_reserve(ctx, m.cg, std::max<size_t>(1, model_compat_params(m)) * sizeof(double)));
+    RV_TRY(model_gradient_on(ctx, cs, iterations, dev, m.stats.as<double>() + 128, unary_grad_out ? m.ug.as<float>() : nullptr,
+                             compat_grad_out ? m.cg.as<double>() : nullptr, nullptr, s));
+    RV_HIP(ctx, hipMemcpyAsync(value_out, m.stats.as<double>() + 128, sizeof(double), hipMemcpyDeviceToHost, s));
+    RV_TRY(model_gradients_home(ctx, m, unary_grad_out, compat_grad_out, s));
+    if (Q_out) RV_HIP(ctx, hipMemcpyAsync(Q_out, m.qs.as<float>() + (size_t)iterations * m.N * m.C, bytes, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
+                                             float* d_unary_grad_out, double* d_compat_grad_out, float* d_Q_out, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_TRY(objective_arg(ctx, obj));
+    RV_MODEL_ARGS(iterations >= 0 && d_value_out);
+    hipStream_t s = stream_of(ctx, hip_stream);
+    timer_reset(ctx);
+    RV_TRY(model_gradient_on(ctx, cs, iterations, *obj, d_value_out, d_unary_grad_out, d_compat_grad_out, d_Q_out, s));
+    timer_mark(ctx, "end", s);
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_set_compat(rvseg_ctx* ctx, int32_t term, const float* params) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(params);
+    CrfModel& m = cs->model;
+    RV_TRY(model_term_arg(ctx, m, term, 0));
+    TermPlan& t = m.plan[term];
+    std::vector<float> hc(t.compat == RVSEG_COMPAT_MATRIX ? (size_t)m.C * m.C : (size_t)m.C);
+    plan_compat(m.C, t.compat, params, t, hc.data());
+    RV_HIP(ctx, hipMemcpyAsync(cs->compat.as<float>() + t.off, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));   // hc is gone when this returns
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_set_unary(rvseg_ctx* ctx, const float* unary, int32_t unary_is_energy) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(unary);
+    CrfModel& m = cs->model;
+    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, (size_t)m.N * m.C * 4, hipMemcpyHostToDevice, ctx->stream));
+    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    m.unary_is_energy = unary_is_energy != 0;
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_set_unary_device(rvseg_ctx* ctx, const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
+    CrfState* cs;
+    RV_TRY(model_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(d_unary);
+    CrfModel& m = cs->model;
+    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, d_unary, (size_t)m.N * m.C * 4, hipMemcpyDeviceToDevice, stream_of(ctx, hip_stream)));
+    m.unary_is_energy = unary_is_energy != 0;
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_logistic_gradient_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* d_unary_grad, const float* d_f,
+                                                double* d_out, void* hip_stream) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    CrfState* cs;
+    RV_TRY(crf_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(N > 0 && C >= 1 && C <= 64 && K >= 1 && d_unary_grad && d_f && d_out);
+    RV_TRY(dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(64) * sizeof(double)));
+    launch_logistic_gradient(d_unary_grad, d_f, N, C, K, cs->learn_partials.as<double>(), d_out, stream_of(ctx, hip_stream));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* unary_grad, const float* f, double* out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    CrfState* cs;
+    RV_TRY(crf_enter(ctx, &cs, __func__));
+    RV_MODEL_ARGS(N > 0 && C >= 1 && C <= 64 && K >= 1 && unary_grad && f && out);
+    hipStream_t s = ctx->stream;
+    // (a live model keeps its own copy of the unary: cs->unary and cs->feat are free staging)
+    RV_TRY(dev_reserve(ctx, cs->unary, (size_t)N * C * 4));
+    RV_TRY(dev_reserve(ctx, cs->feat, (size_t)N * K * 4));
+    RV_TRY(dev_reserve(ctx, cs->lgrad, (size_t)C * K * sizeof(double)));
+    RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_grad, (size_t)N * C * 4, hipMemcpyHostToDevice, s));
+    RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, f, (size_t)N * K * 4, hipMemcpyHostToDevice, s));
+    RV_TRY(rvseg_crf_logistic_gradient_device(ctx, N, C, K, cs->unary.as<float>(), cs->feat.as<float>(), cs->lgrad.as<double>(), s));
+    RV_HIP(ctx, hipMemcpyAsync(out, cs->lgrad.p, (size_t)C * K * sizeof(double), hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
     return RVSEG_OK;
 }
 #undef RV_TRY

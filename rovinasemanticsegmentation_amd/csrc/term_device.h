@@ -1,6 +1,7 @@
 // Device functions of one pairwise term at one (point, class): the slice of the blurred lattice values and the label
 // compatibility.  Shared by the mean field's slice / term update (kernels_meanfield.hip) and by the model kernels
-// (kernels_crf_model.hip), so that all of them round alike.
+// (kernels_crf_model.hip, kernels_crf_learn.hip), so that all of them round alike.  Also the block sum of their double
+// reductions.
 #pragma once
 #include "rvseg_crf.h"
 
@@ -38,6 +39,30 @@ __device__ __forceinline__ float term_compat(bool matrix, const float* wt, const
         out = out + m;
     }
     return out;
+}
+
+// ---- fixed-order double reductions of the model kernels (kernels_crf_model.hip, kernels_crf_learn.hip) ----
+constexpr int KL_THREADS = 256;
+
+// the 64 lanes of a wave, in the fixed order of the xor butterfly (every lane ends with the same sum)
+__device__ __forceinline__ double kl_wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// block sum of one double per thread into *out (thread 0 writes): waves 0..3 added in order
+__device__ __forceinline__ void kl_block_sum(double v, double* sh /* 4 */, double* out) {
+    const double w = kl_wave_sum(v);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();   // sh may still be read by the previous part's thread 0
+    if ((threadIdx.x & 63) == 0) sh[wave] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = sh[0];
+        for (int k = 1; k < KL_THREADS / 64; k++) r = r + sh[k];
+        *out = r;
+    }
 }
 
 }  // namespace rvseg

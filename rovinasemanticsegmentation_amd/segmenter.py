@@ -381,6 +381,7 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_model_set(self.h, N, Cn, len(terms), arr, _ptr(U), 1 if unary_is_energy else 0))
         del keep
         self._crf_model_shape = (N, Cn, len(terms))
+        self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
 
     def crf_model_set_device(self, N, Cn, terms, d_unary, unary_is_energy=True, stream=0):
         arr, keep = _crf_terms(terms, Cn, N, device=True)
@@ -388,6 +389,7 @@ class Context:
                                                              C.c_void_p(stream or None)))
         del keep
         self._crf_model_shape = (N, Cn, len(terms))
+        self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
 
     def crf_model_start(self):
         N, Cn, _ = self._crf_model_shape
@@ -438,6 +440,80 @@ class Context:
         kl = np.empty(iterations + 1, np.float64)
         capi.check(self.h, self.L.rvseg_crf_model_trace(self.h, iterations, _ptr(Q), _ptr(mp), label_mode, unknown_label, _ptr(kl)))
         return Q, mp, kl
+
+    # ---- learning on the kept model (rvseg.h, "Learning on the kept model") ----
+    def crf_model_apply_transpose(self, term, Q):
+        N, Cn, _ = self._crf_model_shape
+        Q = np.ascontiguousarray(Q, np.float32)
+        assert Q.shape == (N, Cn)
+        out = np.empty_like(Q)
+        capi.check(self.h, self.L.rvseg_crf_model_apply_transpose(self.h, term, _ptr(Q), _ptr(out)))
+        return out
+
+    def crf_model_objective(self, objective, Q):
+        """(value, d_mul_Q) of a LogLikelihood / Hamming / IntersectionOverUnion on the marginals Q."""
+        N, Cn, _ = self._crf_model_shape
+        Q = np.ascontiguousarray(Q, np.float32)
+        assert Q.shape == (N, Cn)
+        rec, keep = objective.record(N, Cn)
+        value = np.empty(1, np.float64)
+        dq = np.empty_like(Q)
+        capi.check(self.h, self.L.rvseg_crf_model_objective(self.h, C.byref(rec), _ptr(Q), _ptr(value), _ptr(dq)))
+        del keep
+        return float(value[0]), dq
+
+    def crf_model_backward(self, Q_all, d_mul_Q, unary=True, lbl_cmp=True):
+        """(unary_grad N x C float32, compat_grad float64) from Q[0 .. n] ((n + 1) x N x C) and d_mul_Q; a part not asked
+        for is None."""
+        N, Cn, _ = self._crf_model_shape
+        Q_all = np.ascontiguousarray(Q_all, np.float32)
+        dq = np.ascontiguousarray(d_mul_Q, np.float32)
+        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn) and dq.shape == (N, Cn)
+        ug = np.empty((N, Cn), np.float32) if unary else None
+        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
+        capi.check(self.h, self.L.rvseg_crf_model_backward(self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), _ptr(ug), _ptr(cg)))
+        return ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None)
+
+    def crf_model_gradient(self, iterations, objective, unary=True, lbl_cmp=True, want_Q=False):
+        """rvseg_crf_model_gradient: (value, unary_grad, compat_grad, Q[n]); a part not asked for is None."""
+        N, Cn, _ = self._crf_model_shape
+        rec, keep = objective.record(N, Cn)
+        value = np.empty(1, np.float64)
+        ug = np.empty((N, Cn), np.float32) if unary else None
+        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
+        Q = np.empty((N, Cn), np.float32) if want_Q else None
+        capi.check(self.h, self.L.rvseg_crf_model_gradient(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(Q)))
+        del keep
+        return float(value[0]), ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None), Q
+
+    def crf_model_set_compat(self, term, compatibility):
+        """Replaces the parameters of a term's compatibility (same kind) in the live model: no lattice build."""
+        Cn = self._crf_model_shape[1]
+        cp = np.ascontiguousarray(_compat(compatibility).array(Cn), np.float32)
+        capi.check(self.h, self.L.rvseg_crf_model_set_compat(self.h, term, _ptr(cp)))
+        self._crf_model_params[term] = _compat(compatibility).parameters().shape[0]
+
+    def crf_model_set_unary(self, unary, unary_is_energy=True):
+        N, Cn, _ = self._crf_model_shape
+        U = np.ascontiguousarray(unary, np.float32)
+        assert U.shape == (N, Cn)
+        capi.check(self.h, self.L.rvseg_crf_model_set_unary(self.h, _ptr(U), 1 if unary_is_energy else 0))
+
+    def crf_logistic_gradient(self, unary_grad, f):
+        """LogisticUnaryEnergy::gradient (unary.cpp:64-68): unary_grad (N x C), f (N x K) -> C K doubles, column-major like
+        unaryParameters()."""
+        g = np.ascontiguousarray(unary_grad, np.float32)
+        F = np.ascontiguousarray(f, np.float32)
+        N, Cn = g.shape
+        K = F.shape[1]
+        assert F.shape == (N, K)
+        out = np.empty(Cn * K, np.float64)
+        capi.check(self.h, self.L.rvseg_crf_logistic_gradient(self.h, N, Cn, K, _ptr(g), _ptr(F), _ptr(out)))
+        return out
+
+    def crf_logistic_gradient_device(self, N, Cn, K, d_unary_grad, d_f, d_out, stream=0):
+        capi.check(self.h, self.L.rvseg_crf_logistic_gradient_device(self.h, N, Cn, K, C.c_void_p(d_unary_grad), C.c_void_p(d_f),
+                                                                     C.c_void_p(d_out), C.c_void_p(stream or None)))
 
     def crf_model_call_device(self, name, *args, stream=0):
         """rvseg_crf_model_<name>_device with integer device addresses / integers as in rvseg.h, the stream last; enqueues only."""
@@ -769,6 +845,62 @@ def _crf_terms(terms, M, N, device=False):
     return arr, keep
 
 
+class _Objective:
+    """An ObjectiveFunction of objective.h over ground-truth labels gt (N, int16; a label outside 0 .. C-1 skips its point)."""
+    kind = None
+
+    def __init__(self, gt):
+        self.gt = np.ascontiguousarray(gt, np.int16).reshape(-1)
+        self.robust = 0.0
+
+    def weights(self, M):
+        return None
+
+    def record(self, N, M, d_gt=0, d_class_weight=0):
+        """(rvseg_crf_objective, buffers to keep alive).  d_gt / d_class_weight: device addresses for the _device entries."""
+        assert self.gt.shape == (N,)
+        w = self.weights(M)
+        rec = capi.RvsegCrfObjective(self.kind, d_gt or self.gt.ctypes.data, float(self.robust),
+                                     d_class_weight or (w.ctypes.data if w is not None else None))
+        return rec, (self.gt, w)
+
+
+class LogLikelihood(_Objective):   # objective.cpp:35-50
+    kind = capi.OBJECTIVE_LOGLIKELIHOOD
+
+    def __init__(self, gt, robust=0.0):
+        super().__init__(gt)
+        self.robust = float(robust)
+
+
+class Hamming(_Objective):   # objective.cpp:51-79
+    """Hamming(gt, class_weight_pow) computes the class weights on the host as the reference's constructor does (:51-63,
+    fp32); Hamming(gt, weights) takes them."""
+    kind = capi.OBJECTIVE_HAMMING
+
+    def __init__(self, gt, class_weight_pow=0.0):
+        super().__init__(gt)
+        if np.ndim(class_weight_pow) > 0:
+            self.class_weight = np.array(class_weight_pow, np.float32).reshape(-1)
+            return
+        M = max(0, int(self.gt.max()) + 1) if self.gt.size else 0
+        cnt = np.bincount(self.gt[self.gt >= 0].astype(np.int64), minlength=M).astype(np.float32)
+        with np.errstate(all="ignore"):
+            w = cnt / cnt.sum(dtype=np.float32)
+            w = np.power(w, np.float32(-float(class_weight_pow))).astype(np.float32)
+            self.class_weight = (w / (cnt * w).sum(dtype=np.float32)).astype(np.float32)
+
+    def weights(self, M):
+        w = np.zeros(M, np.float32)   # one weight per class of the model; classes beyond the given ones weigh 0
+        n = min(M, self.class_weight.shape[0])
+        w[:n] = self.class_weight[:n]
+        return w
+
+
+class IntersectionOverUnion(_Objective):   # objective.cpp:80-108
+    kind = capi.OBJECTIVE_IOU
+
+
 class DenseCRF:
     """DenseCRF as Segmenter::processMapFromQueue drives it (src/segmenter.cpp:641-644), and as
     examples/dense_learning.cpp:128-182 builds a learned model (compatibilities, kernel types and parameters,
@@ -815,19 +947,18 @@ class DenseCRF:
         return np.ascontiguousarray(self.logistic[0].T).reshape(-1)
 
     def setUnaryParameters(self, v):   # unary.cpp:58-63
-        self._touch()
         if self.logistic is None:
             return
         L, f = self.logistic
         v = np.asarray(v, np.float32)
         assert v.shape == (L.size,)
         self.logistic = (np.ascontiguousarray(v.reshape(L.shape[1], L.shape[0]).T), f)
+        self._update_model(lambda: self.ctx.crf_model_set_unary(self._unary_energy()))
 
     def labelCompatibilityParameters(self):
         return np.concatenate([np.zeros(0, np.float32)] + [_compat(k[1]).parameters() for k in self.kernels]).astype(np.float32)
 
     def setLabelCompatibilityParameters(self, v):
-        self._touch()
         v = np.asarray(v, np.float32)
         i = 0
         for k in self.kernels:
@@ -836,6 +967,11 @@ class DenseCRF:
             k[1].setParameters(v[i:i + n])
             i += n
         assert i == v.shape[0]
+
+        def update():
+            for t, k in enumerate(self.kernels):
+                self.ctx.crf_model_set_compat(t, k[1])
+        self._update_model(update)
 
     def _kernel_parameters(self, k):   # DenseKernel::parameters, pairwise.cpp:116-125
         d = k[0].shape[1]
@@ -883,6 +1019,19 @@ class DenseCRF:
     def _touch(self):
         self._model_key = None
 
+    def _update_model(self, update):
+        """A parameter change: in place on the context's live model when that model is this object's (no lattice build),
+        else the model is set again by the next call that needs it."""
+        key = getattr(self, "_model_key", None)
+        if key is None or getattr(self.ctx, "_crf_model_owner", None) is not key:
+            return self._touch()
+        try:
+            update()
+        except capi.RvsegError as e:
+            if e.status != capi.ERR_INVALID_ARG or "DenseCRF model" not in str(e):
+                raise
+            self._touch()   # another call replaced the model
+
     def _with_model(self, call):
         """Runs call() on this CRF's model: set lazily, again after any add* / set*Parameters, and again when the context
         reports that another call replaced it."""
@@ -925,6 +1074,64 @@ class DenseCRF:
         """(Q, kl): inference(n) and the KL divergence after the start and after every iteration."""
         Q, _, kl = self._with_model(lambda: self.ctx.crf_model_trace(n_iterations))
         return Q, kl
+
+    # ---- learning (densecrf.cpp:238-297) ----
+    def applyTranspose(self, term, Q):   # pairwise.cpp:179-183
+        return self._with_model(lambda: self.ctx.crf_model_apply_transpose(term, Q))
+
+    def gradient(self, n_iterations, objective, unary=True, lbl_cmp=True, energy_grad=False):
+        """DenseCRF::gradient: (value, unary_grad, lbl_cmp_grad) in fp32 with the reference's signs and layouts: unary_grad
+        is the gradient of unaryParameters() (empty without a logistic unary), lbl_cmp_grad that of
+        labelCompatibilityParameters(); a part not asked for is None.  There is no kernel-parameter gradient.
+        energy_grad: unary_grad is d value / d U (N x M) instead."""
+        value, ug, cg, _ = self._with_model(lambda: self.ctx.crf_model_gradient(n_iterations, objective, unary, lbl_cmp))
+        if unary and not energy_grad:
+            if self.logistic is None:
+                ug = np.zeros(0, np.float32)
+            else:
+                ug = self.ctx.crf_logistic_gradient(ug, self.logistic[1]).astype(np.float32)
+        return value, ug, (cg.astype(np.float32) if lbl_cmp else None)
+
+
+class CRFEnergy:
+    """The EnergyFunction of examples/dense_learning.cpp:38-85 over a DenseCRF: gradient(x) sets the parameters, and returns
+    the negated objective and gradient plus the L2 term, for a minimiser of the caller's.  The kernel parameters cannot be
+    learned: their gradient (Permutohedral::gradient) is outside this library's scope."""
+
+    def __init__(self, crf, objective, NIT, unary=True, pairwise=True, kernel=False):
+        if kernel:
+            raise NotImplementedError("CRFEnergy(kernel=True): the kernel-parameter gradient (DenseCRF::kernelGradient / "
+                                      "Permutohedral::gradient) is out of scope; learn unary and pairwise parameters only")
+        self.crf, self.objective, self.NIT = crf, objective, int(NIT)
+        self.unary, self.pairwise = bool(unary), bool(pairwise)
+        self.initial_u_param = crf.unaryParameters()
+        self.initial_lbl_param = crf.labelCompatibilityParameters()
+        self.l2_norm = np.float32(0.0)
+
+    def setL2Norm(self, norm):
+        self.l2_norm = np.float32(norm)
+
+    def initialValue(self):
+        return np.concatenate([self.initial_u_param if self.unary else np.zeros(0, np.float32),
+                               self.initial_lbl_param if self.pairwise else np.zeros(0, np.float32)]).astype(np.float32)
+
+    def gradient(self, x):
+        """(value, dx) of dense_learning.cpp:60-84."""
+        x = np.asarray(x, np.float32)
+        nu = self.initial_u_param.shape[0] if self.unary else 0
+        nl = self.initial_lbl_param.shape[0] if self.pairwise else 0
+        assert x.shape == (nu + nl,)
+        if self.unary:
+            self.crf.setUnaryParameters(x[:nu])
+        if self.pairwise:
+            self.crf.setLabelCompatibilityParameters(x[nu:])
+        r, du, dl = self.crf.gradient(self.NIT, self.objective, self.unary, self.pairwise)
+        dx = np.concatenate([-du if self.unary else np.zeros(0, np.float32), -dl if self.pairwise else np.zeros(0, np.float32)]).astype(np.float32)
+        r = -r
+        if self.l2_norm > 0:
+            dx = (dx + self.l2_norm * x).astype(np.float32)
+            r += 0.5 * float(self.l2_norm) * float(np.dot(x, x))
+        return r, dx
 
 
 
