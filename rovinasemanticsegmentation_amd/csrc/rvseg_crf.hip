@@ -1,82 +1,14 @@
 // CRF orchestration: lattice construction, normaliser, mean-field loop; the C-ABI entry points rvseg_crf_infer* /
-// rvseg_lattice_* and the CRF stages of the frame pipeline and of the cloud path.
+// rvseg_lattice_* and the CRF stages of the frame pipeline and of the cloud path.  The kept DenseCRF model and learning on it
+// are in rvseg_crf_model.hip; rvseg_crf_state.h holds what the two files share.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-#include "rvseg_crf.h"
-#include "rvseg_pipeline.h"
+#include "rvseg_crf_state.h"
 
 namespace rvseg {
-
-struct LatticeBufs {
-    DevBuf state, tkeys, slot_to_id, counters, vkeys, offsets, bary, nb1, nb2, csr_pw, csr_nrm, vstart, vend, norm;
-    DevBuf keys_in, keys_out, vals_in, vals_out, sort_temp, scan_temp, fstart, vorder, block_hist;
-    DevBuf r_desc, r_vl, r_info, r_small, r_verts, r_jb, r_trace;   // resident band schedule of the splat
-    SplatResidentDev resident{};
-    bool resident_on = false;
-    LatticeDev dev{};
-    SortBuffers sb{};
-    long long n_entries = 0, n_points = 0;
-    bool built = false;
-    bool cleared = false;       // the build's memsets are already enqueued (crf_frames_build_begin)
-    bool has_csr_nrm = false;   // per-entry normaliser (multi-kernel inference only)
-};
-
-// One pairwise term as the mean field runs it.  Potts, and a Diagonal whose entries are all equal, are the same term
-// (Potts(w) == Diagonal(-w, .., -w) bit for bit).
-struct TermPlan {
-    int norm = RVSEG_NORMALIZE_SYMMETRIC;
-    bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
-    float w = 0.f;
-    bool matrix = false;
-    size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
-    int compat = RVSEG_COMPAT_POTTS;   // rvseg_compat_kind: the layout of the term's parameters and of their gradient
-};
-
-// The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
-// CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
-struct CrfModel {
-    bool valid = false;
-    int N = 0, C = 0;
-    bool unary_is_energy = true;
-    std::vector<TermPlan> plan;
-    std::string replaced_by;   // the entry whose lattice build ended the model
-    DevBuf unary;              // N x C, as the caller passed it
-    // staging of the host entries and scratch of the energies / the KL passes (never the mean field's tmp)
-    DevBuf q, rows, onehot, labels, vec, partials, kl;
-    // learning (rvseg_crf_model_objective / _backward / _gradient): Q[0 .. n] of a forward pass, d_mul_Q, the backward
-    // pass's b, tmp1 and tmp2, and the staging of the host entries (gradients, ground truth, class weights)
-    DevBuf qs, dq, bgrad, tsum, tapp, ug, cg, gt, cw;
-    DevBuf stats;              // 128 doubles of IoU sums + the objective's value
-};
-
-struct CrfState {
-    std::vector<LatticeBufs> lat;  // one per pairwise kernel
-    CrfModel model;                // rvseg_crf_model_*
-    const char* entry = "";        // the C-ABI entry at work (crf_enter; the frame and cloud paths name themselves): CrfModel::replaced_by
-    // two slots of mean-field scratch: a second label layer's mean field runs beside the first on its own stream
-    struct { DevBuf val_a, val_b, tmp, qn; } scratch[2];
-    DevBuf q, unary, feat, labels;
-    // learned-model terms (rvseg_crf_infer_terms*): compatibilities of all terms, transformed features, logistic L
-    DevBuf compat, kfeat, lmat;
-    DevBuf learn_partials, lgrad;   // partials of the learning reductions; staging of rvseg_crf_logistic_gradient's result
-    std::vector<float> h_compat;   // host copy of `compat` (the source of its asynchronous upload)
-    Stream layer_stream;   // the second layer's stream; created together with its two events (second_stream)
-    Event layer_fork, layer_join;
-    // pinned read-back of a build: [0] M, [1] overflow, [2] longest vertex list, [3] frames the splat planner gave up on.
-    // Slot 0 (words 0..3) belongs to the asynchronous frame builds (consumed by crf_frames_status), slot 1 (words 4..7)
-    // to the synchronous entry points -- a cloud or host CRF call on the same context must not overwrite a frame
-    // build's status that nobody has polled yet.
-    PinnedBuf h_counters;   // int[8]
-    Event counters_ev;
-    bool counters_pending = false;
-    rvseg_schedule_info info{};    // what the last build ran with (rvseg_last_schedule)
-    int frame_vertices_seen = 0;   // vertices per frame of the last frame build whose status was read (0: none yet)
-    int pending_frames = 0;        // frames of the build whose status is pending
-    bool info_async = false;       // info.vertices / planner_fallback still travel with the pending frame-build status
-};
 
 // the context's CRF state, created by the first call: the pinned counters and their event first, so that a failure
 // leaves nothing behind and the next call tries again
@@ -351,7 +283,7 @@ static rvseg_status lattice_clear(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s)
     return RVSEG_OK;
 }
 
-static void model_replaced(CrfState* cs) {
+void model_replaced(CrfState* cs) {
     if (!cs->model.valid) return;
     cs->model.valid = false;
     cs->model.replaced_by = cs->entry;
@@ -362,7 +294,7 @@ static void model_replaced(CrfState* cs) {
 static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s,
                                   int norm_kind = RVSEG_NORMALIZE_SYMMETRIC) {
     const LatticeDev& L = b.dev;
-    model_replaced(cs);   // a kept model (rvseg_crf_model_*) ends with any lattice build on its context
+    model_replaced(cs);   // a kept DenseCRF model ends with any lattice build on its context
     if (!b.cleared) { rvseg_status stc = lattice_clear(ctx, b, s); if (stc != RVSEG_OK) return stc; }
     b.cleared = false;
     const bool trace = ctx->sched.trace >= 2;
@@ -450,7 +382,7 @@ static rvseg_status lattice_counters(rvseg_ctx* ctx, CrfState* cs, const Lattice
 }
 
 // per-entry copy of the normaliser for the unfused splat (MODE 1); filled once per lattice
-static rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s) {
+rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s) {
     if (b.has_csr_nrm) return RVSEG_OK;
     rvseg_status st = dev_reserve(ctx, b.csr_nrm, (size_t)b.n_entries * 4);
     if (st != RVSEG_OK) return st;
@@ -477,27 +409,11 @@ static TermPlan potts_term(float w) {
 }
 
 // DenseKernel::filter (pairwise.cpp:63-80): the input scaled by the normaliser (SYMMETRIC / BEFORE), the output (SYMMETRIC / AFTER)
-static bool term_pre(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_BEFORE; }
-static bool term_post(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_AFTER; }
-
-// What one mean field reads and where it runs: the terms (term k on cs->lat[k]) with their compatibilities d_compat (may
-// be null when every term is uniform with NORMALIZE_SYMMETRIC), the unary, the shape, the stream and the scratch slot
-// (0 / 1; two layers may run side by side on two streams); timed: record stage marks (only one of two concurrent loops
-// may: the marks are a sequence on ONE stream)
-struct MfRun {
-    const std::vector<TermPlan>& plan;
-    const float* d_compat;
-    ValueView unary;
-    bool unary_is_energy;
-    int C, N;
-    long long n_points;
-    hipStream_t s;
-    int slot;
-    bool timed;
-};
+bool term_pre(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_BEFORE; }
+bool term_post(const TermPlan& t) { return t.norm == RVSEG_NORMALIZE_SYMMETRIC || t.norm == RVSEG_NORMALIZE_AFTER; }
 
 // the scratch of the general loop: tmp and the lattice values of the largest term
-static rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
+rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
     rvseg_status st = dev_reserve(ctx, cs->scratch[r.slot].tmp, (size_t)r.n_points * r.C * 4);
     if (st != RVSEG_OK) return st;
     long long mb = 0;
@@ -506,7 +422,7 @@ static rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
 }
 
 // the general loop scales by the normaliser inside the splat: per-entry copy of norm
-static rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
+rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r) {
     for (size_t k = 0; k < r.plan.size(); k++) {
         rvseg_status st;
         if (term_pre(r.plan[k]) && (st = ensure_csr_nrm(ctx, cs->lat[k], r.s)) != RVSEG_OK) return st;
@@ -515,7 +431,7 @@ static rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r)
 }
 
 // Q = expAndNormalize(-U) (densecrf.cpp:120, :178-186) of the general loop (needs mf_scratch)
-static void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q) {
+void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q) {
     float* tmp = cs->scratch[r.slot].tmp.as<float>();
     if (r.timed) timer_mark(ctx, "softmax", r.s);
     if (!launch_softmax_unary(r.unary, r.unary_is_energy, r.C, r.N, Q, r.n_points, nullptr, r.s)) {
@@ -524,17 +440,13 @@ static void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueVi
     }
 }
 
-// Where a traced step leaves the KL divergence of the Q it starts from: the term passes read the splat and blur the step
-// needs anyway.  partials: [2 + n_terms][KL_MAX_BLOCKS] doubles.
-struct KlTap { double* partials; };
-
 // The entropy and unary parts, and -- when the caller has no blurred values at hand (tap of a step: it has) -- the
 // pairwise parts of Q through a splat and blur of their own.  Q: one dense N x C matrix.
-static void kl_unary_parts(rvseg_ctx* ctx, const MfRun& r, const float* Q, const KlTap& tap) {
+void kl_unary_parts(rvseg_ctx* ctx, const MfRun& r, const float* Q, const KlTap& tap) {
     if (r.timed) timer_mark(ctx, "kl", r.s);
     launch_kl_unary(r.unary.base, r.unary_is_energy, Q, r.C, r.n_points, tap.partials, r.s);
 }
-static void kl_term_part(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* blurred, const float* Q, const KlTap& tap) {
+void kl_term_part(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* blurred, const float* Q, const KlTap& tap) {
     if (r.timed) timer_mark(ctx, "kl", r.s);
     const TermPlan& t = r.plan[k];
     launch_kl_term(cs->lat[k].dev, r.C, r.C <= 2, blurred, term_post(t), t.matrix, r.d_compat + t.off, Q, r.n_points,
@@ -544,7 +456,7 @@ static void kl_term_part(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, co
 // One iteration of the general loop (densecrf.cpp:122-128, stepInference :187-201): tmp = -U, per term splat, blur and
 // slice + compatibility folded into tmp, then Q = expAndNormalize(tmp).  Needs mf_scratch and mf_entry_norms.
 // tap (optional): the KL parts of the incoming Q (a dense N x C matrix then).
-static void mf_step(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q, const KlTap* tap = nullptr) {
+void mf_step(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q, const KlTap* tap) {
     auto& sc = cs->scratch[r.slot];
     float* tmp = sc.tmp.as<float>();
     const int C = r.C, N = r.N;
@@ -635,7 +547,7 @@ static rvseg_status mean_field(rvseg_ctx* ctx, CrfState* cs, const std::vector<T
 
 // PottsCompatibility / DiagonalCompatibility / MatrixCompatibility (labelcompatibility.cpp:38-100) as diagonals and
 // symmetric matrices: W = 0.5 * (m + m^T) elementwise in fp32 when the term is created (:79)
-static void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */) {
+void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */) {
     tp.compat = compat;
     tp.uniform = true;
     tp.matrix = false;
@@ -969,19 +881,35 @@ rvseg_status crf_cloud_layers(rvseg_ctx* ctx, int N, int n_layers, const int* cl
     return RVSEG_OK;
 }
 
-}  // namespace rvseg
-
-using namespace rvseg;
-
 // entry of the C-ABI CRF calls: selects the device; they do not need the frame tables (a bare pipeline will do)
 // (`entry`: its name, which a kept model that it replaces reports)
-static rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
+rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
     const rvseg_status st = crf_state(ctx, cs_out);
     if (st == RVSEG_OK) (*cs_out)->entry = entry;
     return st;
 }
+
+// A learned model's terms (arguments checked by the caller): their plan, their compatibilities in context memory
+// (uploaded from CrfState::h_compat, which outlives the copy; also for Potts terms, which do not read them) and their lattices
+rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
+                           std::vector<TermPlan>& plan, hipStream_t s) {
+    plan_terms(C, n_terms, terms, plan, cs->h_compat);
+    if (!cs->h_compat.empty()) {
+        rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
+        if (st != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemcpyAsync(cs->compat.p, cs->h_compat.data(), cs->h_compat.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    TermInput in[8];
+    for (int k = 0; k < n_terms; k++)
+        in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization};
+    return build_lattices(ctx, cs, N, n_terms, in, s);
+}
+
+}  // namespace rvseg
+
+using namespace rvseg;
 
 extern "C" {
 
@@ -1014,22 +942,6 @@ rvseg_status rvseg_crf_terms_check(int32_t N, int32_t C, int32_t n_terms, const 
         if (t.normalization < RVSEG_NO_NORMALIZATION || t.normalization > RVSEG_NORMALIZE_SYMMETRIC) return RVSEG_ERR_INVALID_ARG;
     }
     return RVSEG_OK;
-}
-
-// A learned model's terms (arguments checked by the caller): their plan, their compatibilities in context memory
-// (uploaded from CrfState::h_compat, which outlives the copy; also for Potts terms, which do not read them) and their lattices
-static rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
-                                  std::vector<TermPlan>& plan, hipStream_t s) {
-    plan_terms(C, n_terms, terms, plan, cs->h_compat);
-    if (!cs->h_compat.empty()) {
-        rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
-        if (st != RVSEG_OK) return st;
-        RV_HIP(ctx, hipMemcpyAsync(cs->compat.p, cs->h_compat.data(), cs->h_compat.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    TermInput in[8];
-    for (int k = 0; k < n_terms; k++)
-        in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization};
-    return build_lattices(ctx, cs, N, n_terms, in, s);
 }
 
 rvseg_status rvseg_crf_infer_terms(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
@@ -1238,675 +1150,5 @@ rvseg_status rvseg_lattice_filter(rvseg_ctx* ctx, const float* in, int32_t C, fl
     RV_HIP(ctx, hipStreamSynchronize(s));
     return RVSEG_OK;
 }
-
-// ---------------------------------------------------------------------------------------------
-// A kept DenseCRF model (rvseg_crf_model_*): the state of the context, valid until its next lattice build.  Each call
-// has one body on device pointers (model_*_on); the host entry stages through CrfModel's buffers and synchronises, the
-// _device entry enqueues on the caller's stream.
-// ---------------------------------------------------------------------------------------------
-static rvseg_status model_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    rvseg_status st = crf_enter(ctx, cs_out, entry);
-    if (st != RVSEG_OK) return st;
-    const CrfModel& m = (*cs_out)->model;
-    if (!m.valid) {
-        ctx->err = m.replaced_by.empty() ? std::string("no DenseCRF model on this context (rvseg_crf_model_set has not succeeded)")
-                                         : "the DenseCRF model of this context was replaced by " + m.replaced_by + ": call rvseg_crf_model_set again";
-        return RVSEG_ERR_INVALID_ARG;
-    }
-    return RVSEG_OK;
-}
-
-static MfRun model_run(CrfState* cs, hipStream_t s, bool timed) {
-    CrfModel& m = cs->model;
-    return MfRun{m.plan, cs->compat.as<float>(), ValueView{m.unary.as<float>(), (size_t)m.N * m.C, 0}, m.unary_is_energy, m.C, m.N, m.N, s, 0, timed};
-}
-
-static ValueView model_view(const CrfModel& m, const float* q) { return ValueView{const_cast<float*>(q), (size_t)m.N * m.C, 0}; }
-
-static rvseg_status model_set_on(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
-                                 int32_t unary_is_energy, bool on_host, void* hip_stream, const char* entry) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    if (rvseg_crf_terms_check(N, C, n_terms, terms) != RVSEG_OK || !unary) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    CrfState* cs;
-    rvseg_status st = crf_enter(ctx, &cs, entry);
-    if (st != RVSEG_OK) return st;
-    hipStream_t s = on_host ? (hipStream_t)ctx->stream : stream_of(ctx, hip_stream);
-    CrfModel& m = cs->model;
-    model_replaced(cs);   // (also a model of no terms, which builds no lattice; a failure below leaves no model)
-    m.replaced_by = entry;
-    const size_t tot = (size_t)N * C;
-    if ((st = dev_reserve(ctx, m.unary, tot * 4)) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, tot * 4, on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    if ((st = terms_prepare(ctx, cs, N, C, n_terms, terms, on_host, m.plan, s)) != RVSEG_OK) return st;
-    // every lattice build has waited for the stream; a model without terms waits here: the caller's buffers are free
-    if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(s));
-    m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
-    m.valid = true;
-    return RVSEG_OK;
-}
-
-static rvseg_status model_start_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, hipStream_t s, bool timed) {
-    const MfRun run = model_run(cs, s, timed);
-    rvseg_status st = mf_scratch(ctx, cs, run);
-    if (st != RVSEG_OK) return st;
-    mf_start(ctx, cs, run, model_view(cs->model, d_Q));
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-static rvseg_status model_step_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, int n_steps, hipStream_t s, bool timed) {
-    const MfRun run = model_run(cs, s, timed);
-    rvseg_status st;
-    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
-    for (int it = 0; it < n_steps; it++) mf_step(ctx, cs, run, model_view(cs->model, d_Q));
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// DenseKernel::filter (pairwise.cpp:63-80) up to its blur: the input scaled where the normalisation says so, splat, blur
-// (transpose: the axes in reverse order).  *post: whether the sliced output is scaled.  Needs mf_scratch.
-static rvseg_status model_filter_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, bool transpose, float** blurred,
-                                      bool* post) {
-    LatticeBufs& b = cs->lat[k];
-    const TermPlan& t = r.plan[k];
-    const bool pre = transpose ? term_post(t) : term_pre(t);
-    *post = transpose ? term_pre(t) : term_post(t);
-    rvseg_status st;
-    if (pre && (st = ensure_csr_nrm(ctx, b, r.s)) != RVSEG_OK) return st;
-    auto& sc = cs->scratch[r.slot];
-    launch_splat(b.dev, model_view(cs->model, d_in), r.C, pre ? 1 : 0, sc.val_a.as<float>(), r.s);
-    *blurred = launch_blur(b.dev, r.C, r.C <= 2, transpose, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
-    return RVSEG_OK;
-}
-
-// pairwise_[term]->apply(out, Q) / applyTranspose (pairwise.cpp:173-183: the filter + the compatibility): needs mf_scratch
-static rvseg_status model_apply_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, float* d_out, bool transpose = false) {
-    const TermPlan& t = r.plan[k];
-    float* blurred;
-    bool post;
-    const rvseg_status st = model_filter_term(ctx, cs, r, k, d_in, transpose, &blurred, &post);
-    if (st != RVSEG_OK) return st;
-    launch_term_update(cs->lat[k].dev, r.C, r.C <= 2, blurred, post, t.matrix, r.d_compat + t.off, d_out, r.n_points, r.s, true);
-    return RVSEG_OK;
-}
-
-static rvseg_status model_term_arg(rvseg_ctx* ctx, const CrfModel& m, int term, int lowest) {
-    if (term >= lowest && term < (int)m.plan.size()) return RVSEG_OK;
-    ctx->err = "no such term in the DenseCRF model";
-    return RVSEG_ERR_INVALID_ARG;
-}
-
-static rvseg_status model_apply_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_in, float* d_out, hipStream_t s, bool transpose = false) {
-    const MfRun run = model_run(cs, s, false);
-    rvseg_status st;
-    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = model_apply_term(ctx, cs, run, term, d_in, d_out, transpose)) != RVSEG_OK) return st;
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// DenseCRF::unaryEnergy / pairwiseEnergy (densecrf.cpp:141-177); term == -1: the terms' energies added in fp32 from 0.0f, ascending
-static rvseg_status model_energy_on(rvseg_ctx* ctx, CrfState* cs, const int8_t* d_labels, int term, float* d_unary_out, float* d_pairwise_out,
-                                    hipStream_t s) {
-    CrfModel& m = cs->model;
-    const MfRun run = model_run(cs, s, false);
-    rvseg_status st;
-    if (d_unary_out) launch_label_gather(m.unary.as<float>(), d_labels, m.N, m.C, m.unary_is_energy ? 1.0f : -1.0f, false, d_unary_out, s);
-    if (d_pairwise_out) {
-        const size_t tot = (size_t)m.N * m.C;
-        if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-        if ((st = dev_reserve(ctx, m.onehot, tot * 4)) != RVSEG_OK) return st;
-        if ((st = dev_reserve(ctx, m.rows, tot * 4)) != RVSEG_OK) return st;
-        if (term < 0) RV_HIP(ctx, hipMemsetAsync(d_pairwise_out, 0, (size_t)m.N * 4, s));
-        launch_onehot(d_labels, m.N, m.C, m.onehot.as<float>(), s);
-        for (int k = term < 0 ? 0 : term; k < (term < 0 ? (int)m.plan.size() : term + 1); k++) {
-            if ((st = model_apply_term(ctx, cs, run, k, m.onehot.as<float>(), m.rows.as<float>())) != RVSEG_OK) return st;
-            launch_label_gather(m.rows.as<float>(), d_labels, m.N, m.C, -0.5f, term < 0, d_pairwise_out, s);
-        }
-    }
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// the KL parts of a Q nobody is about to step: a splat and blur per term of their own.  Needs mf_scratch, mf_entry_norms
-// and CrfModel::partials.
-static void model_kl_parts(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const float* d_Q, const KlTap& tap) {
-    auto& sc = cs->scratch[r.slot];
-    kl_unary_parts(ctx, r, d_Q, tap);
-    for (int k = 0; k < (int)r.plan.size(); k++) {
-        const LatticeBufs& b = cs->lat[k];
-        if (r.timed) timer_mark(ctx, "splat", r.s);
-        launch_splat(b.dev, model_view(cs->model, d_Q), r.C, term_pre(r.plan[k]) ? 1 : 0, sc.val_a.as<float>(), r.s);
-        if (r.timed) timer_mark(ctx, "blur", r.s);
-        float* blurred = launch_blur(b.dev, r.C, r.C <= 2, false, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
-        kl_term_part(ctx, cs, r, k, blurred, d_Q, tap);
-    }
-}
-
-static rvseg_status model_kl_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& run) {
-    rvseg_status st;
-    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
-    return dev_reserve(ctx, cs->model.partials, (size_t)10 * KL_MAX_BLOCKS * sizeof(double));
-}
-
-static rvseg_status model_kl_on(rvseg_ctx* ctx, CrfState* cs, const float* d_Q, double* d_parts, hipStream_t s, bool timed) {
-    CrfModel& m = cs->model;
-    const MfRun run = model_run(cs, s, timed);
-    rvseg_status st = model_kl_scratch(ctx, cs, run);
-    if (st != RVSEG_OK) return st;
-    const KlTap tap{m.partials.as<double>()};
-    model_kl_parts(ctx, cs, run, d_Q, tap);
-    launch_kl_final(tap.partials, kl_blocks(m.C, m.N), 2 + (int)m.plan.size(), d_parts, nullptr, s);
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// inference from the start with the KL divergence after the start and after every iteration: d_kl[0 .. iterations].  The
-// KL of the Q an iteration starts from rides on that iteration's splat and blur (KlTap); only the last Q pays for a filter.
-static rvseg_status model_trace_on(rvseg_ctx* ctx, CrfState* cs, int iterations, float* d_Q, int8_t* d_map, int label_mode, int unknown_label,
-                                   double* d_kl, hipStream_t s, bool timed) {
-    CrfModel& m = cs->model;
-    const MfRun run = model_run(cs, s, timed);
-    rvseg_status st = model_kl_scratch(ctx, cs, run);
-    if (st != RVSEG_OK) return st;
-    const KlTap tap{m.partials.as<double>()};
-    const int blocks = kl_blocks(m.C, m.N), parts = 2 + (int)m.plan.size();
-    const ValueView Q = model_view(m, d_Q);
-    mf_start(ctx, cs, run, Q);
-    for (int it = 0; it < iterations; it++) {
-        mf_step(ctx, cs, run, Q, &tap);
-        launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + it, s);
-    }
-    model_kl_parts(ctx, cs, run, d_Q, tap);
-    launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + iterations, s);
-    if (d_map) {
-        if (timed) timer_mark(ctx, "labels", s);
-        launch_labels(d_Q, (size_t)m.N, m.C, label_mode, unknown_label, d_map, s);
-    }
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Learning on the kept model (include/rvseg.h, "Learning on the kept model"): objective, backward pass, gradient.
-// ---------------------------------------------------------------------------------------------
-static size_t model_compat_params(const CrfModel& m, int upto = -1) {
-    size_t n = 0;
-    const int end = upto < 0 ? (int)m.plan.size() : upto;
-    for (int k = 0; k < end; k++) {
-        const int kind = m.plan[k].compat;
-        n += kind == RVSEG_COMPAT_MATRIX ? (size_t)m.C * (m.C + 1) / 2 : kind == RVSEG_COMPAT_DIAGONAL ? (size_t)m.C : 1;
-    }
-    return n;
-}
-
-static rvseg_status objective_arg(rvseg_ctx* ctx, const rvseg_crf_objective* obj) {
-    if (rvseg_crf_objective_check(obj) == RVSEG_OK) return RVSEG_OK;
-    ctx->err = "bad objective (rvseg_crf_objective_check: kind, gt, class_weight for HAMMING, finite robust)";
-    return RVSEG_ERR_INVALID_ARG;
-}
-
-// obj: device pointers
-static rvseg_status model_objective_on(rvseg_ctx* ctx, CrfState* cs, const rvseg_crf_objective& obj, const float* d_Q, double* d_value,
-                                       float* d_dq, hipStream_t s) {
-    CrfModel& m = cs->model;
-    rvseg_status st;
-    if ((st = dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double))) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.stats, 129 * sizeof(double))) != RVSEG_OK) return st;
-    launch_objective(obj.kind, obj.gt, obj.robust, obj.class_weight, d_Q, m.C, m.N, d_dq, cs->learn_partials.as<double>(), m.stats.as<double>(),
-                     d_value, s);
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// densecrf.cpp:258-296 from d_mul_Q and Q[0 .. n]; d_ug / d_cg may be null
-static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const float* d_Qall, const float* d_dq, float* d_ug,
-                                      double* d_cg, hipStream_t s) {
-    CrfModel& m = cs->model;
-    const MfRun run = model_run(cs, s, false);
-    const size_t tot = (size_t)m.N * m.C;
-    const int n_terms = (int)m.plan.size();
-    rvseg_status st;
-    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.bgrad, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.tsum, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.tapp, tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double))) != RVSEG_OK) return st;
-    float *b = m.bgrad.as<float>(), *tsum = m.tsum.as<float>(), *tapp = m.tapp.as<float>();
-    launch_sum_normalize(d_dq, false, d_Qall + (size_t)iterations * tot, m.C, m.N, b, d_ug, 1, s);
-    if (d_cg && model_compat_params(m)) RV_HIP(ctx, hipMemsetAsync(d_cg, 0, model_compat_params(m) * sizeof(double), s));
-    for (int it = iterations - 1; it >= 0; it--) {
-        const float* Qit = d_Qall + (size_t)it * tot;
-        if (n_terms == 0) RV_HIP(ctx, hipMemsetAsync(tsum, 0, tot * 4, s));   // tmp1.fill(0), :270
-        for (int k = 0; k < n_terms; k++) {
-            if (d_cg) {   // pairwise_[k]->gradient(b, Q[it]) (pairwise.cpp:190-195)
-                float* blurred;
-                bool post;
-                if ((st = model_filter_term(ctx, cs, run, k, Qit, false, &blurred, &post)) != RVSEG_OK) return st;
-                launch_compat_grad(cs->lat[k].dev, m.C, m.C <= 2, blurred, post, m.plan[k].compat, b, m.N, cs->learn_partials.as<double>(),
-                                   d_cg + model_compat_params(m, k), s);
-            }
-            if ((st = model_apply_term(ctx, cs, run, k, b, tapp, true)) != RVSEG_OK) return st;
-            launch_add_rows(k == 0, tapp, tsum, (long long)tot, s);
-        }
-        launch_sum_normalize(tsum, true, Qit, m.C, m.N, b, d_ug, 2, s);
-    }
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-// the forward pass of DenseCRF::gradient (:240-253) keeping Q[0 .. n] in CrfModel::qs, then objective and backward
-static rvseg_status model_gradient_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const rvseg_crf_objective& obj, double* d_value, float* d_ug,
-                                      double* d_cg, float* d_Q_out, hipStream_t s) {
-    CrfModel& m = cs->model;
-    const MfRun run = model_run(cs, s, false);
-    const size_t tot = (size_t)m.N * m.C;
-    rvseg_status st;
-    if ((st = dev_reserve(ctx, m.qs, ((size_t)iterations + 1) * tot * 4)) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.dq, tot * 4)) != RVSEG_OK) return st;
-    if ((st = mf_scratch(ctx, cs, run)) != RVSEG_OK) return st;
-    if ((st = mf_entry_norms(ctx, cs, run)) != RVSEG_OK) return st;
-    float* qs = m.qs.as<float>();
-    mf_start(ctx, cs, run, model_view(m, qs));
-    for (int it = 0; it < iterations; it++) {
-        float* next = qs + (size_t)(it + 1) * tot;
-        RV_HIP(ctx, hipMemcpyAsync(next, qs + (size_t)it * tot, tot * 4, hipMemcpyDeviceToDevice, s));
-        mf_step(ctx, cs, run, model_view(m, next));
-    }
-    RV_LAUNCH_OK(ctx);
-    const float* Qn = qs + (size_t)iterations * tot;
-    if ((st = model_objective_on(ctx, cs, obj, Qn, d_value, m.dq.as<float>(), s)) != RVSEG_OK) return st;
-    if ((st = model_backward_on(ctx, cs, iterations, qs, m.dq.as<float>(), d_ug, d_cg, s)) != RVSEG_OK) return st;
-    if (d_Q_out) RV_HIP(ctx, hipMemcpyAsync(d_Q_out, Qn, tot * 4, hipMemcpyDeviceToDevice, s));
-    return RVSEG_OK;
-}
-
-// the objective of a host entry with gt and class_weight staged in context memory
-static rvseg_status model_objective_stage(rvseg_ctx* ctx, CrfModel& m, const rvseg_crf_objective* obj, rvseg_crf_objective* dev, hipStream_t s) {
-    rvseg_status st;
-    if ((st = dev_reserve(ctx, m.gt, (size_t)m.N * sizeof(int16_t))) != RVSEG_OK) return st;
-    if ((st = dev_reserve(ctx, m.cw, (size_t)m.C * 4)) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(m.gt.p, obj->gt, (size_t)m.N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    if (obj->kind == RVSEG_OBJECTIVE_HAMMING) RV_HIP(ctx, hipMemcpyAsync(m.cw.p, obj->class_weight, (size_t)m.C * 4, hipMemcpyHostToDevice, s));
-    *dev = rvseg_crf_objective{obj->kind, m.gt.as<int16_t>(), obj->robust, m.cw.as<float>()};
-    return RVSEG_OK;
-}
-
-#define RV_TRY(call) do { const rvseg_status st_ = (call); if (st_ != RVSEG_OK) return st_; } while (0)
-#define RV_MODEL_ARGS(ok) do { if (!(ok)) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; } } while (0)
-
-rvseg_status rvseg_crf_model_set(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
-                                 int32_t unary_is_energy) {
-    return model_set_on(ctx, N, C, n_terms, terms, unary, unary_is_energy, true, nullptr, __func__);
-}
-
-rvseg_status rvseg_crf_model_set_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
-                                        const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
-    return model_set_on(ctx, N, C, n_terms, terms, d_unary, unary_is_energy, false, hip_stream, __func__);
-}
-
-rvseg_status rvseg_crf_model_start(rvseg_ctx* ctx, float* Q_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(Q_out);
-    CrfModel& m = cs->model;
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(model_start_on(ctx, cs, m.q.as<float>(), ctx->stream, false));
-    RV_HIP(ctx, hipMemcpyAsync(Q_out, m.q.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_start_device(rvseg_ctx* ctx, float* d_Q_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_Q_out);
-    hipStream_t s = stream_of(ctx, hip_stream);
-    timer_reset(ctx);
-    RV_TRY(model_start_on(ctx, cs, d_Q_out, s, true));
-    timer_mark(ctx, "end", s);
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_step(rvseg_ctx* ctx, float* Q_inout, int32_t n_steps) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(Q_inout && n_steps >= 0);
-    CrfModel& m = cs->model;
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q_inout, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RV_TRY(model_step_on(ctx, cs, m.q.as<float>(), n_steps, ctx->stream, false));
-    RV_HIP(ctx, hipMemcpyAsync(Q_inout, m.q.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_step_device(rvseg_ctx* ctx, float* d_Q_inout, int32_t n_steps, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_Q_inout && n_steps >= 0);
-    hipStream_t s = stream_of(ctx, hip_stream);
-    timer_reset(ctx);
-    RV_TRY(model_step_on(ctx, cs, d_Q_inout, n_steps, s, true));
-    timer_mark(ctx, "end", s);
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_apply(rvseg_ctx* ctx, int32_t term, const float* Q_in, float* out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(Q_in && out);
-    CrfModel& m = cs->model;
-    RV_TRY(model_term_arg(ctx, m, term, 0));
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(dev_reserve(ctx, m.rows, bytes));
-    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q_in, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RV_TRY(model_apply_on(ctx, cs, term, m.q.as<float>(), m.rows.as<float>(), ctx->stream));
-    RV_HIP(ctx, hipMemcpyAsync(out, m.rows.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_apply_device(rvseg_ctx* ctx, int32_t term, const float* d_Q_in, float* d_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_Q_in && d_out);
-    RV_TRY(model_term_arg(ctx, cs->model, term, 0));
-    return model_apply_on(ctx, cs, term, d_Q_in, d_out, stream_of(ctx, hip_stream));
-}
-
-rvseg_status rvseg_crf_model_energy(rvseg_ctx* ctx, const int8_t* labels, int32_t term, float* unary_out, float* pairwise_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(labels && (unary_out || pairwise_out));
-    CrfModel& m = cs->model;
-    if (pairwise_out) RV_TRY(model_term_arg(ctx, m, term, -1));
-    hipStream_t s = ctx->stream;
-    const size_t N = (size_t)m.N;
-    RV_TRY(dev_reserve(ctx, m.labels, N));
-    RV_TRY(dev_reserve(ctx, m.vec, 2 * N * 4));
-    RV_HIP(ctx, hipMemcpyAsync(m.labels.p, labels, N, hipMemcpyHostToDevice, s));
-    float* d_u = m.vec.as<float>();
-    float* d_p = d_u + N;
-    RV_TRY(model_energy_on(ctx, cs, m.labels.as<int8_t>(), term, unary_out ? d_u : nullptr, pairwise_out ? d_p : nullptr, s));
-    if (unary_out) RV_HIP(ctx, hipMemcpyAsync(unary_out, d_u, N * 4, hipMemcpyDeviceToHost, s));
-    if (pairwise_out) RV_HIP(ctx, hipMemcpyAsync(pairwise_out, d_p, N * 4, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_energy_device(rvseg_ctx* ctx, const int8_t* d_labels, int32_t term, float* d_unary_out, float* d_pairwise_out,
-                                           void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_labels && (d_unary_out || d_pairwise_out));
-    if (d_pairwise_out) RV_TRY(model_term_arg(ctx, cs->model, term, -1));
-    return model_energy_on(ctx, cs, d_labels, term, d_unary_out, d_pairwise_out, stream_of(ctx, hip_stream));
-}
-
-rvseg_status rvseg_crf_model_kl(rvseg_ctx* ctx, const float* Q, double* parts) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(Q && parts);
-    CrfModel& m = cs->model;
-    hipStream_t s = ctx->stream;
-    const size_t bytes = (size_t)m.N * m.C * 4, n_parts = 2 + m.plan.size();
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(dev_reserve(ctx, m.kl, n_parts * sizeof(double)));
-    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q, bytes, hipMemcpyHostToDevice, s));
-    RV_TRY(model_kl_on(ctx, cs, m.q.as<float>(), m.kl.as<double>(), s, false));
-    RV_HIP(ctx, hipMemcpyAsync(parts, m.kl.p, n_parts * sizeof(double), hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_kl_device(rvseg_ctx* ctx, const float* d_Q, double* d_parts, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_Q && d_parts);
-    hipStream_t s = stream_of(ctx, hip_stream);
-    timer_reset(ctx);
-    RV_TRY(model_kl_on(ctx, cs, d_Q, d_parts, s, true));
-    timer_mark(ctx, "end", s);
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_trace(rvseg_ctx* ctx, int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label,
-                                   double* kl_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(iterations >= 0 && Q_out && kl_out && label_mode >= 0 && label_mode <= 3);
-    CrfModel& m = cs->model;
-    hipStream_t s = ctx->stream;
-    const size_t N = (size_t)m.N, bytes = N * m.C * 4, n_kl = (size_t)iterations + 1;
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(dev_reserve(ctx, m.kl, n_kl * sizeof(double)));
-    if (map_out) RV_TRY(dev_reserve(ctx, m.labels, N));
-    RV_TRY(model_trace_on(ctx, cs, iterations, m.q.as<float>(), map_out ? m.labels.as<int8_t>() : nullptr, label_mode, unknown_label,
-                          m.kl.as<double>(), s, false));
-    RV_HIP(ctx, hipMemcpyAsync(Q_out, m.q.p, bytes, hipMemcpyDeviceToHost, s));
-    if (map_out) RV_HIP(ctx, hipMemcpyAsync(map_out, m.labels.p, N, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipMemcpyAsync(kl_out, m.kl.p, n_kl * sizeof(double), hipMemcpyDeviceToHost, s));   // the one read-back
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_trace_device(rvseg_ctx* ctx, int32_t iterations, float* d_Q_out, int8_t* d_map_out, int32_t label_mode,
-                                          int32_t unknown_label, double* d_kl_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(iterations >= 0 && d_Q_out && d_kl_out && label_mode >= 0 && label_mode <= 3);
-    hipStream_t s = stream_of(ctx, hip_stream);
-    timer_reset(ctx);
-    RV_TRY(model_trace_on(ctx, cs, iterations, d_Q_out, d_map_out, label_mode, unknown_label, d_kl_out, s, true));
-    timer_mark(ctx, "end", s);
-    return RVSEG_OK;
-}
-rvseg_status rvseg_crf_objective_check(const rvseg_crf_objective* obj) {
-    if (!obj || obj->kind < RVSEG_OBJECTIVE_LOGLIKELIHOOD || obj->kind > RVSEG_OBJECTIVE_IOU || !obj->gt) return RVSEG_ERR_INVALID_ARG;
-    if (obj->kind == RVSEG_OBJECTIVE_HAMMING && !obj->class_weight) return RVSEG_ERR_INVALID_ARG;
-    if (!std::isfinite(obj->robust)) return RVSEG_ERR_INVALID_ARG;
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_apply_transpose(rvseg_ctx* ctx, int32_t term, const float* in, float* out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(in && out);
-    CrfModel& m = cs->model;
-    RV_TRY(model_term_arg(ctx, m, term, 0));
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(dev_reserve(ctx, m.rows, bytes));
-    RV_HIP(ctx, hipMemcpyAsync(m.q.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RV_TRY(model_apply_on(ctx, cs, term, m.q.as<float>(), m.rows.as<float>(), ctx->stream, true));
-    RV_HIP(ctx, hipMemcpyAsync(out, m.rows.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_apply_transpose_device(rvseg_ctx* ctx, int32_t term, const float* d_in, float* d_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_in && d_out);
-    RV_TRY(model_term_arg(ctx, cs->model, term, 0));
-    return model_apply_on(ctx, cs, term, d_in, d_out, stream_of(ctx, hip_stream), true);
-}
-
-rvseg_status rvseg_crf_model_objective(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* Q, double* value_out, float* d_mul_Q_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_TRY(objective_arg(ctx, obj));
-    RV_MODEL_ARGS(Q && value_out && d_mul_Q_out);
-    CrfModel& m = cs->model;
-    hipStream_t s = ctx->stream;
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    rvseg_crf_objective dev;
-    RV_TRY(model_objective_stage(ctx, m, obj, &dev, s));
-    RV_TRY(dev_reserve(ctx, m.q, bytes));
-    RV_TRY(dev_reserve(ctx, m.dq, bytes));
-    RV_TRY(dev_reserve(ctx, m.stats, 129 * sizeof(double)));
-    RV_HIP(ctx, hipMemcpyAsync(m.q.p, Q, bytes, hipMemcpyHostToDevice, s));
-    RV_TRY(model_objective_on(ctx, cs, dev, m.q.as<float>(), m.stats.as<double>() + 128, m.dq.as<float>(), s));
-    RV_HIP(ctx, hipMemcpyAsync(value_out, m.stats.as<double>() + 128, sizeof(double), hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipMemcpyAsync(d_mul_Q_out, m.dq.p, bytes, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_objective_device(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* d_Q, double* d_value_out,
-                                              float* d_d_mul_Q_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_TRY(objective_arg(ctx, obj));
-    RV_MODEL_ARGS(d_Q && d_value_out && d_d_mul_Q_out);
-    return model_objective_on(ctx, cs, *obj, d_Q, d_value_out, d_d_mul_Q_out, stream_of(ctx, hip_stream));
-}
-
-// downloads of the gradients a host entry staged in CrfModel::ug / cg
-static rvseg_status model_gradients_home(rvseg_ctx* ctx, CrfModel& m, float* unary_grad_out, double* compat_grad_out, hipStream_t s) {
-    if (unary_grad_out) RV_HIP(ctx, hipMemcpyAsync(unary_grad_out, m.ug.p, (size_t)m.N * m.C * 4, hipMemcpyDeviceToHost, s));
-    const size_t n_cg = model_compat_params(m);
-    if (compat_grad_out && n_cg) RV_HIP(ctx, hipMemcpyAsync(compat_grad_out, m.cg.p, n_cg * sizeof(double), hipMemcpyDeviceToHost, s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_backward(rvseg_ctx* ctx, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
-                                      double* compat_grad_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(iterations >= 0 && Q_all && d_mul_Q);
-    CrfModel& m = cs->model;
-    hipStream_t s = ctx->stream;
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    RV_TRY(dev_reserve(ctx, m.qs, ((size_t)iterations + 1) * bytes));
-    RV_TRY(dev_reserve(ctx, m.dq, bytes));
-    if (unary_grad_out) RV_TRY(dev_reserve(ctx, m.ug, bytes));
-    if (compat_grad_out) RV_TRY(dev_reserve(ctx, m.cg, std::max<size_t>(1, model_compat_params(m)) * sizeof(double)));
-    RV_HIP(ctx, hipMemcpyAsync(m.qs.p, Q_all, ((size_t)iterations + 1) * bytes, hipMemcpyHostToDevice, s));
-    RV_HIP(ctx, hipMemcpyAsync(m.dq.p, d_mul_Q, bytes, hipMemcpyHostToDevice, s));
-    RV_TRY(model_backward_on(ctx, cs, iterations, m.qs.as<float>(), m.dq.as<float>(), unary_grad_out ? m.ug.as<float>() : nullptr,
-                             compat_grad_out ? m.cg.as<double>() : nullptr, s));
-    RV_TRY(model_gradients_home(ctx, m, unary_grad_out, compat_grad_out, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_backward_device(rvseg_ctx* ctx, int32_t iterations, const float* d_Q_all, const float* d_d_mul_Q,
-                                             float* d_unary_grad_out, double* d_compat_grad_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(iterations >= 0 && d_Q_all && d_d_mul_Q);
-    return model_backward_on(ctx, cs, iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out, stream_of(ctx, hip_stream));
-}
-
-rvseg_status rvseg_crf_model_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
-                                      float* unary_grad_out, double* compat_grad_out, float* Q_out) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_TRY(objective_arg(ctx, obj));
-    RV_MODEL_ARGS(iterations >= 0 && value_out);
-    CrfModel& m = cs->model;
-    hipStream_t s = ctx->stream;
-    const size_t bytes = (size_t)m.N * m.C * 4;
-    rvseg_crf_objective dev;
-    RV_TRY(model_objective_stage(ctx, m, obj, &dev, s));
-    RV_TRY(dev_reserve(ctx, m.stats, 129 * sizeof(double)));
-    if (unary_grad_out) RV_TRY(dev_reserve(ctx, m.ug, bytes));
-    if (compat_grad_out) RV_TRY(dev_reserve(ctx, m.cg, std::max<size_t>(1, model_compat_params(m)) * sizeof(double)));
-    RV_TRY(model_gradient_on(ctx, cs, iterations, dev, m.stats.as<double>() + 128, unary_grad_out ? m.ug.as<float>() : nullptr,
-                             compat_grad_out ? m.cg.as<double>() : nullptr, nullptr, s));
-    RV_HIP(ctx, hipMemcpyAsync(value_out, m.stats.as<double>() + 128, sizeof(double), hipMemcpyDeviceToHost, s));
-    RV_TRY(model_gradients_home(ctx, m, unary_grad_out, compat_grad_out, s));
-    if (Q_out) RV_HIP(ctx, hipMemcpyAsync(Q_out, m.qs.as<float>() + (size_t)iterations * m.N * m.C, bytes, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
-                                             float* d_unary_grad_out, double* d_compat_grad_out, float* d_Q_out, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_TRY(objective_arg(ctx, obj));
-    RV_MODEL_ARGS(iterations >= 0 && d_value_out);
-    hipStream_t s = stream_of(ctx, hip_stream);
-    timer_reset(ctx);
-    RV_TRY(model_gradient_on(ctx, cs, iterations, *obj, d_value_out, d_unary_grad_out, d_compat_grad_out, d_Q_out, s));
-    timer_mark(ctx, "end", s);
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_set_compat(rvseg_ctx* ctx, int32_t term, const float* params) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(params);
-    CrfModel& m = cs->model;
-    RV_TRY(model_term_arg(ctx, m, term, 0));
-    TermPlan& t = m.plan[term];
-    std::vector<float> hc(t.compat == RVSEG_COMPAT_MATRIX ? (size_t)m.C * m.C : (size_t)m.C);
-    plan_compat(m.C, t.compat, params, t, hc.data());
-    RV_HIP(ctx, hipMemcpyAsync(cs->compat.as<float>() + t.off, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));   // hc is gone when this returns
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_set_unary(rvseg_ctx* ctx, const float* unary, int32_t unary_is_energy) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(unary);
-    CrfModel& m = cs->model;
-    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, (size_t)m.N * m.C * 4, hipMemcpyHostToDevice, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m.unary_is_energy = unary_is_energy != 0;
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_model_set_unary_device(rvseg_ctx* ctx, const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
-    CrfState* cs;
-    RV_TRY(model_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(d_unary);
-    CrfModel& m = cs->model;
-    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, d_unary, (size_t)m.N * m.C * 4, hipMemcpyDeviceToDevice, stream_of(ctx, hip_stream)));
-    m.unary_is_energy = unary_is_energy != 0;
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_logistic_gradient_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* d_unary_grad, const float* d_f,
-                                                double* d_out, void* hip_stream) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    CrfState* cs;
-    RV_TRY(crf_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(N > 0 && C >= 1 && C <= 64 && K >= 1 && d_unary_grad && d_f && d_out);
-    RV_TRY(dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(64) * sizeof(double)));
-    launch_logistic_gradient(d_unary_grad, d_f, N, C, K, cs->learn_partials.as<double>(), d_out, stream_of(ctx, hip_stream));
-    RV_LAUNCH_OK(ctx);
-    return RVSEG_OK;
-}
-
-rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* unary_grad, const float* f, double* out) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    CrfState* cs;
-    RV_TRY(crf_enter(ctx, &cs, __func__));
-    RV_MODEL_ARGS(N > 0 && C >= 1 && C <= 64 && K >= 1 && unary_grad && f && out);
-    hipStream_t s = ctx->stream;
-    // (a live model keeps its own copy of the unary: cs->unary and cs->feat are free staging)
-    RV_TRY(dev_reserve(ctx, cs->unary, (size_t)N * C * 4));
-    RV_TRY(dev_reserve(ctx, cs->feat, (size_t)N * K * 4));
-    RV_TRY(dev_reserve(ctx, cs->lgrad, (size_t)C * K * sizeof(double)));
-    RV_HIP(ctx, hipMemcpyAsync(cs->unary.p, unary_grad, (size_t)N * C * 4, hipMemcpyHostToDevice, s));
-    RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, f, (size_t)N * K * 4, hipMemcpyHostToDevice, s));
-    RV_TRY(rvseg_crf_logistic_gradient_device(ctx, N, C, K, cs->unary.as<float>(), cs->feat.as<float>(), cs->lgrad.as<double>(), s));
-    RV_HIP(ctx, hipMemcpyAsync(out, cs->lgrad.p, (size_t)C * K * sizeof(double), hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    return RVSEG_OK;
-}
-#undef RV_TRY
-#undef RV_MODEL_ARGS
 
 }  // extern "C"

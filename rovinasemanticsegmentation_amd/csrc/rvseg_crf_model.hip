@@ -1,0 +1,611 @@
+// A kept DenseCRF model (rvseg_crf_model_*) and learning on it: the state of the context, valid until its next lattice
+// build.  Each call has one body on device pointers (model_*_on) and one entry body (arguments, staging); a ModelIo
+// tells the entry body whether it serves the host entry or the _device entry.
+#include <algorithm>
+#include <cassert>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "rvseg_crf_state.h"
+
+using namespace rvseg;
+
+#define RV_TRY(call) do { const rvseg_status st_ = (call); if (st_ != RVSEG_OK) return st_; } while (0)
+#define RV_MODEL_ARGS(ok) do { if (!(ok)) { io.ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; } } while (0)
+
+// How the arrays of an entry reach the device (what PointIo is to crf_points).  on_host: caller host memory, staged through
+// buffers of the context on ctx->stream; the call returns with its outputs complete and records no stage marks.
+// Otherwise device memory, used in place on the caller's stream, and the call only enqueues.  in() and out() turn an
+// entry's pointer argument into the pointer its kernels use (a null pointer stays null).
+namespace {
+struct ModelIo {
+    rvseg_ctx* ctx;
+    bool on_host;
+    void* hip_stream;      // of a device entry (null: the context's own)
+    const char* entry;     // the public entry's name
+    CrfState* cs = nullptr;    // (enter)
+    hipStream_t s = nullptr;   // (enter)
+    bool timed = false;        // a device entry that records stage marks (time)
+    static constexpr int MAX_HOME = 4;
+    struct { void* host; const void* dev; size_t bytes; } home[MAX_HOME];   // the downloads of a host entry, in order (done)
+    int n_home = 0;
+
+    // the entry's first step: the device, the CRF state and (need_model) its live model, the stream
+    rvseg_status enter(bool need_model = true) {
+        RV_TRY(crf_enter(ctx, &cs, entry));   // (refuses a null ctx)
+        s = on_host ? (hipStream_t)ctx->stream : stream_of(ctx, hip_stream);
+        const CrfModel& m = cs->model;
+        if (!need_model || m.valid) return RVSEG_OK;
+        ctx->err = m.replaced_by.empty() ? std::string("no DenseCRF model on this context (rvseg_crf_model_set has not succeeded)")
+                                         : "the DenseCRF model of this context was replaced by " + m.replaced_by + ": call rvseg_crf_model_set again";
+        return RVSEG_ERR_INVALID_ARG;
+    }
+    // the n elements of *p copied into `stage`
+    template <class T> rvseg_status in(DevBuf& stage, T** p, size_t n) {
+        if (!on_host || !*p) return RVSEG_OK;
+        RV_TRY(dev_reserve(ctx, stage, n * sizeof(T)));
+        RV_HIP(ctx, hipMemcpyAsync(stage.p, *p, n * sizeof(T), hipMemcpyHostToDevice, s));
+        *p = stage.as<T>();
+        return RVSEG_OK;
+    }
+    // the n elements of *p written into `stage` and downloaded by done()
+    template <class T> rvseg_status out(DevBuf& stage, T** p, size_t n) {
+        if (!on_host || !*p) return RVSEG_OK;
+        RV_TRY(dev_reserve(ctx, stage, std::max<size_t>(1, n * sizeof(T))));
+        out_at(stage.as<T>(), p, n);
+        return RVSEG_OK;
+    }
+    // the same from device memory `d` that out() did not reserve (at most MAX_HOME downloads per call)
+    template <class T> void out_at(T* d, T** p, size_t n) {
+        if (!on_host || !*p) return;
+        assert(n == 0 || n_home < MAX_HOME);
+        if (n) home[n_home++] = {*p, d, n * sizeof(T)};
+        *p = d;
+    }
+    // start, step, kl, trace and gradient record stage marks when they are device entries
+    bool time() {
+        timed = !on_host;
+        if (timed) timer_reset(ctx);
+        return timed;
+    }
+    rvseg_status done() {
+        if (timed) timer_mark(ctx, "end", s);
+        if (!on_host) return RVSEG_OK;
+        for (int i = 0; i < n_home; i++) RV_HIP(ctx, hipMemcpyAsync(home[i].host, home[i].dev, home[i].bytes, hipMemcpyDeviceToHost, s));
+        RV_HIP(ctx, hipStreamSynchronize(s));
+        return RVSEG_OK;
+    }
+};
+}  // namespace
+
+static ModelIo host_io(rvseg_ctx* ctx, const char* entry) { return ModelIo{ctx, true, nullptr, entry}; }
+static ModelIo device_io(rvseg_ctx* ctx, void* hip_stream, const char* entry) { return ModelIo{ctx, false, hip_stream, entry}; }
+
+static MfRun model_run(CrfState* cs, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    return MfRun{m.plan, cs->compat.as<float>(), ValueView{m.unary.as<float>(), (size_t)m.N * m.C, 0}, m.unary_is_energy, m.C, m.N, m.N, s, 0, timed};
+}
+
+static ValueView model_view(const CrfModel& m, const float* q) { return ValueView{const_cast<float*>(q), (size_t)m.N * m.C, 0}; }
+
+static rvseg_status model_set(ModelIo io, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
+                              int32_t unary_is_energy) {
+    rvseg_ctx* ctx = io.ctx;
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    RV_MODEL_ARGS(rvseg_crf_terms_check(N, C, n_terms, terms) == RVSEG_OK && unary);
+    RV_TRY(io.enter(false));
+    CrfModel& m = io.cs->model;
+    model_replaced(io.cs);   // (also a model of no terms, which builds no lattice; a failure below leaves no model)
+    m.replaced_by = io.entry;
+    const size_t tot = (size_t)N * C;
+    RV_TRY(dev_reserve(ctx, m.unary, tot * 4));
+    RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, tot * 4, io.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, io.s));
+    RV_TRY(terms_prepare(ctx, io.cs, N, C, n_terms, terms, io.on_host, m.plan, io.s));
+    // every lattice build has waited for the stream; a model without terms waits here: the caller's buffers are free
+    if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(io.s));
+    m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
+    m.valid = true;
+    return RVSEG_OK;
+}
+
+static rvseg_status model_start_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, hipStream_t s, bool timed) {
+    const MfRun run = model_run(cs, s, timed);
+    RV_TRY(mf_scratch(ctx, cs, run));
+    mf_start(ctx, cs, run, model_view(cs->model, d_Q));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+static rvseg_status model_step_on(rvseg_ctx* ctx, CrfState* cs, float* d_Q, int n_steps, hipStream_t s, bool timed) {
+    const MfRun run = model_run(cs, s, timed);
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(mf_entry_norms(ctx, cs, run));
+    for (int it = 0; it < n_steps; it++) mf_step(ctx, cs, run, model_view(cs->model, d_Q));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// DenseKernel::filter (pairwise.cpp:63-80) up to its blur: the input scaled where the normalisation says so, splat, blur
+// (transpose: the axes in reverse order).  *post: whether the sliced output is scaled.  Needs mf_scratch.
+static rvseg_status model_filter_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, bool transpose, float** blurred,
+                                      bool* post) {
+    LatticeBufs& b = cs->lat[k];
+    const TermPlan& t = r.plan[k];
+    const bool pre = transpose ? term_post(t) : term_pre(t);
+    *post = transpose ? term_pre(t) : term_post(t);
+    if (pre) RV_TRY(ensure_csr_nrm(ctx, b, r.s));
+    auto& sc = cs->scratch[r.slot];
+    if (r.timed) timer_mark(ctx, "splat", r.s);
+    launch_splat(b.dev, model_view(cs->model, d_in), r.C, pre ? 1 : 0, sc.val_a.as<float>(), r.s);
+    if (r.timed) timer_mark(ctx, "blur", r.s);
+    *blurred = launch_blur(b.dev, r.C, r.C <= 2, transpose, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+    return RVSEG_OK;
+}
+
+// pairwise_[term]->apply(out, Q) / applyTranspose (pairwise.cpp:173-183: the filter + the compatibility): needs mf_scratch
+static rvseg_status model_apply_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* d_in, float* d_out, bool transpose = false) {
+    const TermPlan& t = r.plan[k];
+    float* blurred;
+    bool post;
+    RV_TRY(model_filter_term(ctx, cs, r, k, d_in, transpose, &blurred, &post));
+    launch_term_update(cs->lat[k].dev, r.C, r.C <= 2, blurred, post, t.matrix, r.d_compat + t.off, d_out, r.n_points, r.s, true);
+    return RVSEG_OK;
+}
+
+static rvseg_status model_term_arg(rvseg_ctx* ctx, const CrfModel& m, int term, int lowest) {
+    if (term >= lowest && term < (int)m.plan.size()) return RVSEG_OK;
+    ctx->err = "no such term in the DenseCRF model";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+static rvseg_status model_apply_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_in, float* d_out, hipStream_t s, bool transpose) {
+    const MfRun run = model_run(cs, s, false);
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(model_apply_term(ctx, cs, run, term, d_in, d_out, transpose));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// DenseCRF::unaryEnergy / pairwiseEnergy (densecrf.cpp:141-177); term == -1: the terms' energies added in fp32 from 0.0f, ascending
+static rvseg_status model_energy_on(rvseg_ctx* ctx, CrfState* cs, const int8_t* d_labels, int term, float* d_unary_out, float* d_pairwise_out,
+                                    hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    if (d_unary_out) launch_label_gather(m.unary.as<float>(), d_labels, m.N, m.C, m.unary_is_energy ? 1.0f : -1.0f, false, d_unary_out, s);
+    if (d_pairwise_out) {
+        const size_t tot = (size_t)m.N * m.C;
+        RV_TRY(mf_scratch(ctx, cs, run));
+        RV_TRY(dev_reserve(ctx, m.onehot, tot * 4));
+        RV_TRY(dev_reserve(ctx, m.rows, tot * 4));
+        if (term < 0) RV_HIP(ctx, hipMemsetAsync(d_pairwise_out, 0, (size_t)m.N * 4, s));
+        launch_onehot(d_labels, m.N, m.C, m.onehot.as<float>(), s);
+        for (int k = term < 0 ? 0 : term; k < (term < 0 ? (int)m.plan.size() : term + 1); k++) {
+            RV_TRY(model_apply_term(ctx, cs, run, k, m.onehot.as<float>(), m.rows.as<float>()));
+            launch_label_gather(m.rows.as<float>(), d_labels, m.N, m.C, -0.5f, term < 0, d_pairwise_out, s);
+        }
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// the KL parts of a Q nobody is about to step: a filter per term of their own.  Needs mf_scratch, mf_entry_norms (which
+// leaves model_filter_term's ensure_csr_nrm nothing to do) and CrfModel::partials.
+static rvseg_status model_kl_parts(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const float* d_Q, const KlTap& tap) {
+    kl_unary_parts(ctx, r, d_Q, tap);
+    for (int k = 0; k < (int)r.plan.size(); k++) {
+        float* blurred;
+        bool post;
+        RV_TRY(model_filter_term(ctx, cs, r, k, d_Q, false, &blurred, &post));
+        kl_term_part(ctx, cs, r, k, blurred, d_Q, tap);
+    }
+    return RVSEG_OK;
+}
+
+static rvseg_status model_kl_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& run) {
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(mf_entry_norms(ctx, cs, run));
+    return dev_reserve(ctx, cs->model.partials, (size_t)10 * KL_MAX_BLOCKS * sizeof(double));
+}
+
+static rvseg_status model_kl_on(rvseg_ctx* ctx, CrfState* cs, const float* d_Q, double* d_parts, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, timed);
+    RV_TRY(model_kl_scratch(ctx, cs, run));
+    const KlTap tap{m.partials.as<double>()};
+    RV_TRY(model_kl_parts(ctx, cs, run, d_Q, tap));
+    launch_kl_final(tap.partials, kl_blocks(m.C, m.N), 2 + (int)m.plan.size(), d_parts, nullptr, s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// inference from the start with the KL divergence after the start and after every iteration: d_kl[0 .. iterations].  The
+// KL of the Q an iteration starts from rides on that iteration's splat and blur (KlTap); only the last Q pays for a filter.
+static rvseg_status model_trace_on(rvseg_ctx* ctx, CrfState* cs, int iterations, float* d_Q, int8_t* d_map, int label_mode, int unknown_label,
+                                   double* d_kl, hipStream_t s, bool timed) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, timed);
+    RV_TRY(model_kl_scratch(ctx, cs, run));
+    const KlTap tap{m.partials.as<double>()};
+    const int blocks = kl_blocks(m.C, m.N), parts = 2 + (int)m.plan.size();
+    const ValueView Q = model_view(m, d_Q);
+    mf_start(ctx, cs, run, Q);
+    for (int it = 0; it < iterations; it++) {
+        mf_step(ctx, cs, run, Q, &tap);
+        launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + it, s);
+    }
+    RV_TRY(model_kl_parts(ctx, cs, run, d_Q, tap));
+    launch_kl_final(tap.partials, blocks, parts, nullptr, d_kl + iterations, s);
+    if (d_map) {
+        if (timed) timer_mark(ctx, "labels", s);
+        launch_labels(d_Q, (size_t)m.N, m.C, label_mode, unknown_label, d_map, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Learning on the kept model (include/rvseg.h, "Learning on the kept model"): objective, backward pass, gradient.
+// ---------------------------------------------------------------------------------------------
+static size_t model_compat_params(const CrfModel& m, int upto = -1) {
+    size_t n = 0;
+    const int end = upto < 0 ? (int)m.plan.size() : upto;
+    for (int k = 0; k < end; k++) {
+        const int kind = m.plan[k].compat;
+        n += kind == RVSEG_COMPAT_MATRIX ? (size_t)m.C * (m.C + 1) / 2 : kind == RVSEG_COMPAT_DIAGONAL ? (size_t)m.C : 1;
+    }
+    return n;
+}
+
+static rvseg_status objective_arg(rvseg_ctx* ctx, const rvseg_crf_objective* obj) {
+    if (rvseg_crf_objective_check(obj) == RVSEG_OK) return RVSEG_OK;
+    ctx->err = "bad objective (rvseg_crf_objective_check: kind, gt, class_weight for HAMMING, finite robust)";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+// obj: device pointers
+static rvseg_status model_objective_on(rvseg_ctx* ctx, CrfState* cs, const rvseg_crf_objective& obj, const float* d_Q, double* d_value,
+                                       float* d_dq, hipStream_t s) {
+    CrfModel& m = cs->model;
+    RV_TRY(dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double)));
+    RV_TRY(dev_reserve(ctx, m.stats, 129 * sizeof(double)));
+    launch_objective(obj.kind, obj.gt, obj.robust, obj.class_weight, d_Q, m.C, m.N, d_dq, cs->learn_partials.as<double>(), m.stats.as<double>(),
+                     d_value, s);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// densecrf.cpp:258-296 from d_mul_Q and Q[0 .. n]; d_ug / d_cg may be null
+static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const float* d_Qall, const float* d_dq, float* d_ug,
+                                      double* d_cg, hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    const size_t tot = (size_t)m.N * m.C;
+    const int n_terms = (int)m.plan.size();
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(dev_reserve(ctx, m.bgrad, tot * 4));
+    RV_TRY(dev_reserve(ctx, m.tsum, tot * 4));
+    RV_TRY(dev_reserve(ctx, m.tapp, tot * 4));
+    RV_TRY(dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(m.C) * sizeof(double)));
+    float *b = m.bgrad.as<float>(), *tsum = m.tsum.as<float>(), *tapp = m.tapp.as<float>();
+    launch_sum_normalize(d_dq, false, d_Qall + (size_t)iterations * tot, m.C, m.N, b, d_ug, 1, s);
+    if (d_cg && model_compat_params(m)) RV_HIP(ctx, hipMemsetAsync(d_cg, 0, model_compat_params(m) * sizeof(double), s));
+    for (int it = iterations - 1; it >= 0; it--) {
+        const float* Qit = d_Qall + (size_t)it * tot;
+        if (n_terms == 0) RV_HIP(ctx, hipMemsetAsync(tsum, 0, tot * 4, s));   // tmp1.fill(0), :270
+        for (int k = 0; k < n_terms; k++) {
+            if (d_cg) {   // pairwise_[k]->gradient(b, Q[it]) (pairwise.cpp:190-195)
+                float* blurred;
+                bool post;
+                RV_TRY(model_filter_term(ctx, cs, run, k, Qit, false, &blurred, &post));
+                launch_compat_grad(cs->lat[k].dev, m.C, m.C <= 2, blurred, post, m.plan[k].compat, b, m.N, cs->learn_partials.as<double>(),
+                                   d_cg + model_compat_params(m, k), s);
+            }
+            RV_TRY(model_apply_term(ctx, cs, run, k, b, tapp, true));
+            launch_add_rows(k == 0, tapp, tsum, (long long)tot, s);
+        }
+        launch_sum_normalize(tsum, true, Qit, m.C, m.N, b, d_ug, 2, s);
+    }
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// the forward pass of DenseCRF::gradient (:240-253) keeping Q[0 .. n] in CrfModel::qs, then objective and backward
+static rvseg_status model_gradient_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const rvseg_crf_objective& obj, double* d_value, float* d_ug,
+                                      double* d_cg, float* d_Q_out, hipStream_t s) {
+    CrfModel& m = cs->model;
+    const MfRun run = model_run(cs, s, false);
+    const size_t tot = (size_t)m.N * m.C;
+    RV_TRY(dev_reserve(ctx, m.qs, ((size_t)iterations + 1) * tot * 4));
+    RV_TRY(dev_reserve(ctx, m.dq, tot * 4));
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(mf_entry_norms(ctx, cs, run));
+    float* qs = m.qs.as<float>();
+    mf_start(ctx, cs, run, model_view(m, qs));
+    for (int it = 0; it < iterations; it++) {
+        float* next = qs + (size_t)(it + 1) * tot;
+        RV_HIP(ctx, hipMemcpyAsync(next, qs + (size_t)it * tot, tot * 4, hipMemcpyDeviceToDevice, s));
+        mf_step(ctx, cs, run, model_view(m, next));
+    }
+    RV_LAUNCH_OK(ctx);
+    const float* Qn = qs + (size_t)iterations * tot;
+    RV_TRY(model_objective_on(ctx, cs, obj, Qn, d_value, m.dq.as<float>(), s));
+    RV_TRY(model_backward_on(ctx, cs, iterations, qs, m.dq.as<float>(), d_ug, d_cg, s));
+    if (d_Q_out) RV_HIP(ctx, hipMemcpyAsync(d_Q_out, Qn, tot * 4, hipMemcpyDeviceToDevice, s));
+    return RVSEG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The entry bodies: the live model, the arguments, the arrays through `io`, the call on device pointers, io.done().
+// ---------------------------------------------------------------------------------------------
+static rvseg_status model_start(ModelIo io, float* Q_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(Q_out);
+    CrfModel& m = io.cs->model;
+    RV_TRY(io.out(m.q, &Q_out, (size_t)m.N * m.C));
+    RV_TRY(model_start_on(io.ctx, io.cs, Q_out, io.s, io.time()));
+    return io.done();
+}
+
+static rvseg_status model_step(ModelIo io, float* Q_inout, int32_t n_steps) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(Q_inout && n_steps >= 0);
+    CrfModel& m = io.cs->model;
+    const float* Q_in = Q_inout;   // in and out through the same buffer
+    RV_TRY(io.out(m.q, &Q_inout, (size_t)m.N * m.C));
+    RV_TRY(io.in(m.q, &Q_in, (size_t)m.N * m.C));
+    RV_TRY(model_step_on(io.ctx, io.cs, Q_inout, n_steps, io.s, io.time()));
+    return io.done();
+}
+
+static rvseg_status model_apply(ModelIo io, int32_t term, const float* in, float* out, bool transpose) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(in && out);
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    RV_TRY(io.in(m.q, &in, (size_t)m.N * m.C));
+    RV_TRY(io.out(m.rows, &out, (size_t)m.N * m.C));
+    RV_TRY(model_apply_on(io.ctx, io.cs, term, in, out, io.s, transpose));
+    return io.done();
+}
+
+static rvseg_status model_energy(ModelIo io, const int8_t* labels, int32_t term, float* unary_out, float* pairwise_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(labels && (unary_out || pairwise_out));
+    CrfModel& m = io.cs->model;
+    if (pairwise_out) RV_TRY(model_term_arg(io.ctx, m, term, -1));
+    const size_t N = (size_t)m.N;
+    RV_TRY(io.in(m.labels, &labels, N));
+    if (io.on_host) {   // both vectors in CrfModel::vec
+        RV_TRY(dev_reserve(io.ctx, m.vec, 2 * N * 4));
+        io.out_at(m.vec.as<float>(), &unary_out, N);
+        io.out_at(m.vec.as<float>() + N, &pairwise_out, N);
+    }
+    RV_TRY(model_energy_on(io.ctx, io.cs, labels, term, unary_out, pairwise_out, io.s));
+    return io.done();
+}
+
+static rvseg_status model_kl(ModelIo io, const float* Q, double* parts) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(Q && parts);
+    CrfModel& m = io.cs->model;
+    RV_TRY(io.in(m.q, &Q, (size_t)m.N * m.C));
+    RV_TRY(io.out(m.kl, &parts, 2 + m.plan.size()));
+    RV_TRY(model_kl_on(io.ctx, io.cs, Q, parts, io.s, io.time()));
+    return io.done();
+}
+
+static rvseg_status model_trace(ModelIo io, int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label,
+                                double* kl_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(iterations >= 0 && Q_out && kl_out && label_mode >= 0 && label_mode <= 3);
+    CrfModel& m = io.cs->model;
+    RV_TRY(io.out(m.q, &Q_out, (size_t)m.N * m.C));
+    RV_TRY(io.out(m.labels, &map_out, (size_t)m.N));
+    RV_TRY(io.out(m.kl, &kl_out, (size_t)iterations + 1));   // written on the device, read back once
+    RV_TRY(model_trace_on(io.ctx, io.cs, iterations, Q_out, map_out, label_mode, unknown_label, kl_out, io.s, io.time()));
+    return io.done();
+}
+
+// *obj on device pointers: gt and (HAMMING only) the class weights of a host entry staged.  For the other kinds
+// class_weight stays the caller's pointer, host or device: no kernel of theirs reads it (launch_objective).
+static rvseg_status model_objective_in(ModelIo& io, CrfModel& m, rvseg_crf_objective* obj) {
+    RV_TRY(io.in(m.gt, &obj->gt, (size_t)m.N));
+    if (obj->kind == RVSEG_OBJECTIVE_HAMMING) RV_TRY(io.in(m.cw, &obj->class_weight, (size_t)m.C));
+    return RVSEG_OK;
+}
+
+static rvseg_status model_objective(ModelIo io, const rvseg_crf_objective* obj, const float* Q, double* value_out, float* d_mul_Q_out) {
+    RV_TRY(io.enter());
+    RV_TRY(objective_arg(io.ctx, obj));
+    RV_MODEL_ARGS(Q && value_out && d_mul_Q_out);
+    CrfModel& m = io.cs->model;
+    rvseg_crf_objective dev = *obj;
+    RV_TRY(model_objective_in(io, m, &dev));
+    RV_TRY(io.in(m.q, &Q, (size_t)m.N * m.C));
+    RV_TRY(dev_reserve(io.ctx, m.stats, 129 * sizeof(double)));
+    io.out_at(m.stats.as<double>() + 128, &value_out, 1);   // where a host entry's value lands
+    RV_TRY(io.out(m.dq, &d_mul_Q_out, (size_t)m.N * m.C));
+    RV_TRY(model_objective_on(io.ctx, io.cs, dev, Q, value_out, d_mul_Q_out, io.s));
+    return io.done();
+}
+
+static rvseg_status model_backward(ModelIo io, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
+                                   double* compat_grad_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(iterations >= 0 && Q_all && d_mul_Q);
+    CrfModel& m = io.cs->model;
+    const size_t tot = (size_t)m.N * m.C;
+    RV_TRY(io.in(m.qs, &Q_all, ((size_t)iterations + 1) * tot));
+    RV_TRY(io.in(m.dq, &d_mul_Q, tot));
+    RV_TRY(io.out(m.ug, &unary_grad_out, tot));
+    RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
+    RV_TRY(model_backward_on(io.ctx, io.cs, iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out, io.s));
+    return io.done();
+}
+
+static rvseg_status model_gradient(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, float* unary_grad_out,
+                                   double* compat_grad_out, float* Q_out) {
+    RV_TRY(io.enter());
+    RV_TRY(objective_arg(io.ctx, obj));
+    RV_MODEL_ARGS(iterations >= 0 && value_out);
+    CrfModel& m = io.cs->model;
+    const size_t tot = (size_t)m.N * m.C;
+    rvseg_crf_objective dev = *obj;
+    RV_TRY(model_objective_in(io, m, &dev));
+    RV_TRY(dev_reserve(io.ctx, m.stats, 129 * sizeof(double)));
+    io.out_at(m.stats.as<double>() + 128, &value_out, 1);
+    RV_TRY(io.out(m.ug, &unary_grad_out, tot));
+    RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
+    io.time();   // (the forward pass itself records no marks)
+    // a host entry downloads Q[n] from where the forward pass has left it: no device copy of it
+    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, unary_grad_out, compat_grad_out, io.on_host ? nullptr : Q_out, io.s));
+    io.out_at(m.qs.as<float>() + (size_t)iterations * tot, &Q_out, tot);
+    return io.done();
+}
+
+static rvseg_status model_set_compat(ModelIo io, int32_t term, const float* params) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(params);
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    TermPlan& t = m.plan[term];
+    std::vector<float> hc(t.compat == RVSEG_COMPAT_MATRIX ? (size_t)m.C * m.C : (size_t)m.C);
+    plan_compat(m.C, t.compat, params, t, hc.data());
+    RV_HIP(io.ctx, hipMemcpyAsync(io.cs->compat.as<float>() + t.off, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, io.s));
+    return io.done();   // waits: hc is gone when this returns
+}
+
+static rvseg_status model_set_unary(ModelIo io, const float* unary, int32_t unary_is_energy) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(unary);
+    CrfModel& m = io.cs->model;
+    RV_HIP(io.ctx, hipMemcpyAsync(m.unary.p, unary, (size_t)m.N * m.C * 4, io.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, io.s));
+    RV_TRY(io.done());   // a host entry waits: the caller's array is free when it returns
+    m.unary_is_energy = unary_is_energy != 0;
+    return RVSEG_OK;
+}
+
+// needs no model; a host entry stages through CrfState::unary / feat / lgrad (a live model keeps its own copy of the unary)
+static rvseg_status logistic_gradient(ModelIo io, int32_t N, int32_t C, int32_t K, const float* unary_grad, const float* f, double* out) {
+    RV_TRY(io.enter(false));
+    RV_MODEL_ARGS(N > 0 && C >= 1 && C <= 64 && K >= 1 && unary_grad && f && out);
+    CrfState* cs = io.cs;
+    RV_TRY(io.in(cs->unary, &unary_grad, (size_t)N * C));
+    RV_TRY(io.in(cs->feat, &f, (size_t)N * K));
+    RV_TRY(io.out(cs->lgrad, &out, (size_t)C * K));
+    RV_TRY(dev_reserve(io.ctx, cs->learn_partials, learn_partials_doubles(64) * sizeof(double)));
+    launch_logistic_gradient(unary_grad, f, N, C, K, cs->learn_partials.as<double>(), out, io.s);
+    RV_LAUNCH_OK(io.ctx);
+    return io.done();
+}
+
+extern "C" {
+
+rvseg_status rvseg_crf_model_set(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms, const float* unary,
+                                 int32_t unary_is_energy) {
+    return model_set(host_io(ctx, __func__), N, C, n_terms, terms, unary, unary_is_energy);
+}
+rvseg_status rvseg_crf_model_set_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
+                                        const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
+    return model_set(device_io(ctx, hip_stream, __func__), N, C, n_terms, terms, d_unary, unary_is_energy);
+}
+
+rvseg_status rvseg_crf_model_start(rvseg_ctx* ctx, float* Q_out) { return model_start(host_io(ctx, __func__), Q_out); }
+rvseg_status rvseg_crf_model_start_device(rvseg_ctx* ctx, float* d_Q_out, void* hip_stream) {
+    return model_start(device_io(ctx, hip_stream, __func__), d_Q_out);
+}
+
+rvseg_status rvseg_crf_model_step(rvseg_ctx* ctx, float* Q_inout, int32_t n_steps) { return model_step(host_io(ctx, __func__), Q_inout, n_steps); }
+rvseg_status rvseg_crf_model_step_device(rvseg_ctx* ctx, float* d_Q_inout, int32_t n_steps, void* hip_stream) {
+    return model_step(device_io(ctx, hip_stream, __func__), d_Q_inout, n_steps);
+}
+
+rvseg_status rvseg_crf_model_apply(rvseg_ctx* ctx, int32_t term, const float* Q_in, float* out) {
+    return model_apply(host_io(ctx, __func__), term, Q_in, out, false);
+}
+rvseg_status rvseg_crf_model_apply_device(rvseg_ctx* ctx, int32_t term, const float* d_Q_in, float* d_out, void* hip_stream) {
+    return model_apply(device_io(ctx, hip_stream, __func__), term, d_Q_in, d_out, false);
+}
+rvseg_status rvseg_crf_model_apply_transpose(rvseg_ctx* ctx, int32_t term, const float* in, float* out) {
+    return model_apply(host_io(ctx, __func__), term, in, out, true);
+}
+rvseg_status rvseg_crf_model_apply_transpose_device(rvseg_ctx* ctx, int32_t term, const float* d_in, float* d_out, void* hip_stream) {
+    return model_apply(device_io(ctx, hip_stream, __func__), term, d_in, d_out, true);
+}
+
+rvseg_status rvseg_crf_model_energy(rvseg_ctx* ctx, const int8_t* labels, int32_t term, float* unary_out, float* pairwise_out) {
+    return model_energy(host_io(ctx, __func__), labels, term, unary_out, pairwise_out);
+}
+rvseg_status rvseg_crf_model_energy_device(rvseg_ctx* ctx, const int8_t* d_labels, int32_t term, float* d_unary_out, float* d_pairwise_out,
+                                           void* hip_stream) {
+    return model_energy(device_io(ctx, hip_stream, __func__), d_labels, term, d_unary_out, d_pairwise_out);
+}
+
+rvseg_status rvseg_crf_model_kl(rvseg_ctx* ctx, const float* Q, double* parts) { return model_kl(host_io(ctx, __func__), Q, parts); }
+rvseg_status rvseg_crf_model_kl_device(rvseg_ctx* ctx, const float* d_Q, double* d_parts, void* hip_stream) {
+    return model_kl(device_io(ctx, hip_stream, __func__), d_Q, d_parts);
+}
+
+rvseg_status rvseg_crf_model_trace(rvseg_ctx* ctx, int32_t iterations, float* Q_out, int8_t* map_out, int32_t label_mode, int32_t unknown_label,
+                                   double* kl_out) {
+    return model_trace(host_io(ctx, __func__), iterations, Q_out, map_out, label_mode, unknown_label, kl_out);
+}
+rvseg_status rvseg_crf_model_trace_device(rvseg_ctx* ctx, int32_t iterations, float* d_Q_out, int8_t* d_map_out, int32_t label_mode,
+                                          int32_t unknown_label, double* d_kl_out, void* hip_stream) {
+    return model_trace(device_io(ctx, hip_stream, __func__), iterations, d_Q_out, d_map_out, label_mode, unknown_label, d_kl_out);
+}
+
+rvseg_status rvseg_crf_objective_check(const rvseg_crf_objective* obj) {
+    if (!obj || obj->kind < RVSEG_OBJECTIVE_LOGLIKELIHOOD || obj->kind > RVSEG_OBJECTIVE_IOU || !obj->gt) return RVSEG_ERR_INVALID_ARG;
+    if (obj->kind == RVSEG_OBJECTIVE_HAMMING && !obj->class_weight) return RVSEG_ERR_INVALID_ARG;
+    if (!std::isfinite(obj->robust)) return RVSEG_ERR_INVALID_ARG;
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_crf_model_objective(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* Q, double* value_out, float* d_mul_Q_out) {
+    return model_objective(host_io(ctx, __func__), obj, Q, value_out, d_mul_Q_out);
+}
+rvseg_status rvseg_crf_model_objective_device(rvseg_ctx* ctx, const rvseg_crf_objective* obj, const float* d_Q, double* d_value_out,
+                                              float* d_d_mul_Q_out, void* hip_stream) {
+    return model_objective(device_io(ctx, hip_stream, __func__), obj, d_Q, d_value_out, d_d_mul_Q_out);
+}
+
+rvseg_status rvseg_crf_model_backward(rvseg_ctx* ctx, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
+                                      double* compat_grad_out) {
+    return model_backward(host_io(ctx, __func__), iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out);
+}
+rvseg_status rvseg_crf_model_backward_device(rvseg_ctx* ctx, int32_t iterations, const float* d_Q_all, const float* d_d_mul_Q,
+                                             float* d_unary_grad_out, double* d_compat_grad_out, void* hip_stream) {
+    return model_backward(device_io(ctx, hip_stream, __func__), iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out);
+}
+
+rvseg_status rvseg_crf_model_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
+                                      float* unary_grad_out, double* compat_grad_out, float* Q_out) {
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, Q_out);
+}
+rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
+                                             float* d_unary_grad_out, double* d_compat_grad_out, float* d_Q_out, void* hip_stream) {
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out, d_Q_out);
+}
+
+rvseg_status rvseg_crf_model_set_compat(rvseg_ctx* ctx, int32_t term, const float* params) {
+    return model_set_compat(host_io(ctx, __func__), term, params);
+}
+
+rvseg_status rvseg_crf_model_set_unary(rvseg_ctx* ctx, const float* unary, int32_t unary_is_energy) {
+    return model_set_unary(host_io(ctx, __func__), unary, unary_is_energy);
+}
+rvseg_status rvseg_crf_model_set_unary_device(rvseg_ctx* ctx, const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
+    return model_set_unary(device_io(ctx, hip_stream, __func__), d_unary, unary_is_energy);
+}
+
+rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* unary_grad, const float* f, double* out) {
+    return logistic_gradient(host_io(ctx, __func__), N, C, K, unary_grad, f, out);
+}
+rvseg_status rvseg_crf_logistic_gradient_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* d_unary_grad, const float* d_f,
+                                                double* d_out, void* hip_stream) {
+    return logistic_gradient(device_io(ctx, hip_stream, __func__), N, C, K, d_unary_grad, d_f, d_out);
+}
+
+}  // extern "C"

@@ -1,0 +1,121 @@
+// The CRF state of a context and the mean-field pieces that rvseg_crf.hip (lattices, mean field, frame and cloud paths) and
+// rvseg_crf_model.hip (the kept DenseCRF model) share.  Private to those two files; the functions are defined in rvseg_crf.hip.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "rvseg_crf.h"
+#include "rvseg_pipeline.h"
+
+namespace rvseg {
+
+struct LatticeBufs {
+    DevBuf state, tkeys, slot_to_id, counters, vkeys, offsets, bary, nb1, nb2, csr_pw, csr_nrm, vstart, vend, norm;
+    DevBuf keys_in, keys_out, vals_in, vals_out, sort_temp, scan_temp, fstart, vorder, block_hist;
+    DevBuf r_desc, r_vl, r_info, r_small, r_verts, r_jb, r_trace;   // resident band schedule of the splat
+    SplatResidentDev resident{};
+    bool resident_on = false;
+    LatticeDev dev{};
+    SortBuffers sb{};
+    long long n_entries = 0, n_points = 0;
+    bool built = false;
+    bool cleared = false;       // the build's memsets are already enqueued (crf_frames_build_begin)
+    bool has_csr_nrm = false;   // per-entry normaliser (multi-kernel inference only)
+};
+
+// One pairwise term as the mean field runs it.  Potts, and a Diagonal whose entries are all equal, are the same term
+// (Potts(w) == Diagonal(-w, .., -w) bit for bit).
+struct TermPlan {
+    int norm = RVSEG_NORMALIZE_SYMMETRIC;
+    bool uniform = true;   // Potts or uniform Diagonal: out = fl(-w * t)
+    float w = 0.f;
+    bool matrix = false;
+    size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
+    int compat = RVSEG_COMPAT_POTTS;   // rvseg_compat_kind: the layout of the term's parameters and of their gradient
+};
+
+// The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
+// CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
+struct CrfModel {
+    bool valid = false;
+    int N = 0, C = 0;
+    bool unary_is_energy = true;
+    std::vector<TermPlan> plan;
+    std::string replaced_by;   // the entry whose lattice build ended the model
+    DevBuf unary;              // N x C, as the caller passed it
+    // staging of the host entries only: an N x C input or in-out matrix, labels, the two energy vectors, KL values,
+    // gradients, ground truth, class weights
+    DevBuf q, labels, vec, kl, ug, cg, gt, cw;
+    // staging of a host entry, the caller's memory in a device entry: an N x C output (work memory of the energies), Q[0 .. n]
+    // (work memory of the gradient's forward pass), d_mul_Q (work memory of the gradient)
+    DevBuf rows, qs, dq;
+    // work memory (never the mean field's tmp): the energies' one-hot rows, the KL partials, the backward pass's b, tmp1, tmp2
+    DevBuf onehot, partials, bgrad, tsum, tapp;
+    DevBuf stats;              // 128 doubles of IoU sums + the objective's value (of a host entry)
+};
+
+struct CrfState {
+    std::vector<LatticeBufs> lat;  // one per pairwise kernel
+    CrfModel model;                // rvseg_crf_model_*
+    const char* entry = "";        // the C-ABI entry at work (crf_enter; the frame and cloud paths name themselves): CrfModel::replaced_by
+    // two slots of mean-field scratch: a second label layer's mean field runs beside the first on its own stream
+    struct { DevBuf val_a, val_b, tmp, qn; } scratch[2];
+    DevBuf q, unary, feat, labels;
+    // learned-model terms (rvseg_crf_infer_terms*): compatibilities of all terms, transformed features, logistic L
+    DevBuf compat, kfeat, lmat;
+    DevBuf learn_partials, lgrad;   // partials of the learning reductions; staging of rvseg_crf_logistic_gradient's result
+    std::vector<float> h_compat;   // host copy of `compat` (the source of its asynchronous upload)
+    Stream layer_stream;   // the second layer's stream; created together with its two events (second_stream)
+    Event layer_fork, layer_join;
+    // pinned read-back of a build: [0] M, [1] overflow, [2] longest vertex list, [3] frames the splat planner gave up on.
+    // Slot 0 (words 0..3) belongs to the asynchronous frame builds (consumed by crf_frames_status), slot 1 (words 4..7)
+    // to the synchronous entry points -- a cloud or host CRF call on the same context must not overwrite a frame
+    // build's status that nobody has polled yet.
+    PinnedBuf h_counters;   // int[8]
+    Event counters_ev;
+    bool counters_pending = false;
+    rvseg_schedule_info info{};    // what the last build ran with (rvseg_last_schedule)
+    int frame_vertices_seen = 0;   // vertices per frame of the last frame build whose status was read (0: none yet)
+    int pending_frames = 0;        // frames of the build whose status is pending
+    bool info_async = false;       // info.vertices / planner_fallback still travel with the pending frame-build status
+};
+
+// What one mean field reads and where it runs: the terms (term k on cs->lat[k]) with their compatibilities d_compat (may
+// be null when every term is uniform with NORMALIZE_SYMMETRIC), the unary, the shape, the stream and the scratch slot
+// (0 / 1; two layers may run side by side on two streams); timed: record stage marks (only one of two concurrent loops
+// may: the marks are a sequence on ONE stream)
+struct MfRun {
+    const std::vector<TermPlan>& plan;
+    const float* d_compat;
+    ValueView unary;
+    bool unary_is_energy;
+    int C, N;
+    long long n_points;
+    hipStream_t s;
+    int slot;
+    bool timed;
+};
+
+// Where a traced step leaves the KL divergence of the Q it starts from: the term passes read the splat and blur the step
+// needs anyway.  partials: [2 + n_terms][KL_MAX_BLOCKS] doubles.
+struct KlTap { double* partials; };
+
+// ---- rvseg_crf.hip (each is described where it is defined); not exported by the library ----
+#pragma GCC visibility push(hidden)
+rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry);
+void model_replaced(CrfState* cs);
+rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
+                           std::vector<TermPlan>& plan, hipStream_t s);
+void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */);
+bool term_pre(const TermPlan& t);
+bool term_post(const TermPlan& t);
+rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s);
+rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r);
+rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r);
+void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q);
+void mf_step(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q, const KlTap* tap = nullptr);
+void kl_unary_parts(rvseg_ctx* ctx, const MfRun& r, const float* Q, const KlTap& tap);
+void kl_term_part(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* blurred, const float* Q, const KlTap& tap);
+#pragma GCC visibility pop
+
+}  // namespace rvseg

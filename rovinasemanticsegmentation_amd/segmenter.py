@@ -380,16 +380,25 @@ class Context:
         arr, keep = _crf_terms(terms, Cn, N)
         capi.check(self.h, self.L.rvseg_crf_model_set(self.h, N, Cn, len(terms), arr, _ptr(U), 1 if unary_is_energy else 0))
         del keep
-        self._crf_model_shape = (N, Cn, len(terms))
-        self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
+        self._crf_model_is(N, Cn, terms)
 
     def crf_model_set_device(self, N, Cn, terms, d_unary, unary_is_energy=True, stream=0):
         arr, keep = _crf_terms(terms, Cn, N, device=True)
         capi.check(self.h, self.L.rvseg_crf_model_set_device(self.h, N, Cn, len(terms), arr, C.c_void_p(d_unary), 1 if unary_is_energy else 0,
                                                              C.c_void_p(stream or None)))
         del keep
+        self._crf_model_is(N, Cn, terms)
+
+    def _crf_model_is(self, N, Cn, terms):
         self._crf_model_shape = (N, Cn, len(terms))
         self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
+
+    def _crf_model_matrix(self, Q, copy=False):
+        """Q as a C-contiguous float32 N x C matrix of the live model; copy: never the caller's array."""
+        N, Cn, _ = self._crf_model_shape
+        Q = np.array(Q, np.float32, order="C") if copy else np.ascontiguousarray(Q, np.float32)
+        assert Q.shape == (N, Cn)
+        return Q
 
     def crf_model_start(self):
         N, Cn, _ = self._crf_model_shape
@@ -399,16 +408,12 @@ class Context:
 
     def crf_model_step(self, Q, n_steps=1):
         """n_steps of stepInference on a copy of Q (any N x C matrix), which is returned."""
-        N, Cn, _ = self._crf_model_shape
-        Q = np.array(Q, np.float32, order="C")
-        assert Q.shape == (N, Cn)
+        Q = self._crf_model_matrix(Q, copy=True)
         capi.check(self.h, self.L.rvseg_crf_model_step(self.h, _ptr(Q), n_steps))
         return Q
 
     def crf_model_apply(self, term, Q):
-        N, Cn, _ = self._crf_model_shape
-        Q = np.ascontiguousarray(Q, np.float32)
-        assert Q.shape == (N, Cn)
+        Q = self._crf_model_matrix(Q)
         out = np.empty_like(Q)
         capi.check(self.h, self.L.rvseg_crf_model_apply(self.h, term, _ptr(Q), _ptr(out)))
         return out
@@ -425,10 +430,8 @@ class Context:
 
     def crf_model_kl(self, Q):
         """The parts of the KL divergence: entropy, unary, one per term (float64); their sum in that order is the KL."""
-        N, Cn, n_terms = self._crf_model_shape
-        Q = np.ascontiguousarray(Q, np.float32)
-        assert Q.shape == (N, Cn)
-        parts = np.empty(2 + n_terms, np.float64)
+        Q = self._crf_model_matrix(Q)
+        parts = np.empty(2 + self._crf_model_shape[2], np.float64)
         capi.check(self.h, self.L.rvseg_crf_model_kl(self.h, _ptr(Q), _ptr(parts)))
         return parts
 
@@ -443,19 +446,15 @@ class Context:
 
     # ---- learning on the kept model (rvseg.h, "Learning on the kept model") ----
     def crf_model_apply_transpose(self, term, Q):
-        N, Cn, _ = self._crf_model_shape
-        Q = np.ascontiguousarray(Q, np.float32)
-        assert Q.shape == (N, Cn)
+        Q = self._crf_model_matrix(Q)
         out = np.empty_like(Q)
         capi.check(self.h, self.L.rvseg_crf_model_apply_transpose(self.h, term, _ptr(Q), _ptr(out)))
         return out
 
     def crf_model_objective(self, objective, Q):
         """(value, d_mul_Q) of a LogLikelihood / Hamming / IntersectionOverUnion on the marginals Q."""
-        N, Cn, _ = self._crf_model_shape
-        Q = np.ascontiguousarray(Q, np.float32)
-        assert Q.shape == (N, Cn)
-        rec, keep = objective.record(N, Cn)
+        Q = self._crf_model_matrix(Q)
+        rec, keep = objective.record(*Q.shape)
         value = np.empty(1, np.float64)
         dq = np.empty_like(Q)
         capi.check(self.h, self.L.rvseg_crf_model_objective(self.h, C.byref(rec), _ptr(Q), _ptr(value), _ptr(dq)))
@@ -467,8 +466,8 @@ class Context:
         for is None."""
         N, Cn, _ = self._crf_model_shape
         Q_all = np.ascontiguousarray(Q_all, np.float32)
-        dq = np.ascontiguousarray(d_mul_Q, np.float32)
-        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn) and dq.shape == (N, Cn)
+        dq = self._crf_model_matrix(d_mul_Q)
+        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn)
         ug = np.empty((N, Cn), np.float32) if unary else None
         cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
         capi.check(self.h, self.L.rvseg_crf_model_backward(self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), _ptr(ug), _ptr(cg)))
@@ -494,9 +493,7 @@ class Context:
         self._crf_model_params[term] = _compat(compatibility).parameters().shape[0]
 
     def crf_model_set_unary(self, unary, unary_is_energy=True):
-        N, Cn, _ = self._crf_model_shape
-        U = np.ascontiguousarray(unary, np.float32)
-        assert U.shape == (N, Cn)
+        U = self._crf_model_matrix(unary)
         capi.check(self.h, self.L.rvseg_crf_model_set_unary(self.h, _ptr(U), 1 if unary_is_energy else 0))
 
     def crf_logistic_gradient(self, unary_grad, f):

@@ -337,6 +337,72 @@ def test_device_entries(gpu_ctx_factory, oracle):
     del keep
 
 
+def _same_bits(a, b):
+    a, b = (v if isinstance(v, tuple) else (v,) for v in (a, b))
+    return len(a) == len(b) and all((p is None) == (q is None) and (p is None or np.asarray(p).tobytes() == np.asarray(q).tobytes())
+                                    for p, q in zip(a, b))
+
+
+@pytest.mark.parametrize("C", [2, 11])   # C = 2: the sequential blur
+def test_entries_leave_each_other_alone(gpu_ctx_factory, C):
+    """The host entries share the model's staging and work memory.  On one context with a two-term model every host entry
+    runs once, then all run again in reverse order with a _device step and a _device backward on a torch stream among
+    them: every output must equal its first value bit for bit, and that of the same call as the only one on a fresh
+    context.  The inputs are the same arrays throughout, none of them an output of another entry."""
+    torch = pytest.importorskip("torch")
+    import rovinasemanticsegmentation_amd as rv
+    N, n = 300, 2
+    rng, U, terms = M.random_model(2100 + C, N, C, [(3, R.DIAGONAL, R.NORMALIZE_BEFORE), (5, R.MATRIX, R.NORMALIZE_SYMMETRIC)])
+
+    def marginals(*shape):
+        e = np.exp(rng.normal(size=shape + (C,)))
+        return np.ascontiguousarray(e / e.sum(-1, keepdims=True), f32)
+    Q, Q_all = marginals(N), marginals(n + 1, N)
+    x = rng.normal(size=(N, C)).astype(f32)
+    dq = (rng.normal(size=(N, C)) * 0.1).astype(f32)
+    labels = rng.integers(0, C, N).astype(np.int8)
+    obj = rv.Hamming(_gt(rng, N, C), rng.uniform(0.1, 1.0, C).astype(f32))
+    entries = [
+        ("start", lambda c: c.crf_model_start()),
+        ("step", lambda c: c.crf_model_step(Q, 2)),
+        ("apply", lambda c: c.crf_model_apply(1, x)),
+        ("apply_transpose", lambda c: c.crf_model_apply_transpose(0, x)),
+        ("energy, unary only", lambda c: c.crf_model_energy(labels, pairwise=False)),
+        ("energy, pairwise only", lambda c: c.crf_model_energy(labels, term=1, unary=False)),
+        ("energy", lambda c: c.crf_model_energy(labels)),
+        ("kl", lambda c: c.crf_model_kl(Q)),
+        ("trace", lambda c: c.crf_model_trace(n, label_mode=3, unknown_label=C)),
+        ("objective", lambda c: c.crf_model_objective(obj, Q)),
+        ("backward, no unary_grad", lambda c: c.crf_model_backward(Q_all, dq, unary=False)),
+        ("backward, no compat_grad", lambda c: c.crf_model_backward(Q_all, dq, lbl_cmp=False)),
+        ("backward", lambda c: c.crf_model_backward(Q_all, dq)),
+        ("gradient with Q", lambda c: c.crf_model_gradient(n, obj, want_Q=True)),
+        ("gradient", lambda c: c.crf_model_gradient(n, obj)),
+    ]
+    ctx = gpu_ctx_factory()
+    _set(ctx, rv, U, terms)
+    first = {name: call(ctx) for name, call in entries}
+    assert first["backward, no unary_grad"][0] is None and first["backward, no compat_grad"][1] is None and first["gradient"][3] is None
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    d_Q, d_Qall, d_dq = (torch.from_numpy(a).to(dev) for a in (Q, Q_all, dq))
+    d_ug = torch.zeros((N, C), dtype=torch.float32, device=dev)
+    d_cg = torch.ones(C + C * (C + 1) // 2, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    for k, (name, call) in enumerate(reversed(entries)):
+        if k == len(entries) // 2:
+            ctx.crf_model_call_device("step", d_Q.data_ptr(), 2, stream=stream.cuda_stream)
+            ctx.crf_model_call_device("backward", n, d_Qall.data_ptr(), d_dq.data_ptr(), d_ug.data_ptr(), d_cg.data_ptr(), stream=stream.cuda_stream)
+            stream.synchronize()
+        assert _same_bits(call(ctx), first[name]), name + " after the others"
+    assert _same_bits(d_Q.cpu().numpy(), first["step"]) and _same_bits((d_ug.cpu().numpy(), d_cg.cpu().numpy()), first["backward"])
+    for name, call in entries:
+        fresh = gpu_ctx_factory()
+        _set(fresh, rv, U, terms)
+        assert _same_bits(call(fresh), first[name]), name + " on a fresh context"
+        fresh.close()
+
+
 def _labeling(anno, M):
     """getLabeling (examples/common.cpp:49-66): colours in order of appearance, black = unlabelled (-1)."""
     col = anno[:, 0].astype(np.int64) | (anno[:, 1].astype(np.int64) << 8) | (anno[:, 2].astype(np.int64) << 16)
