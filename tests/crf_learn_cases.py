@@ -225,6 +225,25 @@ def logistic_gradient(ug, f):
     return (f64.T @ g64).reshape(-1), (np.abs(f64).T @ np.abs(g64)).reshape(-1)
 
 
+def invalid_gt(N, C):
+    """A ground truth without one valid label: -1, other negatives and labels >= C mixed."""
+    gt = np.full(N, -1, np.int16)
+    gt[1::2] = C
+    gt[2::5] = C + 3
+    gt[3::7] = -7
+    return gt
+
+
+def gt_without_class(rng, N, C, absent):
+    """Labels of every class but `absent` (each occurs when N >= 2 C), with a skipped point of either kind when N > 5."""
+    gt = rng.integers(0, C - 1, N)
+    gt[:C - 1] = np.arange(C - 1)
+    gt[gt >= absent] += 1
+    if N > 5:
+        gt[C], gt[C + 1] = -1, C
+    return gt.astype(np.int16)
+
+
 def hamming_weights(gt, class_weight_pow):
     """Hamming::Hamming(gt, class_weight_pow), objective.cpp:51-63, in float32."""
     gt = np.asarray(gt, np.int64)

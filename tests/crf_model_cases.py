@@ -51,6 +51,22 @@ def random_model(seed, N, C, specs):
     return rng, U, terms
 
 
+def clamp_q(rng, N, C):
+    """Rows for klDivergence's max(Q, 1e-20f) (densecrf.cpp:219): exact zeros, values in (0, 1e-20), the clamp's own value,
+    the first float above it, and one exactly one-hot row (N >= 12, C >= 3).  Everything else is a positive marginal."""
+    assert N >= 12 and C >= 3
+    e = rng.random((N, C)) + 0.05
+    Q = (e / e.sum(1, keepdims=True)).astype(f32)
+    Q[::3, 0] = 0.0
+    Q[1::5, C - 1] = f32(1e-30)
+    Q[2::7, 1] = f32(9.9e-21)
+    Q[4::11, 1] = f32(1e-20)
+    Q[5::11, 2] = np.nextafter(f32(1e-20), f32(1))
+    Q[N // 2] = 0.0
+    Q[N // 2, C // 2] = 1.0
+    return Q
+
+
 class Model:
     def __init__(self, oracle, U, terms):
         self.oracle = oracle

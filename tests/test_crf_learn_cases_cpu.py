@@ -1,6 +1,8 @@
 """The learning restatement (crf_learn_cases.py) against central finite differences, in float64 on an explicit dense
 filter matrix: this guards the mathematics of the yardstick the GPU tests compare with.  Also the host-only
 rvseg_crf_objective_check and CRFEnergy's signs and L2 term.  No GPU."""
+import math
+
 import numpy as np
 import pytest
 
@@ -45,15 +47,19 @@ def _pack(compat, cp):
 
 
 class Case:
-    def __init__(self, seed, specs):
+    def __init__(self, seed, specs, n=N, gt=None):
+        """n points (below six: every one labelled); gt: a ground truth in place of the random one."""
         rng = np.random.default_rng(seed)
         self.L = rng.uniform(-1.0, 1.0, (C, K))
-        self.f = rng.uniform(0.0, 1.0, (N, K))
+        self.f = rng.uniform(0.0, 1.0, (n, K))
         self.specs = specs
-        self.filters = [LC.DenseFilter(rng.uniform(0.0, 1.0, (N, N)) * rng.uniform(0.5, 1.5) / N) for _ in specs]
+        self.filters = [LC.DenseFilter(rng.uniform(0.0, 1.0, (n, n)) * rng.uniform(0.5, 1.5) / n) for _ in specs]
         self.params = [_pack(c, _params(rng, c)) for c, _ in specs]
-        gt = rng.integers(0, C, N)
-        gt[1], gt[5] = -1, C   # skipped points
+        if gt is None:
+            gt = rng.integers(0, C, n)
+            if n > 5:
+                gt[1], gt[5] = -1, C   # skipped points
+        assert len(gt) == n
         self.gt = gt
         self.objectives = {
             "loglikelihood": (LC.LOGLIKELIHOOD, gt, 0.0, None),
@@ -100,11 +106,7 @@ def test_specs_cover_every_normalisation_and_compatibility():
     assert {c for spec in SPECS for c, _ in spec} == set(COMPATS) and {n for spec in SPECS for _, n in spec} == set(NORMS)
 
 
-@pytest.mark.parametrize("name", ["loglikelihood", "loglikelihood robust", "hamming", "iou"])
-@pytest.mark.parametrize("i", range(len(SPECS)))
-def test_gradients_match_central_differences(i, name):
-    case = Case(40 + i, SPECS[i])
-    obj = case.objectives[name]
+def _gradients_match_central_differences(case, obj):
     lr = case.learn()
     value, ug, cg, Qn, _, _ = lr.gradient(NIT, obj)
     assert value == case.value(obj)
@@ -120,6 +122,91 @@ def test_gradients_match_central_differences(i, name):
     # logistic L, column-major like unaryParameters()
     lg, _ = LC.logistic_gradient(ug, case.f)
     _close(lg, _fd(lambda v: case.value(obj, L=v.reshape(K, C).T), case.L.T.reshape(-1)), "logistic")
+
+
+@pytest.mark.parametrize("name", ["loglikelihood", "loglikelihood robust", "hamming", "iou"])
+@pytest.mark.parametrize("i", range(len(SPECS)))
+def test_gradients_match_central_differences(i, name):
+    case = Case(40 + i, SPECS[i])
+    _gradients_match_central_differences(case, case.objectives[name])
+
+
+@pytest.mark.parametrize("name", ["loglikelihood robust", "hamming", "iou"])
+@pytest.mark.parametrize("n", [1, 2])
+@pytest.mark.parametrize("i", [1, 2])   # (Diagonal, Matrix) and (Matrix, Potts), three normalisations
+def test_gradients_of_one_and_two_points(i, n, name):
+    """N = 1: the filter is one number, IoU's union is 1e-20 + 1 + the other classes' q of the one point."""
+    case = Case(140 + 10 * i + n, SPECS[i], n=n)
+    assert ((case.gt >= 0) & (case.gt < C)).all()
+    _gradients_match_central_differences(case, case.objectives[name])
+
+
+@pytest.mark.parametrize("i", range(0, len(SPECS), 2))
+def test_gradients_of_a_negative_robust(i):
+    """LogLikelihood with robust < 0 where every labelled q + robust stays above the 1e-20 clamp (by a margin the finite
+    differences' steps cannot cross): there the objective is differentiable and d_mul_Q = q / (q + robust) / N its derivative."""
+    case = Case(240 + i, SPECS[i])
+    lr = case.learn()
+    Qn = lr.forward(NIT)[NIT]
+    ok = (case.gt >= 0) & (case.gt < C)
+    qmin = Qn[ok, case.gt[ok]].min()
+    robust = -0.5 * qmin
+    assert robust < -1e-3 and qmin + robust > 1e3 * H
+    obj = (LC.LOGLIKELIHOOD, case.gt, robust, None)
+    value, dq, _ = lr.objective(obj, Qn)
+    assert value < lr.objective((LC.LOGLIKELIHOOD, case.gt, 0.0, None), Qn)[0] and (dq[ok, case.gt[ok]] > 1.0 / N).all()
+    _gradients_match_central_differences(case, obj)
+
+
+def test_negative_robust_below_the_clamp_by_hand():
+    """Below the clamp the term is log(1e-20) / N and d_mul_Q is q / 1e-20 / N (objective.cpp:44-46), whatever q + robust is."""
+    Q = np.array([[0.25, 0.75], [0.5, 0.5], [0.9, 0.1]])
+    lr = LC.Learn(np.zeros((3, 2)), [], np.float64)
+    value, dq, S = lr.objective((LC.LOGLIKELIHOOD, np.array([0, 0, 0]), -0.5, None), Q)
+    want = (2 * math.log(1e-20) + math.log(0.9 - 0.5)) / 3
+    assert value == pytest.approx(want, rel=1e-15) and S == pytest.approx(-want, rel=1e-15)
+    assert dq[:, 0] == pytest.approx([0.25 / 1e-20 / 3, 0.5 / 1e-20 / 3, 0.9 / (0.9 - 0.5) / 3], rel=1e-15) and not dq[:, 1].any()
+    # in float32 the same entries are finite, of the order 1e19
+    lr32 = LC.Learn(np.zeros((3, 2), np.float32), [], np.float32)
+    _, dq32, _ = lr32.objective((LC.LOGLIKELIHOOD, np.array([0, 0, 0]), -0.5, None), Q.astype(np.float32))
+    assert dq32.dtype == np.float32 and np.isfinite(dq32).all() and dq32[1, 0] == np.float32(np.float32(np.float32(0.5) / np.float32(1e-20)) / np.float32(3))
+
+
+@pytest.mark.parametrize("absent", range(C))
+def test_iou_gradients_without_one_class(absent):
+    rng = np.random.default_rng(340 + absent)
+    gt = LC.gt_without_class(rng, N, C, absent)
+    assert set(gt[(gt >= 0) & (gt < C)].tolist()) == set(range(C)) - {absent} and (gt < 0).any() and (gt >= C).any()
+    case = Case(340 + absent, SPECS[absent], gt=gt)
+    _gradients_match_central_differences(case, (LC.IOU, gt, 0.0, None))
+
+
+def test_iou_without_one_class_by_hand():
+    """Class 1 never occurs: in = 0 and un = 1e-20 + its q over the labelled points, so its ratio and its column of
+    d_mul_Q are zero; class 0: in = q00 + q10, un = 1e-20 + 2; the skipped point counts nowhere."""
+    Q = np.array([[0.25, 0.75], [0.5, 0.5], [0.9, 0.1]])
+    lr = LC.Learn(np.zeros((3, 2)), [], np.float64)
+    value, dq, S = lr.objective((LC.IOU, np.array([0, 0, -1]), 0.0, None), Q)
+    inn, un = 0.75, 1e-20 + 2.0
+    assert value == pytest.approx((inn / un + 0.0 / (1e-20 + 1.25)) / 2, rel=1e-15) and S == pytest.approx(value, rel=1e-15)
+    assert dq[:2, 0] == pytest.approx([0.25 / (un * 2), 0.5 / (un * 2)], rel=1e-15)
+    assert not dq[:, 1].any() and not dq[2].any()
+
+
+@pytest.mark.parametrize("i", range(0, len(SPECS), 2))
+def test_a_ground_truth_without_a_valid_label_gives_zeros(i):
+    """Closed form: no point counts, so every value is 0 (IoU: C times 0 / 1e-20) and so is every gradient."""
+    gt = LC.invalid_gt(N, C)
+    assert not ((gt >= 0) & (gt < C)).any() and (gt < 0).any() and (gt >= C).any()
+    case = Case(440 + i, SPECS[i], gt=gt)
+    lr = case.learn()
+    for obj in ((LC.LOGLIKELIHOOD, gt, 0.01, None), (LC.LOGLIKELIHOOD, gt, -0.3, None), (LC.HAMMING, gt, 0.0, np.ones(C)), (LC.IOU, gt, 0.0, None)):
+        value, dq, S = lr.objective(obj, lr.forward(NIT)[NIT])
+        assert value == 0.0 and S == 0.0 and not dq.any()
+        value, ug, cg, _, vS, cS = lr.gradient(NIT, obj)
+        assert value == 0.0 and vS == 0.0 and not ug.any() and not cg.any() and not cS.any()
+        assert cg.shape == (sum(p.size for p in case.params),)
+        assert not LC.logistic_gradient(ug, case.f)[0].any()
 
 
 def test_apply_transpose_is_the_adjoint_of_the_kernel_apply():

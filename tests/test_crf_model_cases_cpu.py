@@ -67,3 +67,57 @@ def test_model_calls_without_a_context_are_refused():
     assert L.rvseg_crf_model_start(None, None) == capi.ERR_INVALID_ARG
     assert L.rvseg_crf_model_set(None, 1, 1, 0, None, None, 1) == capi.ERR_INVALID_ARG
     assert L.rvseg_crf_model_kl_device(None, None, None, None) == capi.ERR_INVALID_ARG
+
+
+def test_kl_entropy_at_the_clamp_by_hand(oracle):
+    """clamp_q's rows: q = 0 adds 0 log 1e-20f = 0, q <= 1e-20f adds q log 1e-20f, the one-hot row adds 1 log 1 = 0; every
+    element term is finite and the entropy is the plain sum of q log max(q, 1e-20f)."""
+    N, C = 40, 5
+    rng, U, terms = M.random_model(21, N, C, [(2, R.POTTS, R.NORMALIZE_SYMMETRIC)])
+    Q = M.clamp_q(rng, N, C)
+    lo = float(np.float32(1e-20))
+    assert (Q == 0).sum() >= N // 3 and (Q == np.float32(1e-30)).sum() >= N // 5 and (Q == np.float32(1e-20)).any()
+    assert (Q[N // 2] == np.eye(C, dtype=np.float32)[C // 2]).all()
+    above = np.nextafter(np.float32(1e-20), np.float32(1))
+    assert (Q == above).any() and float(above) > lo
+    terms_by_hand = [float(q) * math.log(max(float(q), lo)) for q in Q.ravel()]
+    assert all(math.isfinite(t) and t <= 0.0 for t in terms_by_hand)
+    assert terms_by_hand[(N // 2) * C + C // 2] == 0.0 and terms_by_hand[0] == 0.0
+    assert terms_by_hand[1 * C + C - 1] == pytest.approx(1e-30 * math.log(1e-20), rel=1e-7)   # (fp32 roundings of 1e-30, 1e-20)
+    parts, S = M.Model(oracle, U, terms).kl_parts(Q)
+    assert parts[0] == math.fsum(terms_by_hand) and S[0] == -parts[0] and np.isfinite(parts).all()
+
+
+def test_energy_of_labels_at_the_edges_by_hand(oracle):
+    """C = 64: label 63 reads the last column; 64, -1 and -128 are out of range and give 0 in both energies."""
+    N, C = 8, 64
+    _, U, terms = M.random_model(22, N, C, [(2, R.POTTS, R.NORMALIZE_SYMMETRIC)])
+    model = M.Model(oracle, U, terms)
+    labels = np.array([63, 64, -1, -128, 0, 63, 127, 5], np.int8)
+    u, p = model.unary_energy(labels), model.pairwise_energy(labels, -1)
+    assert np.array_equal(u, np.array([U[0, 63], 0, 0, 0, U[4, 0], U[5, 63], 0, U[7, 5]], np.float32))
+    assert not p[[1, 2, 3, 6]].any() and p[[0, 4, 5, 7]].all()
+    onehot = np.zeros((N, C), np.float32)
+    onehot[[0, 4, 5, 7], [63, 0, 63, 5]] = 1.0
+    assert p[5] == np.float32(-0.5) * model.apply(0, onehot)[5, 63]
+
+
+def test_one_class_and_ten_parts(oracle):
+    """C = 1: the marginals are all one, the entropy has no term (S = 0) and the unary part is the sum of U.  Eight terms:
+    ten parts, added in order by kl_sum."""
+    N = 30
+    _, U, terms = M.random_model(23, N, 1, [(2, R.MATRIX, R.NORMALIZE_SYMMETRIC), (3, R.POTTS, R.NORMALIZE_AFTER)])
+    model = M.Model(oracle, U, terms)
+    Q = model.step(model.start())
+    assert np.array_equal(Q, np.ones((N, 1), np.float32))
+    parts, S = model.kl_parts(Q)
+    assert parts[0] == 0.0 and S[0] == 0.0 and parts[1] == math.fsum(U.astype(np.float64).ravel())
+    assert parts[3] == math.fsum(model.apply(1, Q).astype(np.float64).ravel()) and parts[3] < 0   # q = 1: the Potts apply itself
+    specs = [(1 + k % 3, [R.POTTS, R.DIAGONAL, R.MATRIX][k % 3], k % 4) for k in range(8)]
+    rng, U, terms = M.random_model(24, 50, 3, specs)
+    parts, S = M.Model(oracle, U, terms).kl_parts(M.clamp_q(rng, 50, 3))
+    assert parts.shape == S.shape == (10,) and (S > 0).all()
+    kl = parts[0]
+    for v in parts[1:]:
+        kl = kl + v
+    assert M.kl_sum(parts) == kl
