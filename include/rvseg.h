@@ -405,10 +405,11 @@ rvseg_status rvseg_crf_model_trace_device(rvseg_ctx *ctx, int32_t iterations, fl
                                           int32_t unknown_label, double *d_kl_out, void *hip_stream);
 
 /* ---- Learning on the kept model: the objectives of objective.cpp:35-108 and the mean-field gradient of DenseCRF::gradient
- *      (densecrf.cpp:238-297) with respect to the unary energy and the label-compatibility parameters.  No gradient of the
- *      kernel parameters (Permutohedral::gradient needs the per-point rank, which the lattice here does not keep) and no
- *      optimiser: the caller hands (value, gradient) to its own.  Same conventions as the model calls above (host entries
- *      synchronise, _device entries enqueue on hip_stream, a stale model is RVSEG_ERR_INVALID_ARG).
+ *      (densecrf.cpp:238-297) with respect to the unary energy, the label-compatibility parameters and the kernel
+ *      parameters (the last under "Kernel-parameter gradient" below: the model keeps the per-point ranks of every term's
+ *      lattice and, for DIAG and FULL kernels, a copy of the features as passed).  No optimiser: the caller hands (value,
+ *      gradient) to its own.  Same conventions as the model calls above (host entries synchronise, _device entries enqueue
+ *      on hip_stream, a stale model is RVSEG_ERR_INVALID_ARG).
  *
  *      Definitions (fp32 with the library's pinned orders unless stated):
  *        apply_transpose   pairwise_[term]->applyTranspose(out, in) (pairwise.cpp:179-183, :63-80 with transpose = true): the
@@ -487,6 +488,71 @@ rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx *ctx, int32_t N, int32_t C, i
                                          double *out);
 rvseg_status rvseg_crf_logistic_gradient_device(rvseg_ctx *ctx, int32_t N, int32_t C, int32_t K, const float *d_unary_grad,
                                                 const float *d_f, double *d_out, void *hip_stream);
+
+/* ---- Kernel-parameter gradient on the kept model: DenseCRF::gradient's kernel_grad (densecrf.cpp:238-297) with what is
+ *      underneath it -- Permutohedral::gradient (permutohedral.cpp:611-695), DenseKernel::featureGradient / gradient
+ *      (pairwise.cpp:82-114, :152-163), PairwisePotential::kernelGradient (:202-207).  a, b: N x C point-major, C the
+ *      model's class count.  Conventions and argument rules of the learning calls above (stale model, term out of range and
+ *      NULL a / b are RVSEG_ERR_INVALID_ARG).
+ *
+ *      Definitions (fp32, one rounding per operation written, unless stated):
+ *        lattice_gradient   df (N x d) = Permutohedral::gradient(a, b), the reference's formula, with respect to the lattice
+ *                features.  With K the term's unnormalised lattice filter it is the exact derivative of b^T K a = a^T K^T b
+ *                (K^T: the blur axes in reverse); it equals that of a^T K b only for d = 1, where the two blurs commute, and
+ *                featureGradient's normalised kinds below, which mix K and K^T, are the derivative of neither form for
+ *                d > 1 (DESIGN section 16 has the measured deviations).  The formula is the contract.  Two
+ *                passes, dir = 0, 1:  the ordered splat of a (dir 0) or b (dir 1) -- per vertex, points ascending, each
+ *                product rounded; the blur (float)((double)o + 0.5 * (double)(n1 + n2)) over the axes 0 .. d (dir 0) or
+ *                d .. 0 (dir 1); then per point i with x = b (dir 0) or a (dir 1), alpha = 1.0f / (1 + powf(2, -d)) / (d + 1),
+ *                sf = the lattice's scale factors (permutohedral.cpp:623-625), o(r) the point's vertex of remainder r:
+ *                  for j = 0 .. d:  r0 = d - rank[j], r1 = r0 + 1 > d ? 0 : r0 + 1,
+ *                                   ra[j][k] = fl(alpha * values[o(r0)][k]) - fl(alpha * values[o(r1)][k])
+ *                  sm[k] = ra[0][k]
+ *                  for j = 1 .. d:  v = fl(sf[j-1] * fl(sm[k] - fl(j * ra[j][k]))),  grad_j = grad_j + fl(x[i][k] * v) over k
+ *                                   ascending from 0.0f, then sm[k] += ra[j][k]
+ *                  df[i][j-1] = grad (dir 0), fl(df[i][j-1] + grad) (dir 1)
+ *                rank: the d+1 ranks of the point (permutohedral.cpp:223-242), computed with the arithmetic of the lattice
+ *                build from the features the lattice was built from (after the kernel parameters).
+ *        lbl_Q   compat_apply: compatibility(Q) with no filter (pairwise.cpp:203-205): POTTS fl(-w q), DIAGONAL fl(v[c] q),
+ *                MATRIX sum_c' W[c][c'] q[c'] from c' = 0 up, each product and add rounded
+ *        featureGradient   fg (N x d), by the term's normalisation; n = the term's norm, K the unnormalised lattice filter
+ *                with the blur apply uses for C, K^T the same with the blur axes in reverse, G = lattice_gradient:
+ *                  NONE       fg = G(a, b)
+ *                  SYMMETRIC  fa = K^T(a n), fb = K(b n), X = fl(fl(0.5f * fl(fl(a fb) + fl(fa b))) * fl(fl(n n) n)),
+ *                             fg = fl(G(a n, b n) - G(X, 1))
+ *                  AFTER      fb = K(b), X = fl(fl(a fb) * fl(n n)), fg = fl(G(a n, b) - G(X, 1))
+ *                  BEFORE     fa = K^T(a), X = fl(fl(fa b) * fl(n n)), fg = fl(G(a, b n) - G(X, 1))
+ *        kernel_gradient   DenseKernel::gradient(a, b): CONST 0 values; FULL grad[b*d + a] = sum over i of
+ *                (double)fg[i][a] (double)f[i][b], d x d column-major like kernelParameters(); DIAG its diagonal, d values.
+ *                f: the features as passed to rvseg_crf_model_set (before the kernel parameters).  Products and sums in double,
+ *                reduced in the fixed order of rvseg_crf_logistic_gradient: the same input gives the same 64 bits on every
+ *                call.  fg_out (optional, N x d) receives featureGradient for every kernel type.
+ *        backward_kernel / gradient_kernel   _backward / _gradient with kernel_grad_out: doubles, the terms concatenated
+ *                in the layout of kernelParameters().  Per it = n-1 .. 0 and per term, kernel_gradient(b, lbl_Q(Q[it])) is
+ *                accumulated in double, from the same b the compatibility gradient uses.  iterations == 0 gives zeros.  With
+ *                kernel_grad_out == NULL they equal _backward / _gradient bit for bit (which are these calls with NULL). */
+/* Q, out: N x C */
+rvseg_status rvseg_crf_model_compat_apply(rvseg_ctx *ctx, int32_t term, const float *Q, float *out);
+rvseg_status rvseg_crf_model_compat_apply_device(rvseg_ctx *ctx, int32_t term, const float *d_Q, float *d_out, void *hip_stream);
+/* df_out: N x d floats, d the term's feature dimension */
+rvseg_status rvseg_crf_model_lattice_gradient(rvseg_ctx *ctx, int32_t term, const float *a, const float *b, float *df_out);
+rvseg_status rvseg_crf_model_lattice_gradient_device(rvseg_ctx *ctx, int32_t term, const float *d_a, const float *d_b, float *d_df_out,
+                                                     void *hip_stream);
+/* grad_out: doubles (CONST 0, DIAG d, FULL d x d), may be NULL;  fg_out: N x d floats, may be NULL */
+rvseg_status rvseg_crf_model_kernel_gradient(rvseg_ctx *ctx, int32_t term, const float *a, const float *b, double *grad_out,
+                                             float *fg_out);
+rvseg_status rvseg_crf_model_kernel_gradient_device(rvseg_ctx *ctx, int32_t term, const float *d_a, const float *d_b,
+                                                    double *d_grad_out, float *d_fg_out, void *hip_stream);
+rvseg_status rvseg_crf_model_backward_kernel(rvseg_ctx *ctx, int32_t iterations, const float *Q_all, const float *d_mul_Q,
+                                             float *unary_grad_out, double *compat_grad_out, double *kernel_grad_out);
+rvseg_status rvseg_crf_model_backward_kernel_device(rvseg_ctx *ctx, int32_t iterations, const float *d_Q_all, const float *d_d_mul_Q,
+                                                    float *d_unary_grad_out, double *d_compat_grad_out, double *d_kernel_grad_out,
+                                                    void *hip_stream);
+rvseg_status rvseg_crf_model_gradient_kernel(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj, double *value_out,
+                                             float *unary_grad_out, double *compat_grad_out, double *kernel_grad_out, float *Q_out);
+rvseg_status rvseg_crf_model_gradient_kernel_device(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj,
+                                                    double *d_value_out, float *d_unary_grad_out, double *d_compat_grad_out,
+                                                    double *d_kernel_grad_out, float *d_Q_out, void *hip_stream);
 
 /* ---- lattice introspection for parity tests: Permutohedral::init + compute
  *      (densecrf permutohedral.cpp:140-321,596-603).  offsets_out / bary_out: N x (d+1);

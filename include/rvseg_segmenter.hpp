@@ -964,26 +964,43 @@ public:
         onModel([&] { return rvseg_crf_model_trace(ctx_, n_iterations, Q.data(), map_out ? map_out->data() : nullptr, RVSEG_LABEL_ARGMAX, 0, kl.data()); });
         return Q;
     }
-    // ---- learning (densecrf.cpp:238-297) on the kept model.  No kernel-parameter gradient and no optimiser.
+    // ---- learning (densecrf.cpp:238-297) on the kept model.  No optimiser: the caller hands (value, gradient) to its own.
     std::vector<float> applyTranspose(int term, const std::vector<float>& in) {   // pairwise.cpp:179-183
         check(in.size() == (size_t)N_ * M_);
         std::vector<float> out((size_t)N_ * M_);
         onModel([&] { return rvseg_crf_model_apply_transpose(ctx_, term, in.data(), out.data()); });
         return out;
     }
+    // PairwisePotential::kernelGradient(b, Q) (pairwise.cpp:202-207): kernel_->gradient(b, compatibility(Q)), the layout of
+    // the term's kernel parameters, rounded to fp32 from the library's doubles
+    std::vector<float> kernelGradient(int term, const std::vector<float>& b, const std::vector<float>& Q) {
+        check(term >= 0 && term < (int)terms_.size() && b.size() == (size_t)N_ * M_ && Q.size() == b.size());
+        std::vector<float> lbl_Q(Q.size());
+        std::vector<double> g(kernelParams(terms_[(size_t)term]).size() + 1);
+        onModel([&] {
+            const rvseg_status st = rvseg_crf_model_compat_apply(ctx_, term, Q.data(), lbl_Q.data());
+            return st != RVSEG_OK ? st : rvseg_crf_model_kernel_gradient(ctx_, term, b.data(), lbl_Q.data(), g.data(), nullptr);
+        });
+        return std::vector<float>(g.begin(), g.end() - 1);
+    }
     // DenseCRF::gradient: the objective's value; unary_grad (optional) the gradient of unaryParameters() (empty without a
     // logistic unary), lbl_cmp_grad (optional) that of labelCompatibilityParameters(), both rounded to fp32 from the
-    // library's doubles; unary_energy_grad (optional): d value / d U, N x M
+    // library's doubles; unary_energy_grad (optional): d value / d U, N x M; kernel_grad (optional): the gradient of
+    // kernelParameters(), rounded to fp32 from the library's doubles
     double gradient(int n_iterations, const ObjectiveFunction& objective, std::vector<float>* unary_grad, std::vector<float>* lbl_cmp_grad,
-                    std::vector<float>* unary_energy_grad = nullptr) {
+                    std::vector<float>* unary_energy_grad = nullptr, std::vector<float>* kernel_grad = nullptr) {
         check(objective.gt.size() == (size_t)N_ && (objective.kind != RVSEG_OBJECTIVE_HAMMING || objective.class_weight.size() == (size_t)M_));
         const rvseg_crf_objective rec = objective.record();
         double value = 0;
         std::vector<float> ug((size_t)N_ * M_);
-        std::vector<double> cg(labelCompatibilityParameters().size() + 1);
+        std::vector<double> cg(labelCompatibilityParameters().size() + 1), kg(kernelParameters().size() + 1);
         const bool want_ug = unary_grad || unary_energy_grad;
-        onModel([&] { return rvseg_crf_model_gradient(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, lbl_cmp_grad ? cg.data() : nullptr, nullptr); });
+        onModel([&] {
+            return rvseg_crf_model_gradient_kernel(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, lbl_cmp_grad ? cg.data() : nullptr,
+                                                   kernel_grad ? kg.data() : nullptr, nullptr);
+        });
         if (lbl_cmp_grad) lbl_cmp_grad->assign(cg.begin(), cg.end() - 1);
+        if (kernel_grad) kernel_grad->assign(kg.begin(), kg.end() - 1);
         if (unary_grad) {
             unary_grad->clear();
             if (!logistic_f_.empty()) {

@@ -56,6 +56,10 @@ SYMBOLS = [
     "rvseg_crf_model_objective", "rvseg_crf_model_objective_device", "rvseg_crf_model_backward", "rvseg_crf_model_backward_device",
     "rvseg_crf_model_gradient", "rvseg_crf_model_gradient_device", "rvseg_crf_model_set_compat", "rvseg_crf_model_set_unary",
     "rvseg_crf_model_set_unary_device", "rvseg_crf_logistic_gradient", "rvseg_crf_logistic_gradient_device",
+    "rvseg_crf_model_compat_apply", "rvseg_crf_model_compat_apply_device",
+    "rvseg_crf_model_lattice_gradient", "rvseg_crf_model_lattice_gradient_device", "rvseg_crf_model_kernel_gradient",
+    "rvseg_crf_model_kernel_gradient_device", "rvseg_crf_model_backward_kernel", "rvseg_crf_model_backward_kernel_device",
+    "rvseg_crf_model_gradient_kernel", "rvseg_crf_model_gradient_kernel_device",
 ]
 
 
@@ -234,6 +238,16 @@ def lib():
     L.rvseg_crf_model_set_unary_device.argtypes = [vp, vp, i32, vp]
     L.rvseg_crf_logistic_gradient.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.rvseg_crf_logistic_gradient_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.rvseg_crf_model_compat_apply.argtypes = [vp, i32, vp, vp]
+    L.rvseg_crf_model_compat_apply_device.argtypes = [vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_lattice_gradient.argtypes = [vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_lattice_gradient_device.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rvseg_crf_model_kernel_gradient.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rvseg_crf_model_kernel_gradient_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_backward_kernel.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_backward_kernel_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_gradient_kernel.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_gradient_kernel_device.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp, vp]
     L.rvseg_rectify_depth.argtypes = [vp, i32, vp, vp, f32, f32, vp]
     L.rvseg_rectify_depth_device.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp]
     L.rvseg_external_layers_set.argtypes = [vp, i32, vp]

@@ -228,4 +228,22 @@ void launch_compat_grad(const LatticeDev& L, int C, bool seq, const float* value
 // out[k * C + m] = sum_i g[i][m] f[i][k]; partials: learn_partials_doubles(64)
 void launch_logistic_gradient(const float* g, const float* f, long long n_points, int C, int K, double* partials, double* out, hipStream_t s);
 
+
+// ---- kernels_crf_kgrad.hip: the kernel-parameter gradient of a kept model ------------------------------------------------
+// ranks[i]: the d+1 ranks of point i of the lattice's one frame (0 .. d, 3 bits each, rank[0] lowest), from the features
+// the lattice was built from
+void launch_point_ranks(const LatticeDev& L, const float* feat, unsigned* ranks, hipStream_t s);
+// one direction of Permutohedral::gradient's slicing gradient: values = the blurred table (M x C), x = the weighting
+// matrix (N x C); df (N x d) assigned (dir 0) or added to (dir 1).  Grid: kl_blocks(C, n_points)
+void launch_slice_gradient(const LatticeDev& L, int C, const float* values, const float* x, const unsigned* ranks, int dir, long long n_points,
+                           float* df, hipStream_t s);
+// out = compatibility(Q) without a filter; compat: the term's C (Diagonal / Potts) or C x C (Matrix) floats
+void launch_compat_rows(int C, bool matrix, const float* compat, const float* Q, long long n_points, float* out, hipStream_t s);
+// element-wise steps of featureGradient over `total` elements in rows of C (n: per row): mode 0 a n; 1 the SYMMETRIC X;
+// 2 fl(a b) fl(n n); 3 a - b; 4 ones
+void launch_kgrad_mix(int mode, const float* a, const float* b, const float* fa, const float* fb, const float* n, int C, long long total,
+                      float* out, hipStream_t s);
+// out += the d x d column-major `full` (FULL) or its diagonal (DIAG)
+void launch_kgrad_accumulate(bool diag, int d, const double* full, double* out, hipStream_t s);
+
 }  // namespace rvseg

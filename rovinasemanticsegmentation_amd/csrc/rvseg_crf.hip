@@ -754,10 +754,11 @@ rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& f
 
 // One pairwise term's lattice input: N x d features in host or device memory, the kernel parameters that transform them
 // (pairwise.cpp:140-152; none for CONST_KERNEL or a null pointer) and the normaliser the term needs (rvseg_norm_kind)
-struct TermInput { int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; };
+// keep (a kept model's term only): where the point ranks and, for a DIAG or FULL kernel, a copy of the features go
+struct TermInput { int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; TermKeep* keep = nullptr; };
 
 static TermInput potts_input(int d, const float* features, bool on_host) {
-    return TermInput{d, features, on_host, RVSEG_CONST_KERNEL, nullptr, RVSEG_NORMALIZE_SYMMETRIC};
+    return TermInput{d, features, on_host, RVSEG_CONST_KERNEL, nullptr, RVSEG_NORMALIZE_SYMMETRIC, nullptr};
 }
 
 // Permutohedral::init + normaliser of term `t` on lattice `lb` (host features are copied into cs->feat, kernel
@@ -771,6 +772,10 @@ static rvseg_status build_lattice(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb,
         RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, t.features, (size_t)N * t.d * 4, hipMemcpyHostToDevice, s));
         f = cs->feat.as<float>();
     }
+    if (t.keep && t.kernel_type != RVSEG_CONST_KERNEL) {   // f_ of the kernel-parameter gradient
+        if ((st = dev_reserve(ctx, t.keep->feat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
+        RV_HIP(ctx, hipMemcpyAsync(t.keep->feat.p, f, (size_t)N * t.d * 4, hipMemcpyDeviceToDevice, s));
+    }
     if (t.kernel_params && t.kernel_type != RVSEG_CONST_KERNEL) {
         KernelParams kp{};
         const int np = t.kernel_type == RVSEG_DIAG_KERNEL ? t.d : t.d * t.d;
@@ -782,6 +787,11 @@ static rvseg_status build_lattice(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb,
     FeatureSource fs{};
     fs.feat = f;   // (mode 0)
     if ((st = lattice_build(ctx, cs, lb, fs, s, t.norm)) != RVSEG_OK) return st;
+    if (t.keep) {   // the ranks, from the features the lattice was built from
+        if ((st = dev_reserve(ctx, t.keep->rank, (size_t)N * 4)) != RVSEG_OK) return st;
+        launch_point_ranks(lb.dev, f, t.keep->rank.as<unsigned>(), s);
+        RV_LAUNCH_OK(ctx);
+    }
     return lattice_counters(ctx, cs, lb, s, cnt);
 }
 
@@ -894,8 +904,9 @@ rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry) {
 // A learned model's terms (arguments checked by the caller): their plan, their compatibilities in context memory
 // (uploaded from CrfState::h_compat, which outlives the copy; also for Potts terms, which do not read them) and their lattices
 rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
-                           std::vector<TermPlan>& plan, hipStream_t s) {
+                           std::vector<TermPlan>& plan, hipStream_t s, TermKeep* keep) {
     plan_terms(C, n_terms, terms, plan, cs->h_compat);
+    for (int k = 0; k < n_terms; k++) { plan[k].kernel = terms[k].kernel_type; plan[k].d = terms[k].d; }
     if (!cs->h_compat.empty()) {
         rvseg_status st = dev_reserve(ctx, cs->compat, cs->h_compat.size() * 4);
         if (st != RVSEG_OK) return st;
@@ -903,7 +914,8 @@ rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_ter
     }
     TermInput in[8];
     for (int k = 0; k < n_terms; k++)
-        in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization};
+        in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization,
+                          keep ? keep + k : nullptr};
     return build_lattices(ctx, cs, N, n_terms, in, s);
 }
 

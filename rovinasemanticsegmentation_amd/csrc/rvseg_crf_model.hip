@@ -27,7 +27,7 @@ struct ModelIo {
     CrfState* cs = nullptr;    // (enter)
     hipStream_t s = nullptr;   // (enter)
     bool timed = false;        // a device entry that records stage marks (time)
-    static constexpr int MAX_HOME = 4;
+    static constexpr int MAX_HOME = 6;
     struct { void* host; const void* dev; size_t bytes; } home[MAX_HOME];   // the downloads of a host entry, in order (done)
     int n_home = 0;
 
@@ -101,7 +101,7 @@ static rvseg_status model_set(ModelIo io, int32_t N, int32_t C, int32_t n_terms,
     const size_t tot = (size_t)N * C;
     RV_TRY(dev_reserve(ctx, m.unary, tot * 4));
     RV_HIP(ctx, hipMemcpyAsync(m.unary.p, unary, tot * 4, io.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, io.s));
-    RV_TRY(terms_prepare(ctx, io.cs, N, C, n_terms, terms, io.on_host, m.plan, io.s));
+    RV_TRY(terms_prepare(ctx, io.cs, N, C, n_terms, terms, io.on_host, m.plan, io.s, m.keep));
     // every lattice build has waited for the stream; a model without terms waits here: the caller's buffers are free
     if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(io.s));
     m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
@@ -275,9 +275,147 @@ static rvseg_status model_objective_on(rvseg_ctx* ctx, CrfState* cs, const rvseg
     return RVSEG_OK;
 }
 
-// densecrf.cpp:258-296 from d_mul_Q and Q[0 .. n]; d_ug / d_cg may be null
+// ---------------------------------------------------------------------------------------------
+// The kernel-parameter gradient (include/rvseg.h, "Kernel-parameter gradient"): Permutohedral::gradient, DenseKernel::
+// featureGradient / gradient, PairwisePotential::kernelGradient.
+// ---------------------------------------------------------------------------------------------
+static size_t term_kernel_params(const TermPlan& t) {
+    return t.kernel == RVSEG_FULL_KERNEL ? (size_t)t.d * t.d : t.kernel == RVSEG_DIAG_KERNEL ? (size_t)t.d : 0;
+}
+
+// the layout of kernelParameters(): the terms concatenated
+static size_t model_kernel_params(const CrfModel& m, int upto = -1) {
+    size_t n = 0;
+    const int end = upto < 0 ? (int)m.plan.size() : upto;
+    for (int k = 0; k < end; k++) n += term_kernel_params(m.plan[k]);
+    return n;
+}
+
+// the work memory of model_kernel_gradient_term for term k (beside mf_scratch), by what the term needs: a term without
+// normalisation mixes nothing (fg alone), SYMMETRIC scales and filters both matrices, AFTER / BEFORE one of each
+static rvseg_status model_kgrad_scratch(rvseg_ctx* ctx, CrfState* cs, int k) {
+    CrfModel& m = cs->model;
+    const TermPlan& t = m.plan[k];
+    const size_t tot = (size_t)m.N * m.C * 4, nd = (size_t)m.N * t.d * 4;
+    RV_TRY(dev_reserve(ctx, m.kg_fg, nd));
+    if (t.norm != RVSEG_NO_NORMALIZATION) {
+        const bool sym = t.norm == RVSEG_NORMALIZE_SYMMETRIC;
+        for (DevBuf* b : {&m.kg_x, &m.kg_ones}) RV_TRY(dev_reserve(ctx, *b, tot));
+        if (sym || t.norm == RVSEG_NORMALIZE_AFTER) for (DevBuf* b : {&m.kg_an, &m.kg_fb}) RV_TRY(dev_reserve(ctx, *b, tot));
+        if (sym || t.norm == RVSEG_NORMALIZE_BEFORE) for (DevBuf* b : {&m.kg_bn, &m.kg_fa}) RV_TRY(dev_reserve(ctx, *b, tot));
+        for (DevBuf* b : {&m.kg_g1, &m.kg_g2}) RV_TRY(dev_reserve(ctx, *b, nd));
+    }
+    if (t.kernel == RVSEG_CONST_KERNEL) return RVSEG_OK;
+    RV_TRY(dev_reserve(ctx, m.kg_full, 49 * sizeof(double)));
+    return dev_reserve(ctx, cs->learn_partials, learn_partials_doubles(std::max(m.C, 7)) * sizeof(double));
+}
+
+// Permutohedral::gradient (permutohedral.cpp:611-695) of term k: per direction the ordered splat of a (dir 0) or b (dir 1),
+// the blur of seqCompute's rounding with the axes ascending (dir 0) or descending (dir 1), the slicing gradient weighted
+// by the other matrix.  df: N x d.  Needs mf_scratch.
+static void model_lattice_gradient_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* a, const float* b, float* df) {
+    const LatticeDev& L = cs->lat[k].dev;
+    auto& sc = cs->scratch[r.slot];
+    const unsigned* ranks = cs->model.keep[k].rank.as<unsigned>();
+    for (int dir = 0; dir < 2; dir++) {
+        launch_splat(L, model_view(cs->model, dir ? b : a), r.C, 0, sc.val_a.as<float>(), r.s);
+        const float* blurred = launch_blur(L, r.C, true, dir == 1, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+        launch_slice_gradient(L, r.C, blurred, dir ? a : b, ranks, dir, r.n_points, df, r.s);
+    }
+}
+
+// lattice_.compute(in, transpose): the filter without any normalisation, with the blur apply / apply_transpose use
+static void model_plain_filter(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* in, bool transpose, float* out) {
+    const LatticeDev& L = cs->lat[k].dev;
+    auto& sc = cs->scratch[r.slot];
+    launch_splat(L, model_view(cs->model, in), r.C, 0, sc.val_a.as<float>(), r.s);
+    const float* blurred = launch_blur(L, r.C, r.C <= 2, transpose, sc.val_a.as<float>(), sc.val_b.as<float>(), r.s);
+    launch_slice(L, r.C, r.C <= 2, 0, blurred, 0.f, out, r.n_points, r.s);
+}
+
+// DenseKernel::featureGradient (pairwise.cpp:87-114) of term k into fg (N x d).  Needs mf_scratch and model_kgrad_scratch.
+// Stage marks of a timed call, each once, where its work starts: "filter" (the scaled matrices, K / K^T and X; normalised
+// terms only), then "lattice_gradient" (every G, and their difference).
+static void model_feature_gradient_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* a, const float* b, float* fg) {
+    CrfModel& m = cs->model;
+    const TermPlan& t = r.plan[k];
+    if (t.norm == RVSEG_NO_NORMALIZATION) {
+        if (r.timed) timer_mark(ctx, "lattice_gradient", r.s);
+        return model_lattice_gradient_term(ctx, cs, r, k, a, b, fg);
+    }
+    const long long tot = (long long)m.N * m.C, nd = (long long)m.N * t.d;
+    const float* n = cs->lat[k].dev.norm;
+    float *an = m.kg_an.as<float>(), *bn = m.kg_bn.as<float>(), *fa = m.kg_fa.as<float>(), *fb = m.kg_fb.as<float>(), *X = m.kg_x.as<float>();
+    float *ones = m.kg_ones.as<float>(), *g1 = m.kg_g1.as<float>(), *g2 = m.kg_g2.as<float>();
+    const auto mix = [&](int mode, const float* x, const float* y, const float* fx, const float* fy, float* out) {
+        launch_kgrad_mix(mode, x, y, fx, fy, n, m.C, tot, out, r.s);
+    };
+    const float *ga = a, *gb = b;   // the arguments of the first G
+    if (r.timed) timer_mark(ctx, "filter", r.s);
+    if (t.norm == RVSEG_NORMALIZE_SYMMETRIC) {   // :90-97
+        mix(0, a, nullptr, nullptr, nullptr, an);
+        mix(0, b, nullptr, nullptr, nullptr, bn);
+        model_plain_filter(ctx, cs, r, k, an, true, fa);
+        model_plain_filter(ctx, cs, r, k, bn, false, fb);
+        mix(1, a, b, fa, fb, X);
+        ga = an; gb = bn;
+    } else if (t.norm == RVSEG_NORMALIZE_AFTER) {   // :98-105
+        model_plain_filter(ctx, cs, r, k, b, false, fb);
+        mix(2, a, fb, nullptr, nullptr, X);
+        mix(0, a, nullptr, nullptr, nullptr, an);
+        ga = an;
+    } else {   // NORMALIZE_BEFORE, :106-113
+        model_plain_filter(ctx, cs, r, k, a, true, fa);
+        mix(2, fa, b, nullptr, nullptr, X);
+        mix(0, b, nullptr, nullptr, nullptr, bn);
+        gb = bn;
+    }
+    mix(4, nullptr, nullptr, nullptr, nullptr, ones);
+    if (r.timed) timer_mark(ctx, "lattice_gradient", r.s);
+    model_lattice_gradient_term(ctx, cs, r, k, ga, gb, g1);
+    model_lattice_gradient_term(ctx, cs, r, k, X, ones, g2);
+    launch_kgrad_mix(3, g1, g2, nullptr, nullptr, nullptr, t.d, nd, fg, r.s);
+}
+
+// DenseKernel::gradient(a, b) (pairwise.cpp:152-163) of term k: the feature gradient into fg (null: work memory), and for
+// a DIAG or FULL kernel its product with the raw features ADDED to the term's doubles d_grad (null: none)
+static void model_kernel_gradient_term(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, int k, const float* a, const float* b, double* d_grad,
+                                       float* fg) {
+    CrfModel& m = cs->model;
+    const TermPlan& t = r.plan[k];
+    if (!fg) fg = m.kg_fg.as<float>();
+    model_feature_gradient_term(ctx, cs, r, k, a, b, fg);
+    if (!d_grad || t.kernel == RVSEG_CONST_KERNEL) return;
+    if (r.timed) timer_mark(ctx, "reduce", r.s);
+    launch_logistic_gradient(fg, m.keep[k].feat.as<float>(), m.N, t.d, t.d, cs->learn_partials.as<double>(), m.kg_full.as<double>(), r.s);
+    launch_kgrad_accumulate(t.kernel == RVSEG_DIAG_KERNEL, t.d, m.kg_full.as<double>(), d_grad, r.s);
+}
+
+static rvseg_status model_lattice_gradient_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_a, const float* d_b, float* d_df,
+                                              hipStream_t s) {
+    const MfRun run = model_run(cs, s, false);
+    RV_TRY(mf_scratch(ctx, cs, run));
+    model_lattice_gradient_term(ctx, cs, run, term, d_a, d_b, d_df);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// d_grad (may be null): the term's doubles, assigned
+static rvseg_status model_kernel_gradient_on(rvseg_ctx* ctx, CrfState* cs, int term, const float* d_a, const float* d_b, double* d_grad,
+                                             float* d_fg, hipStream_t s, bool timed) {
+    const MfRun run = model_run(cs, s, timed);
+    RV_TRY(mf_scratch(ctx, cs, run));
+    RV_TRY(model_kgrad_scratch(ctx, cs, term));
+    const size_t n = term_kernel_params(cs->model.plan[term]);
+    if (d_grad && n) RV_HIP(ctx, hipMemsetAsync(d_grad, 0, n * sizeof(double), s));
+    model_kernel_gradient_term(ctx, cs, run, term, d_a, d_b, d_grad, d_fg);
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// densecrf.cpp:258-296 from d_mul_Q and Q[0 .. n]; d_ug / d_cg / d_kg may be null
 static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const float* d_Qall, const float* d_dq, float* d_ug,
-                                      double* d_cg, hipStream_t s) {
+                                      double* d_cg, double* d_kg, hipStream_t s) {
     CrfModel& m = cs->model;
     const MfRun run = model_run(cs, s, false);
     const size_t tot = (size_t)m.N * m.C;
@@ -290,6 +428,13 @@ static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iteratio
     float *b = m.bgrad.as<float>(), *tsum = m.tsum.as<float>(), *tapp = m.tapp.as<float>();
     launch_sum_normalize(d_dq, false, d_Qall + (size_t)iterations * tot, m.C, m.N, b, d_ug, 1, s);
     if (d_cg && model_compat_params(m)) RV_HIP(ctx, hipMemsetAsync(d_cg, 0, model_compat_params(m) * sizeof(double), s));
+    if (d_kg && !model_kernel_params(m)) d_kg = nullptr;
+    if (d_kg) {   // (a grow-only reserve per term with kernel parameters, before anything of the pass is enqueued)
+        RV_TRY(dev_reserve(ctx, m.kg_lbl, tot * 4));
+        for (int k = 0; k < n_terms; k++)
+            if (m.plan[k].kernel != RVSEG_CONST_KERNEL) RV_TRY(model_kgrad_scratch(ctx, cs, k));
+        RV_HIP(ctx, hipMemsetAsync(d_kg, 0, model_kernel_params(m) * sizeof(double), s));
+    }
     for (int it = iterations - 1; it >= 0; it--) {
         const float* Qit = d_Qall + (size_t)it * tot;
         if (n_terms == 0) RV_HIP(ctx, hipMemsetAsync(tsum, 0, tot * 4, s));   // tmp1.fill(0), :270
@@ -300,6 +445,10 @@ static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iteratio
                 RV_TRY(model_filter_term(ctx, cs, run, k, Qit, false, &blurred, &post));
                 launch_compat_grad(cs->lat[k].dev, m.C, m.C <= 2, blurred, post, m.plan[k].compat, b, m.N, cs->learn_partials.as<double>(),
                                    d_cg + model_compat_params(m, k), s);
+            }
+            if (d_kg && m.plan[k].kernel != RVSEG_CONST_KERNEL) {   // pairwise_[k]->kernelGradient(b, Q[it]) (pairwise.cpp:202-207)
+                launch_compat_rows(m.C, m.plan[k].matrix, run.d_compat + m.plan[k].off, Qit, m.N, m.kg_lbl.as<float>(), s);
+                model_kernel_gradient_term(ctx, cs, run, k, b, m.kg_lbl.as<float>(), d_kg + model_kernel_params(m, k), nullptr);
             }
             RV_TRY(model_apply_term(ctx, cs, run, k, b, tapp, true));
             launch_add_rows(k == 0, tapp, tsum, (long long)tot, s);
@@ -312,7 +461,7 @@ static rvseg_status model_backward_on(rvseg_ctx* ctx, CrfState* cs, int iteratio
 
 // the forward pass of DenseCRF::gradient (:240-253) keeping Q[0 .. n] in CrfModel::qs, then objective and backward
 static rvseg_status model_gradient_on(rvseg_ctx* ctx, CrfState* cs, int iterations, const rvseg_crf_objective& obj, double* d_value, float* d_ug,
-                                      double* d_cg, float* d_Q_out, hipStream_t s) {
+                                      double* d_cg, double* d_kg, float* d_Q_out, hipStream_t s) {
     CrfModel& m = cs->model;
     const MfRun run = model_run(cs, s, false);
     const size_t tot = (size_t)m.N * m.C;
@@ -330,7 +479,7 @@ static rvseg_status model_gradient_on(rvseg_ctx* ctx, CrfState* cs, int iteratio
     RV_LAUNCH_OK(ctx);
     const float* Qn = qs + (size_t)iterations * tot;
     RV_TRY(model_objective_on(ctx, cs, obj, Qn, d_value, m.dq.as<float>(), s));
-    RV_TRY(model_backward_on(ctx, cs, iterations, qs, m.dq.as<float>(), d_ug, d_cg, s));
+    RV_TRY(model_backward_on(ctx, cs, iterations, qs, m.dq.as<float>(), d_ug, d_cg, d_kg, s));
     if (d_Q_out) RV_HIP(ctx, hipMemcpyAsync(d_Q_out, Qn, tot * 4, hipMemcpyDeviceToDevice, s));
     return RVSEG_OK;
 }
@@ -430,8 +579,48 @@ static rvseg_status model_objective(ModelIo io, const rvseg_crf_objective* obj, 
     return io.done();
 }
 
+// lbl_Q = compatibility(Q) with no filter (pairwise.cpp:203-205)
+static rvseg_status model_compat_apply(ModelIo io, int32_t term, const float* Q, float* out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(Q && out);
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    RV_TRY(io.in(m.kg_a, &Q, (size_t)m.N * m.C));
+    RV_TRY(io.out(m.kg_b, &out, (size_t)m.N * m.C));
+    launch_compat_rows(m.C, m.plan[term].matrix, io.cs->compat.as<float>() + m.plan[term].off, Q, m.N, out, io.s);
+    RV_LAUNCH_OK(io.ctx);
+    return io.done();
+}
+
+static rvseg_status model_lattice_gradient(ModelIo io, int32_t term, const float* a, const float* b, float* df_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(a && b && df_out);
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    const size_t tot = (size_t)m.N * m.C;
+    RV_TRY(io.in(m.kg_a, &a, tot));
+    RV_TRY(io.in(m.kg_b, &b, tot));
+    RV_TRY(io.out(m.kg_out, &df_out, (size_t)m.N * m.plan[term].d));
+    RV_TRY(model_lattice_gradient_on(io.ctx, io.cs, term, a, b, df_out, io.s));
+    return io.done();
+}
+
+static rvseg_status model_kernel_gradient(ModelIo io, int32_t term, const float* a, const float* b, double* grad_out, float* fg_out) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(a && b);
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    const size_t tot = (size_t)m.N * m.C;
+    RV_TRY(io.in(m.kg_a, &a, tot));
+    RV_TRY(io.in(m.kg_b, &b, tot));
+    RV_TRY(io.out(m.kg_grad, &grad_out, term_kernel_params(m.plan[term])));
+    RV_TRY(io.out(m.kg_out, &fg_out, (size_t)m.N * m.plan[term].d));
+    RV_TRY(model_kernel_gradient_on(io.ctx, io.cs, term, a, b, grad_out, fg_out, io.s, io.time()));
+    return io.done();
+}
+
 static rvseg_status model_backward(ModelIo io, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
-                                   double* compat_grad_out) {
+                                   double* compat_grad_out, double* kernel_grad_out) {
     RV_TRY(io.enter());
     RV_MODEL_ARGS(iterations >= 0 && Q_all && d_mul_Q);
     CrfModel& m = io.cs->model;
@@ -440,12 +629,13 @@ static rvseg_status model_backward(ModelIo io, int32_t iterations, const float* 
     RV_TRY(io.in(m.dq, &d_mul_Q, tot));
     RV_TRY(io.out(m.ug, &unary_grad_out, tot));
     RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
-    RV_TRY(model_backward_on(io.ctx, io.cs, iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out, io.s));
+    RV_TRY(io.out(m.kg_grad, &kernel_grad_out, model_kernel_params(m)));
+    RV_TRY(model_backward_on(io.ctx, io.cs, iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out, kernel_grad_out, io.s));
     return io.done();
 }
 
 static rvseg_status model_gradient(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, float* unary_grad_out,
-                                   double* compat_grad_out, float* Q_out) {
+                                   double* compat_grad_out, double* kernel_grad_out, float* Q_out) {
     RV_TRY(io.enter());
     RV_TRY(objective_arg(io.ctx, obj));
     RV_MODEL_ARGS(iterations >= 0 && value_out);
@@ -457,9 +647,11 @@ static rvseg_status model_gradient(ModelIo io, int32_t iterations, const rvseg_c
     io.out_at(m.stats.as<double>() + 128, &value_out, 1);
     RV_TRY(io.out(m.ug, &unary_grad_out, tot));
     RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
+    RV_TRY(io.out(m.kg_grad, &kernel_grad_out, model_kernel_params(m)));
     io.time();   // (the forward pass itself records no marks)
     // a host entry downloads Q[n] from where the forward pass has left it: no device copy of it
-    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, unary_grad_out, compat_grad_out, io.on_host ? nullptr : Q_out, io.s));
+    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, unary_grad_out, compat_grad_out, kernel_grad_out,
+                             io.on_host ? nullptr : Q_out, io.s));
     io.out_at(m.qs.as<float>() + (size_t)iterations * tot, &Q_out, tot);
     return io.done();
 }
@@ -573,20 +765,65 @@ rvseg_status rvseg_crf_model_objective_device(rvseg_ctx* ctx, const rvseg_crf_ob
 
 rvseg_status rvseg_crf_model_backward(rvseg_ctx* ctx, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
                                       double* compat_grad_out) {
-    return model_backward(host_io(ctx, __func__), iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out);
+    return model_backward(host_io(ctx, __func__), iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out, nullptr);
 }
 rvseg_status rvseg_crf_model_backward_device(rvseg_ctx* ctx, int32_t iterations, const float* d_Q_all, const float* d_d_mul_Q,
                                              float* d_unary_grad_out, double* d_compat_grad_out, void* hip_stream) {
-    return model_backward(device_io(ctx, hip_stream, __func__), iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out);
+    return model_backward(device_io(ctx, hip_stream, __func__), iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out, nullptr);
 }
 
 rvseg_status rvseg_crf_model_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
                                       float* unary_grad_out, double* compat_grad_out, float* Q_out) {
-    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, Q_out);
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, nullptr, Q_out);
 }
 rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
                                              float* d_unary_grad_out, double* d_compat_grad_out, float* d_Q_out, void* hip_stream) {
-    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out, d_Q_out);
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out, nullptr, d_Q_out);
+}
+
+rvseg_status rvseg_crf_model_compat_apply(rvseg_ctx* ctx, int32_t term, const float* Q, float* out) {
+    return model_compat_apply(host_io(ctx, __func__), term, Q, out);
+}
+rvseg_status rvseg_crf_model_compat_apply_device(rvseg_ctx* ctx, int32_t term, const float* d_Q, float* d_out, void* hip_stream) {
+    return model_compat_apply(device_io(ctx, hip_stream, __func__), term, d_Q, d_out);
+}
+
+rvseg_status rvseg_crf_model_lattice_gradient(rvseg_ctx* ctx, int32_t term, const float* a, const float* b, float* df_out) {
+    return model_lattice_gradient(host_io(ctx, __func__), term, a, b, df_out);
+}
+rvseg_status rvseg_crf_model_lattice_gradient_device(rvseg_ctx* ctx, int32_t term, const float* d_a, const float* d_b, float* d_df_out,
+                                                     void* hip_stream) {
+    return model_lattice_gradient(device_io(ctx, hip_stream, __func__), term, d_a, d_b, d_df_out);
+}
+
+rvseg_status rvseg_crf_model_kernel_gradient(rvseg_ctx* ctx, int32_t term, const float* a, const float* b, double* grad_out, float* fg_out) {
+    return model_kernel_gradient(host_io(ctx, __func__), term, a, b, grad_out, fg_out);
+}
+rvseg_status rvseg_crf_model_kernel_gradient_device(rvseg_ctx* ctx, int32_t term, const float* d_a, const float* d_b, double* d_grad_out,
+                                                    float* d_fg_out, void* hip_stream) {
+    return model_kernel_gradient(device_io(ctx, hip_stream, __func__), term, d_a, d_b, d_grad_out, d_fg_out);
+}
+
+rvseg_status rvseg_crf_model_backward_kernel(rvseg_ctx* ctx, int32_t iterations, const float* Q_all, const float* d_mul_Q, float* unary_grad_out,
+                                             double* compat_grad_out, double* kernel_grad_out) {
+    return model_backward(host_io(ctx, __func__), iterations, Q_all, d_mul_Q, unary_grad_out, compat_grad_out, kernel_grad_out);
+}
+rvseg_status rvseg_crf_model_backward_kernel_device(rvseg_ctx* ctx, int32_t iterations, const float* d_Q_all, const float* d_d_mul_Q,
+                                                    float* d_unary_grad_out, double* d_compat_grad_out, double* d_kernel_grad_out,
+                                                    void* hip_stream) {
+    return model_backward(device_io(ctx, hip_stream, __func__), iterations, d_Q_all, d_d_mul_Q, d_unary_grad_out, d_compat_grad_out,
+                          d_kernel_grad_out);
+}
+
+rvseg_status rvseg_crf_model_gradient_kernel(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
+                                             float* unary_grad_out, double* compat_grad_out, double* kernel_grad_out, float* Q_out) {
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, kernel_grad_out, Q_out);
+}
+rvseg_status rvseg_crf_model_gradient_kernel_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
+                                                    float* d_unary_grad_out, double* d_compat_grad_out, double* d_kernel_grad_out,
+                                                    float* d_Q_out, void* hip_stream) {
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out,
+                          d_kernel_grad_out, d_Q_out);
 }
 
 rvseg_status rvseg_crf_model_set_compat(rvseg_ctx* ctx, int32_t term, const float* params) {

@@ -32,7 +32,13 @@ struct TermPlan {
     bool matrix = false;
     size_t off = 0;        // first float of the term's compatibility in CrfState::compat (C, or C x C symmetric)
     int compat = RVSEG_COMPAT_POTTS;   // rvseg_compat_kind: the layout of the term's parameters and of their gradient
+    int kernel = RVSEG_CONST_KERNEL;   // rvseg_kernel_kind and the feature dimension: the layout of the kernel parameters'
+    int d = 0;                         // gradient (terms_prepare)
 };
+
+// What a kept model keeps of a term beside its lattice, for the kernel-parameter gradient: the ranks of every point (3 bits
+// each in one word) and, for a DIAG or FULL kernel, the features as the caller passed them (f_, N x d).
+struct TermKeep { DevBuf rank, feat; };
 
 // The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
 // CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
@@ -52,6 +58,12 @@ struct CrfModel {
     // work memory (never the mean field's tmp): the energies' one-hot rows, the KL partials, the backward pass's b, tmp1, tmp2
     DevBuf onehot, partials, bgrad, tsum, tapp;
     DevBuf stats;              // 128 doubles of IoU sums + the objective's value (of a host entry)
+    // the kernel-parameter gradient.  Per term: ranks and raw features.  Staging of the host entries: a, b (N x C), df / fg
+    // (N x d), the gradient's doubles.  Work memory: a n, b n, K(b ..), K^T(a ..), X, ones, lbl_Q (N x C each), the two
+    // lattice gradients and fg (N x d each), the d x d product
+    TermKeep keep[8];
+    DevBuf kg_a, kg_b, kg_out, kg_grad;
+    DevBuf kg_an, kg_bn, kg_fa, kg_fb, kg_x, kg_ones, kg_lbl, kg_g1, kg_g2, kg_fg, kg_full;
 };
 
 struct CrfState {
@@ -105,7 +117,7 @@ struct KlTap { double* partials; };
 rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry);
 void model_replaced(CrfState* cs);
 rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
-                           std::vector<TermPlan>& plan, hipStream_t s);
+                           std::vector<TermPlan>& plan, hipStream_t s, TermKeep* keep = nullptr);
 void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */);
 bool term_pre(const TermPlan& t);
 bool term_post(const TermPlan& t);

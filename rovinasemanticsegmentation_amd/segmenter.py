@@ -387,11 +387,15 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_model_set_device(self.h, N, Cn, len(terms), arr, C.c_void_p(d_unary), 1 if unary_is_energy else 0,
                                                              C.c_void_p(stream or None)))
         del keep
-        self._crf_model_is(N, Cn, terms)
+        self._crf_model_is(N, Cn, terms, device=True)
 
-    def _crf_model_is(self, N, Cn, terms):
+    def _crf_model_is(self, N, Cn, terms, device=False):
         self._crf_model_shape = (N, Cn, len(terms))
         self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
+        # per term: the feature dimension and the kernel parameters' count (CONST 0, DIAG d, FULL d x d)
+        self._crf_model_dims = [int(t[0][1]) if device else np.shape(t[0])[1] for t in terms]   # (device: (address, d))
+        self._crf_model_kparams = [{CONST_KERNEL: 0, DIAG_KERNEL: d, FULL_KERNEL: d * d}[int(t[2])]
+                                   for t, d in zip(terms, self._crf_model_dims)]
 
     def _crf_model_matrix(self, Q, copy=False):
         """Q as a C-contiguous float32 N x C matrix of the live model; copy: never the caller's array."""
@@ -484,6 +488,61 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_model_gradient(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(Q)))
         del keep
         return float(value[0]), ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None), Q
+
+    # ---- the kernel-parameter gradient (rvseg.h, "Kernel-parameter gradient") ----
+    def crf_model_compat_apply(self, term, Q):
+        """lbl_Q: the term's compatibility on Q (N x C) with no filter (pairwise.cpp:203-205)."""
+        Q = self._crf_model_matrix(Q)
+        out = np.empty_like(Q)
+        capi.check(self.h, self.L.rvseg_crf_model_compat_apply(self.h, term, _ptr(Q), _ptr(out)))
+        return out
+
+    def crf_model_lattice_gradient(self, term, a, b):
+        """Permutohedral::gradient(a, b) of a term's lattice with respect to its features, N x d float32 (a, b: N x C)."""
+        a, b = self._crf_model_matrix(a), self._crf_model_matrix(b)
+        df = np.empty((a.shape[0], self._crf_model_dims[term] if 0 <= term < len(self._crf_model_dims) else 1), np.float32)
+        capi.check(self.h, self.L.rvseg_crf_model_lattice_gradient(self.h, term, _ptr(a), _ptr(b), _ptr(df)))
+        return df
+
+    def crf_model_kernel_gradient(self, term, a, b, want_fg=False):
+        """DenseKernel::gradient(a, b) of a term: float64 (CONST 0, DIAG d, FULL d x d column-major values); want_fg: (that,
+        featureGradient N x d float32)."""
+        a, b = self._crf_model_matrix(a), self._crf_model_matrix(b)
+        ok = 0 <= term < len(self._crf_model_dims)
+        n = self._crf_model_kparams[term] if ok else 0
+        grad = np.zeros(max(1, n), np.float64)
+        fg = np.empty((a.shape[0], self._crf_model_dims[term] if ok else 1), np.float32) if want_fg else None
+        capi.check(self.h, self.L.rvseg_crf_model_kernel_gradient(self.h, term, _ptr(a), _ptr(b), _ptr(grad), _ptr(fg)))
+        return (grad[:n], fg) if want_fg else grad[:n]
+
+    def crf_model_backward_kernel(self, Q_all, d_mul_Q, unary=True, lbl_cmp=True, kernel=True):
+        """crf_model_backward with the kernel-parameter gradient (float64, the layout of kernelParameters()) as a third
+        element; a part not asked for is None."""
+        N, Cn, _ = self._crf_model_shape
+        Q_all = np.ascontiguousarray(Q_all, np.float32)
+        dq = self._crf_model_matrix(d_mul_Q)
+        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn)
+        ug = np.empty((N, Cn), np.float32) if unary else None
+        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
+        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
+        capi.check(self.h, self.L.rvseg_crf_model_backward_kernel(self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), _ptr(ug), _ptr(cg),
+                                                                  _ptr(kg)))
+        return ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None), (kg[:sum(self._crf_model_kparams)] if kernel else None)
+
+    def crf_model_gradient_kernel(self, iterations, objective, unary=True, lbl_cmp=True, kernel=True, want_Q=False):
+        """rvseg_crf_model_gradient_kernel: (value, unary_grad, compat_grad, kernel_grad, Q[n]); a part not asked for is None."""
+        N, Cn, _ = self._crf_model_shape
+        rec, keep = objective.record(N, Cn)
+        value = np.empty(1, np.float64)
+        ug = np.empty((N, Cn), np.float32) if unary else None
+        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
+        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
+        Q = np.empty((N, Cn), np.float32) if want_Q else None
+        capi.check(self.h, self.L.rvseg_crf_model_gradient_kernel(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(kg),
+                                                                  _ptr(Q)))
+        del keep
+        return (float(value[0]), ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None),
+                (kg[:sum(self._crf_model_kparams)] if kernel else None), Q)
 
     def crf_model_set_compat(self, term, compatibility):
         """Replaces the parameters of a term's compatibility (same kind) in the live model: no lattice build."""
@@ -762,6 +821,7 @@ class PottsCompatibility:
 
     def array(self, M):
         return np.array([self.w], np.float32)
+
 
 
 class DiagonalCompatibility:
@@ -1076,60 +1136,87 @@ class DenseCRF:
     def applyTranspose(self, term, Q):   # pairwise.cpp:179-183
         return self._with_model(lambda: self.ctx.crf_model_apply_transpose(term, Q))
 
-    def gradient(self, n_iterations, objective, unary=True, lbl_cmp=True, energy_grad=False):
+    def kernelGradient(self, term, b, Q):   # pairwise.cpp:202-207: kernel_->gradient(b, compatibility(Q)), fp32
+        return self._with_model(lambda: self.ctx.crf_model_kernel_gradient(term, b, self.ctx.crf_model_compat_apply(term, Q))).astype(np.float32)
+
+    def gradient(self, n_iterations, objective, unary=True, lbl_cmp=True, energy_grad=False, kernel=False):
         """DenseCRF::gradient: (value, unary_grad, lbl_cmp_grad) in fp32 with the reference's signs and layouts: unary_grad
         is the gradient of unaryParameters() (empty without a logistic unary), lbl_cmp_grad that of
-        labelCompatibilityParameters(); a part not asked for is None.  There is no kernel-parameter gradient.
-        energy_grad: unary_grad is d value / d U (N x M) instead."""
-        value, ug, cg, _ = self._with_model(lambda: self.ctx.crf_model_gradient(n_iterations, objective, unary, lbl_cmp))
+        labelCompatibilityParameters(); a part not asked for is None.  kernel: a fourth element, the gradient of
+        kernelParameters().  energy_grad: unary_grad is d value / d U (N x M) instead."""
+        if kernel:
+            value, ug, cg, kg, _ = self._with_model(lambda: self.ctx.crf_model_gradient_kernel(n_iterations, objective, unary, lbl_cmp))
+        else:
+            value, ug, cg, _ = self._with_model(lambda: self.ctx.crf_model_gradient(n_iterations, objective, unary, lbl_cmp))
         if unary and not energy_grad:
             if self.logistic is None:
                 ug = np.zeros(0, np.float32)
             else:
                 ug = self.ctx.crf_logistic_gradient(ug, self.logistic[1]).astype(np.float32)
-        return value, ug, (cg.astype(np.float32) if lbl_cmp else None)
+        out = (value, ug, (cg.astype(np.float32) if lbl_cmp else None))
+        return out + (kg.astype(np.float32),) if kernel else out
 
 
 class CRFEnergy:
     """The EnergyFunction of examples/dense_learning.cpp:38-85 over a DenseCRF: gradient(x) sets the parameters, and returns
-    the negated objective and gradient plus the L2 term, for a minimiser of the caller's.  The kernel parameters cannot be
-    learned: their gradient (Permutohedral::gradient) is outside this library's scope."""
+    the negated objective and gradient plus the L2 term, for a minimiser of the caller's.  Unary and label-compatibility
+    parameters only: CRFKernelEnergy also learns the kernel parameters."""
 
     def __init__(self, crf, objective, NIT, unary=True, pairwise=True, kernel=False):
         if kernel:
-            raise NotImplementedError("CRFEnergy(kernel=True): the kernel-parameter gradient (DenseCRF::kernelGradient / "
-                                      "Permutohedral::gradient) is out of scope; learn unary and pairwise parameters only")
+            raise NotImplementedError("CRFEnergy(kernel=True): this class learns unary and pairwise parameters only; use "
+                                      "CRFKernelEnergy for the kernel parameters as well")
         self.crf, self.objective, self.NIT = crf, objective, int(NIT)
         self.unary, self.pairwise = bool(unary), bool(pairwise)
         self.initial_u_param = crf.unaryParameters()
         self.initial_lbl_param = crf.labelCompatibilityParameters()
         self.l2_norm = np.float32(0.0)
+        # the parameter groups of x in order: (learned?, initial value, setter); a subclass appends its own
+        self.groups = [(self.unary, self.initial_u_param, crf.setUnaryParameters),
+                       (self.pairwise, self.initial_lbl_param, crf.setLabelCompatibilityParameters)]
+
+    def _crf_gradient(self):
+        """(value, [one gradient per group, None where the group is not learned])."""
+        r, du, dl = self.crf.gradient(self.NIT, self.objective, self.unary, self.pairwise)
+        return r, [du, dl]
 
     def setL2Norm(self, norm):
         self.l2_norm = np.float32(norm)
 
     def initialValue(self):
-        return np.concatenate([self.initial_u_param if self.unary else np.zeros(0, np.float32),
-                               self.initial_lbl_param if self.pairwise else np.zeros(0, np.float32)]).astype(np.float32)
+        return np.concatenate([np.zeros(0, np.float32)] + [p for on, p, _ in self.groups if on]).astype(np.float32)
 
     def gradient(self, x):
         """(value, dx) of dense_learning.cpp:60-84."""
         x = np.asarray(x, np.float32)
-        nu = self.initial_u_param.shape[0] if self.unary else 0
-        nl = self.initial_lbl_param.shape[0] if self.pairwise else 0
-        assert x.shape == (nu + nl,)
-        if self.unary:
-            self.crf.setUnaryParameters(x[:nu])
-        if self.pairwise:
-            self.crf.setLabelCompatibilityParameters(x[nu:])
-        r, du, dl = self.crf.gradient(self.NIT, self.objective, self.unary, self.pairwise)
-        dx = np.concatenate([-du if self.unary else np.zeros(0, np.float32), -dl if self.pairwise else np.zeros(0, np.float32)]).astype(np.float32)
+        assert x.shape == (sum(p.shape[0] for on, p, _ in self.groups if on),)
+        i = 0
+        for on, p, setter in self.groups:
+            if on:
+                setter(x[i:i + p.shape[0]])
+                i += p.shape[0]
+        r, grads = self._crf_gradient()
+        dx = np.concatenate([np.zeros(0, np.float32)] + [-g for (on, _, _), g in zip(self.groups, grads) if on]).astype(np.float32)
         r = -r
         if self.l2_norm > 0:
             dx = (dx + self.l2_norm * x).astype(np.float32)
             r += 0.5 * float(self.l2_norm) * float(np.dot(x, x))
         return r, dx
 
+
+class CRFKernelEnergy(CRFEnergy):
+    """The whole EnergyFunction of examples/dense_learning.cpp:38-85: CRFEnergy with the kernel parameters as the third
+    group of x.  Every gradient(x) with kernel=True sets the kernel parameters, which sets the model (its lattices) again."""
+
+    def __init__(self, crf, objective, NIT, unary=True, pairwise=True, kernel=True):
+        CRFEnergy.__init__(self, crf, objective, NIT, unary, pairwise, False)
+        self.kernel = bool(kernel)
+        self.initial_knl_param = crf.kernelParameters()
+        self.groups.append((self.kernel, self.initial_knl_param, crf.setKernelParameters))
+
+    def _crf_gradient(self):
+        g = self.crf.gradient(self.NIT, self.objective, self.unary, self.pairwise, kernel=self.kernel)
+        return g[0], [g[1], g[2], g[3] if self.kernel else None]
 
 
 class LocalMapStore:
