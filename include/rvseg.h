@@ -407,8 +407,8 @@ rvseg_status rvseg_crf_model_trace_device(rvseg_ctx *ctx, int32_t iterations, fl
 /* ---- Learning on the kept model: the objectives of objective.cpp:35-108 and the mean-field gradient of DenseCRF::gradient
  *      (densecrf.cpp:238-297) with respect to the unary energy, the label-compatibility parameters and the kernel
  *      parameters (the last under "Kernel-parameter gradient" below: the model keeps the per-point ranks of every term's
- *      lattice and, for DIAG and FULL kernels, a copy of the features as passed).  No optimiser: the caller hands (value,
- *      gradient) to its own.  Same conventions as the model calls above (host entries synchronise, _device entries enqueue
+ *      lattice and, for DIAG and FULL kernels, a copy of the features as passed).  "The learning loop" below sets parameters in
+ *      place, evaluates CRFEnergy::gradient in one call and minimises it.  Same conventions as the model calls above (host entries synchronise, _device entries enqueue
  *      on hip_stream, a stale model is RVSEG_ERR_INVALID_ARG).
  *
  *      Definitions (fp32 with the library's pinned orders unless stated):
@@ -553,6 +553,98 @@ rvseg_status rvseg_crf_model_gradient_kernel(rvseg_ctx *ctx, int32_t iterations,
 rvseg_status rvseg_crf_model_gradient_kernel_device(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj,
                                                     double *d_value_out, float *d_unary_grad_out, double *d_compat_grad_out,
                                                     double *d_kernel_grad_out, float *d_Q_out, void *hip_stream);
+
+/* ---- The learning loop on the kept model: the parameters of examples/dense_learning.cpp:126-182 changed in place, its
+ *      EnergyFunction (:38-85) as one entry, and a minimiser.  Conventions of the learning calls above: a stale model, a
+ *      term out of range and a NULL array that is not optional are RVSEG_ERR_INVALID_ARG; host entries synchronise.
+ *
+ *      Definitions:
+ *        set_kernel   replaces the kernel parameters of a DIAG (d values) or FULL (d x d, column-major) term: that term's
+ *                lattice, normaliser and point ranks are rebuilt from the features the model keeps; nothing is uploaded but
+ *                the parameters, and no other term, the unary or the compatibilities are touched.  params == NULL: the
+ *                features as passed.  A CONST term is RVSEG_ERR_INVALID_ARG.  A hash overflow rebuilds this term once at the
+ *                capacity that cannot overflow.  The model stays live; afterwards every model call equals a fresh
+ *                rvseg_crf_model_set with these kernel_params bit for bit (vertex numbering and capacity do not show).
+ *        set_logistic   the model copies f (N x K) and L (C x K row-major, host memory always) and its unary becomes the
+ *                energy U = L f of rvseg_crf_logistic_unary, computed into the model's memory: the bits of that call followed
+ *                by rvseg_crf_model_set_unary.  Limits of rvseg_crf_logistic_unary (K >= 1).  set_logistic_params: U again
+ *                from a new L and the kept f; RVSEG_ERR_INVALID_ARG without a kept logistic unary.  rvseg_crf_model_set,
+ *                _set_unary and _set_unary_device drop the kept f.
+ *        gradient_params   rvseg_crf_model_gradient_kernel with rvseg_crf_logistic_gradient applied on the device to its
+ *                unary gradient and the kept f: unary_grad_out is C K doubles, column-major like unaryParameters(), and must
+ *                be NULL on a model without a kept logistic unary.  The two-call composition bit for bit; only the
+ *                parameters' doubles are read back.
+ *        energy_gradient   CRFEnergy::gradient (dense_learning.cpp:60-84).  learn_mask: 1 unary, 2 pairwise, 4 kernel.  x: the
+ *                learned groups in the order unaryParameters() (C K values, column-major; none without a kept logistic
+ *                unary) | labelCompatibilityParameters() (per term POTTS 1, DIAGONAL C, MATRIX the C (C + 1) / 2 values of the
+ *                upper triangle row by row, W[i][j] = W[j][i] = v) | kernelParameters() (per term CONST 0, DIAG d, FULL d x d);
+ *                n must be their count.  Each learned group is set in place (set_logistic_params; set_compat per term;
+ *                set_kernel per DIAG / FULL term whose values differ bitwise from those its lattice was built from -- a
+ *                lattice built from NULL parameters differs from any values), then gradient_params runs with the outputs of
+ *                the groups that are not learned NULL.  With g the gradients in the order of x:
+ *                  dx[i] = -(float)g[i];  when l2_norm > 0:  dx[i] = fl(dx[i] + fl(l2_norm * x[i])) in fp32
+ *                  value = -objective;    when l2_norm > 0:  value += (0.5 * (double)l2_norm) * S,  S = sum of
+ *                                                            (double)x[i] * (double)x[i] from i = 0 up, in double
+ *        The minimiser   rvseg_minimize_lbfgs: limited-memory BFGS in double on the host (no context, no GPU), the project's
+ *                own and pinned to no other implementation.  From x with f, g = energy(x): stop at once when
+ *                ||g|| / max(1, ||x||) < epsilon.  Direction d = -H g by the two-loop recursion over the last m pairs
+ *                (s = x' - x, y = g' - g; a pair with s.y <= 0 is left out; H0 = (s.y / y.y) I of the newest pair); the first
+ *                direction, and any that is not a descent direction, is -g with the history dropped.  Line search: t = 1 / ||g||
+ *                for a -g direction, else 1, clamped to [min_step, max_step], halved until the Armijo condition
+ *                f(x + t d) <= f(x) + ftol t g.d holds; at most max_linesearch evaluations, t never below min_step.  After
+ *                every accepted step: the progress callback (k = iterations so far from 1, ls = evaluations of this line
+ *                search; a non-zero return stops), the convergence test, then max_iterations (0: no limit).  A failed line
+ *                search returns the best point evaluated, which is never worse than the start.  A value or gradient that is
+ *                not finite ends the run with RVSEG_ERR_INVALID_ARG and x at the best finite point (x unchanged when the
+ *                first evaluation is the one).  Every other end returns RVSEG_OK; rvseg_lbfgs_report.status tells which. */
+rvseg_status rvseg_crf_model_set_kernel(rvseg_ctx *ctx, int32_t term, const float *params);
+/* f: N x K (host / device); L: C x K row-major, host memory, copied before the call returns (the _device entry only enqueues) */
+rvseg_status rvseg_crf_model_set_logistic(rvseg_ctx *ctx, int32_t K, const float *L, const float *f);
+rvseg_status rvseg_crf_model_set_logistic_device(rvseg_ctx *ctx, int32_t K, const float *L, const float *d_f, void *hip_stream);
+rvseg_status rvseg_crf_model_set_logistic_params(rvseg_ctx *ctx, const float *L);
+/* value_out: 1 double.  unary_grad_out (C K doubles), compat_grad_out and kernel_grad_out may be NULL. */
+rvseg_status rvseg_crf_model_gradient_params(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj, double *value_out,
+                                             double *unary_grad_out, double *compat_grad_out, double *kernel_grad_out);
+rvseg_status rvseg_crf_model_gradient_params_device(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj,
+                                                    double *d_value_out, double *d_unary_grad_out, double *d_compat_grad_out,
+                                                    double *d_kernel_grad_out, void *hip_stream);
+/* obj, x, value_out, dx_out: host memory; x and dx_out hold n floats */
+rvseg_status rvseg_crf_model_energy_gradient(rvseg_ctx *ctx, int32_t iterations, const rvseg_crf_objective *obj, int32_t learn_mask,
+                                             float l2_norm, const float *x, int32_t n, double *value_out, float *dx_out);
+
+typedef enum rvseg_lbfgs_status {
+    RVSEG_LBFGS_CONVERGED = 0,            /* ||g|| / max(1, ||x||) < epsilon                         */
+    RVSEG_LBFGS_MAX_ITERATIONS = 1,
+    RVSEG_LBFGS_STOPPED = 2,              /* the progress callback returned non-zero                 */
+    RVSEG_LBFGS_LINESEARCH_FAILED = 3,    /* no step satisfied the Armijo condition                  */
+    RVSEG_LBFGS_NOT_FINITE = -1,          /* the energy returned a value or gradient that is not finite */
+    RVSEG_LBFGS_BAD_ARGUMENTS = -2
+} rvseg_lbfgs_status;
+typedef struct rvseg_lbfgs_params {
+    int32_t m;                /* corrections kept: 6                   */
+    int32_t max_iterations;   /* 0: no limit                           */
+    int32_t max_linesearch;   /* evaluations per line search: 20       */
+    int32_t reserved;
+    double epsilon;           /* 1e-5                                  */
+    double ftol;              /* Armijo constant: 1e-4                 */
+    double min_step;          /* 1e-20                                 */
+    double max_step;          /* 1e20                                  */
+} rvseg_lbfgs_params;
+typedef struct rvseg_lbfgs_report {
+    int32_t status;           /* rvseg_lbfgs_status                    */
+    int32_t iterations;       /* accepted steps                        */
+    int32_t evaluations;      /* calls of the energy                   */
+    int32_t reserved;
+    double gnorm, xnorm;      /* at the point returned (gnorm: at the last accepted point) */
+} rvseg_lbfgs_report;
+/* returns f(x) and writes its gradient into g (n doubles) */
+typedef double (*rvseg_energy_fn)(void *user, const double *x, double *g, int32_t n);
+typedef int32_t (*rvseg_progress_fn)(void *user, const double *x, const double *g, double fx, double xnorm, double gnorm, double step,
+                                     int32_t n, int32_t k, int32_t ls);
+void rvseg_lbfgs_params_default(rvseg_lbfgs_params *p);
+/* x: n doubles, start in, result out.  fx_out, progress, params (defaults) and report_out may be NULL. */
+rvseg_status rvseg_minimize_lbfgs(int32_t n, double *x, double *fx_out, rvseg_energy_fn energy, rvseg_progress_fn progress, void *user,
+                                  const rvseg_lbfgs_params *params, rvseg_lbfgs_report *report_out);
 
 /* ---- lattice introspection for parity tests: Permutohedral::init + compute
  *      (densecrf permutohedral.cpp:140-321,596-603).  offsets_out / bary_out: N x (d+1);

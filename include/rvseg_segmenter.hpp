@@ -823,12 +823,13 @@ public:
     ~DenseCRF() { if (crf_model_owner(ctx_) == this) crf_model_owner(ctx_, true, nullptr); }
     void setUnaryEnergy(const float* unary /* N x M */) { model_set_ = false; unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
     // LogisticUnaryEnergy (unary.cpp:44-63): L M x K row-major, f N x K point-major
+    // A live model of this object keeps f and computes L f itself (rvseg_crf_model_set_logistic): no lattice is built again.
     void setUnaryEnergy(const float* L, const float* f, int K) {
-        model_set_ = false;
         K_ = K;
         logistic_L_.assign(L, L + (size_t)M_ * K);
         logistic_f_.assign(f, f + (size_t)N_ * K);
         unary_.clear();
+        inPlace([&] { return rvseg_crf_model_set_logistic(ctx_, K_, logistic_L_.data(), logistic_f_.data()); });
     }
     void addPairwiseEnergy(const float* features /* N x d */, int d, float potts_w) {                       // densecrf.cpp:54-60
         addTerm(features, d, PottsCompatibility(potts_w), RVSEG_DIAG_KERNEL, RVSEG_NORMALIZE_SYMMETRIC, true);
@@ -845,12 +846,12 @@ public:
             for (int m = 0; m < M_; m++) r.push_back(logistic_L_[(size_t)m * K_ + k]);
         return r;
     }
+    // The set*Parameters calls change a live model of this object in place (rvseg_crf_model_set_logistic_params, _set_compat,
+    // _set_kernel for the terms whose values changed); without one, the next call that needs the model sets it.
     void setUnaryParameters(const std::vector<float>& v) {
         if (logistic_f_.empty()) return;
-        check(v.size() == logistic_L_.size());
-        model_set_ = false;
-        for (int k = 0; k < K_; k++)
-            for (int m = 0; m < M_; m++) logistic_L_[(size_t)m * K_ + k] = v[(size_t)k * M_ + m];
+        assignUnary(v.data(), v.size());
+        inPlace([&] { return rvseg_crf_model_set_logistic_params(ctx_, logistic_L_.data()); });
     }
     std::vector<float> labelCompatibilityParameters() const {
         std::vector<float> r;
@@ -858,16 +859,12 @@ public:
         return r;
     }
     void setLabelCompatibilityParameters(const std::vector<float>& v) {
-        model_set_ = false;
-        size_t i = 0;
-        for (auto& t : terms_) {
-            const size_t n = t.compat.parameters().size();
-            check(i + n <= v.size());
-            t.compat.setParameters(v.data() + i);
-            t.bare = false;
-            i += n;
-        }
-        check(i == v.size());
+        assignCompat(v.data(), v.size());
+        inPlace([&] {
+            rvseg_status st = RVSEG_OK;
+            for (size_t t = 0; t < terms_.size() && st == RVSEG_OK; t++) st = rvseg_crf_model_set_compat(ctx_, (int32_t)t, terms_[t].compat.params.data());
+            return st;
+        });
     }
     std::vector<float> kernelParameters() const {   // DenseKernel::parameters (pairwise.cpp:116-125)
         std::vector<float> r;
@@ -875,15 +872,37 @@ public:
         return r;
     }
     void setKernelParameters(const std::vector<float>& v) {   // pairwise.cpp:140-152
-        model_set_ = false;
-        size_t i = 0;
-        for (auto& t : terms_) {
-            const size_t n = kernelParams(t).size();
-            check(i + n <= v.size());
-            if (t.kernel_type != RVSEG_CONST_KERNEL) t.kp.assign(v.begin() + i, v.begin() + i + n);
-            i += n;
+        const std::vector<int> changed = assignKernel(v.data(), v.size());
+        inPlace([&] {
+            rvseg_status st = RVSEG_OK;
+            for (size_t c = 0; c < changed.size() && st == RVSEG_OK; c++) st = rvseg_crf_model_set_kernel(ctx_, changed[c], terms_[(size_t)changed[c]].kp.data());
+            return st;
+        });
+    }
+    // CRFEnergy::gradient (dense_learning.cpp:60-84) as one rvseg_crf_model_energy_gradient: x (the learned groups in the order
+    // unary | label compatibility | kernel) becomes this object's parameters and the live model's, dx receives the negated
+    // gradient plus l2_norm x, the value returned is the negated objective plus the L2 term (definitions in rvseg.h)
+    double energyGradient(int n_iterations, const ObjectiveFunction& objective, bool unary, bool pairwise, bool kernel, float l2_norm,
+                          const std::vector<float>& x, std::vector<float>& dx) {
+        check(objective.gt.size() == (size_t)N_ && (objective.kind != RVSEG_OBJECTIVE_HAMMING || objective.class_weight.size() == (size_t)M_));
+        const size_t nu = unary ? unaryParameters().size() : 0, nc = pairwise ? labelCompatibilityParameters().size() : 0,
+                     nk = kernel ? kernelParameters().size() : 0;
+        check(x.size() == nu + nc + nk);
+        const rvseg_crf_objective rec = objective.record();
+        double value = 0;
+        dx.assign(x.size() + 1, 0.f);
+        try {
+            if (nu) assignUnary(x.data(), nu);
+            if (pairwise) assignCompat(x.data() + nu, nc);
+            if (kernel) assignKernel(x.data() + nu + nc, nk);
+            const int32_t mask = (unary ? 1 : 0) | (pairwise ? 2 : 0) | (kernel ? 4 : 0);
+            onModel([&] { return rvseg_crf_model_energy_gradient(ctx_, n_iterations, &rec, mask, l2_norm, x.data(), (int32_t)x.size(), &value, dx.data()); });
+        } catch (...) {
+            model_set_ = false;   // the model may hold a part of x only
+            throw;
         }
-        check(i == v.size());
+        dx.pop_back();
+        return value;
     }
     // DenseCRF::inference (densecrf.cpp:115-131); map_out (optional) = DenseCRF::map (:132-137).  A logistic unary is
     // computed on the GPU and read back (N x M floats), then uploaded with the model like a constant unary; callers that
@@ -964,7 +983,7 @@ public:
         onModel([&] { return rvseg_crf_model_trace(ctx_, n_iterations, Q.data(), map_out ? map_out->data() : nullptr, RVSEG_LABEL_ARGMAX, 0, kl.data()); });
         return Q;
     }
-    // ---- learning (densecrf.cpp:238-297) on the kept model.  No optimiser: the caller hands (value, gradient) to its own.
+    // ---- learning (densecrf.cpp:238-297) on the kept model; rvseg::minimizeLBFGS below minimises an EnergyFunction over it
     std::vector<float> applyTranspose(int term, const std::vector<float>& in) {   // pairwise.cpp:179-183
         check(in.size() == (size_t)N_ * M_);
         std::vector<float> out((size_t)N_ * M_);
@@ -994,6 +1013,17 @@ public:
         double value = 0;
         std::vector<float> ug((size_t)N_ * M_);
         std::vector<double> cg(labelCompatibilityParameters().size() + 1), kg(kernelParameters().size() + 1);
+        if (unary_grad && !unary_energy_grad && !logistic_f_.empty()) {   // the parameters' doubles alone come back
+            std::vector<double> lg((size_t)M_ * K_);
+            onModel([&] {
+                return rvseg_crf_model_gradient_params(ctx_, n_iterations, &rec, &value, lg.data(), lbl_cmp_grad ? cg.data() : nullptr,
+                                                       kernel_grad ? kg.data() : nullptr);
+            });
+            unary_grad->assign(lg.begin(), lg.end());
+            if (lbl_cmp_grad) lbl_cmp_grad->assign(cg.begin(), cg.end() - 1);
+            if (kernel_grad) kernel_grad->assign(kg.begin(), kg.end() - 1);
+            return value;
+        }
         const bool want_ug = unary_grad || unary_energy_grad;
         onModel([&] {
             return rvseg_crf_model_gradient_kernel(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, lbl_cmp_grad ? cg.data() : nullptr,
@@ -1039,6 +1069,49 @@ protected:
         return p;
     }
     static void check(bool ok) { if (!ok) throw std::runtime_error("bad parameter vector"); }
+    // the parameters of this object alone (no model call); assignKernel returns the terms whose values changed
+    void assignUnary(const float* v, size_t n) {
+        check(n == logistic_L_.size());
+        for (int k = 0; k < K_; k++)
+            for (int m = 0; m < M_; m++) logistic_L_[(size_t)m * K_ + k] = v[(size_t)k * M_ + m];
+    }
+    void assignCompat(const float* v, size_t n_all) {
+        size_t i = 0;
+        for (auto& t : terms_) {
+            const size_t n = t.compat.parameters().size();
+            check(i + n <= n_all);
+            t.compat.setParameters(v + i);
+            t.bare = false;
+            i += n;
+        }
+        check(i == n_all);
+    }
+    std::vector<int> assignKernel(const float* v, size_t n_all) {
+        std::vector<int> changed;
+        size_t i = 0;
+        for (size_t k = 0; k < terms_.size(); k++) {
+            Term& t = terms_[k];
+            const size_t n = kernelParams(t).size();
+            check(i + n <= n_all);
+            if (t.kernel_type != RVSEG_CONST_KERNEL) {
+                if (t.kp.size() != n || std::memcmp(t.kp.data(), v + i, n * sizeof(float)) != 0) changed.push_back((int)k);
+                t.kp.assign(v + i, v + i + n);
+            }
+            i += n;
+        }
+        check(i == n_all);
+        return changed;
+    }
+    // a parameter change on the live model of this object; without one (or when another call has replaced it) the next
+    // onModel sets the model
+    template <class F>
+    void inPlace(F&& update) {
+        if (!model_set_ || crf_model_owner(ctx_) != this) { model_set_ = false; return; }
+        const rvseg_status st = update();
+        if (st == RVSEG_OK) return;
+        model_set_ = false;
+        if (!(st == RVSEG_ERR_INVALID_ARG && std::string(rvseg_last_error(ctx_)).find("DenseCRF model") != std::string::npos)) status(st);
+    }
     // the unary energy as N x M values: the constant one, the logistic one computed on the GPU into U, or zeros in U
     const float* unaryEnergyMatrix(std::vector<float>& U) {
         const size_t N = (size_t)N_;
@@ -1067,9 +1140,14 @@ protected:
         for (int attempt = 0;; attempt++) {
             if (!model_set_ || crf_model_owner(ctx_) != this) {
                 std::vector<float> U;
-                const float* u = unaryEnergyMatrix(U);
                 const std::vector<rvseg_crf_term> tt = termRecords();
-                status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), u, 1));
+                if (!logistic_f_.empty()) {   // the model computes L f itself and keeps f
+                    U.assign((size_t)N_ * M_, 0.f);
+                    status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), U.data(), 1));
+                    status(rvseg_crf_model_set_logistic(ctx_, K_, logistic_L_.data(), logistic_f_.data()));
+                } else {
+                    status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), unaryEnergyMatrix(U), 1));
+                }
                 model_set_ = true;
                 crf_model_owner(ctx_, true, this);
             }
@@ -1252,6 +1330,82 @@ private:
     rvseg_ctx* ctx_;
     std::vector<int> class_counts_;
     std::vector<std::unique_ptr<RgbLabelConversion>> conv_;
+};
+
+// EnergyFunction / minimizeLBFGS of optimization.h / optimization.cpp:68-103 over rvseg_minimize_lbfgs: epsilon = 1e-6, at
+// most 50 iterations per run, up to restart + 1 runs, ending after the first whose value is not below the lowest before it.
+// x crosses to the energy as float (the reference's VectorXf).  An energy that is not finite, or whose gradient has another
+// size than x, ends the loop with std::runtime_error.
+class EnergyFunction {
+public:
+    virtual ~EnergyFunction() {}
+    virtual std::vector<float> initialValue() = 0;
+    virtual double gradient(const std::vector<float>& x, std::vector<float>& dx) = 0;
+};
+
+inline std::vector<float> minimizeLBFGS(EnergyFunction& efun, int restart = 0, bool verbose = false, const rvseg_lbfgs_params* params = nullptr) {
+    std::vector<float> x0 = efun.initialValue();
+    const int32_t n = (int32_t)x0.size();
+    if (n == 0) return x0;
+    std::vector<double> x(x0.begin(), x0.end());
+    const rvseg_energy_fn evaluate = [](void* user, const double* xd, double* g, int32_t m) -> double {
+        std::vector<float> vx(xd, xd + m), vg;
+        const double r = static_cast<EnergyFunction*>(user)->gradient(vx, vg);
+        if ((int32_t)vg.size() != m) return std::numeric_limits<double>::quiet_NaN();   // ends the run: RVSEG_LBFGS_NOT_FINITE
+        for (int32_t i = 0; i < m; i++) g[i] = (double)vg[i];
+        return r;
+    };
+    const rvseg_progress_fn progress = [](void*, const double*, const double*, double fx, double xnorm, double gnorm, double step, int32_t,
+                                          int32_t k, int32_t) -> int32_t {
+        std::printf("Iteration %d:\n  fx = %f, xnorm = %f, gnorm = %f, step = %f\n\n", k, fx, xnorm, gnorm, step);
+        return 0;
+    };
+    rvseg_lbfgs_params param;
+    rvseg_lbfgs_params_default(&param);
+    param.epsilon = 1e-6;
+    param.max_iterations = 50;
+    if (params) param = *params;   // (the caller's instead of the reference's two settings)
+    rvseg_lbfgs_report rep{};
+    double last_f = 1e100;
+    for (int i = 0; i <= restart; i++) {
+        double fx = 0.0;
+        if (rvseg_minimize_lbfgs(n, x.data(), &fx, evaluate, verbose ? progress : nullptr, &efun, &param, &rep) != RVSEG_OK)
+            throw std::runtime_error("minimizeLBFGS: the energy returned a value or a gradient that is not finite, or a gradient of another "
+                                     "size than x (rvseg_lbfgs_status " + std::to_string(rep.status) + ")");
+        if (last_f > fx) last_f = fx;
+        else break;
+    }
+    if (verbose) std::printf("L-BFGS optimization terminated with status code = %d\n", rep.status);
+    for (int32_t i = 0; i < n; i++) x0[i] = (float)x[i];
+    return x0;
+}
+
+// The EnergyFunction of examples/dense_learning.cpp:38-85 over a DenseCRF: the learned groups of x are the unary, the label
+// compatibility and the kernel parameters; one evaluation is one DenseCRF::energyGradient.
+class CRFEnergy : public EnergyFunction {
+public:
+    CRFEnergy(DenseCRF& crf, const ObjectiveFunction& objective, int NIT, bool unary = true, bool pairwise = true, bool kernel = true)
+        : crf_(crf), objective_(objective), NIT_(NIT), unary_(unary), pairwise_(pairwise), kernel_(kernel),
+          initial_u_param_(crf.unaryParameters()), initial_lbl_param_(crf.labelCompatibilityParameters()),
+          initial_knl_param_(crf.kernelParameters()) {}
+    void setL2Norm(float norm) { l2_norm_ = norm; }
+    std::vector<float> initialValue() override {
+        std::vector<float> p;
+        if (unary_) p.insert(p.end(), initial_u_param_.begin(), initial_u_param_.end());
+        if (pairwise_) p.insert(p.end(), initial_lbl_param_.begin(), initial_lbl_param_.end());
+        if (kernel_) p.insert(p.end(), initial_knl_param_.begin(), initial_knl_param_.end());
+        return p;
+    }
+    double gradient(const std::vector<float>& x, std::vector<float>& dx) override {
+        return crf_.energyGradient(NIT_, objective_, unary_, pairwise_, kernel_, l2_norm_, x, dx);
+    }
+protected:
+    DenseCRF& crf_;
+    const ObjectiveFunction& objective_;
+    int NIT_;
+    bool unary_, pairwise_, kernel_;
+    float l2_norm_ = 0.f;
+    std::vector<float> initial_u_param_, initial_lbl_param_, initial_knl_param_;
 };
 
 }  // namespace rvseg

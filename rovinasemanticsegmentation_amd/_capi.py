@@ -60,7 +60,13 @@ SYMBOLS = [
     "rvseg_crf_model_lattice_gradient", "rvseg_crf_model_lattice_gradient_device", "rvseg_crf_model_kernel_gradient",
     "rvseg_crf_model_kernel_gradient_device", "rvseg_crf_model_backward_kernel", "rvseg_crf_model_backward_kernel_device",
     "rvseg_crf_model_gradient_kernel", "rvseg_crf_model_gradient_kernel_device",
+    "rvseg_crf_model_set_kernel", "rvseg_crf_model_set_logistic", "rvseg_crf_model_set_logistic_device",
+    "rvseg_crf_model_set_logistic_params", "rvseg_crf_model_gradient_params", "rvseg_crf_model_gradient_params_device",
+    "rvseg_crf_model_energy_gradient", "rvseg_lbfgs_params_default", "rvseg_minimize_lbfgs",
 ]
+# rvseg_lbfgs_status
+LBFGS_CONVERGED, LBFGS_MAX_ITERATIONS, LBFGS_STOPPED, LBFGS_LINESEARCH_FAILED, LBFGS_NOT_FINITE, LBFGS_BAD_ARGUMENTS = 0, 1, 2, 3, -1, -2
+LEARN_UNARY, LEARN_PAIRWISE, LEARN_KERNEL = 1, 2, 4   # learn_mask of rvseg_crf_model_energy_gradient
 
 
 class RvsegParams(C.Structure):
@@ -112,6 +118,22 @@ class RvsegCrfObjective(C.Structure):
     """rvseg_crf_objective: a learning objective of a kept DenseCRF model."""
     _fields_ = [("kind", C.c_int32), ("gt", C.c_void_p), ("robust", C.c_float), ("class_weight", C.c_void_p)]
 
+
+class RvsegLbfgsParams(C.Structure):
+    """rvseg_lbfgs_params"""
+    _fields_ = [("m", C.c_int32), ("max_iterations", C.c_int32), ("max_linesearch", C.c_int32), ("reserved", C.c_int32),
+                ("epsilon", C.c_double), ("ftol", C.c_double), ("min_step", C.c_double), ("max_step", C.c_double)]
+
+
+class RvsegLbfgsReport(C.Structure):
+    """rvseg_lbfgs_report"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("reserved", C.c_int32),
+                ("gnorm", C.c_double), ("xnorm", C.c_double)]
+
+
+ENERGY_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32)
+PROGRESS_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+                          C.c_double, C.c_int32, C.c_int32, C.c_int32)
 
 SPLAT_NAMES = {0: "none", 1: "list-major", 2: "resident"}
 
@@ -248,6 +270,17 @@ def lib():
     L.rvseg_crf_model_backward_kernel_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.rvseg_crf_model_gradient_kernel.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp]
     L.rvseg_crf_model_gradient_kernel_device.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_set_kernel.argtypes = [vp, i32, vp]
+    L.rvseg_crf_model_set_logistic.argtypes = [vp, i32, vp, vp]
+    L.rvseg_crf_model_set_logistic_device.argtypes = [vp, i32, vp, vp, vp]
+    L.rvseg_crf_model_set_logistic_params.argtypes = [vp, vp]
+    L.rvseg_crf_model_gradient_params.argtypes = [vp, i32, OP, vp, vp, vp, vp]
+    L.rvseg_crf_model_gradient_params_device.argtypes = [vp, i32, OP, vp, vp, vp, vp, vp]
+    L.rvseg_crf_model_energy_gradient.argtypes = [vp, i32, OP, i32, f32, vp, i32, vp, vp]
+    L.rvseg_lbfgs_params_default.argtypes = [C.POINTER(RvsegLbfgsParams)]
+    L.rvseg_lbfgs_params_default.restype = None
+    L.rvseg_minimize_lbfgs.argtypes = [i32, vp, C.POINTER(C.c_double), ENERGY_FN, PROGRESS_FN, vp, C.POINTER(RvsegLbfgsParams),
+                                       C.POINTER(RvsegLbfgsReport)]
     L.rvseg_rectify_depth.argtypes = [vp, i32, vp, vp, f32, f32, vp]
     L.rvseg_rectify_depth_device.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp]
     L.rvseg_external_layers_set.argtypes = [vp, i32, vp]
@@ -260,6 +293,7 @@ def lib():
     # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
     L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
     L.rvseg_debug_live_resources.restype = None
+    L.rvseg_debug_lattice_builds.argtypes = [vp, C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
         getattr(L, name)  # raises AttributeError if the library does not export it
     _lib = L
@@ -382,3 +416,47 @@ def eval_scores_from_counts(counts):
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return {"global_acc": g.value, "class_avg_acc": a.value, "iou": u.value, "row_pct": row}
+
+
+def minimize_lbfgs(fun, x0, progress=None, **params):
+    """rvseg_minimize_lbfgs (host only, no context): fun(x float64 array) -> (value, gradient); progress(x, g, fx, xnorm,
+    gnorm, step, k, ls) -> non-zero stops.  params: fields of rvseg_lbfgs_params.  Returns (x, fx, report dict with status,
+    iterations, evaluations, gnorm, xnorm and the call's rvseg_status as "rvseg_status").  An exception of a callback ends
+    the run (the energy's as a value that is not finite) and is raised again here."""
+    import numpy as np
+    L = lib()
+    p = RvsegLbfgsParams()
+    L.rvseg_lbfgs_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_) or k == "reserved":
+            raise TypeError("no such L-BFGS parameter: %s" % k)
+        setattr(p, k, v)
+    x = np.array(x0, np.float64).reshape(-1)
+    n = x.shape[0]
+    raised = []
+
+    def energy(user, xp, gp, nn):
+        try:
+            value, grad = fun(np.ctypeslib.as_array(xp, (nn,)).copy())
+            np.ctypeslib.as_array(gp, (nn,))[:] = np.asarray(grad, np.float64).reshape(nn)
+            return float(value)
+        except BaseException as e:   # never through the C frames
+            raised.append(e)
+            return float("nan")
+
+    def report(user, xp, gp, fx, xnorm, gnorm, step, nn, k, ls):
+        try:
+            return int(progress(np.ctypeslib.as_array(xp, (nn,)).copy(), np.ctypeslib.as_array(gp, (nn,)).copy(), fx, xnorm, gnorm, step,
+                                k, ls) or 0)
+        except BaseException as e:
+            raised.append(e)
+            return 1
+
+    fx = C.c_double(float("nan"))
+    rep = RvsegLbfgsReport()
+    st = L.rvseg_minimize_lbfgs(n, x.ctypes.data_as(C.c_void_p), C.byref(fx), ENERGY_FN(energy),
+                                PROGRESS_FN(report) if progress is not None else C.cast(None, PROGRESS_FN), None, C.byref(p), C.byref(rep))
+    if raised:
+        raise raised[0]
+    return x, fx.value, {"status": rep.status, "iterations": rep.iterations, "evaluations": rep.evaluations, "gnorm": rep.gnorm,
+                         "xnorm": rep.xnorm, "rvseg_status": st}

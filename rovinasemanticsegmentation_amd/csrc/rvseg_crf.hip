@@ -291,10 +291,12 @@ void model_replaced(CrfState* cs) {
 
 // norm_kind: the normaliser the term needs (rvseg_norm_kind): SYMMETRIC 1/sqrt(n + 1e-20), BEFORE / AFTER 1/(n + 1e-20),
 // NONE none at all (pairwise.cpp:40-56; the mean norm NO_NORMALIZATION computes is never read in inference)
+// ends_model: false only for the rebuild of a kept model's own term in place (term_rebuild)
 static rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s,
-                                  int norm_kind = RVSEG_NORMALIZE_SYMMETRIC) {
+                                  int norm_kind = RVSEG_NORMALIZE_SYMMETRIC, bool ends_model = true) {
     const LatticeDev& L = b.dev;
-    model_replaced(cs);   // a kept DenseCRF model ends with any lattice build on its context
+    cs->lattice_builds++;
+    if (ends_model) model_replaced(cs);   // a kept DenseCRF model ends with any other lattice build on its context
     if (!b.cleared) { rvseg_status stc = lattice_clear(ctx, b, s); if (stc != RVSEG_OK) return stc; }
     b.cleared = false;
     const bool trace = ctx->sched.trace >= 2;
@@ -755,7 +757,11 @@ rvseg_status crf_frames_infer(rvseg_ctx* ctx, Pipeline* im, const LayerLayout& f
 // One pairwise term's lattice input: N x d features in host or device memory, the kernel parameters that transform them
 // (pairwise.cpp:140-152; none for CONST_KERNEL or a null pointer) and the normaliser the term needs (rvseg_norm_kind)
 // keep (a kept model's term only): where the point ranks and, for a DIAG or FULL kernel, a copy of the features go
-struct TermInput { int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; TermKeep* keep = nullptr; };
+// in_place (term_rebuild): the features ARE keep->feat, and the model the term belongs to stays live
+struct TermInput {
+    int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; TermKeep* keep = nullptr;
+    bool in_place = false;
+};
 
 static TermInput potts_input(int d, const float* features, bool on_host) {
     return TermInput{d, features, on_host, RVSEG_CONST_KERNEL, nullptr, RVSEG_NORMALIZE_SYMMETRIC, nullptr};
@@ -772,7 +778,7 @@ static rvseg_status build_lattice(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb,
         RV_HIP(ctx, hipMemcpyAsync(cs->feat.p, t.features, (size_t)N * t.d * 4, hipMemcpyHostToDevice, s));
         f = cs->feat.as<float>();
     }
-    if (t.keep && t.kernel_type != RVSEG_CONST_KERNEL) {   // f_ of the kernel-parameter gradient
+    if (t.keep && t.kernel_type != RVSEG_CONST_KERNEL && !t.in_place) {   // f_ of the kernel-parameter gradient
         if ((st = dev_reserve(ctx, t.keep->feat, (size_t)N * t.d * 4)) != RVSEG_OK) return st;
         RV_HIP(ctx, hipMemcpyAsync(t.keep->feat.p, f, (size_t)N * t.d * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -786,7 +792,7 @@ static rvseg_status build_lattice(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& lb,
     }
     FeatureSource fs{};
     fs.feat = f;   // (mode 0)
-    if ((st = lattice_build(ctx, cs, lb, fs, s, t.norm)) != RVSEG_OK) return st;
+    if ((st = lattice_build(ctx, cs, lb, fs, s, t.norm, !t.in_place)) != RVSEG_OK) return st;
     if (t.keep) {   // the ranks, from the features the lattice was built from
         if ((st = dev_reserve(ctx, t.keep->rank, (size_t)N * 4)) != RVSEG_OK) return st;
         launch_point_ranks(lb.dev, f, t.keep->rank.as<unsigned>(), s);
@@ -810,6 +816,26 @@ static rvseg_status build_lattices(rvseg_ctx* ctx, CrfState* cs, int N, int n, c
         if (cnt) std::memcpy(cnt, c, sizeof(c));
         if (!c[1]) return RVSEG_OK;
     }
+    ctx->err = "lattice hash table overflow";
+    return RVSEG_ERR_CAPACITY;
+}
+
+// rvseg_crf_model_set_kernel: term k of the live model rebuilt on cs->lat[k] from the raw features the model keeps, with new
+// kernel parameters (host; null: none) -- lattice, normaliser, point ranks and, where the term had one, the per-entry
+// normaliser.  A hash overflow rebuilds this term once at the safe capacity.  No other lattice is touched.
+rvseg_status term_rebuild(rvseg_ctx* ctx, CrfState* cs, int k, const float* kernel_params, hipStream_t s) {
+    CrfModel& m = cs->model;
+    const TermPlan& tp = m.plan[k];
+    LatticeBufs& lb = cs->lat[k];
+    const bool entry_norms = lb.has_csr_nrm;
+    TermInput in{tp.d, m.keep[k].feat.as<float>(), false, tp.kernel, kernel_params, tp.norm, &m.keep[k], true};
+    int c[3] = {0, 0, 0};
+    for (int attempt = 0; attempt < 2; attempt++) {
+        rvseg_status st = build_lattice(ctx, cs, lb, m.N, in, attempt == 1, s, c);
+        if (st != RVSEG_OK) { model_replaced(cs); return st; }   // (a lattice half built: the model is gone)
+        if (!c[1]) return entry_norms ? ensure_csr_nrm(ctx, lb, s) : RVSEG_OK;
+    }
+    model_replaced(cs);
     ctx->err = "lattice hash table overflow";
     return RVSEG_ERR_CAPACITY;
 }
@@ -916,7 +942,13 @@ rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_ter
     for (int k = 0; k < n_terms; k++)
         in[k] = TermInput{terms[k].d, terms[k].features, on_host, terms[k].kernel_type, terms[k].kernel_params, terms[k].normalization,
                           keep ? keep + k : nullptr};
-    return build_lattices(ctx, cs, N, n_terms, in, s);
+    const rvseg_status st = build_lattices(ctx, cs, N, n_terms, in, s);
+    for (int k = 0; keep && st == RVSEG_OK && k < n_terms; k++) {   // what term_rebuild's callers compare new parameters with
+        const int np = terms[k].kernel_type == RVSEG_DIAG_KERNEL ? terms[k].d : terms[k].kernel_type == RVSEG_FULL_KERNEL ? terms[k].d * terms[k].d : 0;
+        keep[k].has_kparams = np > 0 && terms[k].kernel_params;
+        keep[k].kparams.assign(terms[k].kernel_params, terms[k].kernel_params + (keep[k].has_kparams ? np : 0));
+    }
+    return st;
 }
 
 }  // namespace rvseg
@@ -1122,6 +1154,13 @@ extern "C" rvseg_status rvseg_debug_resident(rvseg_ctx* ctx, void* trace_out, si
         RV_HIP(ctx, hipMemcpy(trace_out, b.resident.trace, (size_t)nf * RES_MAXB * 64, hipMemcpyDeviceToHost));
     if (tile0_out && tile0_cap >= (size_t)nf * (RES_MAXB + 1) * 4)
         RV_HIP(ctx, hipMemcpy(tile0_out, b.resident.blk_tile0, (size_t)nf * (RES_MAXB + 1) * 4, hipMemcpyDeviceToHost));
+    return RVSEG_OK;
+}
+
+// debug (not in rvseg.h): how many lattices have been built on this context, overflow retries included
+extern "C" rvseg_status rvseg_debug_lattice_builds(rvseg_ctx* ctx, long long* out) {
+    if (!ctx || !out) return RVSEG_ERR_INVALID_ARG;
+    *out = ctx->impl && ctx->impl->crf ? ctx->impl->crf->lattice_builds : 0;
     return RVSEG_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cassert>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -105,6 +106,7 @@ static rvseg_status model_set(ModelIo io, int32_t N, int32_t C, int32_t n_terms,
     // every lattice build has waited for the stream; a model without terms waits here: the caller's buffers are free
     if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(io.s));
     m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
+    m.K = 0;
     m.valid = true;
     return RVSEG_OK;
 }
@@ -675,6 +677,159 @@ static rvseg_status model_set_unary(ModelIo io, const float* unary, int32_t unar
     RV_HIP(io.ctx, hipMemcpyAsync(m.unary.p, unary, (size_t)m.N * m.C * 4, io.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, io.s));
     RV_TRY(io.done());   // a host entry waits: the caller's array is free when it returns
     m.unary_is_energy = unary_is_energy != 0;
+    m.K = 0;   // (a kept logistic unary ends here)
+    return RVSEG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The learning loop (include/rvseg.h, "The learning loop"): parameters in place, the parameter gradient, CRFEnergy::gradient.
+// ---------------------------------------------------------------------------------------------
+static rvseg_status model_set_kernel(ModelIo io, int32_t term, const float* params) {
+    RV_TRY(io.enter());
+    CrfModel& m = io.cs->model;
+    RV_TRY(model_term_arg(io.ctx, m, term, 0));
+    const size_t np = term_kernel_params(m.plan[term]);
+    if (!np) { io.ctx->err = "a CONST_KERNEL term has no kernel parameters"; return RVSEG_ERR_INVALID_ARG; }
+    RV_TRY(term_rebuild(io.ctx, io.cs, term, params, io.s));   // (has waited for the stream)
+    TermKeep& keep = m.keep[term];
+    keep.has_kparams = params != nullptr;
+    keep.kparams.assign(params, params + (params ? np : 0));
+    return RVSEG_OK;
+}
+
+// U = L f from the model's copies of L (host memory, uploaded here) and f
+static rvseg_status model_logistic_unary(ModelIo& io, const float* L) {
+    CrfModel& m = io.cs->model;
+    const size_t bytes = (size_t)m.C * m.K * 4;
+    // L is the caller's and may be gone once the entry returns: it is uploaded from a pinned copy of the model's, which the
+    // previous upload has left (long ago, as a rule) before it is written again.  A device entry only enqueues.
+    if (!m.lmat_ev) RV_HIP(io.ctx, event_create(m.lmat_ev, hipEventDisableTiming));
+    else RV_HIP(io.ctx, hipEventSynchronize(m.lmat_ev));
+    RV_TRY(m.h_lmat.reserve(io.ctx, bytes));
+    std::memcpy(m.h_lmat.p, L, bytes);
+    RV_TRY(dev_reserve(io.ctx, m.lmat, bytes));
+    RV_HIP(io.ctx, hipMemcpyAsync(m.lmat.p, m.h_lmat.p, bytes, hipMemcpyHostToDevice, io.s));
+    RV_HIP(io.ctx, hipEventRecord(m.lmat_ev, io.s));
+    launch_logistic_unary(m.lmat.as<float>(), m.lfeat.as<float>(), m.N, m.C, m.K, m.unary.as<float>(), io.s);
+    RV_LAUNCH_OK(io.ctx);
+    m.unary_is_energy = true;
+    return RVSEG_OK;
+}
+
+static rvseg_status model_set_logistic(ModelIo io, int32_t K, const float* L, const float* f) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(K >= 1 && L && f);
+    CrfModel& m = io.cs->model;
+    m.K = 0;   // (a failure below leaves the unary as it was, without a kept f)
+    RV_TRY(dev_reserve(io.ctx, m.lfeat, (size_t)m.N * K * 4));
+    RV_HIP(io.ctx, hipMemcpyAsync(m.lfeat.p, f, (size_t)m.N * K * 4, io.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, io.s));
+    m.K = K;
+    RV_TRY(model_logistic_unary(io, L));
+    return io.done();   // a host entry waits: f is free when it returns
+}
+
+static rvseg_status model_logistic_arg(rvseg_ctx* ctx, const CrfModel& m) {
+    if (m.K > 0) return RVSEG_OK;
+    ctx->err = "the DenseCRF model keeps no logistic unary (rvseg_crf_model_set_logistic)";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+static rvseg_status model_set_logistic_params(ModelIo io, const float* L) {
+    RV_TRY(io.enter());
+    RV_MODEL_ARGS(L);
+    RV_TRY(model_logistic_arg(io.ctx, io.cs->model));
+    RV_TRY(model_logistic_unary(io, L));
+    return io.done();
+}
+
+// model_gradient whose unary gradient stays on the device (CrfModel::ug) and leaves as the C K doubles of
+// rvseg_crf_logistic_gradient over the kept f
+static rvseg_status model_gradient_params(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, double* lgrad_out,
+                                          double* compat_grad_out, double* kernel_grad_out) {
+    RV_TRY(io.enter());
+    RV_TRY(objective_arg(io.ctx, obj));
+    RV_MODEL_ARGS(iterations >= 0 && value_out);
+    CrfModel& m = io.cs->model;
+    if (lgrad_out) RV_TRY(model_logistic_arg(io.ctx, m));
+    const size_t tot = (size_t)m.N * m.C;
+    rvseg_crf_objective dev = *obj;
+    RV_TRY(model_objective_in(io, m, &dev));
+    RV_TRY(dev_reserve(io.ctx, m.stats, 129 * sizeof(double)));
+    io.out_at(m.stats.as<double>() + 128, &value_out, 1);
+    RV_TRY(io.out(m.lgrad, &lgrad_out, (size_t)m.C * m.K));
+    RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
+    RV_TRY(io.out(m.kg_grad, &kernel_grad_out, model_kernel_params(m)));
+    float* d_ug = nullptr;
+    if (lgrad_out) {   // (the partials at their largest before anything is enqueued: no later reserve moves them)
+        RV_TRY(dev_reserve(io.ctx, m.ug, tot * 4));
+        RV_TRY(dev_reserve(io.ctx, io.cs->learn_partials, learn_partials_doubles(64) * sizeof(double)));
+        d_ug = m.ug.as<float>();
+    }
+    io.time();
+    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, d_ug, compat_grad_out, kernel_grad_out, nullptr, io.s));
+    if (lgrad_out) {
+        if (io.timed) timer_mark(io.ctx, "logistic_gradient", io.s);
+        launch_logistic_gradient(d_ug, m.lfeat.as<float>(), m.N, m.C, m.K, io.cs->learn_partials.as<double>(), lgrad_out, io.s);
+        RV_LAUNCH_OK(io.ctx);
+    }
+    return io.done();
+}
+
+// the compatibility parameters of term `t` as rvseg_crf_term.compat_params from their slice of labelCompatibilityParameters()
+static void compat_from_x(int C, int compat, const float* v, std::vector<float>& out) {
+    if (compat != RVSEG_COMPAT_MATRIX) { out.assign(v, v + (compat == RVSEG_COMPAT_DIAGONAL ? C : 1)); return; }
+    out.assign((size_t)C * C, 0.f);
+    for (int i = 0, k = 0; i < C; i++)
+        for (int j = i; j < C; j++, k++) out[(size_t)i * C + j] = out[(size_t)j * C + i] = v[k];
+}
+
+static rvseg_status model_energy_gradient(rvseg_ctx* ctx, const char* entry, int32_t iterations, const rvseg_crf_objective* obj, int32_t mask,
+                                          float l2, const float* x, int32_t n, double* value_out, float* dx_out) {
+    ModelIo io = host_io(ctx, entry);
+    RV_TRY(io.enter());
+    RV_TRY(objective_arg(ctx, obj));
+    CrfModel& m = io.cs->model;
+    RV_MODEL_ARGS(iterations >= 0 && value_out && mask >= 0 && mask <= 7 && n >= 0 && (n == 0 || (x && dx_out)) && std::isfinite(l2));
+    const size_t nu = (mask & 1) ? (size_t)m.C * m.K : 0, nc = (mask & 2) ? model_compat_params(m) : 0,
+                 nk = (mask & 4) ? model_kernel_params(m) : 0;
+    if ((size_t)n != nu + nc + nk) { ctx->err = "n is not the number of learned parameters of the model"; return RVSEG_ERR_INVALID_ARG; }
+    const int n_terms = (int)m.plan.size();
+    if (nu) {   // unaryParameters(): L column-major
+        std::vector<float> L(nu);
+        for (int c = 0; c < m.C; c++)
+            for (int k = 0; k < m.K; k++) L[(size_t)c * m.K + k] = x[(size_t)k * m.C + c];
+        RV_TRY(model_set_logistic_params(host_io(ctx, entry), L.data()));
+    }
+    if (mask & 2) {
+        std::vector<float> cp;
+        for (int t = 0; t < n_terms; t++) {
+            compat_from_x(m.C, m.plan[t].compat, x + nu + model_compat_params(m, t), cp);
+            RV_TRY(model_set_compat(host_io(ctx, entry), t, cp.data()));
+        }
+    }
+    if (mask & 4)
+        for (int t = 0; t < n_terms; t++) {
+            const size_t np = term_kernel_params(m.plan[t]);
+            const float* v = x + nu + nc + model_kernel_params(m, t);
+            const TermKeep& keep = m.keep[t];
+            if (!np || (keep.has_kparams && std::memcmp(keep.kparams.data(), v, np * sizeof(float)) == 0)) continue;
+            RV_TRY(model_set_kernel(host_io(ctx, entry), t, v));
+        }
+    std::vector<double> g(nu + nc + nk);   // the gradients of the learned groups in the order of x
+    double* gu = g.data();
+    double* gc = gu + nu;
+    double* gk = gc + nc;
+    RV_TRY(model_gradient_params(host_io(ctx, entry), iterations, obj, value_out, nu ? gu : nullptr, nc ? gc : nullptr, nk ? gk : nullptr));
+    for (int i = 0; i < n; i++) {
+        dx_out[i] = -(float)g[i];
+        if (l2 > 0) { const float reg = l2 * x[i]; dx_out[i] = dx_out[i] + reg; }
+    }
+    *value_out = -*value_out;
+    if (l2 > 0) {
+        double sum = 0.0;
+        for (int i = 0; i < n; i++) sum += (double)x[i] * (double)x[i];
+        *value_out += (0.5 * (double)l2) * sum;
+    }
     return RVSEG_OK;
 }
 
@@ -835,6 +990,36 @@ rvseg_status rvseg_crf_model_set_unary(rvseg_ctx* ctx, const float* unary, int32
 }
 rvseg_status rvseg_crf_model_set_unary_device(rvseg_ctx* ctx, const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
     return model_set_unary(device_io(ctx, hip_stream, __func__), d_unary, unary_is_energy);
+}
+
+rvseg_status rvseg_crf_model_set_kernel(rvseg_ctx* ctx, int32_t term, const float* params) {
+    return model_set_kernel(host_io(ctx, __func__), term, params);
+}
+
+rvseg_status rvseg_crf_model_set_logistic(rvseg_ctx* ctx, int32_t K, const float* L, const float* f) {
+    return model_set_logistic(host_io(ctx, __func__), K, L, f);
+}
+rvseg_status rvseg_crf_model_set_logistic_device(rvseg_ctx* ctx, int32_t K, const float* L, const float* d_f, void* hip_stream) {
+    return model_set_logistic(device_io(ctx, hip_stream, __func__), K, L, d_f);
+}
+rvseg_status rvseg_crf_model_set_logistic_params(rvseg_ctx* ctx, const float* L) {
+    return model_set_logistic_params(host_io(ctx, __func__), L);
+}
+
+rvseg_status rvseg_crf_model_gradient_params(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
+                                             double* unary_grad_out, double* compat_grad_out, double* kernel_grad_out) {
+    return model_gradient_params(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, kernel_grad_out);
+}
+rvseg_status rvseg_crf_model_gradient_params_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
+                                                    double* d_unary_grad_out, double* d_compat_grad_out, double* d_kernel_grad_out,
+                                                    void* hip_stream) {
+    return model_gradient_params(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out,
+                                 d_kernel_grad_out);
+}
+
+rvseg_status rvseg_crf_model_energy_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, int32_t learn_mask,
+                                             float l2_norm, const float* x, int32_t n, double* value_out, float* dx_out) {
+    return model_energy_gradient(ctx, __func__, iterations, obj, learn_mask, l2_norm, x, n, value_out, dx_out);
 }
 
 rvseg_status rvseg_crf_logistic_gradient(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t K, const float* unary_grad, const float* f, double* out) {

@@ -38,7 +38,8 @@ struct TermPlan {
 
 // What a kept model keeps of a term beside its lattice, for the kernel-parameter gradient: the ranks of every point (3 bits
 // each in one word) and, for a DIAG or FULL kernel, the features as the caller passed them (f_, N x d).
-struct TermKeep { DevBuf rank, feat; };
+// kparams: the kernel parameters the term's lattice was built from (has_kparams false: none, the features as passed).
+struct TermKeep { DevBuf rank, feat; std::vector<float> kparams; bool has_kparams = false; };
 
 // The DenseCRF model a context keeps between calls (rvseg_crf_model_*): term k on CrfState::lat[k], the compatibilities in
 // CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
@@ -64,11 +65,18 @@ struct CrfModel {
     TermKeep keep[8];
     DevBuf kg_a, kg_b, kg_out, kg_grad;
     DevBuf kg_an, kg_bn, kg_fa, kg_fb, kg_x, kg_ones, kg_lbl, kg_g1, kg_g2, kg_fg, kg_full;
+    // a kept logistic unary (rvseg_crf_model_set_logistic): K > 0, f (N x K) and L (C x K) in memory of the model; staging of
+    // the parameter gradient's C K doubles
+    int K = 0;
+    DevBuf lfeat, lmat, lgrad;
+    PinnedBuf h_lmat;   // the source of L's asynchronous upload; lmat_ev: that upload has left it
+    Event lmat_ev;
 };
 
 struct CrfState {
     std::vector<LatticeBufs> lat;  // one per pairwise kernel
     CrfModel model;                // rvseg_crf_model_*
+    long long lattice_builds = 0;  // lattice_build calls on this context (rvseg_debug_lattice_builds)
     const char* entry = "";        // the C-ABI entry at work (crf_enter; the frame and cloud paths name themselves): CrfModel::replaced_by
     // two slots of mean-field scratch: a second label layer's mean field runs beside the first on its own stream
     struct { DevBuf val_a, val_b, tmp, qn; } scratch[2];
@@ -118,6 +126,7 @@ rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry);
 void model_replaced(CrfState* cs);
 rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
                            std::vector<TermPlan>& plan, hipStream_t s, TermKeep* keep = nullptr);
+rvseg_status term_rebuild(rvseg_ctx* ctx, CrfState* cs, int k, const float* kernel_params, hipStream_t s);
 void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */);
 bool term_pre(const TermPlan& t);
 bool term_post(const TermPlan& t);

@@ -391,6 +391,7 @@ class Context:
 
     def _crf_model_is(self, N, Cn, terms, device=False):
         self._crf_model_shape = (N, Cn, len(terms))
+        self._crf_model_K = 0   # no kept logistic unary (crf_model_set_logistic)
         self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
         # per term: the feature dimension and the kernel parameters' count (CONST 0, DIAG d, FULL d x d)
         self._crf_model_dims = [int(t[0][1]) if device else np.shape(t[0])[1] for t in terms]   # (device: (address, d))
@@ -554,6 +555,64 @@ class Context:
     def crf_model_set_unary(self, unary, unary_is_energy=True):
         U = self._crf_model_matrix(unary)
         capi.check(self.h, self.L.rvseg_crf_model_set_unary(self.h, _ptr(U), 1 if unary_is_energy else 0))
+        self._crf_model_K = 0
+
+    # ---- the learning loop (rvseg.h, "The learning loop") ----
+    def crf_model_set_kernel(self, term, params):
+        """Rebuilds one DIAG / FULL term's lattice in the live model from the features it keeps; params None: the features
+        as passed."""
+        kp = None if params is None else np.ascontiguousarray(params, np.float32).reshape(-1)
+        counts = getattr(self, "_crf_model_kparams", [])
+        if kp is not None and 0 <= term < len(counts):
+            assert kp.shape == (counts[term],)
+        capi.check(self.h, self.L.rvseg_crf_model_set_kernel(self.h, term, _ptr(kp)))
+
+    def crf_model_set_logistic(self, L, f):
+        """The live model keeps f (N x K) and its unary becomes the energy L f (L: C x K)."""
+        N, Cn, _ = self._crf_model_shape
+        Lm = np.ascontiguousarray(L, np.float32)
+        F = np.ascontiguousarray(f, np.float32)
+        assert Lm.ndim == 2 and Lm.shape[0] == Cn and F.shape == (N, Lm.shape[1])
+        capi.check(self.h, self.L.rvseg_crf_model_set_logistic(self.h, Lm.shape[1], _ptr(Lm), _ptr(F)))
+        self._crf_model_K = Lm.shape[1]
+
+    def crf_model_set_logistic_device(self, L, d_f, stream=0):
+        Lm = np.ascontiguousarray(L, np.float32)
+        assert Lm.ndim == 2 and Lm.shape[0] == self._crf_model_shape[1]
+        self.crf_model_call_device("set_logistic", Lm.shape[1], Lm.ctypes.data, d_f, stream=stream)
+
+    def crf_model_set_logistic_params(self, L):
+        Lm = np.ascontiguousarray(L, np.float32)
+        K = getattr(self, "_crf_model_K", 0)
+        assert Lm.ndim == 2 and Lm.shape[0] == self._crf_model_shape[1] and (K == 0 or Lm.shape[1] == K)   # (K == 0: the library refuses)
+        capi.check(self.h, self.L.rvseg_crf_model_set_logistic_params(self.h, _ptr(Lm)))
+
+    def crf_model_gradient_params(self, iterations, objective, unary=True, lbl_cmp=True, kernel=True):
+        """rvseg_crf_model_gradient_params: (value, unary_grad C K float64 column-major, compat_grad, kernel_grad); a part not
+        asked for is None.  K is the one every call of this class that sets or drops the kept logistic unary records."""
+        N, Cn, _ = self._crf_model_shape
+        K = self._crf_model_K
+        rec, keep = objective.record(N, Cn)
+        value = np.empty(1, np.float64)
+        ug = np.zeros(max(1, Cn * K), np.float64) if unary else None
+        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
+        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
+        capi.check(self.h, self.L.rvseg_crf_model_gradient_params(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(kg)))
+        del keep
+        return (float(value[0]), (ug[:Cn * K] if unary else None), (cg[:sum(self._crf_model_params)] if lbl_cmp else None),
+                (kg[:sum(self._crf_model_kparams)] if kernel else None))
+
+    def crf_model_energy_gradient(self, iterations, objective, learn_mask, l2_norm, x):
+        """rvseg_crf_model_energy_gradient: CRFEnergy::gradient on the live model -> (value, dx float32)."""
+        N, Cn, _ = self._crf_model_shape
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        rec, keep = objective.record(N, Cn)
+        value = np.empty(1, np.float64)
+        dx = np.zeros(max(1, x.shape[0]), np.float32)
+        capi.check(self.h, self.L.rvseg_crf_model_energy_gradient(self.h, iterations, C.byref(rec), int(learn_mask), C.c_float(float(l2_norm)),
+                                                                  _ptr(x if x.shape[0] else dx), x.shape[0], _ptr(value), _ptr(dx)))
+        del keep
+        return float(value[0]), dx[:x.shape[0]]
 
     def crf_logistic_gradient(self, unary_grad, f):
         """LogisticUnaryEnergy::gradient (unary.cpp:64-68): unary_grad (N x C), f (N x K) -> C K doubles, column-major like
@@ -576,6 +635,10 @@ class Context:
         fn = getattr(self.L, "rvseg_crf_model_%s_device" % name)
         conv = [C.c_void_p(a or None) if t is C.c_void_p else a for a, t in zip(args, fn.argtypes[1:])]
         capi.check(self.h, fn(self.h, *conv, C.c_void_p(stream or None)))
+        if name == "set_logistic":   # the one record of the kept logistic unary's K (crf_model_gradient_params sizes its buffer by it)
+            self._crf_model_K = int(args[0])
+        elif name == "set_unary":
+            self._crf_model_K = 0
 
     # ---- local-map fusion -------------------------------------------------------------------
     def fuse_posteriors(self, index_images, posteriors, class_counts, cloud_size):
@@ -754,6 +817,12 @@ class Context:
         oor = C.c_uint64()
         capi.check(self.h, self.L.rvseg_eval_confusion(self.h, layer, _ptr(counts), C.byref(oor)))
         return counts, oor.value
+
+    def debug_lattice_builds(self):
+        """Lattices built on this context so far (overflow retries included): a call that must build none leaves it unchanged."""
+        n = C.c_longlong()
+        capi.check(self.h, self.L.rvseg_debug_lattice_builds(self.h, C.byref(n)))
+        return n.value
 
     def last_timing(self):
         names = C.create_string_buffer(4096)
@@ -971,13 +1040,14 @@ class DenseCRF:
         self.kernels = []
 
     def setUnaryEnergy(self, unary, f=None):  # densecrf.cpp:85-91; unary is N x M energy (= -log-posterior)
-        self._touch()
         if f is not None:   # setUnaryEnergy(L, f): LogisticUnaryEnergy, unary.cpp:44-52 (L: M x K, f: N x K point-major)
             L = np.array(unary, np.float32)
             f = np.ascontiguousarray(f, np.float32)
             assert L.shape[0] == self.M and f.shape == (self.N, L.shape[1])
             self.logistic, self.unary = (L, f), None
+            self._update_model(lambda: self.ctx.crf_model_set_logistic(L, f))   # the live model keeps f
             return
+        self._touch()
         unary = np.ascontiguousarray(unary, np.float32)
         assert unary.shape == (self.N, self.M)
         self.unary, self.logistic = unary, None
@@ -1003,19 +1073,22 @@ class DenseCRF:
             return np.zeros(0, np.float32)
         return np.ascontiguousarray(self.logistic[0].T).reshape(-1)
 
-    def setUnaryParameters(self, v):   # unary.cpp:58-63
-        if self.logistic is None:
-            return
+    def _assign_unary(self, v):   # this object's copy only, as the other _assign_*: no model call
         L, f = self.logistic
         v = np.asarray(v, np.float32)
         assert v.shape == (L.size,)
         self.logistic = (np.ascontiguousarray(v.reshape(L.shape[1], L.shape[0]).T), f)
-        self._update_model(lambda: self.ctx.crf_model_set_unary(self._unary_energy()))
+
+    def setUnaryParameters(self, v):   # unary.cpp:58-63
+        if self.logistic is None:
+            return
+        self._assign_unary(v)
+        self._update_model(lambda: self.ctx.crf_model_set_logistic_params(self.logistic[0]))   # U = L f again from the kept f
 
     def labelCompatibilityParameters(self):
         return np.concatenate([np.zeros(0, np.float32)] + [_compat(k[1]).parameters() for k in self.kernels]).astype(np.float32)
 
-    def setLabelCompatibilityParameters(self, v):
+    def _assign_compat(self, v):
         v = np.asarray(v, np.float32)
         i = 0
         for k in self.kernels:
@@ -1024,6 +1097,9 @@ class DenseCRF:
             k[1].setParameters(v[i:i + n])
             i += n
         assert i == v.shape[0]
+
+    def setLabelCompatibilityParameters(self, v):
+        self._assign_compat(v)
 
         def update():
             for t, k in enumerate(self.kernels):
@@ -1041,16 +1117,29 @@ class DenseCRF:
     def kernelParameters(self):
         return np.concatenate([np.zeros(0, np.float32)] + [self._kernel_parameters(k) for k in self.kernels]).astype(np.float32)
 
-    def setKernelParameters(self, v):   # pairwise.cpp:140-152: DIAG d values, FULL d x d column-major, CONST none
-        self._touch()
+    def _assign_kernel(self, v):
+        """Returns the terms whose values changed: those whose lattice a live model has to build again."""
         v = np.asarray(v, np.float32)
         i = 0
-        for k in self.kernels:
+        changed = []
+        for t, k in enumerate(self.kernels):
             n = self._kernel_parameters(k).shape[0]
             if k[2] != CONST_KERNEL:
-                k[4] = v[i:i + n].copy()
+                new = v[i:i + n].copy()
+                if k[4] is None or k[4].tobytes() != new.tobytes():
+                    changed.append(t)
+                k[4] = new
             i += n
         assert i == v.shape[0]
+        return changed
+
+    def setKernelParameters(self, v):   # pairwise.cpp:140-152: DIAG d values, FULL d x d column-major, CONST none
+        changed = self._assign_kernel(v)
+
+        def update():
+            for t in changed:
+                self.ctx.crf_model_set_kernel(t, self.kernels[t][4])
+        self._update_model(update)
 
     def _unary_energy(self):
         # A logistic unary is computed on the GPU and read back, then uploaded with the model (an N x M round trip per
@@ -1096,7 +1185,11 @@ class DenseCRF:
         for attempt in range(2):
             if key is None or getattr(self.ctx, "_crf_model_owner", None) is not key:
                 key = self._model_key = object()
-                self.ctx.crf_model_set(self._unary_energy(), [tuple(k) for k in self.kernels])
+                if self.logistic is not None:   # the model computes L f itself and keeps f
+                    self.ctx.crf_model_set(np.zeros((self.N, self.M), np.float32), [tuple(k) for k in self.kernels])
+                    self.ctx.crf_model_set_logistic(*self.logistic)
+                else:
+                    self.ctx.crf_model_set(self._unary_energy(), [tuple(k) for k in self.kernels])
                 self.ctx._crf_model_owner = key
             try:
                 return call()
@@ -1144,6 +1237,10 @@ class DenseCRF:
         is the gradient of unaryParameters() (empty without a logistic unary), lbl_cmp_grad that of
         labelCompatibilityParameters(); a part not asked for is None.  kernel: a fourth element, the gradient of
         kernelParameters().  energy_grad: unary_grad is d value / d U (N x M) instead."""
+        if self.logistic is not None and unary and not energy_grad:   # one call; C K doubles come back, not N x M floats
+            value, ug, cg, kg = self._with_model(lambda: self.ctx.crf_model_gradient_params(n_iterations, objective, True, lbl_cmp, kernel))
+            out = (value, ug.astype(np.float32), (cg.astype(np.float32) if lbl_cmp else None))
+            return out + (kg.astype(np.float32),) if kernel else out
         if kernel:
             value, ug, cg, kg, _ = self._with_model(lambda: self.ctx.crf_model_gradient_kernel(n_iterations, objective, unary, lbl_cmp))
         else:
@@ -1157,10 +1254,32 @@ class DenseCRF:
         return out + (kg.astype(np.float32),) if kernel else out
 
 
+    def energy_gradient(self, n_iterations, objective, unary, pairwise, kernel, l2_norm, x):
+        """CRFEnergy::gradient (dense_learning.cpp:60-84) as one rvseg_crf_model_energy_gradient: x becomes this object's
+        parameters and the live model's; (value, dx)."""
+        x = np.asarray(x, np.float32)
+        nu = self.unaryParameters().shape[0] if unary else 0
+        nc = self.labelCompatibilityParameters().shape[0] if pairwise else 0
+        nk = self.kernelParameters().shape[0] if kernel else 0
+        assert x.shape == (nu + nc + nk,)
+        mask = (capi.LEARN_UNARY if unary else 0) | (capi.LEARN_PAIRWISE if pairwise else 0) | (capi.LEARN_KERNEL if kernel else 0)
+        try:
+            if nu:
+                self._assign_unary(x[:nu])
+            if pairwise:
+                self._assign_compat(x[nu:nu + nc])
+            if kernel:
+                self._assign_kernel(x[nu + nc:])
+            return self._with_model(lambda: self.ctx.crf_model_energy_gradient(n_iterations, objective, mask, l2_norm, x))
+        except BaseException:
+            self._touch()   # the model may hold a part of x only: the next call sets it afresh
+            raise
+
+
 class CRFEnergy:
     """The EnergyFunction of examples/dense_learning.cpp:38-85 over a DenseCRF: gradient(x) sets the parameters, and returns
-    the negated objective and gradient plus the L2 term, for a minimiser of the caller's.  Unary and label-compatibility
-    parameters only: CRFKernelEnergy also learns the kernel parameters."""
+    the negated objective and gradient plus the L2 term (one rvseg_crf_model_energy_gradient on the kept model), for
+    minimizeLBFGS.  Unary and label-compatibility parameters only: CRFKernelEnergy also learns the kernel parameters."""
 
     def __init__(self, crf, objective, NIT, unary=True, pairwise=True, kernel=False):
         if kernel:
@@ -1187,9 +1306,17 @@ class CRFEnergy:
         return np.concatenate([np.zeros(0, np.float32)] + [p for on, p, _ in self.groups if on]).astype(np.float32)
 
     def gradient(self, x):
-        """(value, dx) of dense_learning.cpp:60-84."""
+        """(value, dx) of dense_learning.cpp:60-84: one rvseg_crf_model_energy_gradient on the kept model of a DenseCRF (its
+        definition in rvseg.h: the L2 term of the value is summed in double)."""
         x = np.asarray(x, np.float32)
         assert x.shape == (sum(p.shape[0] for on, p, _ in self.groups if on),)
+        if not hasattr(getattr(self.crf, "ctx", None), "crf_model_energy_gradient"):
+            return self._compose(x)
+        return self.crf.energy_gradient(self.NIT, self.objective, self.unary, self.pairwise, getattr(self, "kernel", False), self.l2_norm, x)
+
+    def _compose(self, x):
+        """gradient(x) over any object with DenseCRF's setters and gradient(), call by call.  dx as the one entry gives it; the
+        L2 term of the value is 0.5 l2 x.x with the dot product in fp32."""
         i = 0
         for on, p, setter in self.groups:
             if on:
@@ -1206,7 +1333,8 @@ class CRFEnergy:
 
 class CRFKernelEnergy(CRFEnergy):
     """The whole EnergyFunction of examples/dense_learning.cpp:38-85: CRFEnergy with the kernel parameters as the third
-    group of x.  Every gradient(x) with kernel=True sets the kernel parameters, which sets the model (its lattices) again."""
+    group of x.  A gradient(x) with kernel=True builds again only the lattices of the terms whose parameters changed, from
+    the features the model keeps."""
 
     def __init__(self, crf, objective, NIT, unary=True, pairwise=True, kernel=True):
         CRFEnergy.__init__(self, crf, objective, NIT, unary, pairwise, False)
@@ -1217,6 +1345,60 @@ class CRFKernelEnergy(CRFEnergy):
     def _crf_gradient(self):
         g = self.crf.gradient(self.NIT, self.objective, self.unary, self.pairwise, kernel=self.kernel)
         return g[0], [g[1], g[2], g[3] if self.kernel else None]
+
+
+def minimizeLBFGS(energy, restart=0, verbose=False, report=None, **params):
+    """minimizeLBFGS of optimization.cpp:68-103 on rvseg_minimize_lbfgs: epsilon = 1e-6 and max_iterations = 50 unless given
+    in params (fields of rvseg_lbfgs_params), up to restart + 1 runs from where the last one ended, stopping when a run's
+    value is no lower than the lowest before it.  energy: initialValue() and gradient(x float32) -> (value, dx), as
+    CRFEnergy.  x crosses to the energy as float32 (the reference's VectorXf).  Returns the parameters, float32.
+    report (optional list): one dict per run, capi.minimize_lbfgs's with "fx"."""
+    x = np.array(energy.initialValue(), np.float64).reshape(-1)
+    if x.shape[0] == 0:
+        return x.astype(np.float32)
+    p = dict(epsilon=1e-6, max_iterations=50)
+    p.update(params)
+
+    def fun(xd):
+        value, dx = energy.gradient(xd.astype(np.float32))
+        return value, np.asarray(dx, np.float64)
+
+    def progress(xd, g, fx, xnorm, gnorm, step, k, ls):
+        print("Iteration %d:\n  fx = %f, xnorm = %f, gnorm = %f, step = %f\n" % (k, fx, xnorm, gnorm, step))
+        return 0
+
+    last_f = 1e100
+    rep = {}
+    for _ in range(int(restart) + 1):
+        x, fx, rep = capi.minimize_lbfgs(fun, x, progress if verbose else None, **p)
+        if report is not None:
+            report.append(dict(rep, fx=fx))
+        if last_f > fx:
+            last_f = fx
+        else:
+            break
+    if verbose:
+        print("L-BFGS optimization terminated with status code = %d" % rep.get("status", 0))
+    return x.astype(np.float32)
+
+
+def numericGradient(energy, x, EPS=1e-3):   # optimization.cpp:104-115
+    x = np.asarray(x, np.float32)
+    g = np.empty(x.shape[0], np.float32)
+    for i in range(x.shape[0]):
+        xx = x.copy()
+        xx[i] = x[i] + np.float32(EPS)
+        v1 = energy.gradient(xx)[0]
+        xx[i] = x[i] - np.float32(EPS)
+        v0 = energy.gradient(xx)[0]
+        g[i] = (v1 - v0) / (2 * EPS)
+    return g
+
+
+def gradCheck(energy, x, EPS=1e-3):   # optimization.cpp:121-126: the norm of numeric minus analytic gradient
+    ng = numericGradient(energy, x, EPS)
+    g = np.asarray(energy.gradient(np.asarray(x, np.float32))[1], np.float32)
+    return float(np.linalg.norm((ng - g).astype(np.float32)))
 
 
 class LocalMapStore:
