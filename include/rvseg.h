@@ -403,6 +403,22 @@ rvseg_status rvseg_crf_model_trace(rvseg_ctx *ctx, int32_t iterations, float *Q_
                                    int32_t unknown_label, double *kl_out);
 rvseg_status rvseg_crf_model_trace_device(rvseg_ctx *ctx, int32_t iterations, float *d_Q_out, int8_t *d_map_out, int32_t label_mode,
                                           int32_t unknown_label, double *d_kl_out, void *hip_stream);
+/* Which model the context keeps and its shape: what a caller needs to size the arrays of the model calls and to tell its
+ * own model from one that somebody else set.  serial: taken by every successful rvseg_crf_model_set[_device] from one
+ * process-wide counter that starts at 1, so it never names two models, not even across contexts or a context address
+ * that is reused; the in-place setters (set_compat, set_unary, set_kernel, set_logistic, set_logistic_params,
+ * energy_gradient) leave it alone.  K: the kept logistic unary's feature count, 0 without one.  Per term (arrays of the
+ * term limit of rvseg_crf_terms_check): the feature dimension, the count of its labelCompatibilityParameters() and of
+ * its kernelParameters(); then the two totals.  Host only: it enqueues nothing, waits for nothing and allocates
+ * nothing.  *out is zeroed first; without a live model the status and rvseg_last_error are those of any model call
+ * (RVSEG_ERR_INVALID_ARG, naming the call that replaced the model). */
+struct rvseg_crf_model_info {   /* (a struct tag only: the entry below has the name) */
+    uint64_t serial;
+    int32_t N, C, n_terms, K;
+    int32_t d[8], compat_params[8], kernel_params[8];
+    int32_t n_compat_params, n_kernel_params;
+};
+rvseg_status rvseg_crf_model_info(rvseg_ctx *ctx, struct rvseg_crf_model_info *out);
 
 /* ---- Learning on the kept model: the objectives of objective.cpp:35-108 and the mean-field gradient of DenseCRF::gradient
  *      (densecrf.cpp:238-297) with respect to the unary energy, the label-compatibility parameters and the kernel

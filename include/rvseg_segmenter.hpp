@@ -802,17 +802,6 @@ struct IntersectionOverUnion : ObjectiveFunction {
     explicit IntersectionOverUnion(std::vector<int16_t> g) { kind = RVSEG_OBJECTIVE_IOU; gt = std::move(g); }
 };
 
-// Which DenseCRF object set the model a context keeps (rvseg_crf_model_*): the context has one model and no handle for it,
-// so two objects that share a context take turns.  set: record `owner` (nullptr: nobody).
-inline const void* crf_model_owner(rvseg_ctx* ctx, bool set = false, const void* owner = nullptr) {
-    static std::mutex mtx;
-    static std::map<rvseg_ctx*, const void*> owners;
-    std::lock_guard<std::mutex> lock(mtx);
-    if (set) owners[ctx] = owner;
-    const auto it = owners.find(ctx);
-    return it == owners.end() ? nullptr : it->second;
-}
-
 // DenseCRF (densecrf.h:36-121) over feature matrices the caller builds: N points, M labels.  addPairwiseEnergy with a bare
 // weight is PottsCompatibility; a model of bare weights with NORMALIZE_SYMMETRIC and no kernel parameters runs through
 // rvseg_crf_infer_multi as before, every other model (learned compatibilities, normalisations, kernel parameters, a
@@ -820,8 +809,7 @@ inline const void* crf_model_owner(rvseg_ctx* ctx, bool set = false, const void*
 class DenseCRF {
 public:
     DenseCRF(rvseg_ctx* ctx, int N, int M) : ctx_(ctx), N_(N), M_(M) {}
-    ~DenseCRF() { if (crf_model_owner(ctx_) == this) crf_model_owner(ctx_, true, nullptr); }
-    void setUnaryEnergy(const float* unary /* N x M */) { model_set_ = false; unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
+    void setUnaryEnergy(const float* unary /* N x M */) { model_serial_ = 0; unary_.assign(unary, unary + (size_t)N_ * M_); logistic_f_.clear(); }
     // LogisticUnaryEnergy (unary.cpp:44-63): L M x K row-major, f N x K point-major
     // A live model of this object keeps f and computes L f itself (rvseg_crf_model_set_logistic): no lattice is built again.
     void setUnaryEnergy(const float* L, const float* f, int K) {
@@ -898,7 +886,7 @@ public:
             const int32_t mask = (unary ? 1 : 0) | (pairwise ? 2 : 0) | (kernel ? 4 : 0);
             onModel([&] { return rvseg_crf_model_energy_gradient(ctx_, n_iterations, &rec, mask, l2_norm, x.data(), (int32_t)x.size(), &value, dx.data()); });
         } catch (...) {
-            model_set_ = false;   // the model may hold a part of x only
+            model_serial_ = 0;   // the model may hold a part of x only
             throw;
         }
         dx.pop_back();
@@ -937,7 +925,7 @@ public:
     }
     // ---- stepwise inference, energies and KL divergence (densecrf.h:77-94) on a model the context keeps
     // (rvseg_crf_model_*): set by the first of these calls, again after any add* / set* call, and again when the context
-    // reports that another call replaced it.  Q: N x M point-major.
+    // keeps another model or none (modelIsLive).  Q: N x M point-major.
     std::vector<float> startInference() {   // densecrf.cpp:178-186
         std::vector<float> Q((size_t)N_ * M_);
         onModel([&] { return rvseg_crf_model_start(ctx_, Q.data()); });
@@ -1012,33 +1000,20 @@ public:
         const rvseg_crf_objective rec = objective.record();
         double value = 0;
         std::vector<float> ug((size_t)N_ * M_);
-        std::vector<double> cg(labelCompatibilityParameters().size() + 1), kg(kernelParameters().size() + 1);
-        if (unary_grad && !unary_energy_grad && !logistic_f_.empty()) {   // the parameters' doubles alone come back
-            std::vector<double> lg((size_t)M_ * K_);
-            onModel([&] {
-                return rvseg_crf_model_gradient_params(ctx_, n_iterations, &rec, &value, lg.data(), lbl_cmp_grad ? cg.data() : nullptr,
-                                                       kernel_grad ? kg.data() : nullptr);
-            });
-            unary_grad->assign(lg.begin(), lg.end());
-            if (lbl_cmp_grad) lbl_cmp_grad->assign(cg.begin(), cg.end() - 1);
-            if (kernel_grad) kernel_grad->assign(kg.begin(), kg.end() - 1);
-            return value;
-        }
+        std::vector<double> cg(labelCompatibilityParameters().size() + 1), kg(kernelParameters().size() + 1), lg((size_t)M_ * K_);
+        double* const cgp = lbl_cmp_grad ? cg.data() : nullptr;
+        double* const kgp = kernel_grad ? kg.data() : nullptr;
+        const bool logistic = unary_grad && !logistic_f_.empty();
+        const bool params = logistic && !unary_energy_grad;   // the parameters' doubles alone come back
         const bool want_ug = unary_grad || unary_energy_grad;
         onModel([&] {
-            return rvseg_crf_model_gradient_kernel(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, lbl_cmp_grad ? cg.data() : nullptr,
-                                                   kernel_grad ? kg.data() : nullptr, nullptr);
+            return params ? rvseg_crf_model_gradient_params(ctx_, n_iterations, &rec, &value, lg.data(), cgp, kgp)
+                          : rvseg_crf_model_gradient_kernel(ctx_, n_iterations, &rec, &value, want_ug ? ug.data() : nullptr, cgp, kgp, nullptr);
         });
+        if (logistic && !params) status(rvseg_crf_logistic_gradient(ctx_, N_, M_, K_, ug.data(), logistic_f_.data(), lg.data()));
+        if (unary_grad) unary_grad->assign(lg.begin(), logistic ? lg.end() : lg.begin());
         if (lbl_cmp_grad) lbl_cmp_grad->assign(cg.begin(), cg.end() - 1);
         if (kernel_grad) kernel_grad->assign(kg.begin(), kg.end() - 1);
-        if (unary_grad) {
-            unary_grad->clear();
-            if (!logistic_f_.empty()) {
-                std::vector<double> lg((size_t)M_ * K_);
-                status(rvseg_crf_logistic_gradient(ctx_, N_, M_, K_, ug.data(), logistic_f_.data(), lg.data()));
-                unary_grad->assign(lg.begin(), lg.end());
-            }
-        }
         if (unary_energy_grad) *unary_energy_grad = std::move(ug);
         return value;
     }
@@ -1055,7 +1030,7 @@ protected:
         const size_t want = c.kind == RVSEG_COMPAT_POTTS ? 1 : c.kind == RVSEG_COMPAT_DIAGONAL ? (size_t)M_ : (size_t)M_ * M_;
         if (c.params.size() != want || (c.kind == RVSEG_COMPAT_MATRIX && c.M != M_))
             throw std::runtime_error("label compatibility does not match the class count");
-        model_set_ = false;
+        model_serial_ = 0;
         Term t;
         t.f.assign(features, features + (size_t)N_ * d);
         t.d = d; t.compat = c; t.kernel_type = kernel_type; t.normalization = normalization; t.bare = bare;
@@ -1102,15 +1077,20 @@ protected:
         check(i == n_all);
         return changed;
     }
-    // a parameter change on the live model of this object; without one (or when another call has replaced it) the next
-    // onModel sets the model
+    // Whether the context's live model is the one this object set.  The context has one model and no handle for it, so
+    // objects that share a context take turns, and anybody may set a model on it directly: the library's serial tells.
+    // Check-then-call needs no lock of its own: a context is not safe for concurrent calls in the first place.
+    bool modelIsLive() const {
+        struct rvseg_crf_model_info info;
+        return model_serial_ != 0 && rvseg_crf_model_info(ctx_, &info) == RVSEG_OK && info.serial == model_serial_;
+    }
+    // a parameter change on the live model of this object; without one the next onModel sets the model
     template <class F>
     void inPlace(F&& update) {
-        if (!model_set_ || crf_model_owner(ctx_) != this) { model_set_ = false; return; }
+        if (!modelIsLive()) { model_serial_ = 0; return; }
         const rvseg_status st = update();
-        if (st == RVSEG_OK) return;
-        model_set_ = false;
-        if (!(st == RVSEG_ERR_INVALID_ARG && std::string(rvseg_last_error(ctx_)).find("DenseCRF model") != std::string::npos)) status(st);
+        if (st != RVSEG_OK) model_serial_ = 0;
+        status(st);
     }
     // the unary energy as N x M values: the constant one, the logistic one computed on the GPU into U, or zeros in U
     const float* unaryEnergyMatrix(std::vector<float>& U) {
@@ -1134,30 +1114,23 @@ protected:
         }
         return tt;
     }
-    // runs a model call, (re)setting the context's model first when this object changed or another call replaced it
+    // runs a model call, (re)setting the context's model first when this object changed or the context keeps another model
     template <class F>
     void onModel(F&& call) {
-        for (int attempt = 0;; attempt++) {
-            if (!model_set_ || crf_model_owner(ctx_) != this) {
-                std::vector<float> U;
-                const std::vector<rvseg_crf_term> tt = termRecords();
-                if (!logistic_f_.empty()) {   // the model computes L f itself and keeps f
-                    U.assign((size_t)N_ * M_, 0.f);
-                    status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), U.data(), 1));
-                    status(rvseg_crf_model_set_logistic(ctx_, K_, logistic_L_.data(), logistic_f_.data()));
-                } else {
-                    status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), unaryEnergyMatrix(U), 1));
-                }
-                model_set_ = true;
-                crf_model_owner(ctx_, true, this);
-            }
-            const rvseg_status st = call();
-            const bool replaced = st == RVSEG_ERR_INVALID_ARG && std::string(rvseg_last_error(ctx_)).find("DenseCRF model") != std::string::npos;
-            if (!replaced || attempt) { status(st); return; }
-            model_set_ = false;
+        if (!modelIsLive()) {
+            model_serial_ = 0;   // (a failure below leaves no model of this object)
+            std::vector<float> U;
+            const std::vector<rvseg_crf_term> tt = termRecords();
+            if (!logistic_f_.empty()) U.assign((size_t)N_ * M_, 0.f);   // the model computes L f itself and keeps f
+            status(rvseg_crf_model_set(ctx_, N_, M_, (int32_t)tt.size(), tt.data(), logistic_f_.empty() ? unaryEnergyMatrix(U) : U.data(), 1));
+            if (!logistic_f_.empty()) status(rvseg_crf_model_set_logistic(ctx_, K_, logistic_L_.data(), logistic_f_.data()));
+            struct rvseg_crf_model_info info;
+            status(rvseg_crf_model_info(ctx_, &info));
+            model_serial_ = info.serial;
         }
+        status(call());
     }
-    bool model_set_ = false;
+    uint64_t model_serial_ = 0;   // the serial of the model this object set (rvseg_crf_model_info); 0: none, or changed since
     void status(rvseg_status st) {
         if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
     }

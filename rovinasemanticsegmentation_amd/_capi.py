@@ -63,6 +63,7 @@ SYMBOLS = [
     "rvseg_crf_model_set_kernel", "rvseg_crf_model_set_logistic", "rvseg_crf_model_set_logistic_device",
     "rvseg_crf_model_set_logistic_params", "rvseg_crf_model_gradient_params", "rvseg_crf_model_gradient_params_device",
     "rvseg_crf_model_energy_gradient", "rvseg_lbfgs_params_default", "rvseg_minimize_lbfgs",
+    "rvseg_crf_model_info",
 ]
 # rvseg_lbfgs_status
 LBFGS_CONVERGED, LBFGS_MAX_ITERATIONS, LBFGS_STOPPED, LBFGS_LINESEARCH_FAILED, LBFGS_NOT_FINITE, LBFGS_BAD_ARGUMENTS = 0, 1, 2, 3, -1, -2
@@ -107,7 +108,7 @@ class RvsegScheduleInfo(C.Structure):
 
 
 class RvsegCrfTerm(C.Structure):
-    """rvseg_crf_term: one pairwise term of a learned DenseCRF model."""
+    """rvseg_crf_term: one pairwise term of a learned DenseCRF."""
     _fields_ = [
         ("d", C.c_int32), ("compat", C.c_int32), ("kernel_type", C.c_int32), ("normalization", C.c_int32),
         ("features", C.c_void_p), ("compat_params", C.c_void_p), ("kernel_params", C.c_void_p),
@@ -115,8 +116,15 @@ class RvsegCrfTerm(C.Structure):
 
 
 class RvsegCrfObjective(C.Structure):
-    """rvseg_crf_objective: a learning objective of a kept DenseCRF model."""
+    """rvseg_crf_objective: a learning objective of a DenseCRF kept on a context."""
     _fields_ = [("kind", C.c_int32), ("gt", C.c_void_p), ("robust", C.c_float), ("class_weight", C.c_void_p)]
+
+
+class RvsegCrfModelInfo(C.Structure):
+    """struct rvseg_crf_model_info: which model a context keeps, and its shape."""
+    _fields_ = [("serial", C.c_uint64), ("N", C.c_int32), ("C", C.c_int32), ("n_terms", C.c_int32), ("K", C.c_int32),
+                ("d", C.c_int32 * 8), ("compat_params", C.c_int32 * 8), ("kernel_params", C.c_int32 * 8),
+                ("n_compat_params", C.c_int32), ("n_kernel_params", C.c_int32)]
 
 
 class RvsegLbfgsParams(C.Structure):
@@ -233,6 +241,7 @@ def lib():
     L.rvseg_crf_logistic_unary_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.rvseg_crf_model_set.argtypes = [vp, i32, i32, i32, TP, vp, i32]
     L.rvseg_crf_model_set_device.argtypes = [vp, i32, i32, i32, TP, vp, i32, vp]
+    L.rvseg_crf_model_info.argtypes = [vp, C.POINTER(RvsegCrfModelInfo)]
     L.rvseg_crf_model_start.argtypes = [vp, vp]
     L.rvseg_crf_model_start_device.argtypes = [vp, vp, vp]
     L.rvseg_crf_model_step.argtypes = [vp, vp, i32]

@@ -2,6 +2,7 @@
 // build.  Each call has one body on device pointers (model_*_on) and one entry body (arguments, staging); a ModelIo
 // tells the entry body whether it serves the host entry or the _device entry.
 #include <algorithm>
+#include <atomic>
 #include <cassert>
 #include <cmath>
 #include <cstring>
@@ -20,6 +21,13 @@ using namespace rvseg;
 // Otherwise device memory, used in place on the caller's stream, and the call only enqueues.  in() and out() turn an
 // entry's pointer argument into the pointer its kernels use (a null pointer stays null).
 namespace {
+// what a model call answers without a live model
+rvseg_status no_model(rvseg_ctx* ctx, const CrfModel* m) {
+    ctx->err = !m || m->replaced_by.empty() ? std::string("no DenseCRF model on this context (rvseg_crf_model_set has not succeeded)")
+                                            : "the DenseCRF model of this context was replaced by " + m->replaced_by + ": call rvseg_crf_model_set again";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
 struct ModelIo {
     rvseg_ctx* ctx;
     bool on_host;
@@ -36,11 +44,7 @@ struct ModelIo {
     rvseg_status enter(bool need_model = true) {
         RV_TRY(crf_enter(ctx, &cs, entry));   // (refuses a null ctx)
         s = on_host ? (hipStream_t)ctx->stream : stream_of(ctx, hip_stream);
-        const CrfModel& m = cs->model;
-        if (!need_model || m.valid) return RVSEG_OK;
-        ctx->err = m.replaced_by.empty() ? std::string("no DenseCRF model on this context (rvseg_crf_model_set has not succeeded)")
-                                         : "the DenseCRF model of this context was replaced by " + m.replaced_by + ": call rvseg_crf_model_set again";
-        return RVSEG_ERR_INVALID_ARG;
+        return !need_model || cs->model.valid ? RVSEG_OK : no_model(ctx, &cs->model);
     }
     // the n elements of *p copied into `stage`
     template <class T> rvseg_status in(DevBuf& stage, T** p, size_t n) {
@@ -107,6 +111,8 @@ static rvseg_status model_set(ModelIo io, int32_t N, int32_t C, int32_t n_terms,
     if (n_terms == 0) RV_HIP(ctx, hipStreamSynchronize(io.s));
     m.N = N; m.C = C; m.unary_is_energy = unary_is_energy != 0;
     m.K = 0;
+    static std::atomic<uint64_t> next_serial{1};   // one for the process: a serial never names two models
+    m.serial = next_serial.fetch_add(1, std::memory_order_relaxed);
     m.valid = true;
     return RVSEG_OK;
 }
@@ -249,13 +255,16 @@ static rvseg_status model_trace_on(rvseg_ctx* ctx, CrfState* cs, int iterations,
 // ---------------------------------------------------------------------------------------------
 // Learning on the kept model (include/rvseg.h, "Learning on the kept model"): objective, backward pass, gradient.
 // ---------------------------------------------------------------------------------------------
+static size_t term_compat_params(const CrfModel& m, int k) {
+    const int kind = m.plan[k].compat;
+    return kind == RVSEG_COMPAT_MATRIX ? (size_t)m.C * (m.C + 1) / 2 : kind == RVSEG_COMPAT_DIAGONAL ? (size_t)m.C : 1;
+}
+
+// the layout of labelCompatibilityParameters(): the terms concatenated
 static size_t model_compat_params(const CrfModel& m, int upto = -1) {
     size_t n = 0;
     const int end = upto < 0 ? (int)m.plan.size() : upto;
-    for (int k = 0; k < end; k++) {
-        const int kind = m.plan[k].compat;
-        n += kind == RVSEG_COMPAT_MATRIX ? (size_t)m.C * (m.C + 1) / 2 : kind == RVSEG_COMPAT_DIAGONAL ? (size_t)m.C : 1;
-    }
+    for (int k = 0; k < end; k++) n += term_compat_params(m, k);
     return n;
 }
 
@@ -636,28 +645,6 @@ static rvseg_status model_backward(ModelIo io, int32_t iterations, const float* 
     return io.done();
 }
 
-static rvseg_status model_gradient(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, float* unary_grad_out,
-                                   double* compat_grad_out, double* kernel_grad_out, float* Q_out) {
-    RV_TRY(io.enter());
-    RV_TRY(objective_arg(io.ctx, obj));
-    RV_MODEL_ARGS(iterations >= 0 && value_out);
-    CrfModel& m = io.cs->model;
-    const size_t tot = (size_t)m.N * m.C;
-    rvseg_crf_objective dev = *obj;
-    RV_TRY(model_objective_in(io, m, &dev));
-    RV_TRY(dev_reserve(io.ctx, m.stats, 129 * sizeof(double)));
-    io.out_at(m.stats.as<double>() + 128, &value_out, 1);
-    RV_TRY(io.out(m.ug, &unary_grad_out, tot));
-    RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
-    RV_TRY(io.out(m.kg_grad, &kernel_grad_out, model_kernel_params(m)));
-    io.time();   // (the forward pass itself records no marks)
-    // a host entry downloads Q[n] from where the forward pass has left it: no device copy of it
-    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, unary_grad_out, compat_grad_out, kernel_grad_out,
-                             io.on_host ? nullptr : Q_out, io.s));
-    io.out_at(m.qs.as<float>() + (size_t)iterations * tot, &Q_out, tot);
-    return io.done();
-}
-
 static rvseg_status model_set_compat(ModelIo io, int32_t term, const float* params) {
     RV_TRY(io.enter());
     RV_MODEL_ARGS(params);
@@ -742,10 +729,11 @@ static rvseg_status model_set_logistic_params(ModelIo io, const float* L) {
     return io.done();
 }
 
-// model_gradient whose unary gradient stays on the device (CrfModel::ug) and leaves as the C K doubles of
-// rvseg_crf_logistic_gradient over the kept f
-static rvseg_status model_gradient_params(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, double* lgrad_out,
-                                          double* compat_grad_out, double* kernel_grad_out) {
+// rvseg_crf_model_gradient[_kernel] and _gradient_params.  lgrad_out: the unary gradient stays on the device (CrfModel::ug)
+// and leaves as the C K doubles of rvseg_crf_logistic_gradient over the kept f (the callers that pass it pass no
+// unary_grad_out and no Q_out)
+static rvseg_status model_gradient(ModelIo io, int32_t iterations, const rvseg_crf_objective* obj, double* value_out, float* unary_grad_out,
+                                   double* lgrad_out, double* compat_grad_out, double* kernel_grad_out, float* Q_out) {
     RV_TRY(io.enter());
     RV_TRY(objective_arg(io.ctx, obj));
     RV_MODEL_ARGS(iterations >= 0 && value_out);
@@ -756,20 +744,23 @@ static rvseg_status model_gradient_params(ModelIo io, int32_t iterations, const 
     RV_TRY(model_objective_in(io, m, &dev));
     RV_TRY(dev_reserve(io.ctx, m.stats, 129 * sizeof(double)));
     io.out_at(m.stats.as<double>() + 128, &value_out, 1);
+    RV_TRY(io.out(m.ug, &unary_grad_out, tot));
     RV_TRY(io.out(m.lgrad, &lgrad_out, (size_t)m.C * m.K));
     RV_TRY(io.out(m.cg, &compat_grad_out, model_compat_params(m)));
     RV_TRY(io.out(m.kg_grad, &kernel_grad_out, model_kernel_params(m)));
-    float* d_ug = nullptr;
     if (lgrad_out) {   // (the partials at their largest before anything is enqueued: no later reserve moves them)
         RV_TRY(dev_reserve(io.ctx, m.ug, tot * 4));
         RV_TRY(dev_reserve(io.ctx, io.cs->learn_partials, learn_partials_doubles(64) * sizeof(double)));
-        d_ug = m.ug.as<float>();
+        unary_grad_out = m.ug.as<float>();
     }
-    io.time();
-    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, d_ug, compat_grad_out, kernel_grad_out, nullptr, io.s));
+    io.time();   // (the forward pass itself records no marks)
+    // a host entry downloads Q[n] from where the forward pass has left it: no device copy of it
+    RV_TRY(model_gradient_on(io.ctx, io.cs, iterations, dev, value_out, unary_grad_out, compat_grad_out, kernel_grad_out,
+                             io.on_host ? nullptr : Q_out, io.s));
+    io.out_at(m.qs.as<float>() + (size_t)iterations * tot, &Q_out, tot);
     if (lgrad_out) {
         if (io.timed) timer_mark(io.ctx, "logistic_gradient", io.s);
-        launch_logistic_gradient(d_ug, m.lfeat.as<float>(), m.N, m.C, m.K, io.cs->learn_partials.as<double>(), lgrad_out, io.s);
+        launch_logistic_gradient(unary_grad_out, m.lfeat.as<float>(), m.N, m.C, m.K, io.cs->learn_partials.as<double>(), lgrad_out, io.s);
         RV_LAUNCH_OK(io.ctx);
     }
     return io.done();
@@ -819,7 +810,7 @@ static rvseg_status model_energy_gradient(rvseg_ctx* ctx, const char* entry, int
     double* gu = g.data();
     double* gc = gu + nu;
     double* gk = gc + nc;
-    RV_TRY(model_gradient_params(host_io(ctx, entry), iterations, obj, value_out, nu ? gu : nullptr, nc ? gc : nullptr, nk ? gk : nullptr));
+    RV_TRY(model_gradient(host_io(ctx, entry), iterations, obj, value_out, nullptr, nu ? gu : nullptr, nc ? gc : nullptr, nk ? gk : nullptr, nullptr));
     for (int i = 0; i < n; i++) {
         dx_out[i] = -(float)g[i];
         if (l2 > 0) { const float reg = l2 * x[i]; dx_out[i] = dx_out[i] + reg; }
@@ -856,6 +847,24 @@ rvseg_status rvseg_crf_model_set(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n
 rvseg_status rvseg_crf_model_set_device(rvseg_ctx* ctx, int32_t N, int32_t C, int32_t n_terms, const rvseg_crf_term* terms,
                                         const float* d_unary, int32_t unary_is_energy, void* hip_stream) {
     return model_set(device_io(ctx, hip_stream, __func__), N, C, n_terms, terms, d_unary, unary_is_energy);
+}
+
+rvseg_status rvseg_crf_model_info(rvseg_ctx* ctx, struct rvseg_crf_model_info* out) {
+    if (out) *out = {};
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!out) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    const CrfModel* m = ctx->impl && ctx->impl->crf ? &ctx->impl->crf->model : nullptr;   // (reads only: no state is made here)
+    if (!m || !m->valid) return no_model(ctx, m);
+    out->serial = m->serial;
+    out->N = m->N; out->C = m->C; out->n_terms = (int32_t)m->plan.size(); out->K = m->K;
+    for (int k = 0; k < out->n_terms; k++) {
+        out->d[k] = m->plan[k].d;
+        out->compat_params[k] = (int32_t)term_compat_params(*m, k);
+        out->kernel_params[k] = (int32_t)term_kernel_params(m->plan[k]);
+    }
+    out->n_compat_params = (int32_t)model_compat_params(*m);
+    out->n_kernel_params = (int32_t)model_kernel_params(*m);
+    return RVSEG_OK;
 }
 
 rvseg_status rvseg_crf_model_start(rvseg_ctx* ctx, float* Q_out) { return model_start(host_io(ctx, __func__), Q_out); }
@@ -929,11 +938,12 @@ rvseg_status rvseg_crf_model_backward_device(rvseg_ctx* ctx, int32_t iterations,
 
 rvseg_status rvseg_crf_model_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
                                       float* unary_grad_out, double* compat_grad_out, float* Q_out) {
-    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, nullptr, Q_out);
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, nullptr, compat_grad_out, nullptr, Q_out);
 }
 rvseg_status rvseg_crf_model_gradient_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
                                              float* d_unary_grad_out, double* d_compat_grad_out, float* d_Q_out, void* hip_stream) {
-    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out, nullptr, d_Q_out);
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, nullptr, d_compat_grad_out, nullptr,
+                          d_Q_out);
 }
 
 rvseg_status rvseg_crf_model_compat_apply(rvseg_ctx* ctx, int32_t term, const float* Q, float* out) {
@@ -972,12 +982,12 @@ rvseg_status rvseg_crf_model_backward_kernel_device(rvseg_ctx* ctx, int32_t iter
 
 rvseg_status rvseg_crf_model_gradient_kernel(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
                                              float* unary_grad_out, double* compat_grad_out, double* kernel_grad_out, float* Q_out) {
-    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, kernel_grad_out, Q_out);
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, nullptr, compat_grad_out, kernel_grad_out, Q_out);
 }
 rvseg_status rvseg_crf_model_gradient_kernel_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
                                                     float* d_unary_grad_out, double* d_compat_grad_out, double* d_kernel_grad_out,
                                                     float* d_Q_out, void* hip_stream) {
-    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out,
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, nullptr, d_compat_grad_out,
                           d_kernel_grad_out, d_Q_out);
 }
 
@@ -1008,13 +1018,13 @@ rvseg_status rvseg_crf_model_set_logistic_params(rvseg_ctx* ctx, const float* L)
 
 rvseg_status rvseg_crf_model_gradient_params(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* value_out,
                                              double* unary_grad_out, double* compat_grad_out, double* kernel_grad_out) {
-    return model_gradient_params(host_io(ctx, __func__), iterations, obj, value_out, unary_grad_out, compat_grad_out, kernel_grad_out);
+    return model_gradient(host_io(ctx, __func__), iterations, obj, value_out, nullptr, unary_grad_out, compat_grad_out, kernel_grad_out, nullptr);
 }
 rvseg_status rvseg_crf_model_gradient_params_device(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, double* d_value_out,
                                                     double* d_unary_grad_out, double* d_compat_grad_out, double* d_kernel_grad_out,
                                                     void* hip_stream) {
-    return model_gradient_params(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, d_unary_grad_out, d_compat_grad_out,
-                                 d_kernel_grad_out);
+    return model_gradient(device_io(ctx, hip_stream, __func__), iterations, obj, d_value_out, nullptr, d_unary_grad_out, d_compat_grad_out,
+                          d_kernel_grad_out, nullptr);
 }
 
 rvseg_status rvseg_crf_model_energy_gradient(rvseg_ctx* ctx, int32_t iterations, const rvseg_crf_objective* obj, int32_t learn_mask,

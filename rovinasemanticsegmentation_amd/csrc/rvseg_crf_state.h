@@ -1,6 +1,7 @@
 // The CRF state of a context and the mean-field pieces that rvseg_crf.hip (lattices, mean field, frame and cloud paths) and
 // rvseg_crf_model.hip (the kept DenseCRF model) share.  Private to those two files; the functions are defined in rvseg_crf.hip.
 #pragma once
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -45,6 +46,7 @@ struct TermKeep { DevBuf rank, feat; std::vector<float> kparams; bool has_kparam
 // CrfState::compat, the unary in memory of its own.  It lives until the next lattice build on the context.
 struct CrfModel {
     bool valid = false;
+    uint64_t serial = 0;       // names this model among all of the process (model_set); the in-place setters keep it
     int N = 0, C = 0;
     bool unary_is_energy = true;
     std::vector<TermPlan> plan;

@@ -372,60 +372,70 @@ class Context:
         capi.check(self.h, self.L.rvseg_crf_logistic_unary_device(self.h, N, Cn, K, _ptr(Lm), C.c_void_p(d_f), C.c_void_p(d_U),
                                                                   C.c_void_p(stream or None)))
 
-    # ---- a kept DenseCRF model (rvseg_crf_model_*): the state of this context until its next lattice build ----
+    # ---- a DenseCRF kept on the context (rvseg_crf_model_*): the state of this context until its next lattice build.  Which
+    # model it is and its shape are the library's to say (rvseg_crf_model_info): nothing of it is recorded here ----
     def crf_model_set(self, unary, terms, unary_is_energy=True):
-        """rvseg_crf_model_set: terms as for crf_infer_terms; the arrays are free once this returns."""
+        """rvseg_crf_model_set: terms as for crf_infer_terms; the arrays are free once this returns.  Returns the serial of
+        the new model (crf_model_serial)."""
         U = np.ascontiguousarray(unary, np.float32)
         N, Cn = U.shape
         arr, keep = _crf_terms(terms, Cn, N)
         capi.check(self.h, self.L.rvseg_crf_model_set(self.h, N, Cn, len(terms), arr, _ptr(U), 1 if unary_is_energy else 0))
         del keep
-        self._crf_model_is(N, Cn, terms)
+        return self.crf_model_serial()
 
     def crf_model_set_device(self, N, Cn, terms, d_unary, unary_is_energy=True, stream=0):
         arr, keep = _crf_terms(terms, Cn, N, device=True)
         capi.check(self.h, self.L.rvseg_crf_model_set_device(self.h, N, Cn, len(terms), arr, C.c_void_p(d_unary), 1 if unary_is_energy else 0,
                                                              C.c_void_p(stream or None)))
         del keep
-        self._crf_model_is(N, Cn, terms, device=True)
+        return self.crf_model_serial()
 
-    def _crf_model_is(self, N, Cn, terms, device=False):
-        self._crf_model_shape = (N, Cn, len(terms))
-        self._crf_model_K = 0   # no kept logistic unary (crf_model_set_logistic)
-        self._crf_model_params = [_compat(t[1]).parameters().shape[0] for t in terms]
-        # per term: the feature dimension and the kernel parameters' count (CONST 0, DIAG d, FULL d x d)
-        self._crf_model_dims = [int(t[0][1]) if device else np.shape(t[0])[1] for t in terms]   # (device: (address, d))
-        self._crf_model_kparams = [{CONST_KERNEL: 0, DIAG_KERNEL: d, FULL_KERNEL: d * d}[int(t[2])]
-                                   for t, d in zip(terms, self._crf_model_dims)]
+    def _crf_model(self):
+        """struct rvseg_crf_model_info of the live model; without one, the library's refusal (it names what replaced it)."""
+        info = capi.RvsegCrfModelInfo()
+        capi.check(self.h, self.L.rvseg_crf_model_info(self.h, C.byref(info)))
+        return info
 
-    def _crf_model_matrix(self, Q, copy=False):
-        """Q as a C-contiguous float32 N x C matrix of the live model; copy: never the caller's array."""
-        N, Cn, _ = self._crf_model_shape
+    def crf_model_serial(self):
+        """The serial of the live model: every crf_model_set[_device] of the process gives a new one, the in-place setters
+        keep it.  0 without a live model."""
+        info = capi.RvsegCrfModelInfo()
+        self.L.rvseg_crf_model_info(self.h, C.byref(info))   # (zeroes info when it refuses)
+        return int(info.serial)
+
+    @staticmethod
+    def _model_matrix(m, Q, copy=False):
+        """Q as a C-contiguous float32 N x C matrix of the model m; copy: never the caller's array."""
         Q = np.array(Q, np.float32, order="C") if copy else np.ascontiguousarray(Q, np.float32)
-        assert Q.shape == (N, Cn)
+        assert Q.shape == (m.N, m.C)
         return Q
 
     def crf_model_start(self):
-        N, Cn, _ = self._crf_model_shape
-        Q = np.empty((N, Cn), np.float32)
+        m = self._crf_model()
+        Q = np.empty((m.N, m.C), np.float32)
         capi.check(self.h, self.L.rvseg_crf_model_start(self.h, _ptr(Q)))
         return Q
 
     def crf_model_step(self, Q, n_steps=1):
         """n_steps of stepInference on a copy of Q (any N x C matrix), which is returned."""
-        Q = self._crf_model_matrix(Q, copy=True)
+        Q = self._model_matrix(self._crf_model(), Q, copy=True)
         capi.check(self.h, self.L.rvseg_crf_model_step(self.h, _ptr(Q), n_steps))
         return Q
 
-    def crf_model_apply(self, term, Q):
-        Q = self._crf_model_matrix(Q)
+    def _model_map(self, fn, term, Q):
+        """One of the entries that take a term and an N x C matrix and give an N x C matrix."""
+        Q = self._model_matrix(self._crf_model(), Q)
         out = np.empty_like(Q)
-        capi.check(self.h, self.L.rvseg_crf_model_apply(self.h, term, _ptr(Q), _ptr(out)))
+        capi.check(self.h, fn(self.h, term, _ptr(Q), _ptr(out)))
         return out
+
+    def crf_model_apply(self, term, Q):
+        return self._model_map(self.L.rvseg_crf_model_apply, term, Q)
 
     def crf_model_energy(self, labels, term=-1, unary=True, pairwise=True):
         """(unary energy, pairwise energy) per point of a labelling (int8, N); a part not asked for is None."""
-        N = self._crf_model_shape[0]
+        N = self._crf_model().N
         lab = np.ascontiguousarray(labels, np.int8)
         assert lab.shape == (N,)
         u = np.empty(N, np.float32) if unary else None
@@ -435,30 +445,28 @@ class Context:
 
     def crf_model_kl(self, Q):
         """The parts of the KL divergence: entropy, unary, one per term (float64); their sum in that order is the KL."""
-        Q = self._crf_model_matrix(Q)
-        parts = np.empty(2 + self._crf_model_shape[2], np.float64)
+        m = self._crf_model()
+        Q = self._model_matrix(m, Q)
+        parts = np.empty(2 + m.n_terms, np.float64)
         capi.check(self.h, self.L.rvseg_crf_model_kl(self.h, _ptr(Q), _ptr(parts)))
         return parts
 
     def crf_model_trace(self, iterations, label_mode=capi.LABEL_ARGMAX, unknown_label=0):
         """Inference from the start: (Q, map, kl) with kl[it] the KL divergence after the start and after every iteration."""
-        N, Cn, _ = self._crf_model_shape
-        Q = np.empty((N, Cn), np.float32)
-        mp = np.empty(N, np.int8)
+        m = self._crf_model()
+        Q = np.empty((m.N, m.C), np.float32)
+        mp = np.empty(m.N, np.int8)
         kl = np.empty(iterations + 1, np.float64)
         capi.check(self.h, self.L.rvseg_crf_model_trace(self.h, iterations, _ptr(Q), _ptr(mp), label_mode, unknown_label, _ptr(kl)))
         return Q, mp, kl
 
     # ---- learning on the kept model (rvseg.h, "Learning on the kept model") ----
     def crf_model_apply_transpose(self, term, Q):
-        Q = self._crf_model_matrix(Q)
-        out = np.empty_like(Q)
-        capi.check(self.h, self.L.rvseg_crf_model_apply_transpose(self.h, term, _ptr(Q), _ptr(out)))
-        return out
+        return self._model_map(self.L.rvseg_crf_model_apply_transpose, term, Q)
 
     def crf_model_objective(self, objective, Q):
         """(value, d_mul_Q) of a LogLikelihood / Hamming / IntersectionOverUnion on the marginals Q."""
-        Q = self._crf_model_matrix(Q)
+        Q = self._model_matrix(self._crf_model(), Q)
         rec, keep = objective.record(*Q.shape)
         value = np.empty(1, np.float64)
         dq = np.empty_like(Q)
@@ -466,147 +474,134 @@ class Context:
         del keep
         return float(value[0]), dq
 
+    def _model_grads(self, m, unary, lbl_cmp, kernel, call):
+        """The optional gradient outputs of a backward / gradient entry on the model m: allocated as asked for, handed to
+        call(unary_grad, compat_grad, kernel_grad) as pointers (NULL: not asked for) and returned trimmed to the model's
+        counts, None where not asked for.  unary: False, True (N x C float32) or "params" (the C K doubles of a kept
+        logistic unary).  The doubles are never an empty array, whose pointer would say "not asked for"."""
+        sizes = (m.C * m.K, m.n_compat_params, m.n_kernel_params)
+        outs = [np.zeros(max(1, n), np.float64) if want else None for n, want in zip(sizes, (unary == "params", lbl_cmp, kernel))]
+        if unary and unary != "params":
+            outs[0] = np.empty((m.N, m.C), np.float32)
+        capi.check(self.h, call(*[_ptr(o) for o in outs]))
+        return tuple(o if o is None or o.ndim == 2 else o[:n] for o, n in zip(outs, sizes))
+
+    def _model_backward(self, fn, Q_all, d_mul_Q, unary, lbl_cmp, kernel):
+        """(unary_grad, compat_grad, kernel_grad) of a backward entry; kernel None: fn takes no kernel gradient."""
+        m = self._crf_model()
+        Q_all = np.ascontiguousarray(Q_all, np.float32)
+        dq = self._model_matrix(m, d_mul_Q)
+        assert Q_all.ndim == 3 and Q_all.shape[1:] == (m.N, m.C)
+        return self._model_grads(m, unary, lbl_cmp, kernel, lambda ug, cg, kg: fn(
+            self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), ug, cg, *(() if kernel is None else (kg,))))
+
+    def _model_gradient(self, fn, iterations, objective, unary, lbl_cmp, kernel, want_Q):
+        """(value, unary_grad, compat_grad, kernel_grad, Q[n]) of a gradient entry; kernel / want_Q None: fn has no such
+        argument."""
+        m = self._crf_model()
+        rec, keep = objective.record(m.N, m.C)
+        value = np.empty(1, np.float64)
+        Q = np.empty((m.N, m.C), np.float32) if want_Q else None
+        grads = self._model_grads(m, unary, lbl_cmp, kernel, lambda ug, cg, kg: fn(
+            self.h, iterations, C.byref(rec), _ptr(value), ug, cg, *(() if kernel is None else (kg,)), *(() if want_Q is None else (_ptr(Q),))))
+        del keep
+        return (float(value[0]),) + grads + (Q,)
+
     def crf_model_backward(self, Q_all, d_mul_Q, unary=True, lbl_cmp=True):
         """(unary_grad N x C float32, compat_grad float64) from Q[0 .. n] ((n + 1) x N x C) and d_mul_Q; a part not asked
         for is None."""
-        N, Cn, _ = self._crf_model_shape
-        Q_all = np.ascontiguousarray(Q_all, np.float32)
-        dq = self._crf_model_matrix(d_mul_Q)
-        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn)
-        ug = np.empty((N, Cn), np.float32) if unary else None
-        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
-        capi.check(self.h, self.L.rvseg_crf_model_backward(self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), _ptr(ug), _ptr(cg)))
-        return ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None)
+        return self._model_backward(self.L.rvseg_crf_model_backward, Q_all, d_mul_Q, bool(unary), lbl_cmp, None)[:2]
 
     def crf_model_gradient(self, iterations, objective, unary=True, lbl_cmp=True, want_Q=False):
         """rvseg_crf_model_gradient: (value, unary_grad, compat_grad, Q[n]); a part not asked for is None."""
-        N, Cn, _ = self._crf_model_shape
-        rec, keep = objective.record(N, Cn)
-        value = np.empty(1, np.float64)
-        ug = np.empty((N, Cn), np.float32) if unary else None
-        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
-        Q = np.empty((N, Cn), np.float32) if want_Q else None
-        capi.check(self.h, self.L.rvseg_crf_model_gradient(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(Q)))
-        del keep
-        return float(value[0]), ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None), Q
+        value, ug, cg, _, Q = self._model_gradient(self.L.rvseg_crf_model_gradient, iterations, objective, bool(unary), lbl_cmp, None,
+                                                   bool(want_Q))
+        return value, ug, cg, Q
 
     # ---- the kernel-parameter gradient (rvseg.h, "Kernel-parameter gradient") ----
     def crf_model_compat_apply(self, term, Q):
         """lbl_Q: the term's compatibility on Q (N x C) with no filter (pairwise.cpp:203-205)."""
-        Q = self._crf_model_matrix(Q)
-        out = np.empty_like(Q)
-        capi.check(self.h, self.L.rvseg_crf_model_compat_apply(self.h, term, _ptr(Q), _ptr(out)))
-        return out
+        return self._model_map(self.L.rvseg_crf_model_compat_apply, term, Q)
 
     def crf_model_lattice_gradient(self, term, a, b):
         """Permutohedral::gradient(a, b) of a term's lattice with respect to its features, N x d float32 (a, b: N x C)."""
-        a, b = self._crf_model_matrix(a), self._crf_model_matrix(b)
-        df = np.empty((a.shape[0], self._crf_model_dims[term] if 0 <= term < len(self._crf_model_dims) else 1), np.float32)
+        m = self._crf_model()
+        a, b = self._model_matrix(m, a), self._model_matrix(m, b)
+        df = np.empty((m.N, m.d[term] if 0 <= term < m.n_terms else 1), np.float32)   # (no such term: the library refuses)
         capi.check(self.h, self.L.rvseg_crf_model_lattice_gradient(self.h, term, _ptr(a), _ptr(b), _ptr(df)))
         return df
 
     def crf_model_kernel_gradient(self, term, a, b, want_fg=False):
         """DenseKernel::gradient(a, b) of a term: float64 (CONST 0, DIAG d, FULL d x d column-major values); want_fg: (that,
         featureGradient N x d float32)."""
-        a, b = self._crf_model_matrix(a), self._crf_model_matrix(b)
-        ok = 0 <= term < len(self._crf_model_dims)
-        n = self._crf_model_kparams[term] if ok else 0
+        m = self._crf_model()
+        a, b = self._model_matrix(m, a), self._model_matrix(m, b)
+        ok = 0 <= term < m.n_terms   # (no such term: the library refuses)
+        n = m.kernel_params[term] if ok else 0
         grad = np.zeros(max(1, n), np.float64)
-        fg = np.empty((a.shape[0], self._crf_model_dims[term] if ok else 1), np.float32) if want_fg else None
+        fg = np.empty((m.N, m.d[term] if ok else 1), np.float32) if want_fg else None
         capi.check(self.h, self.L.rvseg_crf_model_kernel_gradient(self.h, term, _ptr(a), _ptr(b), _ptr(grad), _ptr(fg)))
         return (grad[:n], fg) if want_fg else grad[:n]
 
     def crf_model_backward_kernel(self, Q_all, d_mul_Q, unary=True, lbl_cmp=True, kernel=True):
         """crf_model_backward with the kernel-parameter gradient (float64, the layout of kernelParameters()) as a third
         element; a part not asked for is None."""
-        N, Cn, _ = self._crf_model_shape
-        Q_all = np.ascontiguousarray(Q_all, np.float32)
-        dq = self._crf_model_matrix(d_mul_Q)
-        assert Q_all.ndim == 3 and Q_all.shape[1:] == (N, Cn)
-        ug = np.empty((N, Cn), np.float32) if unary else None
-        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
-        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
-        capi.check(self.h, self.L.rvseg_crf_model_backward_kernel(self.h, Q_all.shape[0] - 1, _ptr(Q_all), _ptr(dq), _ptr(ug), _ptr(cg),
-                                                                  _ptr(kg)))
-        return ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None), (kg[:sum(self._crf_model_kparams)] if kernel else None)
+        return self._model_backward(self.L.rvseg_crf_model_backward_kernel, Q_all, d_mul_Q, bool(unary), lbl_cmp, bool(kernel))
 
     def crf_model_gradient_kernel(self, iterations, objective, unary=True, lbl_cmp=True, kernel=True, want_Q=False):
         """rvseg_crf_model_gradient_kernel: (value, unary_grad, compat_grad, kernel_grad, Q[n]); a part not asked for is None."""
-        N, Cn, _ = self._crf_model_shape
-        rec, keep = objective.record(N, Cn)
-        value = np.empty(1, np.float64)
-        ug = np.empty((N, Cn), np.float32) if unary else None
-        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
-        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
-        Q = np.empty((N, Cn), np.float32) if want_Q else None
-        capi.check(self.h, self.L.rvseg_crf_model_gradient_kernel(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(kg),
-                                                                  _ptr(Q)))
-        del keep
-        return (float(value[0]), ug, (cg[:sum(self._crf_model_params)] if lbl_cmp else None),
-                (kg[:sum(self._crf_model_kparams)] if kernel else None), Q)
+        return self._model_gradient(self.L.rvseg_crf_model_gradient_kernel, iterations, objective, bool(unary), lbl_cmp, bool(kernel),
+                                    bool(want_Q))
 
     def crf_model_set_compat(self, term, compatibility):
         """Replaces the parameters of a term's compatibility (same kind) in the live model: no lattice build."""
-        Cn = self._crf_model_shape[1]
-        cp = np.ascontiguousarray(_compat(compatibility).array(Cn), np.float32)
+        cp = np.ascontiguousarray(_compat(compatibility).array(self._crf_model().C), np.float32)
         capi.check(self.h, self.L.rvseg_crf_model_set_compat(self.h, term, _ptr(cp)))
-        self._crf_model_params[term] = _compat(compatibility).parameters().shape[0]
 
     def crf_model_set_unary(self, unary, unary_is_energy=True):
-        U = self._crf_model_matrix(unary)
+        U = self._model_matrix(self._crf_model(), unary)
         capi.check(self.h, self.L.rvseg_crf_model_set_unary(self.h, _ptr(U), 1 if unary_is_energy else 0))
-        self._crf_model_K = 0
 
     # ---- the learning loop (rvseg.h, "The learning loop") ----
     def crf_model_set_kernel(self, term, params):
         """Rebuilds one DIAG / FULL term's lattice in the live model from the features it keeps; params None: the features
         as passed."""
+        m = self._crf_model()
         kp = None if params is None else np.ascontiguousarray(params, np.float32).reshape(-1)
-        counts = getattr(self, "_crf_model_kparams", [])
-        if kp is not None and 0 <= term < len(counts):
-            assert kp.shape == (counts[term],)
+        if kp is not None and 0 <= term < m.n_terms:   # (no such term: the library refuses)
+            assert kp.shape == (m.kernel_params[term],)
         capi.check(self.h, self.L.rvseg_crf_model_set_kernel(self.h, term, _ptr(kp)))
 
     def crf_model_set_logistic(self, L, f):
         """The live model keeps f (N x K) and its unary becomes the energy L f (L: C x K)."""
-        N, Cn, _ = self._crf_model_shape
+        m = self._crf_model()
         Lm = np.ascontiguousarray(L, np.float32)
         F = np.ascontiguousarray(f, np.float32)
-        assert Lm.ndim == 2 and Lm.shape[0] == Cn and F.shape == (N, Lm.shape[1])
+        assert Lm.ndim == 2 and Lm.shape[0] == m.C and F.shape == (m.N, Lm.shape[1])
         capi.check(self.h, self.L.rvseg_crf_model_set_logistic(self.h, Lm.shape[1], _ptr(Lm), _ptr(F)))
-        self._crf_model_K = Lm.shape[1]
 
     def crf_model_set_logistic_device(self, L, d_f, stream=0):
         Lm = np.ascontiguousarray(L, np.float32)
-        assert Lm.ndim == 2 and Lm.shape[0] == self._crf_model_shape[1]
+        assert Lm.ndim == 2 and Lm.shape[0] == self._crf_model().C
         self.crf_model_call_device("set_logistic", Lm.shape[1], Lm.ctypes.data, d_f, stream=stream)
 
     def crf_model_set_logistic_params(self, L):
+        m = self._crf_model()
         Lm = np.ascontiguousarray(L, np.float32)
-        K = getattr(self, "_crf_model_K", 0)
-        assert Lm.ndim == 2 and Lm.shape[0] == self._crf_model_shape[1] and (K == 0 or Lm.shape[1] == K)   # (K == 0: the library refuses)
+        assert Lm.ndim == 2 and Lm.shape[0] == m.C and (m.K == 0 or Lm.shape[1] == m.K)   # (K == 0: the library refuses)
         capi.check(self.h, self.L.rvseg_crf_model_set_logistic_params(self.h, _ptr(Lm)))
 
     def crf_model_gradient_params(self, iterations, objective, unary=True, lbl_cmp=True, kernel=True):
         """rvseg_crf_model_gradient_params: (value, unary_grad C K float64 column-major, compat_grad, kernel_grad); a part not
-        asked for is None.  K is the one every call of this class that sets or drops the kept logistic unary records."""
-        N, Cn, _ = self._crf_model_shape
-        K = self._crf_model_K
-        rec, keep = objective.record(N, Cn)
-        value = np.empty(1, np.float64)
-        ug = np.zeros(max(1, Cn * K), np.float64) if unary else None
-        cg = np.zeros(max(1, sum(self._crf_model_params)), np.float64) if lbl_cmp else None
-        kg = np.zeros(max(1, sum(self._crf_model_kparams)), np.float64) if kernel else None
-        capi.check(self.h, self.L.rvseg_crf_model_gradient_params(self.h, iterations, C.byref(rec), _ptr(value), _ptr(ug), _ptr(cg), _ptr(kg)))
-        del keep
-        return (float(value[0]), (ug[:Cn * K] if unary else None), (cg[:sum(self._crf_model_params)] if lbl_cmp else None),
-                (kg[:sum(self._crf_model_kparams)] if kernel else None))
+        asked for is None."""
+        return self._model_gradient(self.L.rvseg_crf_model_gradient_params, iterations, objective, "params" if unary else False, lbl_cmp,
+                                    bool(kernel), None)[:4]
 
     def crf_model_energy_gradient(self, iterations, objective, learn_mask, l2_norm, x):
         """rvseg_crf_model_energy_gradient: CRFEnergy::gradient on the live model -> (value, dx float32)."""
-        N, Cn, _ = self._crf_model_shape
+        m = self._crf_model()
         x = np.ascontiguousarray(x, np.float32).reshape(-1)
-        rec, keep = objective.record(N, Cn)
+        rec, keep = objective.record(m.N, m.C)
         value = np.empty(1, np.float64)
         dx = np.zeros(max(1, x.shape[0]), np.float32)
         capi.check(self.h, self.L.rvseg_crf_model_energy_gradient(self.h, iterations, C.byref(rec), int(learn_mask), C.c_float(float(l2_norm)),
@@ -635,10 +630,6 @@ class Context:
         fn = getattr(self.L, "rvseg_crf_model_%s_device" % name)
         conv = [C.c_void_p(a or None) if t is C.c_void_p else a for a, t in zip(args, fn.argtypes[1:])]
         capi.check(self.h, fn(self.h, *conv, C.c_void_p(stream or None)))
-        if name == "set_logistic":   # the one record of the kept logistic unary's K (crf_model_gradient_params sizes its buffer by it)
-            self._crf_model_K = int(args[0])
-        elif name == "set_unary":
-            self._crf_model_K = 0
 
     # ---- local-map fusion -------------------------------------------------------------------
     def fuse_posteriors(self, index_images, posteriors, class_counts, cloud_size):
@@ -1162,41 +1153,35 @@ class DenseCRF:
         return self.inference(n_iterations, capi.LABEL_ARGMAX)[1]
 
     # ---- stepwise inference, energies, KL divergence (densecrf.h:77-94) on a model the context keeps ----
+    # The context has one model and no handle for it: objects that share a context take turns, and anybody may set a model
+    # on it directly.  _model_serial is the serial crf_model_set returned for this object's model (0: none, or changed since).
     def _touch(self):
-        self._model_key = None
+        self._model_serial = 0
+
+    def _model_is_live(self):
+        serial = getattr(self, "_model_serial", 0)
+        return serial != 0 and self.ctx.crf_model_serial() == serial
 
     def _update_model(self, update):
         """A parameter change: in place on the context's live model when that model is this object's (no lattice build),
         else the model is set again by the next call that needs it."""
-        key = getattr(self, "_model_key", None)
-        if key is None or getattr(self.ctx, "_crf_model_owner", None) is not key:
-            return self._touch()
-        try:
+        if self._model_is_live():
             update()
-        except capi.RvsegError as e:
-            if e.status != capi.ERR_INVALID_ARG or "DenseCRF model" not in str(e):
-                raise
-            self._touch()   # another call replaced the model
+        else:
+            self._touch()
 
     def _with_model(self, call):
         """Runs call() on this CRF's model: set lazily, again after any add* / set*Parameters, and again when the context
-        reports that another call replaced it."""
-        key = getattr(self, "_model_key", None)
-        for attempt in range(2):
-            if key is None or getattr(self.ctx, "_crf_model_owner", None) is not key:
-                key = self._model_key = object()
-                if self.logistic is not None:   # the model computes L f itself and keeps f
-                    self.ctx.crf_model_set(np.zeros((self.N, self.M), np.float32), [tuple(k) for k in self.kernels])
-                    self.ctx.crf_model_set_logistic(*self.logistic)
-                else:
-                    self.ctx.crf_model_set(self._unary_energy(), [tuple(k) for k in self.kernels])
-                self.ctx._crf_model_owner = key
-            try:
-                return call()
-            except capi.RvsegError as e:
-                if attempt or e.status != capi.ERR_INVALID_ARG or "DenseCRF model" not in str(e):
-                    raise
-                key = None
+        keeps another model or none."""
+        if not self._model_is_live():
+            self._touch()   # (a failure below leaves no model of this object)
+            if self.logistic is not None:   # the model computes L f itself and keeps f
+                serial = self.ctx.crf_model_set(np.zeros((self.N, self.M), np.float32), [tuple(k) for k in self.kernels])
+                self.ctx.crf_model_set_logistic(*self.logistic)
+            else:
+                serial = self.ctx.crf_model_set(self._unary_energy(), [tuple(k) for k in self.kernels])
+            self._model_serial = serial
+        return call()
 
     def startInference(self):  # densecrf.cpp:178-186
         return self._with_model(self.ctx.crf_model_start)
@@ -1239,20 +1224,14 @@ class DenseCRF:
         kernelParameters().  energy_grad: unary_grad is d value / d U (N x M) instead."""
         if self.logistic is not None and unary and not energy_grad:   # one call; C K doubles come back, not N x M floats
             value, ug, cg, kg = self._with_model(lambda: self.ctx.crf_model_gradient_params(n_iterations, objective, True, lbl_cmp, kernel))
-            out = (value, ug.astype(np.float32), (cg.astype(np.float32) if lbl_cmp else None))
-            return out + (kg.astype(np.float32),) if kernel else out
-        if kernel:
+        elif kernel:
             value, ug, cg, kg, _ = self._with_model(lambda: self.ctx.crf_model_gradient_kernel(n_iterations, objective, unary, lbl_cmp))
         else:
             value, ug, cg, _ = self._with_model(lambda: self.ctx.crf_model_gradient(n_iterations, objective, unary, lbl_cmp))
-        if unary and not energy_grad:
-            if self.logistic is None:
-                ug = np.zeros(0, np.float32)
-            else:
-                ug = self.ctx.crf_logistic_gradient(ug, self.logistic[1]).astype(np.float32)
+        if unary and not energy_grad:   # of unaryParameters(): none without a logistic unary
+            ug = np.zeros(0, np.float32) if self.logistic is None else ug.astype(np.float32)
         out = (value, ug, (cg.astype(np.float32) if lbl_cmp else None))
         return out + (kg.astype(np.float32),) if kernel else out
-
 
     def energy_gradient(self, n_iterations, objective, unary, pairwise, kernel, l2_norm, x):
         """CRFEnergy::gradient (dense_learning.cpp:60-84) as one rvseg_crf_model_energy_gradient: x becomes this object's

@@ -57,6 +57,11 @@ int main(int argc, char** argv) {
             std::vector<float> Q2 = crf.startInference();
             crf.stepInference(Q2);
             if (Q2 != Q1) throw std::runtime_error("the first object did not set its model again");
+            // a model that somebody sets on the context directly is not the object's either
+            if (rvseg_crf_model_set(ctx, N, C, 0, nullptr, U.data(), 1) != RVSEG_OK) throw std::runtime_error("rvseg_crf_model_set failed");
+            Q2 = crf.startInference();
+            crf.stepInference(Q2);
+            if (Q2 != Q1) throw std::runtime_error("the object computed on a model set behind its back");
             std::ofstream out(argv[2], std::ios::binary);
             put(out, Q1); put(out, Q); put(out, map); put(out, ue); put(out, pe);
             put(out, std::vector<double>{kl}); put(out, parts); put(out, trace); put(out, Qt);

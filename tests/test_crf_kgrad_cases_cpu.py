@@ -152,6 +152,10 @@ class _FakeCtx:
     def crf_model_set(self, U, terms):
         self.sets += 1
         self.terms = terms
+        return self.sets   # the serial of the new model
+
+    def crf_model_serial(self):
+        return self.sets
 
     def crf_model_set_compat(self, term, compatibility):
         pass

@@ -12,7 +12,7 @@ import crf_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODEL_SYMBOLS = ["rvseg_crf_model_" + n + sfx for n in ("set", "start", "step", "apply", "energy", "kl", "trace") for sfx in ("", "_device")]
+MODEL_SYMBOLS = ["rvseg_crf_model_" + n + sfx for n in ("set", "start", "step", "apply", "energy", "kl", "trace") for sfx in ("", "_device")] + ["rvseg_crf_model_info"]
 
 
 @pytest.mark.parametrize("specs", [
@@ -67,6 +67,8 @@ def test_model_calls_without_a_context_are_refused():
     assert L.rvseg_crf_model_start(None, None) == capi.ERR_INVALID_ARG
     assert L.rvseg_crf_model_set(None, 1, 1, 0, None, None, 1) == capi.ERR_INVALID_ARG
     assert L.rvseg_crf_model_kl_device(None, None, None, None) == capi.ERR_INVALID_ARG
+    info = capi.RvsegCrfModelInfo(serial=7, N=7)
+    assert L.rvseg_crf_model_info(None, ctypes.byref(info)) == capi.ERR_INVALID_ARG and (info.serial, info.N) == (0, 0)   # zeroed first
 
 
 def test_kl_entropy_at_the_clamp_by_hand(oracle):

@@ -152,7 +152,6 @@ def test_lifetime(gpu_ctx_factory, oracle):
     rng, U, terms = M.random_model(700, 400, C, specs)
     a, b = gpu_ctx_factory(), gpu_ctx_factory()
     with pytest.raises(capi.RvsegError) as e:
-        a._crf_model_shape = (400, C, 2)
         a.crf_model_start()
     assert e.value.status == capi.ERR_INVALID_ARG and "rvseg_crf_model_set" in str(e.value)
     _set(a, rv, U, terms)

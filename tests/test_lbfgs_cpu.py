@@ -49,7 +49,7 @@ def test_defaults_are_the_documented_ones():
     assert (p.m, p.epsilon, p.max_iterations, p.max_linesearch, p.ftol, p.min_step, p.max_step) == (6, 1e-5, 0, 20, 1e-4, 1e-20, 1e20)
     for name in ("rvseg_minimize_lbfgs", "rvseg_lbfgs_params_default", "rvseg_crf_model_set_kernel", "rvseg_crf_model_set_logistic",
                  "rvseg_crf_model_set_logistic_device", "rvseg_crf_model_set_logistic_params", "rvseg_crf_model_gradient_params",
-                 "rvseg_crf_model_gradient_params_device", "rvseg_crf_model_energy_gradient"):
+                 "rvseg_crf_model_gradient_params_device", "rvseg_crf_model_energy_gradient", "rvseg_crf_model_info"):
         assert name in capi.SYMBOLS and hasattr(capi.lib(), name), name
 
 
