@@ -591,10 +591,21 @@ csr_count_kernel(LatticeDev L, unsigned* __restrict__ bh, int wbpf, int mcap) {
 // chunk's entries of k, i.e. ascending point order again.  Neighbouring points share their simplex, so a chunk has
 // ~12-20 distinct vertices for 448 entries.  (One lane per ENTRY ranks ~10 distinct vertices per 64 entries; PMC: 438
 // vector instructions per 64 entries.)
+// Ranks and totals depend on the chunk's ids alone, not on the counters, so a chunk is done in two steps:
+//   rank     the loop over the distinct vertices leaves, per slot j of a lane, the rank of its entry (bits 0-7 of rt[j])
+//            and, in the slot with which the lane led its vertex, the vertex's total in the chunk (bits 8-15; 1 .. 64,
+//            0 elsewhere).  Ballots and registers only: neither LDS nor global memory is on this serial path.
+//   place    DP1 independent LDS reads of the counters my[lv[j]], DP1 stores at counter + rank, then every leader adds
+//            its total to its counter.  A vertex has exactly one leader per chunk, so no two lanes write one counter.
+// The LDS reads of a wave are issued before its LDS writes and the wave fence at the end of a chunk orders those writes
+// before the next chunk's reads.  The ids and weights of chunk c + 1 are loaded before chunk c is ranked, so a wave
+// waits for one memory round trip per wave-block, not per chunk; lanes past the wave-block's last point, and every lane
+// behind the last chunk, load the last point again (in bounds, unused).
 // NARROW (LatticeDev::ids16, DP1 == 7): the rows hold frame-local ids as uint16_t.
 template <int DP1, bool NARROW = false>
 __global__ void __launch_bounds__(256)
 csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int mcap) {
+    constexpr int RW = NARROW ? 4 : DP1;   // dwords of a row of ids as loaded
     const CsWaveBlock B = cs_wave_block(L, wbpf, mcap);
     if (B.outside) return;   // no block-wide barrier below
     const int lane = B.lane, frame = B.frame, f0 = B.f0, Mf = B.Mf;
@@ -606,26 +617,43 @@ csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int 
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     const int p0 = (int)B.p0, p1 = (int)B.p1;
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (int pc = p0; pc < p1; pc += 64) {
+    auto point = [&](int pc) {   // this lane's point of the chunk at pc, clamped to the wave-block's last
         const int p = pc + lane;
-        const bool valid = p < p1;
-        const size_t gp = (size_t)frame * L.N + (valid ? p : p1 - 1);
+        return (unsigned)frame * (unsigned)L.N + (unsigned)(p < p1 ? p : p1 - 1);   // below n_frames * N, like the entries' unsigned positions
+    };
+    auto fetch = [&](size_t gp, unsigned (&raw)[RW], float (&w)[DP1]) {
+        if constexpr (NARROW) load_ids16(L.offsets, gp, raw);
+        else load_row<DP1>(reinterpret_cast<const unsigned*>(L.offsets) + gp * DP1, raw);
+        load_row<DP1>(L.bary + gp * DP1, w);
+    };
+    unsigned raw_n[RW];
+    float w_n[DP1];
+    unsigned gp_n = point(p0);
+    fetch(gp_n, raw_n, w_n);
+    for (int pc = p0; pc < p1; pc += 64) {
+        const bool valid = pc + lane < p1;
+        const unsigned gp = gp_n;
         int lv[DP1];
         float w[DP1];
         if constexpr (NARROW) {
-            unsigned raw[4];
-            load_ids16(L.offsets, gp, raw);
-            unpack_ids16(raw, gp, lv);
+            unpack_ids16(raw_n, gp, lv);
         } else {
-            load_row<DP1>(L.offsets + gp * DP1, lv);
+#pragma unroll
+            for (int j = 0; j < DP1; j++) lv[j] = (int)raw_n[j];
         }
-        load_row<DP1>(L.bary + gp * DP1, w);
+#pragma unroll
+        for (int j = 0; j < DP1; j++) w[j] = w_n[j];
+        gp_n = point(pc + 64);
+        fetch(gp_n, raw_n, w_n);   // the next chunk travels while this one is ranked
 #pragma unroll
         for (int j = 0; j < DP1; j++) {
             if (!NARROW) lv[j] -= f0;
             lv[j] = lv[j] < Mf ? lv[j] : Mf - 1;   // overflow case (flagged elsewhere): stay in bounds
             lv[j] = lv[j] < 0 ? 0 : lv[j];
         }
+        unsigned rt[DP1];
+#pragma unroll
+        for (int j = 0; j < DP1; j++) rt[j] = 0u;
         unsigned pend = valid ? (1u << DP1) - 1u : 0u;
 #pragma unroll
         for (int j = 0; j < DP1; j++) {
@@ -637,21 +665,36 @@ csr_scatter_kernel(LatticeDev L, const unsigned* __restrict__ bh, int wbpf, int 
                 // slots below j are already empty for every lane; a vertex handled in an earlier pass
                 // was removed from all slots then, so it cannot come up again in this chunk
                 unsigned long long all = 0ull;
-                float wsel = 0.0f;
-                bool hit = false;
+                unsigned hit = 0u;
 #pragma unroll
                 for (int jj = j; jj < DP1; jj++) {
                     const bool same = ((pend >> jj) & 1u) && lv[jj] == k;
                     all |= __ballot(same);
-                    if (same) { wsel = w[jj]; hit = true; pend &= ~(1u << jj); }
+                    if (same) hit |= 1u << jj;
                 }
-                const unsigned b = my[k];
-                if (hit) {
-                    const unsigned pos = b + (unsigned)__popcll(all & lt);
-                    if (pos < n_entries_total) L.csr_pw[pos] = make_uint2((unsigned)gp, __float_as_uint(wsel));
+                const unsigned r = (unsigned)__popcll(all & lt);
+#pragma unroll
+                for (int jj = j; jj < DP1; jj++) {
+                    if ((hit >> jj) & 1u) rt[jj] = r;
                 }
-                if (lane == leader) my[k] = b + (unsigned)__popcll(all);
+                pend &= ~hit;
+                if (lane == leader) rt[j] |= (unsigned)__popcll(all) << 8;
             }
+        }
+        unsigned base[DP1];
+#pragma unroll
+        for (int j = 0; j < DP1; j++) base[j] = my[lv[j]];
+        if (valid) {
+#pragma unroll
+            for (int j = 0; j < DP1; j++) {
+                const unsigned pos = base[j] + (rt[j] & 0xFFu);
+                if (pos < n_entries_total) L.csr_pw[pos] = make_uint2(gp, __float_as_uint(w[j]));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DP1; j++) {
+            const unsigned total = rt[j] >> 8;
+            if (total) my[lv[j]] = base[j] + total;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
