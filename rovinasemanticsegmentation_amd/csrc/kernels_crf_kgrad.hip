@@ -67,15 +67,7 @@ point_rank_kernel(LatticeDev L, const float* __restrict__ feat, unsigned* __rest
 
 void launch_point_ranks(const LatticeDev& L, const float* feat, unsigned* ranks, hipStream_t s) {
     const dim3 grid((unsigned)((L.N + 255) / 256)), block(256);
-    switch (L.d) {
-        case 1: point_rank_kernel<1><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        case 2: point_rank_kernel<2><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        case 3: point_rank_kernel<3><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        case 4: point_rank_kernel<4><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        case 5: point_rank_kernel<5><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        case 6: point_rank_kernel<6><<<grid, block, 0, s>>>(L, feat, ranks); break;
-        default: point_rank_kernel<7><<<grid, block, 0, s>>>(L, feat, ranks); break;
-    }
+    with_dimension(L.d, [&](auto dim) { point_rank_kernel<decltype(dim)::value><<<grid, block, 0, s>>>(L, feat, ranks); });
     RV_LAUNCHED("point_rank_kernel");
 }
 
@@ -141,7 +133,7 @@ slice_gradient_kernel(LatticeDev L, int C, const float* __restrict__ values, flo
 
 void launch_slice_gradient(const LatticeDev& L, int C, const float* values, const float* x, const unsigned* ranks, int dir, long long n_points,
                            float* df, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d)) / (L.d + 1);   // permutohedral.cpp:628
+    const float alpha = lattice_alpha(L.d) / (L.d + 1);   // permutohedral.cpp:628
     slice_gradient_kernel<<<dim3((unsigned)kl_blocks(C, n_points)), dim3(KL_THREADS), 0, s>>>(L, C, values, alpha, x, ranks, dir, n_points, df);
     RV_LAUNCHED("slice_gradient_kernel");
 }

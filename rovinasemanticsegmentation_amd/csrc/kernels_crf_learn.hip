@@ -370,7 +370,7 @@ void launch_add_rows(bool first, const float* t, float* acc, long long total, hi
 
 void launch_compat_grad(const LatticeDev& L, int C, bool seq, const float* values, bool post, int compat, const float* b, long long n_points,
                         double* partials, double* out, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const float alpha = lattice_alpha(L.d);
     const int po = post ? 1 : 0;
     if (compat == RVSEG_COMPAT_MATRIX) {
         const int blocks = learn_pair_blocks(C, C, n_points);

@@ -124,7 +124,7 @@ kl_term_kernel(LatticeDev L, int C, const float* __restrict__ values, float alph
 
 void launch_kl_term(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
                     const float* Q, long long n_points, double* partial, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const float alpha = lattice_alpha(L.d);
     const dim3 grid((unsigned)kl_blocks(C, n_points)), block(KL_THREADS);
     if (seq) kl_term_kernel<true><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, Q, n_points, partial);
     else kl_term_kernel<false><<<grid, block, 0, s>>>(L, C, values, alpha, post ? 1 : 0, matrix ? 1 : 0, compat, Q, n_points, partial);

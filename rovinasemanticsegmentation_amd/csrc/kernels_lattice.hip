@@ -303,22 +303,6 @@ lattice_points_kernel(LatticeDev L, FeatureSource fs, int n_chunks) {
   }
 }
 
-// The one statement of which dimensions are instantiated: calls f with d as a compile-time constant.  The API entry
-// points take no other d (RVSEG_ERR_INVALID_ARG), so a LatticeDev never carries one.
-template <class F>
-static void with_dimension(int d, F&& f) {
-    switch (d) {
-        case 1: f(std::integral_constant<int, 1>()); break;
-        case 2: f(std::integral_constant<int, 2>()); break;
-        case 3: f(std::integral_constant<int, 3>()); break;
-        case 4: f(std::integral_constant<int, 4>()); break;
-        case 5: f(std::integral_constant<int, 5>()); break;
-        case 6: f(std::integral_constant<int, 6>()); break;
-        case 7: f(std::integral_constant<int, 7>()); break;
-        default: break;   // rejected at the API
-    }
-}
-
 void launch_lattice_points(const LatticeDev& L, const FeatureSource& fs, hipStream_t s) {
     const long long total = (long long)L.Npad * L.n_frames;
     // chunks per block: as many as leave >= 1024 blocks (a single frame or a cloud is a latency case: 150 blocks of

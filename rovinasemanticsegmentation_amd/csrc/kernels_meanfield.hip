@@ -176,34 +176,33 @@ slice_norm_kernel(LatticeDev L, const float* __restrict__ values, float alpha, f
 
 void launch_slice(const LatticeDev& L, int C, bool seq, int out_mode, const float* values, float neg_w, float* out,
                   long long n_points, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));  // permutohedral.cpp:571
-    if (seq && out_mode == 1 && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
+    const float alpha = lattice_alpha(L.d);  // permutohedral.cpp:571
+    if (seq && (out_mode == 1 || out_mode == 3) && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
         const dim3 g1((unsigned)((n_points + 255) / 256)), b1(256);
-        if (L.d == 6 && L.ids16) slice_norm_kernel<7, false, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else if (L.d == 6) slice_norm_kernel<7><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else if (L.d == 5) slice_norm_kernel<6><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else slice_norm_kernel<3><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        RV_LAUNCHED("slice_norm_kernel");
-        return;
-    }
-    if (seq && out_mode == 3 && C == 1 && (L.d == 6 || L.d == 5 || L.d == 2)) {
-        const dim3 g1((unsigned)((n_points + 255) / 256)), b1(256);
-        if (L.d == 6 && L.ids16) slice_norm_kernel<7, true, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else if (L.d == 6) slice_norm_kernel<7, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else if (L.d == 5) slice_norm_kernel<6, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
-        else slice_norm_kernel<3, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        auto norm = [&](auto recip) {
+            constexpr bool RECIP = decltype(recip)::value;
+            if (L.d == 6 && L.ids16) slice_norm_kernel<7, RECIP, true><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+            else if (L.d == 6) slice_norm_kernel<7, RECIP><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+            else if (L.d == 5) slice_norm_kernel<6, RECIP><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+            else slice_norm_kernel<3, RECIP><<<g1, b1, 0, s>>>(L, values, alpha, out, n_points);
+        };
+        if (out_mode == 3) norm(std::bool_constant<true>()); else norm(std::bool_constant<false>());
         RV_LAUNCHED("slice_norm_kernel");
         return;
     }
     const long long total = n_points * C;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define RV_SLICE(SEQ, OM) slice_kernel<SEQ, OM><<<grid, block, 0, s>>>(L, C, values, alpha, neg_w, out, n_points)
-    if (seq) {
-        if (out_mode == 0) RV_SLICE(true, 0); else if (out_mode == 1) RV_SLICE(true, 1); else if (out_mode == 3) RV_SLICE(true, 3); else RV_SLICE(true, 2);
-    } else {
-        if (out_mode == 0) RV_SLICE(false, 0); else if (out_mode == 1) RV_SLICE(false, 1); else if (out_mode == 3) RV_SLICE(false, 3); else RV_SLICE(false, 2);
-    }
-#undef RV_SLICE
+    auto slice = [&](auto seq_c) {
+        constexpr bool SEQ = decltype(seq_c)::value;
+        auto mode = [&](auto om) { slice_kernel<SEQ, decltype(om)::value><<<grid, block, 0, s>>>(L, C, values, alpha, neg_w, out, n_points); };
+        switch (out_mode) {
+            case 0: mode(std::integral_constant<int, 0>()); break;
+            case 1: mode(std::integral_constant<int, 1>()); break;
+            case 3: mode(std::integral_constant<int, 3>()); break;
+            default: mode(std::integral_constant<int, 2>()); break;
+        }
+    };
+    if (seq) slice(std::bool_constant<true>()); else slice(std::bool_constant<false>());
     RV_LAUNCHED("slice_kernel");
 }
 
@@ -447,7 +446,7 @@ bool mf_fused_supported(int C) { return with_fused_class_count(C, [](auto) {}); 
 // returns false when C has no fused instantiation (the caller then runs the unfused kernels)
 bool launch_mf_update(const LatticeDev& L, int C, const float* values, const MfTerm& term, const ValueView& unary, bool negate,
                       const ValueView& Q, bool scale_out, const MfLabels& lab, hipStream_t s) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const float alpha = lattice_alpha(L.d);
     const int bpf = (L.N + MF_PTS - 1) / MF_PTS;
     const dim3 grid((unsigned)(bpf * L.n_frames)), block(256);
     const int neg = negate ? 1 : 0, so = scale_out ? 1 : 0;
@@ -562,7 +561,7 @@ term_update_kernel(LatticeDev L, int C, const float* __restrict__ values, float 
 
 void launch_term_update(const LatticeDev& L, int C, bool seq, const float* values, bool post, bool matrix, const float* compat,
                         float* tmp, long long n_points, hipStream_t s, bool assign) {
-    const float alpha = 1.0f / (1 + powf(2, (float)-L.d));
+    const float alpha = lattice_alpha(L.d);
     const int PB = TERM_THREADS / C;
     long long blocks = (n_points + PB - 1) / PB;
     if (blocks > 4096) blocks = 4096;   // each block loads the compatibility once
@@ -607,15 +606,7 @@ kernel_params_kernel(const float* __restrict__ f, int N, int kind, KernelParams 
 
 void launch_kernel_params(const float* f, int N, int d, int kind, const KernelParams& kp, float* out, hipStream_t s) {
     const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    switch (d) {
-        case 1: kernel_params_kernel<1><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        case 2: kernel_params_kernel<2><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        case 3: kernel_params_kernel<3><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        case 4: kernel_params_kernel<4><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        case 5: kernel_params_kernel<5><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        case 6: kernel_params_kernel<6><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-        default: kernel_params_kernel<7><<<grid, block, 0, s>>>(f, N, kind, kp, out); break;
-    }
+    with_dimension(d, [&](auto dim) { kernel_params_kernel<decltype(dim)::value><<<grid, block, 0, s>>>(f, N, kind, kp, out); });
     RV_LAUNCHED("kernel_params_kernel");
 }
 

@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "rvseg_internal.h"
 
@@ -50,6 +52,26 @@ struct LatticeDev {
     int wbpf;                    // wave-blocks per frame
     float* norm;                 // per point, pairwise.cpp:55-56
 };
+
+// The one statement of which dimensions are instantiated: calls f with d as a compile-time constant.  The API entry
+// points take no other d (RVSEG_ERR_INVALID_ARG), so a LatticeDev never carries one: for a d outside 1 .. 7 every launcher
+// that goes through here launches nothing.
+template <class F>
+void with_dimension(int d, F&& f) {
+    switch (d) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        case 6: f(std::integral_constant<int, 6>()); break;
+        case 7: f(std::integral_constant<int, 7>()); break;
+        default: break;   // rejected at the API
+    }
+}
+
+// the constant every slice multiplies by (permutohedral.cpp:512 / :571; the slicing gradient, :628, divides it by d + 1)
+inline float lattice_alpha(int d) { return 1.0f / (1 + powf(2, (float)-d)); }
 
 // Vertex ids [x, y) of a frame, each clamped to `bound`: the per-vertex arrays' capacity or the vertices that exist.  (The
 // clamp only binds after a flagged hash overflow; it keeps every access in bounds.)
