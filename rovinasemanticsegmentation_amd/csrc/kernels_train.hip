@@ -1,0 +1,461 @@
+// Kernels of the forest trainer (rvseg_train.hip holds the learner and describes the design; train_device.h the
+// interface).  Per level of a tree:
+//   * byte-valued features: one pass adds every bootstrap example into its node's (feature, value, class) histogram with
+//     global atomics; one block per (node, feature) prefix-sums the 256 values in LDS and evaluates every cut between two
+//     occupied values;
+//   * other features: the (node, feature, value) triples of the level are sorted once (64-bit radix sort), one wave per
+//     (node, feature) segment walks its values in ascending order with running class counts (wave scans) and evaluates
+//     every cut between two values at least 1e-6 apart (learning.cpp:578-585);
+//   * one pass routes every example with the evaluator's own rule `x[f] < threshold`.
+// The objective is the oracle's definition 2 (oracle/rvseg_oracle_train.c), in its operation order.
+#include <cstring>   // rocPRIM's headers call memset without including it
+
+#include <rocprim/rocprim.hpp>
+
+#include "rvseg_internal.h"
+#include "train_device.h"
+
+namespace rvseg {
+namespace {
+
+// order-preserving map float -> uint (sort keys)
+__device__ __forceinline__ unsigned f2ord(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f_dev(unsigned o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// fastlog2 (fastlog.h:47-58) and ENTROPY(p) = -(p) * fastlog2(p) (learning.cpp:13), in the oracle's operation order
+__device__ __forceinline__ float fastlog2_dev(float x) {
+    const unsigned vi = __float_as_uint(x);
+    const float mx = __uint_as_float((vi & 0x007FFFFFu) | 0x3f000000u);
+    float y = (float)vi;
+    y = y * 1.1920928955078125e-7f;
+    const float a = 1.498030302f * mx;
+    const float den = 0.3520887068f + mx;
+    const float b = 1.72587999f / den;
+    float r = y - 124.22551499f;
+    r = r - a;
+    r = r - b;
+    return r;
+}
+__device__ __forceinline__ float entropy_term(float p) { return (-p) * fastlog2_dev(p); }
+
+// initEntropies (learning.cpp:279-293) from integer counts: -ENTROPY(mass) + sum of ENTROPY(count) over the classes
+// with a non-zero count, ascending
+__device__ __forceinline__ float hist_entropy(const unsigned (&cnt)[TR_CMAX]) {
+    unsigned mass = 0;
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) mass += cnt[c];
+    float total = -entropy_term((float)mass);
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) {
+        if (cnt[c] == 0) continue;
+        total += entropy_term((float)cnt[c]);
+    }
+    return total;
+}
+
+// ---- the rules every kernel shares ----------------------------------------------------------------------------
+// a feature's value lives in Xb when it is byte-valued, else in its row of Xf
+__device__ __forceinline__ float feature_value(const TrainSetView& v, int f, size_t i) {
+    const int nb = v.nb_index[f];
+    return nb < 0 ? (float)v.Xb[(size_t)f * v.stride + i] : v.Xf[(size_t)nb * v.stride + i];
+}
+__device__ __forceinline__ void store_feature(const TrainSetView& v, int f, size_t i, float x) {
+    const int nb = v.nb_index[f];
+    if (nb < 0) v.Xb[(size_t)f * v.stride + i] = (uint8_t)(int)x;
+    else v.Xf[(size_t)nb * v.stride + i] = x;
+}
+// the slot that example i is searched in and its multiplicity; -1 when i is past the set, was not drawn by the bootstrap
+// or sits in a node outside the batch
+__device__ __forceinline__ int slot_of_example(const TrainSetView& v, const LevelSlots& sl, int i, unsigned* weight) {
+    if (i >= v.P) return -1;
+    *weight = sl.w[i];
+    if (!*weight) return -1;
+    return sl.slot_of[sl.node_of[i]];
+}
+
+// ---- data set construction ------------------------------------------------------------------------------------
+// per feature: is every value an integer in [0, 255]?
+__global__ void __launch_bounds__(256)
+train_feature_stats_kernel(const float* __restrict__ X, int P, int D, int* __restrict__ not_byte, int* __restrict__ not_finite) {
+    const int f = blockIdx.x;
+    int bad = 0, inf = 0;
+    for (int i = threadIdx.x; i < P; i += 256) {
+        const float v = X[(size_t)i * D + f];
+        if (!(v >= 0.f && v <= 255.f && v == floorf(v))) bad = 1;
+        if (!(fabsf(v) <= 3.4e38f)) inf = 1;
+    }
+    if (bad) not_byte[f] = 1;
+    if (inf) not_finite[0] = 1;
+}
+
+__global__ void __launch_bounds__(256)
+train_pack_kernel(const float* __restrict__ X, TrainSetView v) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long long)v.P * v.D) return;
+    const int f = (int)(gid / v.P), i = (int)(gid - (long long)f * v.P);
+    store_feature(v, f, (size_t)i, X[(size_t)i * v.D + f]);
+}
+
+// frames -> training set (src/train.cpp:115-147): flags[p] = the stride-grid point has valid depth (extract's mask) and
+// every label layer is >= 0 there (ExtractType::WITH_POSITIVE_LABEL, feature_extractor.h:93-121)
+__global__ void __launch_bounds__(256)
+train_frame_flags_kernel(FrameGeom g, const uint8_t* __restrict__ valid, const int8_t* __restrict__ labels, int L, int* __restrict__ flags) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= g.lw * g.lh) return;
+    const int ly = p / g.lw, lx = p - ly * g.lw;
+    const size_t px = (size_t)(ly * g.stride) * g.W + (size_t)lx * g.stride;
+    int ok = valid[p] ? 1 : 0;
+    for (int l = 0; l < L; l++) ok = ok && labels[(size_t)l * g.W * g.H + px] >= 0;
+    flags[p] = ok;
+}
+
+__global__ void __launch_bounds__(256)
+train_frame_scatter_kernel(FrameGeom g, const int* __restrict__ flags, const int* __restrict__ offs, const float* __restrict__ dump,
+                           const int8_t* __restrict__ labels, size_t base, TrainSetView v) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int Pg = g.lw * g.lh;
+    if (gid >= (long long)Pg * (g.D + v.L)) return;
+    const int col = (int)(gid / Pg), p = (int)(gid - (long long)col * Pg);
+    if (!flags[p]) return;
+    const size_t dst = base + (size_t)offs[p];
+    if (col < g.D) {
+        store_feature(v, col, dst, dump[(size_t)p * g.D + col]);
+    } else {
+        const int l = col - g.D;
+        const int ly = p / g.lw, lx = p - ly * g.lw;
+        v.lab[(size_t)l * v.stride + dst] = labels[(size_t)l * g.W * g.H + (size_t)(ly * g.stride) * g.W + (size_t)lx * g.stride];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+train_class_count_kernel(TrainSetView v, unsigned* __restrict__ cnt) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long long)v.P * v.L) return;
+    const int l = (int)(gid / v.P), i = (int)(gid - (long long)l * v.P);
+    atomicAdd(&cnt[l * TR_CMAX + v.lab[(size_t)l * v.stride + i]], 1u);
+}
+
+// ---- per tree -------------------------------------------------------------------------------------------------
+// bootstrap: P draws with replacement as multiplicities (DataStorage::bootstrapmulti, data.cpp:325-349)
+__global__ void __launch_bounds__(256)
+train_bootstrap_kernel(int P, uint64_t kt, unsigned* __restrict__ w) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= P) return;
+    atomicAdd(&w[draw64(kt, 0x100000000ull + (uint64_t)n) % (uint64_t)P], 1u);
+}
+
+// class totals of every slot (the node's histogram, learning.cpp:508-516)
+__global__ void __launch_bounds__(256)
+train_slot_totals_kernel(TrainSetView v, LevelSlots sl, unsigned* __restrict__ totals) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    unsigned wi;
+    const int slot = slot_of_example(v, sl, i, &wi);
+    if (slot < 0) return;
+    atomicAdd(&totals[slot * TR_CMAX + v.lab[(size_t)sl.slot_layer[slot] * v.stride + i]], wi);
+}
+
+// hist[slot][k][value][class] += multiplicity, byte features of the slot only
+__global__ void __launch_bounds__(256)
+train_hist_kernel(TrainSetView v, LevelSlots sl, unsigned* __restrict__ hist) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    unsigned wi;
+    const int slot = slot_of_example(v, sl, i, &wi);
+    if (slot < 0) return;
+    const int c = v.lab[(size_t)sl.slot_layer[slot] * v.stride + i];
+    for (int k = 0; k < sl.K; k++) {
+        const int f = sl.slot_feat[slot * sl.K + k];
+        if (v.nb_index[f] >= 0) continue;
+        const int b = v.Xb[(size_t)f * v.stride + i];
+        atomicAdd(&hist[(((size_t)slot * sl.K + k) * TR_BINS + b) * TR_CMAX + c], wi);
+    }
+}
+
+// byte features: one block per (slot, feature), one thread per value
+__global__ void __launch_bounds__(TR_BINS)
+train_best_cut_kernel(TrainSetView ts, LevelSlots sl, const unsigned* __restrict__ hist, CutResult* __restrict__ out) {
+    __shared__ unsigned h[TR_CMAX][TR_BINS + 1];   // inclusive prefix over the values, per class
+    __shared__ unsigned occ[TR_BINS];
+    __shared__ float best_obj[TR_BINS];
+    __shared__ int best_bin[TR_BINS];
+    if (ts.nb_index[sl.slot_feat[blockIdx.x]] >= 0) return;   // a float feature: the sorted path writes this record
+    const int b = threadIdx.x;
+    const unsigned* src = hist + ((size_t)blockIdx.x * TR_BINS + b) * TR_CMAX;
+    unsigned row = 0;
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) { const unsigned v = src[c]; h[c][b] = v; row += v; }
+    occ[b] = row;
+    __syncthreads();
+    for (int off = 1; off < TR_BINS; off <<= 1) {   // inclusive scan over the 256 values, all classes at once
+        unsigned add[TR_CMAX];
+#pragma unroll
+        for (int c = 0; c < TR_CMAX; c++) add[c] = b >= off ? h[c][b - off] : 0u;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < TR_CMAX; c++) h[c][b] += add[c];
+        __syncthreads();
+    }
+    int nb = -1;   // next occupied value above b
+    if (row) for (int q = b + 1; q < TR_BINS; q++) if (occ[q]) { nb = q; break; }
+    float obj = 1e35f;
+    unsigned lm = 0, rm = 0;
+    if (nb >= 0) {
+        unsigned l[TR_CMAX], r[TR_CMAX];
+#pragma unroll
+        for (int c = 0; c < TR_CMAX; c++) { l[c] = h[c][b]; r[c] = h[c][TR_BINS - 1] - l[c]; lm += l[c]; rm += r[c]; }
+        const float el = hist_entropy(l), er = hist_entropy(r);
+        obj = el + er;
+    }
+    best_obj[b] = obj;
+    best_bin[b] = nb >= 0 ? b : TR_BINS;
+    __syncthreads();
+    for (int s = TR_BINS / 2; s > 0; s >>= 1) {   // arg min; the lower value wins a tie (strict '<' in ascending order, :589)
+        if (b < s) {
+            const float o2 = best_obj[b + s];
+            const int b2 = best_bin[b + s];
+            if (o2 < best_obj[b] || (o2 == best_obj[b] && b2 < best_bin[b])) { best_obj[b] = o2; best_bin[b] = b2; }
+        }
+        __syncthreads();
+    }
+    if (best_bin[0] == TR_BINS) {
+        if (b == 0) { CutResult r{}; r.objective = 1e35f; r.valid = 0; out[blockIdx.x] = r; }
+        return;
+    }
+    if (b == best_bin[0]) {
+        CutResult r;
+        r.objective = obj;
+        r.left_value = (float)b;
+        r.right_value = (float)nb;
+        r.left_mass = lm;
+        r.right_mass = rm;
+        r.valid = 1;
+        out[blockIdx.x] = r;
+    }
+}
+
+// float features: (segment << 32 | ordered value, example) for every (bootstrap example, sampled float feature of its node)
+__global__ void __launch_bounds__(256)
+train_nb_emit_kernel(TrainSetView v, LevelSlots sl, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals,
+                     unsigned* __restrict__ counter, unsigned capacity) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    unsigned wi;
+    const int slot = slot_of_example(v, sl, i, &wi);
+    if (slot < 0) return;
+    for (int k = 0; k < sl.K; k++) {
+        const int nb = v.nb_index[sl.slot_feat[slot * sl.K + k]];
+        if (nb < 0) continue;
+        const unsigned pos = atomicAdd(counter, 1u);
+        if (pos >= capacity) continue;   // cannot happen: capacity = P * min(K, n_nb)
+        keys[pos] = ((unsigned long long)(unsigned)(slot * sl.K + k) << 32) | f2ord(v.Xf[(size_t)nb * v.stride + i]);
+        vals[pos] = (unsigned)i;
+    }
+}
+
+// one wave per (slot, feature) segment of the sorted triples: ascending values, running class counts, every cut between
+// two values at least 1e-6 apart (learning.cpp:560-604)
+__global__ void __launch_bounds__(64)
+train_nb_scan_kernel(TrainSetView ts, LevelSlots sl, unsigned n_items, const unsigned long long* __restrict__ keys,
+                     const unsigned* __restrict__ vals, const unsigned* __restrict__ totals, CutResult* __restrict__ out) {
+    const unsigned seg = blockIdx.x;
+    if (ts.nb_index[sl.slot_feat[seg]] < 0) return;   // a byte feature: the histogram path writes this record
+    const int lane = threadIdx.x;
+    const int slot = (int)(seg / (unsigned)sl.K);
+    // the segment's range in the sorted array (keys are unique per segment in their high word)
+    auto lower = [&](unsigned long long key) {
+        unsigned lo = 0, hi = n_items;
+        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
+        return lo;
+    };
+    const unsigned beg = lower((unsigned long long)seg << 32), end = lower((unsigned long long)(seg + 1u) << 32);
+    unsigned tot[TR_CMAX], run[TR_CMAX];
+    unsigned mass = 0;
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) { tot[c] = totals[slot * TR_CMAX + c]; run[c] = 0; mass += tot[c]; }
+    const int* labl = ts.lab + (size_t)sl.slot_layer[slot] * ts.stride;
+    float best_obj = 1e35f, best_lv = 0.f, best_rv = 0.f;
+    unsigned best_lm = 0;
+    float prev_last = 0.f;   // value of the last element of the previous chunk
+    for (unsigned base = beg; base < end; base += 64) {
+        const unsigned m = base + (unsigned)lane;
+        const bool in = m < end;
+        float v = 0.f;
+        int cls = -1;
+        unsigned wt = 0;
+        if (in) {
+            v = ord2f_dev((unsigned)(keys[m] & 0xFFFFFFFFull));
+            const unsigned e = vals[m];
+            cls = labl[e];
+            wt = sl.w[e];
+        }
+        float vprev = __shfl_up(v, 1, 64);
+        if (lane == 0) vprev = prev_last;
+        // class counts of the elements before this lane's element
+        unsigned left[TR_CMAX];
+        unsigned lm = 0;
+#pragma unroll
+        for (int c = 0; c < TR_CMAX; c++) {
+            const unsigned x = cls == c ? wt : 0u;
+            unsigned incl = x;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            left[c] = run[c] + incl - x;
+            lm += left[c];
+            run[c] += __shfl(incl, 63, 64);
+        }
+        float obj = 1e35f;
+        if (in && m > beg && !((v - vprev) < 1e-6f)) {
+            unsigned right[TR_CMAX];
+#pragma unroll
+            for (int c = 0; c < TR_CMAX; c++) right[c] = tot[c] - left[c];
+            const float el = hist_entropy(left), er = hist_entropy(right);
+            obj = el + er;
+        }
+        // the chunk's minimum, lowest position first; strict '<' against the running best
+        float o = obj;
+        int who = lane;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float o2 = __shfl_xor(o, off, 64);
+            const int w2 = __shfl_xor(who, off, 64);
+            if (o2 < o || (o2 == o && w2 < who)) { o = o2; who = w2; }
+        }
+        if (o < best_obj) {
+            best_obj = o;
+            best_lv = __shfl(vprev, who, 64);
+            best_rv = __shfl(v, who, 64);
+            best_lm = __shfl(lm, who, 64);
+        }
+        const unsigned last = (end - base < 64u ? end - base : 64u) - 1u;
+        prev_last = __shfl(v, (int)last, 64);
+    }
+    if (lane == 0) {
+        CutResult r;
+        r.objective = best_obj;
+        r.left_value = best_lv;
+        r.right_value = best_rv;
+        r.left_mass = best_lm;
+        r.right_mass = mass - best_lm;
+        r.valid = best_obj < 1e35f ? 1 : 0;
+        out[seg] = r;
+    }
+}
+
+// findLeafNode's rule on the freshly split nodes: every example (bootstrap or not) moves to a child
+__global__ void __launch_bounds__(256)
+train_route_kernel(TrainSetView v, int* __restrict__ node_of, const int* __restrict__ split_feat, const float* __restrict__ split_thr,
+                   const int* __restrict__ split_left) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= v.P) return;
+    const int node = node_of[i];
+    const int f = split_feat[node];
+    if (f < 0) return;
+    node_of[i] = feature_value(v, f, (size_t)i) < split_thr[node] ? split_left[node] : split_left[node] + 1;   // classifier.cpp:105
+}
+
+// integer leaf counts over ALL examples: cnt[node][layer][class]
+__global__ void __launch_bounds__(256)
+train_leaf_count_kernel(TrainSetView v, const int* __restrict__ node_of, unsigned* __restrict__ cnt) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long long)v.P * v.L) return;
+    const int l = (int)(gid / v.P), i = (int)(gid - (long long)l * v.P);
+    atomicAdd(&cnt[((size_t)node_of[i] * v.L + l) * TR_CMAX + v.lab[(size_t)l * v.stride + i]], 1u);
+}
+
+inline dim3 blocks_of(long long threads) { return dim3((unsigned)((threads + 255) / 256)); }
+
+}  // namespace
+
+void launch_train_feature_stats(const float* X, int P, int D, int* not_byte, int* not_finite, hipStream_t s) {
+    train_feature_stats_kernel<<<dim3((unsigned)D), dim3(256), 0, s>>>(X, P, D, not_byte, not_finite);
+    RV_LAUNCHED("train_feature_stats_kernel");
+}
+
+void launch_train_pack(const float* X, const TrainSetView& v, hipStream_t s) {
+    train_pack_kernel<<<blocks_of((long long)v.P * v.D), dim3(256), 0, s>>>(X, v);
+    RV_LAUNCHED("train_pack_kernel");
+}
+
+void launch_train_frame_flags(const FrameGeom& g, const uint8_t* valid, const int8_t* labels, int L, int* flags, hipStream_t s) {
+    train_frame_flags_kernel<<<blocks_of(g.lw * g.lh), dim3(256), 0, s>>>(g, valid, labels, L, flags);
+    RV_LAUNCHED("train_frame_flags_kernel");
+}
+
+void launch_train_frame_scatter(const FrameGeom& g, const int* flags, const int* offs, const float* dump, const int8_t* labels, size_t base,
+                                const TrainSetView& v, hipStream_t s) {
+    train_frame_scatter_kernel<<<blocks_of((long long)g.lw * g.lh * (g.D + v.L)), dim3(256), 0, s>>>(g, flags, offs, dump, labels, base, v);
+    RV_LAUNCHED("train_frame_scatter_kernel");
+}
+
+size_t train_scan_temp_bytes(size_t n) {
+    size_t bytes = 0;
+    (void)rocprim::exclusive_scan(nullptr, bytes, (const int*)nullptr, (int*)nullptr, 0, n, rocprim::plus<int>());
+    return bytes;
+}
+
+hipError_t launch_train_scan_offsets(void* temp, size_t temp_bytes, const int* flags, int* offs, size_t n, hipStream_t s) {
+    return rocprim::exclusive_scan(temp, temp_bytes, flags, offs, 0, n, rocprim::plus<int>(), s);
+}
+
+void launch_train_class_count(const TrainSetView& v, unsigned* cnt, hipStream_t s) {
+    train_class_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, cnt);
+    RV_LAUNCHED("train_class_count_kernel");
+}
+
+void launch_train_bootstrap(int P, uint64_t kt, unsigned* w, hipStream_t s) {
+    train_bootstrap_kernel<<<blocks_of(P), dim3(256), 0, s>>>(P, kt, w);
+    RV_LAUNCHED("train_bootstrap_kernel");
+}
+
+void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, unsigned* totals, unsigned* hist, CutResult* cuts,
+                               hipStream_t s) {
+    train_slot_totals_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, sl, totals);
+    RV_LAUNCHED("train_slot_totals_kernel");
+    train_hist_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, sl, hist);
+    RV_LAUNCHED("train_hist_kernel");
+    train_best_cut_kernel<<<dim3((unsigned)(S * sl.K)), dim3(TR_BINS), 0, s>>>(v, sl, hist, cuts);
+    RV_LAUNCHED("train_best_cut_kernel");
+}
+
+void launch_train_emit(const TrainSetView& v, const LevelSlots& sl, unsigned long long* keys, unsigned* vals, unsigned* counter,
+                       unsigned capacity, hipStream_t s) {
+    train_nb_emit_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, sl, keys, vals, counter, capacity);
+    RV_LAUNCHED("train_nb_emit_kernel");
+}
+
+size_t train_sort_temp_bytes(size_t n) {
+    size_t bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
+                                    (unsigned*)nullptr, n, 0, 64);
+    return bytes;
+}
+
+hipError_t launch_train_sort(void* temp, size_t temp_bytes, unsigned long long* keys_in, unsigned long long* keys_out, unsigned* vals_in,
+                             unsigned* vals_out, size_t n, unsigned end_bit, hipStream_t s) {
+    return rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, s);
+}
+
+void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, unsigned n_items, const unsigned long long* keys, const unsigned* vals,
+                       const unsigned* totals, CutResult* cuts, hipStream_t s) {
+    train_nb_scan_kernel<<<dim3((unsigned)(S * sl.K)), dim3(64), 0, s>>>(v, sl, n_items, keys, vals, totals, cuts);
+    RV_LAUNCHED("train_nb_scan_kernel");
+}
+
+void launch_train_route(const TrainSetView& v, int* node_of, const int* split_feat, const float* split_thr, const int* split_left,
+                        hipStream_t s) {
+    train_route_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, node_of, split_feat, split_thr, split_left);
+    RV_LAUNCHED("train_route_kernel");
+}
+
+void launch_train_leaf_count(const TrainSetView& v, const int* node_of, unsigned* cnt, hipStream_t s) {
+    train_leaf_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, node_of, cnt);
+    RV_LAUNCHED("train_leaf_count_kernel");
+}
+
+}  // namespace rvseg

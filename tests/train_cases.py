@@ -5,7 +5,7 @@
 A case is a dict: X (P, D) float32, labels (P, L) int32, cc (class counts), kw (training parameters) and, where a
 pin needs them, extra facts about how the data was built (`cut`, `sorted`, ...).
 
-The switches of csrc/rvseg_train.hip the recipes are built around:
+The switches of the trainer (csrc/rvseg_train.hip, train_host.h, kernels_train.hip) the recipes are built around:
   SLOT_BATCH = 1024   frontier nodes per batch of a level;  TR_CMAX = 16 classes per layer;  RVSEG_MAX_LAYERS = 8,
   at most 64 classes over all layers;  byte features (integers in [0, 255]: histograms) against float features
   (sorted, scanned by one wave in chunks of 64);  the 1e-6 cut rule;  the adjacent-floats threshold guard.
