@@ -186,6 +186,74 @@ rvseg_status rvseg_forest_info(const rvseg_ctx *ctx, int32_t *n_trees, int32_t *
  * (libforest classifier.cpp:166-208).  X: P x D host floats; out: P x sumC host floats. */
 rvseg_status rvseg_forest_eval(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, float *out);
 
+/* ---- boosted forest: replaces libf::BoostedRandomForest and BoostedRandomForestLearner (libforest
+ *      classifier.cpp:238-307, learning.cpp:1117-1234, classifiers.h:349-425): multiclass AdaBoost (SAMME) over decision
+ *      trees.  The model is T trees and one float weight per tree; classLogPosterior is a vector of C zeros to which, in
+ *      tree order, weight_t is added at the label tree t votes for (Classifier::classify: the first index with the
+ *      strictly greatest value of the leaf's single-label histogram).  multiClassLogPosterior is "not supported" there
+ *      and here.
+ *   Stream: int32 T, then per tree the weight and the tree.  BoostedRandomForest::write emits the weight first (:250-262),
+ *   ::read expects the tree first (:264-280): the reference cannot read its own files.  The caller names the order; it is
+ *   never guessed from the bytes. */
+typedef enum rvseg_boosted_order {
+    RVSEG_BOOSTED_WEIGHT_FIRST = 0,   /* what BoostedRandomForest::write produces (the default of the bindings) */
+    RVSEG_BOOSTED_TREE_FIRST = 1,     /* what BoostedRandomForest::read accepts                                */
+    RVSEG_BOOSTED_AS_LOADED = -1      /* the write calls only: the order the model was read in                 */
+} rvseg_boosted_order;
+/* Host-only validation, like rvseg_forest_check: its limits (64 trees, 64 classes, split features, child links), and
+ * every leaf carries a non-empty single-label histogram of one class count, and the stream ends with the last tree. */
+rvseg_status rvseg_boosted_check(const void *buf, size_t size, int32_t order, int32_t feature_length, int32_t *n_trees,
+                                 int32_t *n_nodes_total, int32_t *max_depth, char *err_out, size_t err_cap);
+/* Host-only: parse `buf` in in_order, serialise it in out_order.  Equal orders return the stream byte for byte. */
+rvseg_status rvseg_boosted_rewrite(const void *buf, size_t size, int32_t in_order, int32_t out_order, void *out,
+                                   size_t out_cap, size_t *size_out);
+/* Replaces BoostedRandomForest::read.  The model becomes the context's forest: rvseg_forest_eval, rvseg_forest_info and
+ * the single-layer frame path then return its vote sums (each leaf's device row is weight_t at its vote label and +0.0
+ * elsewhere; a weight is stored as w + 0.0f, so -0.0 votes like the reference's 0 + (-0.0)).  A context with
+ * params.multi_layer = 1 refuses it (RVSEG_ERR_INVALID_ARG) and keeps its previous model, as a stream that does not
+ * parse does. */
+rvseg_status rvseg_boosted_load(rvseg_ctx *ctx, const char *path, int32_t order);
+rvseg_status rvseg_boosted_load_mem(rvseg_ctx *ctx, const void *buf, size_t size, int32_t order);
+/* Replaces BoostedRandomForest::write: the loaded boosted model in `order`; a stream is written back byte for byte in
+ * the order it was read in (RVSEG_BOOSTED_AS_LOADED).  RVSEG_ERR_NO_FOREST when the context's forest is not a boosted
+ * one.  rvseg_forest_write and rvseg_forest_write_mem refuse a boosted model (RVSEG_ERR_INVALID_ARG). */
+rvseg_status rvseg_boosted_write(const rvseg_ctx *ctx, const char *path, int32_t order);
+rvseg_status rvseg_boosted_write_mem(const rvseg_ctx *ctx, int32_t order, void *out, size_t out_cap, size_t *size_out);
+/* Replaces BoostedRandomForest::getWeights: the loaded model's tree weights as the stream holds them.  weights_out (cap floats) may be
+ * NULL to query *n_out; order_out (optional): the order the model was read in. */
+rvseg_status rvseg_boosted_weights(const rvseg_ctx *ctx, float *weights_out, int32_t cap, int32_t *n_out,
+                                   int32_t *order_out);
+/* Replaces BoostedRandomForestLearner::learn (learning.cpp:1120-1234) with a DecisionTreeLearner of tp's settings;
+ * tp->num_trees is the number of boosting rounds (1..64).  X: P x D host floats, labels: P class indices of one layer
+ * with C classes (2..16).  Per round: P draws from the example weights pick the tree's data set, the tree is learnt on
+ * it (rvseg_forest_train's learner; tp->use_bootstrap is applied on top of the resample), error = the fp32 sum in
+ * example order of the weights of the examples of the whole set the tree misclassifies, alpha = logf((1 - error) /
+ * error) + log(C - 1) narrowed to float, misclassified weights are multiplied by expf(alpha), every weight is divided
+ * by their fp32 sum.  All of it runs on the device but alpha.  The reference draws from std::random_device and has no
+ * guard for degenerate rounds; here (build-owned definitions):
+ *   1. round key kb = mix64(seed ^ mix64(0x626F6F73 + round)); draw n is u_n = (float)(draw64(kb, n) >> 40) * 2^-24;
+ *      the round's tree is tree 0 of a one-tree forest trained with seed draw64(kb, 2^40) on the resample;
+ *   2. u picks the first index i with !(u > cumsum[i]) (binary search), clamped to P - 1;
+ *   3. error, the total and cumsum are fp32 sums in example order, bit for bit the serial chain;
+ *   4. error == 0: the tree is added with alpha = +inf and boosting ends; error >= 1, or a total that is not positive
+ *      and finite: the tree is not added and boosting ends; otherwise the reference's arithmetic, negative alpha included.
+ * Writes the WEIGHT_FIRST stream (what the reference's write would).  The model is also kept on the context, apart
+ * from any model it has loaded: when out_cap is too small (RVSEG_ERR_INVALID_ARG, *size_out = needed size) or out is
+ * NULL, fetch it with rvseg_boosted_train_result, in either order, instead of training again.  errors_out / alphas_out (optional, tp->num_trees floats): per round that grew a tree;
+ * rounds_out (optional): trees kept -- 0 when the first round stops without a tree; the stream is then the empty
+ * ensemble's four bytes, which no loader accepts. */
+rvseg_status rvseg_boosted_train(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t C,
+                                 const rvseg_train_params *tp, void *out, size_t out_cap, size_t *size_out,
+                                 float *errors_out, float *alphas_out, int32_t *rounds_out);
+rvseg_status rvseg_boosted_train_result(const rvseg_ctx *ctx, int32_t order, void *out, size_t out_cap, size_t *size_out);
+/* The boosting round's kernels on caller-supplied weights, for parity tests (in the spirit of rvseg_extract_features):
+ * error = serial sum of weights[n] over miss[n] != 0 (miss may be NULL: none); weights[n] *= exp_alpha for those;
+ * weights /= their serial sum; cumsum; idx[n] = the draw of definitions 1 and 2 under round key `key`.  weights must
+ * be >= +0 (neither NaN nor -0.0, whose first running sum the chain would turn into +0.0) with a positive finite sum, else RVSEG_ERR_INVALID_ARG.  Every output is optional. */
+rvseg_status rvseg_boosted_resample(rvseg_ctx *ctx, const float *weights, const uint8_t *miss, int32_t N, float exp_alpha,
+                                    uint64_t key, float *error_out, float *weights_out, float *cumsum_out,
+                                    int32_t *idx_out);
+
 /* ---- features: replaces Features::FeatureExtractor::extract, NO_LABEL branch
  *      (include/feature_extractor.h:41-291).  Host buffers, one frame.  feat_out: capacity
  *      (H/stride+1)*(W/stride+1) x D floats; x_v / y_v same capacity.  Exists for parity tests:

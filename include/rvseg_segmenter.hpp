@@ -1381,5 +1381,59 @@ protected:
     std::vector<float> initial_u_param_, initial_lbl_param_, initial_knl_param_;
 };
 
+// libf::BoostedRandomForest (classifiers.h:349-425) over a context with multi_layer = 0: T trees and a weight per tree.
+// The stream's order is named by the caller (rvseg_boosted_order): the reference's write puts the weight before the tree,
+// its read expects it after.
+class BoostedRandomForest {
+public:
+    explicit BoostedRandomForest(rvseg_ctx* ctx) : ctx_(ctx) {}
+    void read(const std::string& path, rvseg_boosted_order order = RVSEG_BOOSTED_WEIGHT_FIRST) { check(rvseg_boosted_load(ctx_, path.c_str(), order)); }   // classifier.cpp:264
+    void read(const void* buf, size_t size, rvseg_boosted_order order = RVSEG_BOOSTED_WEIGHT_FIRST) { check(rvseg_boosted_load_mem(ctx_, buf, size, order)); }
+    void write(const std::string& path, rvseg_boosted_order order = RVSEG_BOOSTED_AS_LOADED) const { check(rvseg_boosted_write(ctx_, path.c_str(), order)); }   // :250
+    std::vector<uint8_t> write(rvseg_boosted_order order = RVSEG_BOOSTED_AS_LOADED) const {
+        size_t size = 0;
+        check(rvseg_boosted_write_mem(ctx_, order, nullptr, 0, &size));
+        std::vector<uint8_t> out(size);
+        check(rvseg_boosted_write_mem(ctx_, order, out.data(), out.size(), &size));
+        return out;
+    }
+    int getSize() const {
+        int32_t n = 0;
+        check(rvseg_boosted_weights(ctx_, nullptr, 0, &n, nullptr));
+        return n;
+    }
+    std::vector<float> getWeights() const {
+        std::vector<float> w((size_t)getSize());
+        int32_t n = 0;
+        check(rvseg_boosted_weights(ctx_, w.data(), (int32_t)w.size(), &n, nullptr));
+        return w;
+    }
+    // the weighted votes per class of P points (X: P x D), P x C (:283-302)
+    std::vector<float> classLogPosterior(const float* X, int P, int D) const {
+        int32_t n_layers = 0, cc[RVSEG_MAX_LAYERS];
+        check(rvseg_forest_info(ctx_, nullptr, nullptr, nullptr, &n_layers, cc));
+        std::vector<float> out((size_t)P * cc[0]);
+        check(rvseg_forest_eval(ctx_, X, P, D, out.data()));
+        return out;
+    }
+    // Classifier::classify (:29-51): the first class with the strictly greatest vote sum
+    std::vector<int> classify(const float* X, int P, int D) const {
+        const std::vector<float> post = classLogPosterior(X, P, D);
+        const size_t C = P ? post.size() / (size_t)P : 0;
+        std::vector<int> label((size_t)P, 0);
+        for (int p = 0; p < P; p++) {
+            float prob = post[(size_t)p * C];
+            for (size_t c = 1; c < C; c++)
+                if (post[(size_t)p * C + c] > prob) { label[(size_t)p] = (int)c; prob = post[(size_t)p * C + c]; }
+        }
+        return label;
+    }
+private:
+    void check(rvseg_status st) const {
+        if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx_));
+    }
+    rvseg_ctx* ctx_;
+};
+
 }  // namespace rvseg
 #endif

@@ -7,14 +7,14 @@ without a GPU `Context()` raises.
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import projection_matrix  # noqa: F401
-from .segmenter import (Context, DenseCRF, Evaluator, FeatureExtractor, LocalMapStore, RandomForest,  # noqa: F401
+from .segmenter import (BoostedRandomForest, Context, DenseCRF, Evaluator, FeatureExtractor, LocalMapStore, RandomForest,  # noqa: F401
                         RgbLabelConversion, Segmenter, PottsCompatibility, DiagonalCompatibility, MatrixCompatibility,
                         CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL, NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER,
                         NORMALIZE_SYMMETRIC, LogLikelihood, Hamming, IntersectionOverUnion, CRFEnergy, CRFKernelEnergy,
                         minimizeLBFGS, numericGradient, gradCheck)
 from . import synthetic  # noqa: F401
 
-__all__ = ["capi", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
+__all__ = ["capi", "BoostedRandomForest", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
            "RgbLabelConversion", "Evaluator", "PottsCompatibility", "DiagonalCompatibility", "MatrixCompatibility",
            "CONST_KERNEL", "DIAG_KERNEL", "FULL_KERNEL", "NO_NORMALIZATION", "NORMALIZE_BEFORE", "NORMALIZE_AFTER",
            "NORMALIZE_SYMMETRIC", "projection_matrix", "LogLikelihood", "Hamming", "IntersectionOverUnion",

@@ -64,7 +64,10 @@ SYMBOLS = [
     "rvseg_crf_model_set_logistic_params", "rvseg_crf_model_gradient_params", "rvseg_crf_model_gradient_params_device",
     "rvseg_crf_model_energy_gradient", "rvseg_lbfgs_params_default", "rvseg_minimize_lbfgs",
     "rvseg_crf_model_info",
+    "rvseg_boosted_check", "rvseg_boosted_rewrite", "rvseg_boosted_load", "rvseg_boosted_load_mem", "rvseg_boosted_write",
+    "rvseg_boosted_write_mem", "rvseg_boosted_weights", "rvseg_boosted_train", "rvseg_boosted_train_result", "rvseg_boosted_resample",
 ]
+BOOSTED_WEIGHT_FIRST, BOOSTED_TREE_FIRST, BOOSTED_AS_LOADED = 0, 1, -1   # rvseg_boosted_order
 # rvseg_lbfgs_status
 LBFGS_CONVERGED, LBFGS_MAX_ITERATIONS, LBFGS_STOPPED, LBFGS_LINESEARCH_FAILED, LBFGS_NOT_FINITE, LBFGS_BAD_ARGUMENTS = 0, 1, 2, 3, -1, -2
 LEARN_UNARY, LEARN_PAIRWISE, LEARN_KERNEL = 1, 2, 4   # learn_mask of rvseg_crf_model_energy_gradient
@@ -210,6 +213,17 @@ def lib():
     L.rvseg_forest_train_result.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rvseg_forest_train_frames.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(RvsegTrainParams), vp, C.c_size_t,
                                             C.POINTER(C.c_size_t), C.POINTER(i32)]
+    L.rvseg_boosted_check.argtypes = [vp, C.c_size_t, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.c_char_p, C.c_size_t]
+    L.rvseg_boosted_rewrite.argtypes = [vp, C.c_size_t, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rvseg_boosted_load.argtypes = [vp, C.c_char_p, i32]
+    L.rvseg_boosted_load_mem.argtypes = [vp, vp, C.c_size_t, i32]
+    L.rvseg_boosted_write.argtypes = [vp, C.c_char_p, i32]
+    L.rvseg_boosted_write_mem.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rvseg_boosted_weights.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.rvseg_boosted_train.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(RvsegTrainParams), vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                      vp, vp, C.POINTER(i32)]
+    L.rvseg_boosted_train_result.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rvseg_boosted_resample.argtypes = [vp, vp, vp, i32, f32, C.c_uint64, C.POINTER(f32), vp, vp, vp]
     L.rvseg_host_register.argtypes = [vp, C.c_size_t]
     L.rvseg_host_unregister.argtypes = [vp]
     L.rvseg_comm_unique_id.argtypes = [vp]
@@ -346,6 +360,30 @@ def forest_rewrite(blob):
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     out = C.create_string_buffer(size.value)
     st = lib().rvseg_forest_rewrite(blob, len(blob), out, size.value, C.byref(size))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    return out.raw[:size.value]
+
+
+def boosted_check(blob, order=BOOSTED_WEIGHT_FIRST, feature_length=0):
+    """Host-only validation of a boosted-forest stream read in `order` (no GPU): returns (status, message, info)."""
+    blob = bytes(blob)
+    nt, nn, md = C.c_int32(), C.c_int32(), C.c_int32()
+    err = C.create_string_buffer(512)
+    st = lib().rvseg_boosted_check(blob, len(blob), order, feature_length, C.byref(nt), C.byref(nn), C.byref(md), err, 512)
+    return st, err.value.decode("utf-8", "replace"), {"n_trees": nt.value, "n_nodes": nn.value, "max_depth": md.value}
+
+
+def boosted_rewrite(blob, in_order=BOOSTED_WEIGHT_FIRST, out_order=None):
+    """Host-only: parse a boosted-forest stream in in_order and serialise it in out_order (default: the same)."""
+    blob = bytes(blob)
+    out_order = in_order if out_order is None else out_order
+    size = C.c_size_t()
+    st = lib().rvseg_boosted_rewrite(blob, len(blob), in_order, out_order, None, 0, C.byref(size))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    out = C.create_string_buffer(size.value)
+    st = lib().rvseg_boosted_rewrite(blob, len(blob), in_order, out_order, out, size.value, C.byref(size))
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return out.raw[:size.value]

@@ -40,6 +40,11 @@ constexpr int kMaxClasses = 64;
 
 struct ForestModel {
     std::vector<RawTree> raw;             // the stream's own trees (what serialize_forest writes)
+    // libf::BoostedRandomForest (classifiers.h:349-425): one weight per tree, as the stream holds it, and the order the
+    // stream was read in (RVSEG_BOOSTED_*).  single_hist then holds the vote rows, see parse_boosted.
+    bool boosted = false;
+    int boosted_order = 0;
+    std::vector<float> tree_weights;
     int n_trees = 0;
     int max_depth = 0;                    // longest root->leaf path, in edges
     std::vector<int32_t> roots;           // per tree: index of its root in `nodes`
@@ -57,6 +62,26 @@ struct ForestModel {
 // segfaults on a model/config mismatch, README.md:30).  Returns false and sets `err`.
 bool parse_forest(const void* buf, size_t size, int feature_length, ForestModel& out,
                   std::string& err);
+
+// Classifier::classify's rule on one histogram (classifier.cpp:29-51): the first index with the strictly greatest value.
+// A NaN never wins and, in h[0], is never beaten.
+inline int vote_label(const float* h, int C) {
+    int label = 0;
+    float prob = h[0];
+    for (int i = 1; i < C; i++)
+        if (h[i] > prob) { label = i; prob = h[i]; }
+    return label;
+}
+
+// The boosted stream (BoostedRandomForest::write / read, classifier.cpp:250-280): int32 T, then per tree the weight and
+// the tree.  `write` emits the weight first, `read` expects the tree first -- the reference cannot read its own files --
+// so the caller names the order (RVSEG_BOOSTED_WEIGHT_FIRST / RVSEG_BOOSTED_TREE_FIRST); it is never guessed from the
+// bytes.  The limits of parse_forest apply; in addition every leaf must carry a non-empty single-label histogram with the
+// same class count, and the stream must end with the last tree.  The model's single_hist rows become the vote rows:
+// weight_t at the leaf's vote label and +0.0 elsewhere, so that the evaluator of an ordinary forest returns
+// BoostedRandomForest::classLogPosterior (:283-302).
+bool parse_boosted(const void* buf, size_t size, int feature_length, int order, ForestModel& out, std::string& err);
+std::vector<uint8_t> serialize_boosted(const ForestModel& m, int order);
 
 // Serialises a forest in the reference's format (RandomForest::write, classifier.cpp:210-220;
 // DecisionTree::write :144-152; writeBinary io.h:34-108): the trees of `m.raw`, node for node.

@@ -7,6 +7,10 @@
 //     (node, feature) segment walks its values in ascending order with running class counts (wave scans) and evaluates
 //     every cut between two values at least 1e-6 apart (learning.cpp:578-585);
 //   * one pass routes every example with the evaluator's own rule `x[f] < threshold`.
+// Per boosting round (BoostedRandomForestLearner::learn, learning.cpp:1162-1217): the weighted resample as a binary search
+// per draw, the misclassification flags, and the three fp32 sums the reference accumulates in example order -- error, the
+// weights' total, their running sum -- each by one wave that adds a tile of 256 values at once where that is exact
+// (ordered_tile) and one after the other where it is not, so the result is the serial chain's bit for bit.
 // The objective is the oracle's definition 2 (oracle/rvseg_oracle_train.c), in its operation order.
 #include <cstring>   // rocPRIM's headers call memset without including it
 
@@ -132,21 +136,25 @@ train_frame_scatter_kernel(FrameGeom g, const int* __restrict__ flags, const int
     }
 }
 
+// mult: how often the tree's data set holds example i (a boosting round's resample), or null: once
 __global__ void __launch_bounds__(256)
-train_class_count_kernel(TrainSetView v, unsigned* __restrict__ cnt) {
+train_class_count_kernel(TrainSetView v, const unsigned* __restrict__ mult, unsigned* __restrict__ cnt) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= (long long)v.P * v.L) return;
     const int l = (int)(gid / v.P), i = (int)(gid - (long long)l * v.P);
-    atomicAdd(&cnt[l * TR_CMAX + v.lab[(size_t)l * v.stride + i]], 1u);
+    const unsigned m = mult ? mult[i] : 1u;
+    if (m) atomicAdd(&cnt[l * TR_CMAX + v.lab[(size_t)l * v.stride + i]], m);
 }
 
 // ---- per tree -------------------------------------------------------------------------------------------------
 // bootstrap: P draws with replacement as multiplicities (DataStorage::bootstrapmulti, data.cpp:325-349)
+// (positions: the examples at the P positions of a resampled data set, or null: position n is example n)
 __global__ void __launch_bounds__(256)
-train_bootstrap_kernel(int P, uint64_t kt, unsigned* __restrict__ w) {
+train_bootstrap_kernel(int P, uint64_t kt, const int* __restrict__ positions, unsigned* __restrict__ w) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= P) return;
-    atomicAdd(&w[draw64(kt, 0x100000000ull + (uint64_t)n) % (uint64_t)P], 1u);
+    const uint64_t pos = draw64(kt, 0x100000000ull + (uint64_t)n) % (uint64_t)P;
+    atomicAdd(&w[positions ? (uint64_t)positions[pos] : pos], 1u);
 }
 
 // class totals of every slot (the node's histogram, learning.cpp:508-516)
@@ -361,11 +369,182 @@ train_route_kernel(TrainSetView v, int* __restrict__ node_of, const int* __restr
 
 // integer leaf counts over ALL examples: cnt[node][layer][class]
 __global__ void __launch_bounds__(256)
-train_leaf_count_kernel(TrainSetView v, const int* __restrict__ node_of, unsigned* __restrict__ cnt) {
+train_leaf_count_kernel(TrainSetView v, const int* __restrict__ node_of, const unsigned* __restrict__ mult, unsigned* __restrict__ cnt) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= (long long)v.P * v.L) return;
     const int l = (int)(gid / v.P), i = (int)(gid - (long long)l * v.P);
-    atomicAdd(&cnt[((size_t)node_of[i] * v.L + l) * TR_CMAX + v.lab[(size_t)l * v.stride + i]], 1u);
+    const unsigned m = mult ? mult[i] : 1u;
+    if (m) atomicAdd(&cnt[((size_t)node_of[i] * v.L + l) * TR_CMAX + v.lab[(size_t)l * v.stride + i]], m);
+}
+
+// ---- per boosting round ---------------------------------------------------------------------------------------
+// the weighted resample (learning.cpp:1166-1175): draw n picks the first index with !(u > cumsum[index]).  cumsum does
+// not decrease (the weights are >= 0), so the binary search finds what the reference's linear scan finds; the index is
+// clamped to N - 1, where the reference reads past the array when rounding leaves cumsum[N-1] < u.
+__global__ void __launch_bounds__(256)
+train_boost_resample_kernel(const float* __restrict__ cumsum, int N, uint64_t kb, int* __restrict__ idx, unsigned* __restrict__ mult) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const float u = boost_uniform(kb, (uint64_t)n);
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (u > cumsum[mid]) lo = mid + 1; else hi = mid;
+    }
+    if (lo > N - 1) lo = N - 1;
+    idx[n] = lo;
+    if (mult) atomicAdd(&mult[lo], 1u);
+}
+
+// miss[n] = the tree's vote for example n of the whole set is not its label (:1182-1194); vote_label: per node of the
+// growing tree, the label its leaf histogram votes for
+__global__ void __launch_bounds__(256)
+train_vote_flags_kernel(const int* __restrict__ node_of, const int* __restrict__ vote_label, const int* __restrict__ label, int N,
+                        uint8_t* __restrict__ miss) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    miss[n] = vote_label[node_of[n]] != label[n] ? 1 : 0;
+}
+
+// The ordered sums, without the serial chain (the idea of the normaliser's splat, kernels_splat.hip / DESIGN section 4,
+// restated here with the running sums kept).  The chain only LOOKS sequential: while the running sum s stays in one
+// binade [2^E, 2^(E+1)) every partial sum is a multiple of u = 2^(E-23), and adding w >= 0 rounds s + w to the nearest
+// multiple of u -- in units of u: n -> n + rne(w / u), unless w / u lies exactly half-way between two integers (then the
+// direction depends on the parity of n).  So for a tile of addends none of which is negative or such a tie, and which
+// does not leave the binade,
+//       s after addend i = (n + sum_{j <= i} rne(w_j / u)) * u,
+// sums of integers below 2^24: exact in fp32 in ANY order, so a wave prefix sum gives all of them at once.  One wave
+// takes a tile of 256 addends, lane l the addends 4 l .. 4 l + 3; a tile that breaks a condition (s not yet a positive
+// normal number, a binade crossing, a tie) is added the reference's way, one addend after the other.  Either way the
+// result is the serial chain's bit for bit.  Addends past the end and examples that are not misses count as +0.0, which
+// leaves the sum as it is: s starts at +0.0 and only takes addends >= +0, so it is never -0.0.
+constexpr int SUM_K = 4;        // addends per lane and tile
+constexpr int SUM_DEPTH = 8;    // tiles in flight: the next 8 load while these are added
+
+__device__ __forceinline__ float wave_inclusive_sum(float v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float t = __shfl_up(v, off, 64);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+// s + (the tile), rounded after every addition; KEEP: out[h] = the running sum after this lane's addend h
+template <bool KEEP>
+__device__ __forceinline__ void ordered_tile(float& s, const float (&w)[SUM_K], float (&out)[SUM_K], int lane) {
+    bool any = false;
+#pragma unroll
+    for (int h = 0; h < SUM_K; h++) any |= w[h] != 0.0f;
+    if (__builtin_amdgcn_ballot_w64(any) == 0ull) {      // nothing to add (x + 0.0 = x)
+#pragma unroll
+        for (int h = 0; h < SUM_K; h++) out[h] = s;
+        return;
+    }
+    const unsigned sb = __float_as_uint(s);
+    const unsigned e = (sb >> 23) & 0xffu;                              // biased exponent of the running sum
+    const bool s_ok = ((int)sb > 0) & (e >= 24u) & (e <= 253u);        // positive, normal, scale factors representable
+    const float scale = __uint_as_float((277u - (s_ok ? e : 127u)) << 23);      // 2^(23 - E) = 1 / u
+    const float unscale = __uint_as_float(((s_ok ? e : 127u) - 23u) << 23);     // u
+    float pre[SUM_K];
+    float rs = 0.0f;
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < SUM_K; h++) {
+        const float k = w[h] * scale;                 // exact (a power of two), or +inf
+        const float r = __builtin_rintf(k);           // round half to even, like the addition itself
+        bad |= !(w[h] >= 0.0f) | !(k < 16777216.0f) | (__builtin_fabsf(k - r) == 0.5f);
+        rs += r;                                      // (sums of integers: exact while below 2^24; rounding is monotone)
+        pre[h] = rs;
+    }
+    const float incl = wave_inclusive_sum(rs, lane);
+    const float n0 = s * scale;
+    const float total = __shfl(incl, 63, 64);
+    if (s_ok & (__builtin_amdgcn_ballot_w64(bad) == 0ull) & (n0 + total < 16777216.0f)) {
+        const float before = n0 + (incl - rs);
+#pragma unroll
+        for (int h = 0; h < SUM_K; h++) out[h] = (before + pre[h]) * unscale;
+        s = (n0 + total) * unscale;
+        return;
+    }
+#pragma unroll 1
+    for (int i = 0; i < 64; i++)                      // the reference's way
+#pragma unroll
+        for (int h = 0; h < SUM_K; h++) {
+            s = s + __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(w[h]), i));
+            if (KEEP && lane == i) out[h] = s;
+        }
+}
+
+// MODE 0: error = sum of w[n] over the misses (:1181-1194)
+// MODE 1: w[n] *= scale for the misses, total = sum of w[n] (:1202-1210)
+// MODE 2: w[n] /= total, cumsum[n] = w[n] + cumsum[n-1] (:1211-1217)
+template <int MODE>
+__global__ void __launch_bounds__(64)
+train_boost_sum_kernel(float* __restrict__ w, const uint8_t* __restrict__ miss, long long N, float scale, float* __restrict__ sum,
+                       float* __restrict__ cumsum) {
+    const int lane = threadIdx.x;
+    const float total = MODE == 2 ? *sum : 0.f;
+    // this lane's 4 addends of the tile that starts at n0 (a multiple of 256), with the mode's update of w written back
+    auto load = [&](long long n0, float (&x)[SUM_K]) {
+        const long long n = n0 + (long long)lane * SUM_K;
+        unsigned char m[SUM_K] = {0, 0, 0, 0};
+        if (n + SUM_K <= N) {
+            const float4 v = *reinterpret_cast<const float4*>(w + n);
+            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+            if (MODE != 2) {
+                const unsigned mm = *reinterpret_cast<const unsigned*>(miss + n);
+#pragma unroll
+                for (int h = 0; h < SUM_K; h++) m[h] = (unsigned char)((mm >> (8 * h)) & 0xffu);
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < SUM_K; h++) {
+                x[h] = n + h < N ? w[n + h] : 0.f;
+                if (MODE != 2) m[h] = n + h < N ? miss[n + h] : (unsigned char)0;
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < SUM_K; h++) {
+            if (MODE == 0) x[h] = m[h] ? x[h] : 0.f;
+            if (MODE == 1) x[h] = m[h] ? x[h] * scale : x[h];
+            if (MODE == 2) x[h] = n + h < N ? x[h] / total : 0.f;
+        }
+        if (MODE != 0) {
+            if (n + SUM_K <= N) {
+                *reinterpret_cast<float4*>(w + n) = make_float4(x[0], x[1], x[2], x[3]);
+            } else {
+#pragma unroll
+                for (int h = 0; h < SUM_K; h++) if (n + h < N) w[n + h] = x[h];
+            }
+        }
+    };
+    constexpr long long TILE = 64 * SUM_K;
+    float cur[SUM_DEPTH][SUM_K], next[SUM_DEPTH][SUM_K];
+#pragma unroll
+    for (int j = 0; j < SUM_DEPTH; j++) load((long long)j * TILE, cur[j]);
+    float run = 0.f;
+    for (long long base = 0; base < N; base += SUM_DEPTH * TILE) {
+#pragma unroll
+        for (int j = 0; j < SUM_DEPTH; j++) load(base + (long long)(SUM_DEPTH + j) * TILE, next[j]);
+#pragma unroll
+        for (int j = 0; j < SUM_DEPTH; j++) {
+            float out[SUM_K];
+            ordered_tile<MODE == 2>(run, cur[j], out, lane);
+            if (MODE == 2) {
+                const long long n = base + (long long)j * TILE + (long long)lane * SUM_K;
+                if (n + SUM_K <= N) {
+                    *reinterpret_cast<float4*>(cumsum + n) = make_float4(out[0], out[1], out[2], out[3]);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < SUM_K; h++) if (n + h < N) cumsum[n + h] = out[h];
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < SUM_K; h++) cur[j][h] = next[j][h];
+        }
+    }
+    if (MODE != 2 && lane == 0) *sum = run;
 }
 
 inline dim3 blocks_of(long long threads) { return dim3((unsigned)((threads + 255) / 256)); }
@@ -403,13 +582,13 @@ hipError_t launch_train_scan_offsets(void* temp, size_t temp_bytes, const int* f
     return rocprim::exclusive_scan(temp, temp_bytes, flags, offs, 0, n, rocprim::plus<int>(), s);
 }
 
-void launch_train_class_count(const TrainSetView& v, unsigned* cnt, hipStream_t s) {
-    train_class_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, cnt);
+void launch_train_class_count(const TrainSetView& v, const unsigned* mult, unsigned* cnt, hipStream_t s) {
+    train_class_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, mult, cnt);
     RV_LAUNCHED("train_class_count_kernel");
 }
 
-void launch_train_bootstrap(int P, uint64_t kt, unsigned* w, hipStream_t s) {
-    train_bootstrap_kernel<<<blocks_of(P), dim3(256), 0, s>>>(P, kt, w);
+void launch_train_bootstrap(int P, uint64_t kt, const int* positions, unsigned* w, hipStream_t s) {
+    train_bootstrap_kernel<<<blocks_of(P), dim3(256), 0, s>>>(P, kt, positions, w);
     RV_LAUNCHED("train_bootstrap_kernel");
 }
 
@@ -453,9 +632,34 @@ void launch_train_route(const TrainSetView& v, int* node_of, const int* split_fe
     RV_LAUNCHED("train_route_kernel");
 }
 
-void launch_train_leaf_count(const TrainSetView& v, const int* node_of, unsigned* cnt, hipStream_t s) {
-    train_leaf_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, node_of, cnt);
+void launch_train_leaf_count(const TrainSetView& v, const int* node_of, const unsigned* mult, unsigned* cnt, hipStream_t s) {
+    train_leaf_count_kernel<<<blocks_of((long long)v.P * v.L), dim3(256), 0, s>>>(v, node_of, mult, cnt);
     RV_LAUNCHED("train_leaf_count_kernel");
+}
+
+void launch_train_boost_resample(const float* cumsum, int N, uint64_t kb, int* idx, unsigned* mult, hipStream_t s) {
+    train_boost_resample_kernel<<<blocks_of(N), dim3(256), 0, s>>>(cumsum, N, kb, idx, mult);
+    RV_LAUNCHED("train_boost_resample_kernel");
+}
+
+void launch_train_vote_flags(const int* node_of, const int* vote_label, const int* label, int N, uint8_t* miss, hipStream_t s) {
+    train_vote_flags_kernel<<<blocks_of(N), dim3(256), 0, s>>>(node_of, vote_label, label, N, miss);
+    RV_LAUNCHED("train_vote_flags_kernel");
+}
+
+void launch_train_boost_error(const float* w, const uint8_t* miss, int N, float* error, hipStream_t s) {
+    train_boost_sum_kernel<0><<<dim3(1), dim3(64), 0, s>>>(const_cast<float*>(w), miss, N, 1.f, error, nullptr);
+    RV_LAUNCHED("train_boost_sum_kernel<error>");
+}
+
+void launch_train_boost_update_total(float* w, const uint8_t* miss, int N, float scale, float* total, hipStream_t s) {
+    train_boost_sum_kernel<1><<<dim3(1), dim3(64), 0, s>>>(w, miss, N, scale, total, nullptr);
+    RV_LAUNCHED("train_boost_sum_kernel<total>");
+}
+
+void launch_train_boost_update_cumsum(float* w, int N, const float* total, float* cumsum, hipStream_t s) {
+    train_boost_sum_kernel<2><<<dim3(1), dim3(64), 0, s>>>(w, nullptr, N, 1.f, const_cast<float*>(total), cumsum);
+    RV_LAUNCHED("train_boost_sum_kernel<cumsum>");
 }
 
 }  // namespace rvseg

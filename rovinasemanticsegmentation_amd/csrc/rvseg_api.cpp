@@ -222,6 +222,26 @@ static rvseg_status copy_out(const std::vector<uint8_t>& bytes, void* out, size_
     return RVSEG_OK;
 }
 
+static rvseg_status write_file(const char* path, const std::vector<uint8_t>& bytes) {
+    std::ofstream os(path, std::ios::binary);
+    if (!os.is_open()) return RVSEG_ERR_IO;          // libf::Exception("Could not open file."), io.h:118-121
+    os.write(reinterpret_cast<const char*>(bytes.data()), (std::streamsize)bytes.size());
+    return os.good() ? RVSEG_OK : RVSEG_ERR_IO;
+}
+
+// RandomForest::write on a boosted model would drop the tree weights
+static rvseg_status refuse_boosted_write(const rvseg_ctx* ctx) {
+    ctx->err = "the context holds a boosted forest: write it with rvseg_boosted_write";
+    return RVSEG_ERR_INVALID_ARG;
+}
+
+static bool boosted_order_ok(int32_t order) { return order == RVSEG_BOOSTED_WEIGHT_FIRST || order == RVSEG_BOOSTED_TREE_FIRST; }
+
+// the boosted model a context has loaded (never the one it trained: rvseg_boosted_train_result)
+static const ForestModel* boosted_model_of(const rvseg_ctx* ctx) {
+    return ctx->forest_loaded && ctx->host_forest.boosted ? &ctx->host_forest : nullptr;
+}
+
 }  // namespace rvseg
 
 using namespace rvseg;
@@ -425,17 +445,15 @@ rvseg_status rvseg_forest_rewrite(const void* buf, size_t size, void* out, size_
 rvseg_status rvseg_forest_write_mem(const rvseg_ctx* ctx, void* out, size_t out_cap, size_t* size_out) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
     if (!ctx->forest_loaded) return RVSEG_ERR_NO_FOREST;
+    if (ctx->host_forest.boosted) return refuse_boosted_write(ctx);
     return copy_out(serialize_forest(ctx->host_forest), out, out_cap, size_out);
 }
 
 rvseg_status rvseg_forest_write(const rvseg_ctx* ctx, const char* path) {
     if (!ctx || !path) return RVSEG_ERR_INVALID_ARG;
     if (!ctx->forest_loaded) return RVSEG_ERR_NO_FOREST;
-    const std::vector<uint8_t> bytes = serialize_forest(ctx->host_forest);
-    std::ofstream os(path, std::ios::binary);
-    if (!os.is_open()) return RVSEG_ERR_IO;          // libf::Exception("Could not open file."), io.h:118-121
-    os.write(reinterpret_cast<const char*>(bytes.data()), (std::streamsize)bytes.size());
-    return os.good() ? RVSEG_OK : RVSEG_ERR_IO;
+    if (ctx->host_forest.boosted) return refuse_boosted_write(ctx);
+    return write_file(path, serialize_forest(ctx->host_forest));
 }
 
 rvseg_status rvseg_forest_load(rvseg_ctx* ctx, const char* path) {
@@ -445,6 +463,107 @@ rvseg_status rvseg_forest_load(rvseg_ctx* ctx, const char* path) {
     if (!is.is_open()) { ctx->err = std::string("Could not open file. (") + path + ")"; return RVSEG_ERR_IO; }
     std::vector<char> data((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
     return rvseg_forest_load_mem(ctx, data.data(), data.size());
+}
+
+// ---- boosted forest: BoostedRandomForest::read / write / getWeights (classifier.cpp:250-280, classifiers.h:349-425) ----
+rvseg_status rvseg_boosted_check(const void* buf, size_t size, int32_t order, int32_t feature_length, int32_t* n_trees,
+                                 int32_t* n_nodes_total, int32_t* max_depth, char* err_out, size_t err_cap) {
+    ForestModel m;
+    std::string err;
+    rvseg_status st = RVSEG_OK;
+    if (!boosted_order_ok(order)) {
+        err = "unknown boosted stream order";
+        st = RVSEG_ERR_INVALID_ARG;
+    } else if (!parse_boosted(buf, size, feature_length > 0 ? feature_length : 0x7fffffff, order, m, err)) {
+        st = parse_error_status(err);
+    } else if (m.single_classes > kMaxClasses) {
+        err = "more than 64 classes are not supported";
+        st = RVSEG_ERR_FORMAT;
+    }
+    if (err_out && err_cap) std::snprintf(err_out, err_cap, "%s", err.c_str());
+    if (st != RVSEG_OK) return st;
+    if (n_trees) *n_trees = m.n_trees;
+    if (n_nodes_total) *n_nodes_total = (int32_t)m.nodes.size();
+    if (max_depth) *max_depth = m.max_depth;
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_boosted_rewrite(const void* buf, size_t size, int32_t in_order, int32_t out_order, void* out, size_t out_cap,
+                                   size_t* size_out) {
+    if (!boosted_order_ok(in_order) || !boosted_order_ok(out_order)) return RVSEG_ERR_INVALID_ARG;
+    ForestModel m;
+    std::string err;
+    if (!parse_boosted(buf, size, 0x7fffffff, in_order, m, err)) return parse_error_status(err);
+    return copy_out(serialize_boosted(m, out_order), out, out_cap, size_out);
+}
+
+rvseg_status rvseg_boosted_load_mem(rvseg_ctx* ctx, const void* buf, size_t size, int32_t order) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!buf) { ctx->err = "null forest buffer"; return RVSEG_ERR_INVALID_ARG; }
+    if (!boosted_order_ok(order)) { ctx->err = "unknown boosted stream order"; return RVSEG_ERR_INVALID_ARG; }
+    if (ctx->params.multi_layer) {   // multiClassLogPosterior: "This is not supported", classifier.cpp:304-307
+        ctx->err = "params.multi_layer is set: a boosted forest has no multi-layer posterior";
+        return RVSEG_ERR_INVALID_ARG;
+    }
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    ForestModel m;
+    std::string err;
+    if (!parse_boosted(buf, size, ctx->feature_length, order, m, err)) {
+        ctx->err = err;
+        return parse_error_status(err);
+    }
+    RV_HIP(ctx, hipDeviceSynchronize());   // as rvseg_forest_load_mem
+    eval_destroy(ctx);
+    ctx->host_forest = std::move(m);
+    ctx->forest_loaded = false;
+    return upload_forest(ctx);
+}
+
+rvseg_status rvseg_boosted_load(rvseg_ctx* ctx, const char* path, int32_t order) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!path) { ctx->err = "null path"; return RVSEG_ERR_INVALID_ARG; }
+    std::ifstream is(path, std::ios::binary);
+    if (!is.is_open()) { ctx->err = std::string("Could not open file. (") + path + ")"; return RVSEG_ERR_IO; }
+    std::vector<char> data((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
+    return rvseg_boosted_load_mem(ctx, data.data(), data.size(), order);
+}
+
+rvseg_status rvseg_boosted_write_mem(const rvseg_ctx* ctx, int32_t order, void* out, size_t out_cap, size_t* size_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    const ForestModel* m = boosted_model_of(ctx);
+    if (!m) { ctx->err = "no boosted forest loaded on this context"; return RVSEG_ERR_NO_FOREST; }
+    if (order == RVSEG_BOOSTED_AS_LOADED) order = m->boosted_order;
+    if (!boosted_order_ok(order)) { ctx->err = "unknown boosted stream order"; return RVSEG_ERR_INVALID_ARG; }
+    return copy_out(serialize_boosted(*m, order), out, out_cap, size_out);
+}
+
+rvseg_status rvseg_boosted_write(const rvseg_ctx* ctx, const char* path, int32_t order) {
+    if (!ctx || !path) return RVSEG_ERR_INVALID_ARG;
+    const ForestModel* m = boosted_model_of(ctx);
+    if (!m) { ctx->err = "no boosted forest loaded on this context"; return RVSEG_ERR_NO_FOREST; }
+    if (order == RVSEG_BOOSTED_AS_LOADED) order = m->boosted_order;
+    if (!boosted_order_ok(order)) { ctx->err = "unknown boosted stream order"; return RVSEG_ERR_INVALID_ARG; }
+    return write_file(path, serialize_boosted(*m, order));
+}
+
+rvseg_status rvseg_boosted_train_result(const rvseg_ctx* ctx, int32_t order, void* out, size_t out_cap, size_t* size_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!ctx->trained_boosted.boosted) { ctx->err = "no boosted forest has been trained on this context"; return RVSEG_ERR_NO_FOREST; }
+    if (!boosted_order_ok(order)) { ctx->err = "unknown boosted stream order"; return RVSEG_ERR_INVALID_ARG; }
+    return copy_out(serialize_boosted(ctx->trained_boosted, order), out, out_cap, size_out);
+}
+
+rvseg_status rvseg_boosted_weights(const rvseg_ctx* ctx, float* weights_out, int32_t cap, int32_t* n_out, int32_t* order_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    const ForestModel* m = boosted_model_of(ctx);
+    if (!m) { ctx->err = "no boosted forest loaded on this context"; return RVSEG_ERR_NO_FOREST; }
+    const int32_t n = (int32_t)m->tree_weights.size();
+    if (n_out) *n_out = n;
+    if (order_out) *order_out = m->boosted_order;
+    if (!weights_out) return RVSEG_OK;
+    if (cap < n) { ctx->err = "weights_out too small"; return RVSEG_ERR_INVALID_ARG; }
+    std::memcpy(weights_out, m->tree_weights.data(), (size_t)n * sizeof(float));
+    return RVSEG_OK;
 }
 
 rvseg_status rvseg_forest_info(const rvseg_ctx* ctx, int32_t* n_trees, int32_t* n_nodes_total,

@@ -118,7 +118,7 @@ struct rvseg_ctx {
     rvseg_params params{};
     rvseg_schedule sched{};        // rvseg_set_schedule; defaults from rvseg_schedule_default
     int feature_length = 0;
-    std::string err;
+    mutable std::string err;       // (a const call that refuses still says why)
     rvseg::ForestModel host_forest;
     bool forest_loaded = false;
     rvseg::DeviceForest forest;
@@ -128,6 +128,7 @@ struct rvseg_ctx {
     rvseg::StageTimer timer;
     rvseg::Pipeline* impl = nullptr;  // frame / crf / fusion state: pipeline_of (rvseg_pipeline.hip)
     std::vector<uint8_t> trained_model;   // forest.dat image of the last rvseg_forest_train* call (rvseg_forest_train_result)
+    rvseg::ForestModel trained_boosted;   // trees and weights of the last rvseg_boosted_train (rvseg_boosted_train_result)
     void* comm = nullptr;  // RCCL communicator of the local-map gather (rvseg_comm.cpp), or null
     int comm_rank = 0, comm_world = 0;
     rvseg::EvalState* eval = nullptr;     // allocated by the first scoring call; discarded by rvseg_forest_load

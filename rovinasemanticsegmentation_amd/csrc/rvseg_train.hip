@@ -23,6 +23,27 @@
 // This file is the learner: train_core is a loop over class_frequencies, start_tree, grow_level (draw_slots,
 // search_batch, decide_split, route_level) and fill_leaves.  The order-sensitive host arithmetic lives in train_host.h.
 //
+// Boosting (BoostedRandomForestLearner::learn, learning.cpp:1120-1234; classifier.cpp:238-307): boosted_core.  The
+// training set is packed once; a round's resample is a multiplicity per example (`mult`, "the tree's data set") plus its
+// index list, never a copy of the features.  The tree's bootstrap draws positions of that list; the class frequencies and
+// the leaf histograms count example n mult[n] times, which is what the reference's learner sees on its treeData; routing
+// moves every example of the whole set, so after fill_leaves node_of is the leaf of every ORIGINAL example and the
+// round's error needs no second walk.  Build-owned definitions (the reference draws from std::random_device and has no
+// guard for degenerate rounds; tests/boost_restate.py restates them independently):
+//   1. Round key kb = mix64(seed ^ mix64(0x626F6F73 + round)).  Draw n is u_n = (float)(draw64(kb, n) >> 40) * 2^-24,
+//      exact in fp32, in [0, 1).  The round's tree is learnt with seed_r = draw64(kb, 2^40) as tree 0 of a one-tree
+//      forest -- tree_key(seed_r, 0), the node keys above, use_bootstrap on top of the resample -- so it equals the
+//      oracle's learner run with num_trees = 1, seed = seed_r on the materialised resample X[idx].
+//   2. Index: the first i with !(u > cumsum[i]), by binary search (cumsum does not decrease: the weights are >= 0),
+//      clamped to N - 1 -- the reference reads past the array when rounding leaves cumsum[N-1] < u.
+//   3. error, total and cumsum are fp32 sums in example order, bit for bit the serial chain.  Before the first round
+//      the weights are 1.0f / N and cumsum[n] is the reference's closed form (n + 1) * 1.0f / N (:1140-1141).
+//   4. Stops.  error == 0: the tree is added with the reference's alpha = +inf and boosting ends.  error >= 1, or a
+//      total that is not positive and finite: the tree is not added and boosting ends.  Otherwise the reference's
+//      arithmetic, negative alpha included.  The call reports how many trees it kept.
+//   5. A loader stores a tree weight as w + 0.0f (forest_model.cpp), so -0.0 votes like the reference's 0 + (-0.0).
+// alpha and exp(alpha) come from the host's libm (train_host.h: boost_round).
+//
 // Oracle: oracle/rvseg_oracle_train.c restates the reference learner depth-first with sorts; tests compare forest.dat
 // byte for byte.  Both sides implement the same build-owned definitions, written down in that file's header: random
 // choices from a counter-based generator keyed by (seed, tree, node path); the objective evaluated from the class counts
@@ -78,7 +99,7 @@ rvseg_status reserve_grown(rvseg_ctx* ctx, DevBuf& b, size_t bytes) {
 
 // device memory of one training call; freed on return
 struct TrainScratch {
-    DevBuf weights, node_of;                    // [P] bootstrap multiplicity, node of every example
+    DevBuf weights, node_of;                    // [P] multiplicity in the tree's examples, node of every example
     DevBuf class_cnt;                           // [L][TR_CMAX]
     DevBuf hist, totals, cuts;                  // one slot batch: [S][K][TR_BINS][TR_CMAX], [S][TR_CMAX], CutResult[S][K]
     DevBuf slot_layer, slot_feat;               // slot tables of the batch
@@ -100,6 +121,9 @@ struct Learner {
     std::vector<CutResult> cuts;                // read-back of a batch
     std::vector<unsigned> totals;
     std::vector<int> perm;
+    // a boosting round's data set (null: every example once): multiplicities [P] and the example at each position [P]
+    const unsigned* mult = nullptr;
+    const int* positions = nullptr;
 };
 
 rvseg_status reserve_scratch(Learner& R) {
@@ -134,13 +158,13 @@ rvseg_status reserve_scratch(Learner& R) {
     return RVSEG_OK;
 }
 
-// inverted class frequencies over the whole set (data.h:358-370): freq[c] = size / count_c, in float
+// inverted class frequencies over the tree's data set (data.h:358-370): freq[c] = size / count_c, in float
 rvseg_status class_frequencies(Learner& R) {
     rvseg_ctx* ctx = R.ctx;
     const int L = R.T.L;
     std::vector<unsigned> class_cnt((size_t)L * TR_CMAX);
     RV_HIP(ctx, hipMemsetAsync(R.sc.class_cnt.p, 0, class_cnt.size() * 4, R.s));
-    launch_train_class_count(R.T.view(), R.sc.class_cnt.as<unsigned>(), R.s);
+    launch_train_class_count(R.T.view(), R.mult, R.sc.class_cnt.as<unsigned>(), R.s);
     RV_HIP(ctx, hipMemcpyAsync(class_cnt.data(), R.sc.class_cnt.p, class_cnt.size() * 4, hipMemcpyDeviceToHost, R.s));
     RV_HIP(ctx, hipStreamSynchronize(R.s));
     RV_LAUNCH_OK(ctx);
@@ -150,13 +174,15 @@ rvseg_status class_frequencies(Learner& R) {
     return RVSEG_OK;
 }
 
-// the tree's examples: P bootstrap draws as multiplicities, or every example once; all of them at the root
+// the tree's examples: P bootstrap draws from its data set as multiplicities, or the data set as it is; all at the root
 rvseg_status start_tree(Learner& R, uint64_t kt) {
     rvseg_ctx* ctx = R.ctx;
     const size_t P = (size_t)R.T.P;
     if (R.tp.use_bootstrap) {
         RV_HIP(ctx, hipMemsetAsync(R.sc.weights.p, 0, P * 4, R.s));
-        launch_train_bootstrap(R.T.P, kt, R.sc.weights.as<unsigned>(), R.s);
+        launch_train_bootstrap(R.T.P, kt, R.positions, R.sc.weights.as<unsigned>(), R.s);
+    } else if (R.mult) {
+        RV_HIP(ctx, hipMemcpyAsync(R.sc.weights.p, R.mult, P * 4, hipMemcpyDeviceToDevice, R.s));
     } else {
         RV_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)R.sc.weights.p, 1, P, R.s));
     }
@@ -292,7 +318,7 @@ rvseg_status grow_level(Learner& R, GrowingTree& tree, std::vector<int>& frontie
     return RVSEG_OK;
 }
 
-// leaf histograms from ALL examples (updateMultiHistograms, learning.cpp:960-1012): integer counts on the device, the
+// leaf histograms from ALL examples of the tree's data set (updateMultiHistograms, learning.cpp:960-1012): integer counts on the device, the
 // float accumulation of leaf_histograms on the host
 rvseg_status fill_leaves(Learner& R, GrowingTree& tree) {
     rvseg_ctx* ctx = R.ctx;
@@ -301,7 +327,7 @@ rvseg_status fill_leaves(Learner& R, GrowingTree& tree) {
     const rvseg_status st = reserve_grown(ctx, R.sc.leaf_cnt, cnt.size() * 4);
     if (st != RVSEG_OK) return st;
     RV_HIP(ctx, hipMemsetAsync(R.sc.leaf_cnt.p, 0, cnt.size() * 4, R.s));
-    launch_train_leaf_count(R.T.view(), R.sc.node_of.as<int>(), R.sc.leaf_cnt.as<unsigned>(), R.s);
+    launch_train_leaf_count(R.T.view(), R.sc.node_of.as<int>(), R.mult, R.sc.leaf_cnt.as<unsigned>(), R.s);
     RV_HIP(ctx, hipMemcpyAsync(cnt.data(), R.sc.leaf_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, R.s));
     RV_HIP(ctx, hipStreamSynchronize(R.s));
     RV_LAUNCH_OK(ctx);
@@ -311,25 +337,133 @@ rvseg_status fill_leaves(Learner& R, GrowingTree& tree) {
     return RVSEG_OK;
 }
 
+// one tree over the learner's data set, in level order, leaves filled
+rvseg_status grow_tree(Learner& R, uint64_t kt, GrowingTree& tree) {
+    rvseg_status st;
+    if ((st = start_tree(R, kt)) != RVSEG_OK) return st;
+    std::vector<int> frontier(1, 0);
+    while (!frontier.empty())
+        if ((st = grow_level(R, tree, frontier)) != RVSEG_OK) return st;
+    return fill_leaves(R, tree);
+}
+
+// autoconf, :363-368
+int features_per_node(int D, const rvseg_train_params& tp) { return std::min(D, tp.num_features > 0 ? tp.num_features : (int)std::ceil(std::sqrt((double)D))); }
+
 // ---- the learner over a device-resident training set ---------------------------------------------------------------
 rvseg_status train_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, std::vector<uint8_t>& bytes_out) {
-    const int K = std::min(T.D, tp.num_features > 0 ? tp.num_features : (int)std::ceil(std::sqrt((double)T.D)));   // autoconf, :363-368
-    Learner R{ctx, T, tp, K, ctx->stream};
+    Learner R{ctx, T, tp, features_per_node(T.D, tp), ctx->stream};
     rvseg_status st;
     if ((st = reserve_scratch(R)) != RVSEG_OK || (st = class_frequencies(R)) != RVSEG_OK) return st;
     ForestModel model;
     model.raw.reserve((size_t)tp.num_trees);
     for (int t = 0; t < tp.num_trees; t++) {
         const uint64_t kt = tree_key(tp.seed, t);
-        if ((st = start_tree(R, kt)) != RVSEG_OK) return st;
         GrowingTree tree(root_key(kt));
-        std::vector<int> frontier(1, 0);
-        while (!frontier.empty())
-            if ((st = grow_level(R, tree, frontier)) != RVSEG_OK) return st;
-        if ((st = fill_leaves(R, tree)) != RVSEG_OK) return st;
+        if ((st = grow_tree(R, kt, tree)) != RVSEG_OK) return st;
         model.raw.push_back(renumber_depth_first(std::move(tree)));
     }
     bytes_out = serialize_forest(model);
+    return RVSEG_OK;
+}
+
+// ---- boosting --------------------------------------------------------------------------------------------------
+// device memory of the boosting rounds; freed on return
+struct BoostScratch {
+    DevBuf w, cumsum;        // [N] example weights and their running sum
+    DevBuf miss;             // [N] bytes
+    DevBuf idx, mult;        // [N] the round's resample: example per draw, draws per example
+    DevBuf vote;             // [nodes] vote label per node of the growing tree (reserve_grown)
+    DevBuf sums;             // error, total
+};
+
+rvseg_status reserve_boost(rvseg_ctx* ctx, BoostScratch& b, size_t N) {
+    rvseg_status st;
+    if ((st = dev_alloc(ctx, b.w, N * 4)) != RVSEG_OK || (st = dev_alloc(ctx, b.cumsum, N * 4)) != RVSEG_OK ||
+        (st = dev_alloc(ctx, b.miss, N)) != RVSEG_OK || (st = dev_alloc(ctx, b.idx, N * 4)) != RVSEG_OK ||
+        (st = dev_alloc(ctx, b.mult, N * 4)) != RVSEG_OK || (st = dev_alloc(ctx, b.sums, 16)) != RVSEG_OK)
+        return st;
+    return RVSEG_OK;
+}
+
+// the two sums the stop rules need on the host
+rvseg_status boost_error(rvseg_ctx* ctx, BoostScratch& b, int N, float* error, hipStream_t s) {
+    launch_train_boost_error(b.w.as<float>(), b.miss.as<uint8_t>(), N, b.sums.as<float>(), s);
+    RV_HIP(ctx, hipMemcpyAsync(error, b.sums.p, 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+rvseg_status boost_total(rvseg_ctx* ctx, BoostScratch& b, int N, float scale, float* total, hipStream_t s) {
+    launch_train_boost_update_total(b.w.as<float>(), b.miss.as<uint8_t>(), N, scale, b.sums.as<float>() + 1, s);
+    RV_HIP(ctx, hipMemcpyAsync(total, b.sums.as<float>() + 1, 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// miss[n] for every example of the whole set from the leaf it was routed to (tree->classify, :1184)
+rvseg_status vote_flags(Learner& R, BoostScratch& b, const GrowingTree& tree) {
+    rvseg_ctx* ctx = R.ctx;
+    std::vector<int> vote((size_t)tree.size(), 0);
+    for (int v = 0; v < tree.size(); v++)
+        if (tree.left[v] == 0) vote[(size_t)v] = vote_label(tree.mhist[(size_t)v][0].data(), (int)tree.mhist[(size_t)v][0].size());
+    const rvseg_status st = reserve_grown(ctx, b.vote, vote.size() * 4);
+    if (st != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(b.vote.p, vote.data(), vote.size() * 4, hipMemcpyHostToDevice, R.s));
+    launch_train_vote_flags(R.sc.node_of.as<int>(), b.vote.as<int>(), R.T.lab.as<int>(), R.T.P, b.miss.as<uint8_t>(), R.s);
+    RV_HIP(ctx, hipStreamSynchronize(R.s));   // `vote` goes out of scope
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
+}
+
+// the rounds; `model` receives the kept trees and their weights, errors / alphas (num_trees each, or null) the rounds'
+rvseg_status boosted_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, int C, ForestModel& model, float* errors,
+                          float* alphas) {
+    const int N = T.P;
+    Learner R{ctx, T, tp, features_per_node(T.D, tp), ctx->stream};
+    BoostScratch b;
+    rvseg_status st;
+    if ((st = reserve_scratch(R)) != RVSEG_OK || (st = reserve_boost(ctx, b, (size_t)N)) != RVSEG_OK) return st;
+    {   // :1138-1143
+        std::vector<float> w((size_t)N), cs((size_t)N);
+        for (int n = 0; n < N; n++) { w[(size_t)n] = 1.0f / N; cs[(size_t)n] = (n + 1) * 1.0f / N; }
+        RV_HIP(ctx, hipMemcpyAsync(b.w.p, w.data(), (size_t)N * 4, hipMemcpyHostToDevice, R.s));
+        RV_HIP(ctx, hipMemcpyAsync(b.cumsum.p, cs.data(), (size_t)N * 4, hipMemcpyHostToDevice, R.s));
+        RV_HIP(ctx, hipStreamSynchronize(R.s));
+    }
+    model = ForestModel();
+    model.boosted = true;
+    model.boosted_order = RVSEG_BOOSTED_WEIGHT_FIRST;
+    R.mult = b.mult.as<unsigned>();
+    R.positions = b.idx.as<int>();
+    for (int round = 0; round < tp.num_trees; round++) {
+        const uint64_t kb = boost_round_key(tp.seed, round);
+        RV_HIP(ctx, hipMemsetAsync(b.mult.p, 0, (size_t)N * 4, R.s));
+        launch_train_boost_resample(b.cumsum.as<float>(), N, kb, b.idx.as<int>(), b.mult.as<unsigned>(), R.s);
+        if ((st = class_frequencies(R)) != RVSEG_OK) return st;
+        const uint64_t kt = tree_key(boost_tree_seed(kb), 0);
+        GrowingTree tree(root_key(kt));
+        if ((st = grow_tree(R, kt, tree)) != RVSEG_OK || (st = vote_flags(R, b, tree)) != RVSEG_OK) return st;
+        float error = 0.f, total = 0.f;
+        if ((st = boost_error(ctx, b, N, &error, R.s)) != RVSEG_OK) return st;
+        if (errors) errors[round] = error;
+        const BoostRound br = boost_round(error, C);
+        if (!br.keep_tree) break;
+        if (br.go_on) {
+            if ((st = boost_total(ctx, b, N, br.scale, &total, R.s)) != RVSEG_OK) return st;
+            if (!boost_total_ok(total)) break;
+        }
+        if (alphas) alphas[round] = br.alpha;
+        model.raw.push_back(renumber_depth_first(std::move(tree)));   // addTree(tree, alpha), :1220
+        model.tree_weights.push_back(br.alpha);
+        if (!br.go_on) break;
+        if (round + 1 < tp.num_trees)   // (nothing reads the weights after the last round)
+            launch_train_boost_update_cumsum(b.w.as<float>(), N, b.sums.as<float>() + 1, b.cumsum.as<float>(), R.s);
+    }
+    RV_HIP(ctx, hipStreamSynchronize(R.s));
+    RV_LAUNCH_OK(ctx);
+    model.n_trees = (int)model.raw.size();
     return RVSEG_OK;
 }
 
@@ -377,6 +511,42 @@ rvseg_status finish_training(rvseg_ctx* ctx, const TrainSet& T, const rvseg_trai
     const rvseg_status st = train_core(ctx, T, tp, ctx->trained_model);
     if (st != RVSEG_OK) return st;
     return hand_out(ctx, forest_out, out_cap, size_out);
+}
+
+// the P x D host matrix and its P x L labels as a packed training set on the device
+rvseg_status pack_matrix(rvseg_ctx* ctx, const float* X, int P, int D, const int32_t* labels, int n_layers, const int32_t* class_counts,
+                         TrainSet& T) {
+    hipStream_t s = ctx->stream;
+    rvseg_status st;
+    T.P = P; T.D = D; T.L = n_layers; T.stride = (size_t)P;
+    T.class_counts.assign(class_counts, class_counts + n_layers);
+    // which features are byte-valued is decided by value
+    DevBuf dX, dNotByte, dNotFinite;
+    if ((st = dev_alloc(ctx, dX, (size_t)P * D * 4)) != RVSEG_OK || (st = dev_alloc(ctx, dNotByte, (size_t)D * 4)) != RVSEG_OK ||
+        (st = dev_alloc(ctx, dNotFinite, 16)) != RVSEG_OK)
+        return st;
+    RV_HIP(ctx, hipMemcpyAsync(dX.p, X, (size_t)P * D * 4, hipMemcpyHostToDevice, s));
+    RV_HIP(ctx, hipMemsetAsync(dNotByte.p, 0, (size_t)D * 4, s));
+    RV_HIP(ctx, hipMemsetAsync(dNotFinite.p, 0, 16, s));
+    launch_train_feature_stats(dX.as<float>(), P, D, dNotByte.as<int>(), dNotFinite.as<int>(), s);
+    std::vector<int> not_byte(D);
+    int not_finite = 0;
+    RV_HIP(ctx, hipMemcpyAsync(not_byte.data(), dNotByte.p, (size_t)D * 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipMemcpyAsync(&not_finite, dNotFinite.p, 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    RV_LAUNCH_OK(ctx);
+    if (not_finite) { ctx->err = "non-finite feature value in the training set"; return RVSEG_ERR_INVALID_ARG; }
+    T.nb_index.assign(D, -1);
+    for (int f = 0; f < D; f++) if (not_byte[f]) T.nb_index[f] = T.n_nb++;
+    if ((st = reserve_train_set(ctx, T)) != RVSEG_OK) return st;
+    std::vector<int> lab_lm((size_t)P * n_layers);   // layer-major, like the rows of X
+    for (int i = 0; i < P; i++)
+        for (int l = 0; l < n_layers; l++) lab_lm[(size_t)l * P + i] = labels[(size_t)i * n_layers + l];
+    RV_HIP(ctx, hipMemcpyAsync(T.lab.p, lab_lm.data(), lab_lm.size() * 4, hipMemcpyHostToDevice, s));
+    launch_train_pack(dX.as<float>(), T.view(), s);
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
 }
 
 // ---- frames -> training set on the device (src/train.cpp:115-147) -------------------------------------------------
@@ -480,36 +650,8 @@ rvseg_status rvseg_forest_train(rvseg_ctx* ctx, const float* X, int32_t P, int32
     for (int l = 0; l < n_layers; l++)
         if ((st = labels_in_range(ctx, labels + l, (size_t)P, (size_t)n_layers, class_counts[l])) != RVSEG_OK) return st;
     RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    hipStream_t s = ctx->stream;
     TrainSet T;
-    T.P = P; T.D = D; T.L = n_layers; T.stride = (size_t)P;
-    T.class_counts.assign(class_counts, class_counts + n_layers);
-    // which features are byte-valued is decided by value
-    DevBuf dX, dNotByte, dNotFinite;
-    if ((st = dev_alloc(ctx, dX, (size_t)P * D * 4)) != RVSEG_OK || (st = dev_alloc(ctx, dNotByte, (size_t)D * 4)) != RVSEG_OK ||
-        (st = dev_alloc(ctx, dNotFinite, 16)) != RVSEG_OK)
-        return st;
-    RV_HIP(ctx, hipMemcpyAsync(dX.p, X, (size_t)P * D * 4, hipMemcpyHostToDevice, s));
-    RV_HIP(ctx, hipMemsetAsync(dNotByte.p, 0, (size_t)D * 4, s));
-    RV_HIP(ctx, hipMemsetAsync(dNotFinite.p, 0, 16, s));
-    launch_train_feature_stats(dX.as<float>(), P, D, dNotByte.as<int>(), dNotFinite.as<int>(), s);
-    std::vector<int> not_byte(D);
-    int not_finite = 0;
-    RV_HIP(ctx, hipMemcpyAsync(not_byte.data(), dNotByte.p, (size_t)D * 4, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipMemcpyAsync(&not_finite, dNotFinite.p, 4, hipMemcpyDeviceToHost, s));
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    RV_LAUNCH_OK(ctx);
-    if (not_finite) { ctx->err = "non-finite feature value in the training set"; return RVSEG_ERR_INVALID_ARG; }
-    T.nb_index.assign(D, -1);
-    for (int f = 0; f < D; f++) if (not_byte[f]) T.nb_index[f] = T.n_nb++;
-    if ((st = reserve_train_set(ctx, T)) != RVSEG_OK) return st;
-    std::vector<int> lab_lm((size_t)P * n_layers);   // layer-major, like the rows of X
-    for (int i = 0; i < P; i++)
-        for (int l = 0; l < n_layers; l++) lab_lm[(size_t)l * P + i] = labels[(size_t)i * n_layers + l];
-    RV_HIP(ctx, hipMemcpyAsync(T.lab.p, lab_lm.data(), lab_lm.size() * 4, hipMemcpyHostToDevice, s));
-    launch_train_pack(dX.as<float>(), T.view(), s);
-    RV_HIP(ctx, hipStreamSynchronize(s));
-    RV_LAUNCH_OK(ctx);
+    if ((st = pack_matrix(ctx, X, P, D, labels, n_layers, class_counts, T)) != RVSEG_OK) return st;
     return finish_training(ctx, T, tp, forest_out, out_cap, size_out);
 }
 
@@ -560,6 +702,64 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
     T.P = (int)base;
     if ((st = check_device_labels(ctx, T)) != RVSEG_OK) return st;
     return finish_training(ctx, T, tp, forest_out, out_cap, size_out);
+}
+
+rvseg_status rvseg_boosted_train(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t C,
+                                 const rvseg_train_params* tp_in, void* out, size_t out_cap, size_t* size_out, float* errors_out,
+                                 float* alphas_out, int32_t* rounds_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    const rvseg_train_params tp = resolve_params(tp_in);
+    if (!X || !labels || !size_out || P < 1 || D < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    rvseg_status st = check_train_args(ctx, 1, &C, tp, D);
+    if (st != RVSEG_OK) return st;
+    if (C < 2) { ctx->err = "boosting needs at least 2 classes (alpha takes log(C - 1))"; return RVSEG_ERR_INVALID_ARG; }
+    if ((st = labels_in_range(ctx, labels, (size_t)P, 1, C)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    TrainSet T;
+    if ((st = pack_matrix(ctx, X, P, D, labels, 1, &C, T)) != RVSEG_OK) return st;
+    const float nan = std::nanf("");
+    for (int r = 0; r < tp.num_trees; r++) {
+        if (errors_out) errors_out[r] = nan;
+        if (alphas_out) alphas_out[r] = nan;
+    }
+    ForestModel model;
+    if ((st = boosted_core(ctx, T, tp, C, model, errors_out, alphas_out)) != RVSEG_OK) return st;
+    if (rounds_out) *rounds_out = model.n_trees;
+    const std::vector<uint8_t> bytes = serialize_boosted(model, RVSEG_BOOSTED_WEIGHT_FIRST);
+    ctx->trained_boosted = std::move(model);   // only a successful training replaces the kept model
+    *size_out = bytes.size();
+    if (!out) return RVSEG_OK;
+    if (out_cap < bytes.size()) { ctx->err = "output buffer too small (the model is kept: rvseg_boosted_train_result)"; return RVSEG_ERR_INVALID_ARG; }
+    std::memcpy(out, bytes.data(), bytes.size());
+    return RVSEG_OK;
+}
+
+rvseg_status rvseg_boosted_resample(rvseg_ctx* ctx, const float* weights, const uint8_t* miss, int32_t N, float exp_alpha, uint64_t key,
+                                    float* error_out, float* weights_out, float* cumsum_out, int32_t* idx_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!weights || N < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    for (int32_t n = 0; n < N; n++)
+        if (!(weights[n] >= 0.0f) || std::signbit(weights[n])) { ctx->err = "example weights must be >= +0"; return RVSEG_ERR_INVALID_ARG; }
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    hipStream_t s = ctx->stream;
+    BoostScratch b;
+    rvseg_status st;
+    if ((st = reserve_boost(ctx, b, (size_t)N)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipMemcpyAsync(b.w.p, weights, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    if (miss) RV_HIP(ctx, hipMemcpyAsync(b.miss.p, miss, (size_t)N, hipMemcpyHostToDevice, s));
+    else RV_HIP(ctx, hipMemsetAsync(b.miss.p, 0, (size_t)N, s));
+    float error = 0.f, total = 0.f;
+    if ((st = boost_error(ctx, b, N, &error, s)) != RVSEG_OK || (st = boost_total(ctx, b, N, exp_alpha, &total, s)) != RVSEG_OK) return st;
+    if (error_out) *error_out = error;
+    if (!boost_total_ok(total)) { ctx->err = "the example weights do not sum to a positive finite total"; return RVSEG_ERR_INVALID_ARG; }
+    launch_train_boost_update_cumsum(b.w.as<float>(), N, b.sums.as<float>() + 1, b.cumsum.as<float>(), s);
+    launch_train_boost_resample(b.cumsum.as<float>(), N, key, b.idx.as<int>(), nullptr, s);
+    if (weights_out) RV_HIP(ctx, hipMemcpyAsync(weights_out, b.w.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    if (cumsum_out) RV_HIP(ctx, hipMemcpyAsync(cumsum_out, b.cumsum.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    if (idx_out) RV_HIP(ctx, hipMemcpyAsync(idx_out, b.idx.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    RV_HIP(ctx, hipStreamSynchronize(s));
+    RV_LAUNCH_OK(ctx);
+    return RVSEG_OK;
 }
 
 }  // extern "C"

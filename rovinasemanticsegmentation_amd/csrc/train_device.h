@@ -46,8 +46,11 @@ size_t train_scan_temp_bytes(size_t n);
 hipError_t launch_train_scan_offsets(void* temp, size_t temp_bytes, const int* flags, int* offs, size_t n, hipStream_t s);
 
 // ---- the learner ----------------------------------------------------------------------------------------------
-void launch_train_class_count(const TrainSetView& v, unsigned* cnt, hipStream_t s);            // cnt[layer][TR_CMAX] += 1
-void launch_train_bootstrap(int P, uint64_t kt, unsigned* w, hipStream_t s);                   // w += P draws with replacement
+// mult (null: every example once): how often the tree's data set holds each example -- a boosting round's resample
+void launch_train_class_count(const TrainSetView& v, const unsigned* mult, unsigned* cnt, hipStream_t s);   // cnt[layer][TR_CMAX] += mult
+// w += P draws with replacement from the P positions of the data set; positions (null: position n is example n): the
+// example at each position of a resample
+void launch_train_bootstrap(int P, uint64_t kt, const int* positions, unsigned* w, hipStream_t s);
 // byte features of S slots: class totals, (feature, value, class) histograms, the best cut of every (slot, feature)
 void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, unsigned* totals, unsigned* hist, CutResult* cuts,
                                hipStream_t s);
@@ -63,6 +66,20 @@ void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, unsig
 // every example of a freshly split node moves to a child
 void launch_train_route(const TrainSetView& v, int* node_of, const int* split_feat, const float* split_thr, const int* split_left,
                         hipStream_t s);
-void launch_train_leaf_count(const TrainSetView& v, const int* node_of, unsigned* cnt, hipStream_t s);   // cnt[node][layer][TR_CMAX] += 1
+void launch_train_leaf_count(const TrainSetView& v, const int* node_of, const unsigned* mult, unsigned* cnt, hipStream_t s);   // cnt[node][layer][TR_CMAX] += mult
+
+// ---- a boosting round (BoostedRandomForestLearner::learn, learning.cpp:1162-1217) ------------------------------
+// idx[n] = the first index with !(u_n > cumsum[index]), clamped to N - 1, u_n = boost_uniform(kb, n); mult[idx[n]] += 1
+// (mult may be null)
+void launch_train_boost_resample(const float* cumsum, int N, uint64_t kb, int* idx, unsigned* mult, hipStream_t s);
+// miss[n] = (vote_label[node_of[n]] != label[n])
+void launch_train_vote_flags(const int* node_of, const int* vote_label, const int* label, int N, uint8_t* miss, hipStream_t s);
+// The ordered fp32 sums, each bit for bit the serial chain in example order, each one wave:
+//   error[0] = sum of w[n] over the misses
+void launch_train_boost_error(const float* w, const uint8_t* miss, int N, float* error, hipStream_t s);
+//   w[n] *= scale for the misses (one fp32 multiply), then total[0] = sum of w[n]
+void launch_train_boost_update_total(float* w, const uint8_t* miss, int N, float scale, float* total, hipStream_t s);
+//   w[n] /= total[0], then cumsum[n] = w[n] + cumsum[n-1]
+void launch_train_boost_update_cumsum(float* w, int N, const float* total, float* cumsum, hipStream_t s);
 
 }  // namespace rvseg

@@ -162,4 +162,31 @@ inline RawTree renumber_depth_first(GrowingTree&& g) {
     return tree;
 }
 
+// ---- boosting (BoostedRandomForestLearner::learn, :1120-1234; rvseg_train.hip lists the build-owned definitions) ----
+// definition 1: the round's key, its uniform draws -- 24 random bits, exact in fp32, in [0, 1) -- and its tree's seed
+inline uint64_t boost_round_key(uint64_t seed, int round) { return mix64(seed ^ mix64(0x626F6F73ull + (uint64_t)round)); }
+RV_TRAIN_HD inline float boost_uniform(uint64_t kb, uint64_t n) { return (float)(draw64(kb, n) >> 40) * 5.9604644775390625e-8f; }
+inline uint64_t boost_tree_seed(uint64_t kb) { return draw64(kb, 1ull << 40); }
+
+// What a round does with its tree, from the tree's error on the whole set (definition 4).  alpha is :1197: the first
+// logarithm is float, the second takes an int and is double, the sum is narrowed to float; scale is :1207's
+// std::exp(alpha), float.
+struct BoostRound {
+    bool keep_tree = false;   // addTree(tree, alpha)
+    bool go_on = false;       // update the weights and run the next round
+    float alpha = 0.f, scale = 1.f;
+};
+inline BoostRound boost_round(float error, int C) {
+    BoostRound r;
+    if (!(error < 1.0f)) return r;                       // error >= 1 (or NaN): the tree is not added, boosting ends
+    r.keep_tree = true;
+    r.alpha = (float)(std::log((1 - error) / error) + std::log(C - 1));
+    if (error == 0.0f) return r;                         // alpha = +inf: the tree is added, boosting ends
+    r.scale = std::exp(r.alpha);
+    r.go_on = true;
+    return r;
+}
+// a total the weights can be divided by (definition 4)
+inline bool boost_total_ok(float total) { return total > 0.0f && total <= 3.4028234663852886e38f; }
+
 }  // namespace rvseg

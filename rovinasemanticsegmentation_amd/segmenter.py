@@ -132,6 +132,69 @@ class Context:
         capi.check(self.h, self.L.rvseg_forest_train_result(self.h, buf, size, C.byref(got)))
         return buf.raw[:got.value]
 
+    # ---- boosted forest (libf::BoostedRandomForest / BoostedRandomForestLearner) ---------------
+    def boosted_load(self, src, order=capi.BOOSTED_WEIGHT_FIRST):
+        """BoostedRandomForest::read (classifier.cpp:264-280) of a stream in `order`: BOOSTED_WEIGHT_FIRST is what the
+        reference's write produces, BOOSTED_TREE_FIRST what its read accepts.  forest_eval then returns the vote sums."""
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            buf = bytes(src)
+            capi.check(self.h, self.L.rvseg_boosted_load_mem(self.h, buf, len(buf), order))
+        else:
+            capi.check(self.h, self.L.rvseg_boosted_load(self.h, str(src).encode(), order))
+
+    def boosted_write(self, path=None, order=capi.BOOSTED_AS_LOADED):
+        """BoostedRandomForest::write (classifier.cpp:250-262): to `path`, or returns the bytes.  The default order is the
+        one the model was read in."""
+        if path is not None:
+            capi.check(self.h, self.L.rvseg_boosted_write(self.h, str(path).encode(), order))
+            return None
+        size = C.c_size_t()
+        capi.check(self.h, self.L.rvseg_boosted_write_mem(self.h, order, None, 0, C.byref(size)))
+        buf = C.create_string_buffer(size.value)
+        capi.check(self.h, self.L.rvseg_boosted_write_mem(self.h, order, buf, size.value, C.byref(size)))
+        return buf.raw[:size.value]
+
+    def boosted_weights(self):
+        """BoostedRandomForest::getWeights: float32 (T,), as the stream holds them."""
+        n = C.c_int32()
+        capi.check(self.h, self.L.rvseg_boosted_weights(self.h, None, 0, C.byref(n), None))
+        out = np.empty(n.value, np.float32)
+        capi.check(self.h, self.L.rvseg_boosted_weights(self.h, _ptr(out), n.value, C.byref(n), None))
+        return out
+
+    def boosted_train(self, X, labels, n_classes, **train_params):
+        """rvseg_boosted_train: X (P, D) float32, labels (P,) int32 class indices of n_classes classes; num_trees is the
+        number of boosting rounds.  Returns dict(model = the BOOSTED_WEIGHT_FIRST stream, rounds = trees kept, errors,
+        alphas = float32 (num_trees,), NaN where a round did not run or kept no tree)."""
+        X = np.ascontiguousarray(X, np.float32)
+        labels = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        P, D = X.shape
+        assert labels.shape == (P,)
+        tp = self._train_params(train_params)
+        errors = np.empty(max(tp.num_trees, 1), np.float32)
+        alphas = np.empty(max(tp.num_trees, 1), np.float32)
+        size, rounds = C.c_size_t(), C.c_int32()
+        capi.check(self.h, self.L.rvseg_boosted_train(self.h, _ptr(X), P, D, _ptr(labels), n_classes, C.byref(tp), None, 0, C.byref(size),
+                                                      _ptr(errors), _ptr(alphas), C.byref(rounds)))
+        # trained once (the model stays on the context, apart from a loaded one), then fetched into a buffer of the right size
+        buf = C.create_string_buffer(size.value)
+        capi.check(self.h, self.L.rvseg_boosted_train_result(self.h, capi.BOOSTED_WEIGHT_FIRST, buf, size.value, C.byref(size)))
+        return {"model": buf.raw[:size.value], "rounds": rounds.value,
+                "errors": errors[:tp.num_trees], "alphas": alphas[:tp.num_trees]}
+
+    def boosted_resample(self, weights, miss=None, exp_alpha=1.0, key=0):
+        """rvseg_boosted_resample: one boosting round's weight kernels on caller-supplied weights (N,) >= 0 and miss flags
+        (N,) or None.  Returns dict(error, weights, cumsum, idx)."""
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        N = w.shape[0]
+        m = None if miss is None else np.ascontiguousarray(np.asarray(miss).reshape(-1) != 0, np.uint8)
+        assert m is None or m.shape == (N,)
+        err = C.c_float()
+        wo, cs, idx = np.empty(N, np.float32), np.empty(N, np.float32), np.empty(N, np.int32)
+        capi.check(self.h, self.L.rvseg_boosted_resample(self.h, _ptr(w), _ptr(m) if m is not None else None, N, float(exp_alpha),
+                                                         int(key), C.byref(err), _ptr(wo), _ptr(cs), _ptr(idx)))
+        return {"error": np.float32(err.value), "weights": wo, "cumsum": cs, "idx": idx}
+
     def forest_train_frames(self, rgb, depth, calib, labels, class_counts, augment=False, **train_params):
         """rvseg_forest_train_frames: rgb (n, H, W, 3) uint8, depth (n, H, W) uint16, labels (n, L, H, W) int8 (< 0 =
         unlabelled).  Returns (forest.dat bytes, number of training points)."""
@@ -849,6 +912,38 @@ class RandomForest:
         cc = self.ctx.forest_info()["class_counts"]
         offs = np.cumsum([0] + cc)
         return [out[:, offs[i]:offs[i + 1]] for i in range(len(cc))]
+
+
+class BoostedRandomForest:
+    """libf::BoostedRandomForest (classifiers.h:349-425) on a context with multi_layer=0."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def read(self, src, order=capi.BOOSTED_WEIGHT_FIRST):  # BoostedRandomForest::read, classifier.cpp:264 (order: see Context.boosted_load)
+        self.ctx.boosted_load(src, order)
+
+    def write(self, dst=None, order=capi.BOOSTED_AS_LOADED):  # BoostedRandomForest::write, classifier.cpp:250
+        return self.ctx.boosted_write(dst, order)
+
+    def getSize(self):
+        return int(self.ctx.boosted_weights().size)
+
+    def getWeights(self):
+        return self.ctx.boosted_weights()
+
+    def classLogPosterior(self, X):  # classifier.cpp:283-302: the weighted votes per class
+        return self.ctx.forest_eval(np.atleast_2d(X))
+
+    def classify(self, X):  # Classifier::classify, classifier.cpp:29-51: the first strictly greatest vote sum
+        post = self.classLogPosterior(X)
+        label = np.zeros(post.shape[0], np.int32)
+        best = post[:, 0].copy()
+        for c in range(1, post.shape[1]):
+            win = post[:, c] > best
+            label[win] = c
+            best[win] = post[win, c]
+        return label
 
 
 class FeatureExtractor:
