@@ -254,6 +254,54 @@ rvseg_status rvseg_boosted_resample(rvseg_ctx *ctx, const float *weights, const 
                                     uint64_t key, float *error_out, float *weights_out, float *cumsum_out,
                                     int32_t *idx_out);
 
+/* ---- forest tools: replaces libforest's tools.h (AccuracyTool, ConfusionMatrixTool, CorrelationTool; tools.cpp) and
+ *      Classifier::classify on a data set, for the loaded model, and re-estimates a loaded forest's leaves.
+ *      X: P x D host floats, D == rvseg_feature_length, P >= 1.  `layer` indexes the layers of the context's active
+ *      mode (what rvseg_forest_info reports): a multi_layer = 0 context has one, the single-label histograms -- the head
+ *      the reference's tools see; on a multi_layer = 1 context the label rule is applied to
+ *      multiClassLogPosterior[layer], which is this build's extension.  C = class_counts[layer].
+ *      The label rule is Classifier::classify (classifier.cpp:29-51): label 0, then index i wins iff post[i] > prob -- equal
+ *      values keep the lower index, a NaN never wins and a NaN at index 0 is never beaten.
+ *      Refused with RVSEG_ERR_INVALID_ARG, nothing written: layer out of range, D != the feature length, P <= 0, a label
+ *      outside [0, C) (the reference indexes out of bounds there).  RVSEG_ERR_NO_FOREST: no model loaded. */
+/* Replaces Classifier::classify(DataStorage) (classifier.cpp:53-62) for the loaded model, forest or boosted: the label rule
+ * on the forest posterior (tree 0's leaf row += trees 1..T-1 in order, as rvseg_forest_eval).  labels_out: P. */
+rvseg_status rvseg_forest_classify(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, int32_t layer, int32_t *labels_out);
+/* Replaces DecisionTree::classify per tree (tools.cpp:214-218): votes_out[t * P + n] = the label rule on tree t's own
+ * leaf histogram of the layer (DecisionTree::classLogPosterior).  For a boosted model these are the trees' own labels,
+ * whatever their weights. */
+rvseg_status rvseg_forest_classify_trees(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, int32_t layer, uint8_t *votes_out);
+/* One pass over X: the forest's labels (pred_out, P), the confusion counts [true][predicted] (confusion_out, C x C;
+ * tools.cpp:121-128) and per tree pair the points on which the two trees vote alike (agree_out, T x T, symmetric, P on the
+ * diagonal; P minus Util::hammingDist, tools.cpp:226).  Every output is optional; labels (P) may be NULL when
+ * confusion_out is NULL. */
+rvseg_status rvseg_forest_measure(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t layer,
+                                  int32_t *pred_out, uint64_t *confusion_out, uint64_t *agree_out);
+/* Host only, no context: the reference's float arithmetic on the counts.  accuracy = 1.0f - errors / (float)size with
+ * errors the off-diagonal total as an int (AccuracyTool::measure, tools.cpp:77).  confusion_norm_out (C x C) =
+ * (float)min(count, 2^24) / (int)row_total (ConfusionMatrixTool::measure, tools.cpp:126-135: the reference grows the cell
+ * with "+= 1" on a float, which stops at 2^24); a true class without examples gives the reference's 0 / 0 = NaN row.
+ * Both outputs are optional. */
+rvseg_status rvseg_forest_tools_scores(const uint64_t *confusion, int32_t C, float *accuracy_out, float *confusion_norm_out);
+/* Host only: CorrelationTool::measure (tools.cpp:226-228) per cell, 1 - (int)(P - agree) / (float)P; the diagonal is 1. */
+rvseg_status rvseg_forest_tools_correlation(const uint64_t *agree, int32_t T, uint64_t P, float *corr_out);
+/* Replaces DecisionTreeLearner::updateHistograms / updateMultiHistograms (learning.cpp:918-1012) on a loaded
+ * RandomForest: the same trees -- features, thresholds and child links byte for byte as loaded -- with every leaf's
+ * histograms re-estimated from (X, labels) as rvseg_forest_train estimates them: per leaf and (layer, class) the
+ * examples that land there, each adding the inverted class frequency of its label in this set, stored as
+ * log((h + smoothing) / (total + C * smoothing)).  labels: P x n_layers class indices; n_layers / class_counts must be
+ * the heads the model carries: its multi layers one to one, or, for a model with only a single-label head, that one
+ * layer; anything else is RVSEG_ERR_INVALID_ARG.  A single-label head beside exactly one multi layer of the same class
+ * count is written from the same labels (what rvseg_forest_train writes); beside other multi layers no labels are its
+ * own and it stays as loaded.  At most 16 classes per layer, as the trainer.
+ * Size protocol of rvseg_forest_write_mem: *size_out receives the needed size, forest_out may be NULL to query (with
+ * counts_out NULL too, nothing runs).  counts_out (optional): n_nodes_total x sumC uint32, [tree][node in stream
+ * order][layers concatenated], zeros at inner nodes.  The loaded model is not replaced.  RVSEG_ERR_NO_FOREST on a
+ * boosted model. */
+rvseg_status rvseg_forest_refit(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t n_layers,
+                                const int32_t *class_counts, float smoothing, void *forest_out, size_t out_cap,
+                                size_t *size_out, uint32_t *counts_out);
+
 /* ---- features: replaces Features::FeatureExtractor::extract, NO_LABEL branch
  *      (include/feature_extractor.h:41-291).  Host buffers, one frame.  feat_out: capacity
  *      (H/stride+1)*(W/stride+1) x D floats; x_v / y_v same capacity.  Exists for parity tests:

@@ -1435,5 +1435,107 @@ private:
     rvseg_ctx* ctx_;
 };
 
+// libforest tools.h on the model a context has loaded (RandomForest or BoostedRandomForest): X is P x D, labels P class
+// indices of `layer` (rvseg.h, "forest tools").  The counts come from one pass on the device, the floats from the
+// reference's arithmetic on them.
+namespace tools_detail {
+inline void check(rvseg_ctx* ctx, rvseg_status st) {
+    if (st != RVSEG_OK) throw std::runtime_error(std::string(rvseg_status_string(st)) + ": " + rvseg_last_error(ctx));
+}
+inline int class_count(rvseg_ctx* ctx, int layer, int* n_trees = nullptr) {
+    int32_t T = 0, n_layers = 0, cc[RVSEG_MAX_LAYERS];
+    check(ctx, rvseg_forest_info(ctx, &T, nullptr, nullptr, &n_layers, cc));
+    if (n_trees) *n_trees = T;
+    if (layer < 0 || layer >= n_layers) throw std::runtime_error("layer outside the layers of the context's active mode");
+    return cc[layer];
+}
+inline std::vector<std::vector<float>> rows_of(const std::vector<float>& flat, int n) {
+    std::vector<std::vector<float>> out((size_t)n);
+    for (int r = 0; r < n; r++) out[(size_t)r].assign(flat.begin() + (size_t)r * n, flat.begin() + (size_t)(r + 1) * n);
+    return out;
+}
+}  // namespace tools_detail
+
+class AccuracyTool {   // tools.cpp:61-89
+public:
+    float measure(rvseg_ctx* classifier, const float* X, int P, int D, const int32_t* labels, int layer = 0) const {
+        const int C = tools_detail::class_count(classifier, layer);
+        std::vector<uint64_t> conf((size_t)C * C);
+        tools_detail::check(classifier, rvseg_forest_measure(classifier, X, P, D, labels, layer, nullptr, conf.data(), nullptr));
+        float accuracy = 0.f;
+        tools_detail::check(classifier, rvseg_forest_tools_scores(conf.data(), C, &accuracy, nullptr));
+        return accuracy;
+    }
+    void print(float accuracy) const { std::printf("Accuracy: %2.2f%% (Error: %2.2f%%)\n", accuracy * 100, (1 - accuracy) * 100); }
+};
+
+class ConfusionMatrixTool {   // tools.cpp:95-186; rows are true classes, a class without examples is a NaN row
+public:
+    std::vector<std::vector<float>> measure(rvseg_ctx* classifier, const float* X, int P, int D, const int32_t* labels, int layer = 0) const {
+        const int C = tools_detail::class_count(classifier, layer);
+        std::vector<uint64_t> conf((size_t)C * C);
+        tools_detail::check(classifier, rvseg_forest_measure(classifier, X, P, D, labels, layer, nullptr, conf.data(), nullptr));
+        std::vector<float> norm((size_t)C * C);
+        tools_detail::check(classifier, rvseg_forest_tools_scores(conf.data(), C, nullptr, norm.data()));
+        return tools_detail::rows_of(norm, C);
+    }
+    void print(const std::vector<std::vector<float>>& result) const {   // without the colour codes
+        const int C = (int)result.size();
+        std::printf("        |");
+        for (int c = 0; c < C; c++) std::printf(" %6d |", c);
+        std::printf("\n");
+        for (int c = 0; c < C + 1; c++) std::printf("--------|");
+        std::printf("\n");
+        for (int c = 0; c < C; c++) {
+            std::printf(" %6d |", c);
+            for (int cc = 0; cc < C; cc++) std::printf(" %5.2f%% |", result[(size_t)c][(size_t)cc] * 100);
+            std::printf("\n");
+            for (int k = 0; k < C + 1; k++) std::printf("--------|");
+            std::printf("\n");
+        }
+    }
+};
+
+class CorrelationTool {   // tools.cpp:192-263
+public:
+    std::vector<std::vector<float>> measure(rvseg_ctx* forest, const float* X, int P, int D, int layer = 0) const {
+        int T = 0;
+        tools_detail::class_count(forest, layer, &T);
+        std::vector<uint64_t> agree((size_t)T * T);
+        tools_detail::check(forest, rvseg_forest_measure(forest, X, P, D, nullptr, layer, nullptr, nullptr, agree.data()));
+        std::vector<float> corr((size_t)T * T);
+        tools_detail::check(forest, rvseg_forest_tools_correlation(agree.data(), T, (uint64_t)P, corr.data()));
+        return tools_detail::rows_of(corr, T);
+    }
+    void print(const std::vector<std::vector<float>>& result) const {
+        const int C = (int)result.size();
+        std::printf("         |");
+        for (int c = 0; c < C; c++) std::printf(" %7d |", c);
+        std::printf("\n");
+        for (int c = 0; c < C + 1; c++) std::printf("---------|");
+        std::printf("\n");
+        for (int c = 0; c < C; c++) {
+            std::printf(" %7d |", c);
+            for (int cc = 0; cc < C; cc++) std::printf(" %6.2f%% |", result[(size_t)c][(size_t)cc] * 100);
+            std::printf("\n");
+            for (int k = 0; k < C + 1; k++) std::printf("---------|");
+            std::printf("\n");
+        }
+    }
+};
+
+// DecisionTreeLearner::updateHistograms / updateMultiHistograms (learning.cpp:918-1012) on the loaded RandomForest: the
+// forest.dat image of the same trees with their leaves re-estimated from (X, labels: P x class_counts.size()).
+inline std::vector<uint8_t> refit(rvseg_ctx* forest, const float* X, int P, int D, const int32_t* labels, const std::vector<int32_t>& class_counts,
+                                  float smoothing = 1.0f) {
+    size_t size = 0;
+    tools_detail::check(forest, rvseg_forest_refit(forest, X, P, D, labels, (int32_t)class_counts.size(), class_counts.data(), smoothing, nullptr, 0,
+                                                   &size, nullptr));
+    std::vector<uint8_t> out(size);
+    tools_detail::check(forest, rvseg_forest_refit(forest, X, P, D, labels, (int32_t)class_counts.size(), class_counts.data(), smoothing, out.data(),
+                                                   out.size(), &size, nullptr));
+    return out;
+}
+
 }  // namespace rvseg
 #endif

@@ -11,11 +11,12 @@ from .segmenter import (BoostedRandomForest, Context, DenseCRF, Evaluator, Featu
                         RgbLabelConversion, Segmenter, PottsCompatibility, DiagonalCompatibility, MatrixCompatibility,
                         CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL, NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER,
                         NORMALIZE_SYMMETRIC, LogLikelihood, Hamming, IntersectionOverUnion, CRFEnergy, CRFKernelEnergy,
-                        minimizeLBFGS, numericGradient, gradCheck)
+                        minimizeLBFGS, numericGradient, gradCheck, AccuracyTool, ConfusionMatrixTool, CorrelationTool)
 from . import synthetic  # noqa: F401
 
 __all__ = ["capi", "BoostedRandomForest", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
            "RgbLabelConversion", "Evaluator", "PottsCompatibility", "DiagonalCompatibility", "MatrixCompatibility",
            "CONST_KERNEL", "DIAG_KERNEL", "FULL_KERNEL", "NO_NORMALIZATION", "NORMALIZE_BEFORE", "NORMALIZE_AFTER",
            "NORMALIZE_SYMMETRIC", "projection_matrix", "LogLikelihood", "Hamming", "IntersectionOverUnion",
-           "CRFEnergy", "CRFKernelEnergy", "minimizeLBFGS", "numericGradient", "gradCheck"]
+           "CRFEnergy", "CRFKernelEnergy", "minimizeLBFGS", "numericGradient", "gradCheck", "AccuracyTool", "ConfusionMatrixTool",
+           "CorrelationTool"]

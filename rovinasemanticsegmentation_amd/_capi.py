@@ -66,6 +66,8 @@ SYMBOLS = [
     "rvseg_crf_model_info",
     "rvseg_boosted_check", "rvseg_boosted_rewrite", "rvseg_boosted_load", "rvseg_boosted_load_mem", "rvseg_boosted_write",
     "rvseg_boosted_write_mem", "rvseg_boosted_weights", "rvseg_boosted_train", "rvseg_boosted_train_result", "rvseg_boosted_resample",
+    "rvseg_forest_classify", "rvseg_forest_classify_trees", "rvseg_forest_measure", "rvseg_forest_tools_scores",
+    "rvseg_forest_tools_correlation", "rvseg_forest_refit",
 ]
 BOOSTED_WEIGHT_FIRST, BOOSTED_TREE_FIRST, BOOSTED_AS_LOADED = 0, 1, -1   # rvseg_boosted_order
 # rvseg_lbfgs_status
@@ -313,6 +315,12 @@ def lib():
     L.rvseg_project_cloud_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
     L.rvseg_process_map_poses_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.rvseg_projection_matrix.argtypes = [vp, vp, vp, vp]
+    L.rvseg_forest_classify.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.rvseg_forest_classify_trees.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.rvseg_forest_measure.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.rvseg_forest_tools_scores.argtypes = [vp, i32, C.POINTER(f32), vp]
+    L.rvseg_forest_tools_correlation.argtypes = [vp, i32, C.c_uint64, vp]
+    L.rvseg_forest_refit.argtypes = [vp, vp, i32, i32, vp, i32, vp, f32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
     L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
     L.rvseg_debug_live_resources.restype = None
@@ -463,6 +471,35 @@ def eval_scores_from_counts(counts):
     if st != OK:
         raise RvsegError(st, lib().rvseg_status_string(st).decode())
     return {"global_acc": g.value, "class_avg_acc": a.value, "iou": u.value, "row_pct": row}
+
+
+def forest_tools_scores(confusion):
+    """Host-only (no GPU): AccuracyTool's and ConfusionMatrixTool's floats (tools.cpp:77, 126-135) from C x C uint64
+    counts [true][predicted].  Returns (accuracy float32, normalised matrix float32 C x C; a class without examples is a
+    NaN row, as in the reference)."""
+    import numpy as np
+    counts = np.ascontiguousarray(confusion, np.uint64)
+    Cn = counts.shape[0]
+    assert counts.shape == (Cn, Cn)
+    acc = C.c_float()
+    norm = np.empty((Cn, Cn), np.float32)
+    st = lib().rvseg_forest_tools_scores(counts.ctypes.data_as(C.c_void_p), Cn, C.byref(acc), norm.ctypes.data_as(C.c_void_p))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    return np.float32(acc.value), norm
+
+
+def forest_tools_correlation(agree, P):
+    """Host-only (no GPU): CorrelationTool's matrix (tools.cpp:226-228) from T x T uint64 agreement counts over P points."""
+    import numpy as np
+    agree = np.ascontiguousarray(agree, np.uint64)
+    T = agree.shape[0]
+    assert agree.shape == (T, T)
+    out = np.empty((T, T), np.float32)
+    st = lib().rvseg_forest_tools_correlation(agree.ctypes.data_as(C.c_void_p), T, int(P), out.ctypes.data_as(C.c_void_p))
+    if st != OK:
+        raise RvsegError(st, lib().rvseg_status_string(st).decode())
+    return out
 
 
 def minimize_lbfgs(fun, x0, progress=None, **params):

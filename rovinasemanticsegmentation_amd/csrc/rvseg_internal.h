@@ -109,6 +109,15 @@ struct StageTimer {
     bool side_used = false;
 };
 
+// scratch of the forest tools (rvseg_forest_tools.hip), sized by a chunk of points and the loaded model; grow-only
+struct ToolsScratch {
+    DevBuf X, labels;               // one chunk of points and of their labels
+    DevBuf rows, votes, pred;       // [T][chunk] leaf rows and votes, [chunk] forest labels
+    DevBuf vote_table;              // [n_leaves] vote label per leaf row
+    DevBuf agree, confusion, flag;  // [T][T] and [C][C] 64-bit counters, the bad-label flag word
+    DevBuf leaf_cnt;                // [n_leaves][sum of the refit's classes]
+};
+
 struct Pipeline;    // state of the frame / CRF / fusion pipelines (rvseg_pipeline.h)
 struct EvalState;   // colour codings + confusion counters of the scoring calls (kernels_eval.hip)
 
@@ -132,6 +141,7 @@ struct rvseg_ctx {
     void* comm = nullptr;  // RCCL communicator of the local-map gather (rvseg_comm.cpp), or null
     int comm_rank = 0, comm_world = 0;
     rvseg::EvalState* eval = nullptr;     // allocated by the first scoring call; discarded by rvseg_forest_load
+    rvseg::ToolsScratch tools;            // rvseg_forest_classify / _measure / _refit
 };
 
 namespace rvseg {

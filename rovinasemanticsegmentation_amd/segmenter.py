@@ -239,6 +239,55 @@ class Context:
         capi.check(self.h, self.L.rvseg_forest_eval(self.h, _ptr(X), P, D, _ptr(out)))
         return out
 
+    # ---- forest tools (libforest tools.h; updateHistograms) --------------------------------------
+    def forest_classify(self, X, layer=0):
+        """rvseg_forest_classify: Classifier::classify on every row of X for the loaded model -> int32 (P,)."""
+        X = np.ascontiguousarray(X, np.float32)
+        P, D = X.shape
+        out = np.empty(P, np.int32)
+        capi.check(self.h, self.L.rvseg_forest_classify(self.h, _ptr(X), P, D, layer, _ptr(out)))
+        return out
+
+    def forest_classify_trees(self, X, layer=0):
+        """rvseg_forest_classify_trees: every tree's own vote -> uint8 (T, P)."""
+        X = np.ascontiguousarray(X, np.float32)
+        P, D = X.shape
+        out = np.empty((self.forest_info()["n_trees"], P), np.uint8)
+        capi.check(self.h, self.L.rvseg_forest_classify_trees(self.h, _ptr(X), P, D, layer, _ptr(out)))
+        return out
+
+    def forest_measure(self, X, labels=None, layer=0, want=("pred", "confusion", "agree")):
+        """rvseg_forest_measure in one pass: dict(pred int32 (P,), confusion uint64 (C, C) [true][predicted], agree uint64
+        (T, T)).  Only the outputs named in `want` are computed; the others, and the confusion without labels, are None."""
+        X = np.ascontiguousarray(X, np.float32)
+        P, D = X.shape
+        info = self.forest_info()
+        T, Cn = info["n_trees"], (info["class_counts"][layer] if 0 <= layer < len(info["class_counts"]) else 1)
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        assert lab is None or lab.shape == (P,)
+        pred = np.empty(P, np.int32) if "pred" in want else None
+        agree = np.empty((T, T), np.uint64) if "agree" in want else None
+        conf = np.empty((Cn, Cn), np.uint64) if "confusion" in want and lab is not None else None
+        capi.check(self.h, self.L.rvseg_forest_measure(self.h, _ptr(X), P, D, _ptr(lab), layer, _ptr(pred), _ptr(conf), _ptr(agree)))
+        return {"pred": pred, "confusion": conf, "agree": agree}
+
+    def forest_refit(self, X, labels, class_counts, smoothing=1.0, return_counts=False):
+        """rvseg_forest_refit: the loaded forest with its leaves re-estimated from (X, labels (P, L)).  Returns the
+        forest.dat bytes, or (bytes, counts uint32 (n_nodes, sumC)) with return_counts.  The loaded model stays."""
+        X = np.ascontiguousarray(X, np.float32)
+        labels = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(X.shape[0], -1))
+        P, D = X.shape
+        L = labels.shape[1]
+        assert len(class_counts) == L
+        cc = (C.c_int32 * L)(*class_counts)
+        size = C.c_size_t()
+        capi.check(self.h, self.L.rvseg_forest_refit(self.h, _ptr(X), P, D, _ptr(labels), L, cc, smoothing, None, 0, C.byref(size), None))
+        buf = C.create_string_buffer(size.value)
+        counts = np.empty((self.forest_info()["n_nodes"], sum(class_counts)), np.uint32) if return_counts else None
+        capi.check(self.h, self.L.rvseg_forest_refit(self.h, _ptr(X), P, D, _ptr(labels), L, cc, smoothing, buf, size.value, C.byref(size),
+                                                     _ptr(counts)))
+        return (buf.raw[:size.value], counts) if return_counts else buf.raw[:size.value]
+
     # ---- features ----------------------------------------------------------------------------
     def extract_features(self, rgb, depth, calib):
         p = self.params
@@ -913,6 +962,14 @@ class RandomForest:
         offs = np.cumsum([0] + cc)
         return [out[:, offs[i]:offs[i + 1]] for i in range(len(cc))]
 
+    def classify(self, X, layer=0):  # Classifier::classify(DataStorage), classifier.cpp:29-62, on the device
+        return self.ctx.forest_classify(np.atleast_2d(X), layer)
+
+    def updateHistograms(self, X, labels, class_counts, smoothing=1.0):
+        """DecisionTreeLearner::updateHistograms / updateMultiHistograms (learning.cpp:918-1012) on every tree: returns
+        the forest.dat bytes of the same trees with their leaves re-estimated; read() them to use them."""
+        return self.ctx.forest_refit(X, labels, class_counts, smoothing)
+
 
 class BoostedRandomForest:
     """libf::BoostedRandomForest (classifiers.h:349-425) on a context with multi_layer=0."""
@@ -944,6 +1001,67 @@ class BoostedRandomForest:
             label[win] = c
             best[win] = post[win, c]
         return label
+
+
+# libforest tools.h: `classifier` / `forest` is a RandomForest or BoostedRandomForest wrapper; X (P, D), labels (P,).  The
+# counts come from the device in one pass (Context.forest_measure), the floats from the reference's arithmetic on them.
+class AccuracyTool:
+    """libf::AccuracyTool (tools.cpp:61-89)."""
+
+    def measure(self, classifier, X, labels, layer=0):
+        return capi.forest_tools_scores(classifier.ctx.forest_measure(np.atleast_2d(X), labels, layer, want=("confusion",))["confusion"])[0]
+
+    def format(self, accuracy):
+        return "Accuracy: %2.2f%% (Error: %2.2f%%)\n" % (accuracy * 100, (1 - accuracy) * 100)
+
+    def print(self, accuracy):
+        print(self.format(accuracy), end="")
+
+    def measureAndPrint(self, classifier, X, labels, layer=0):
+        self.print(self.measure(classifier, X, labels, layer))
+
+
+class ConfusionMatrixTool:
+    """libf::ConfusionMatrixTool (tools.cpp:95-186): rows are true classes, a class without examples is a NaN row."""
+
+    def measure(self, classifier, X, labels, layer=0):
+        return capi.forest_tools_scores(classifier.ctx.forest_measure(np.atleast_2d(X), labels, layer, want=("confusion",))["confusion"])[1]
+
+    def format(self, result):  # tools.cpp:140-179 without the colour codes
+        n = len(result)
+        rule = "--------|" * (n + 1) + "\n"
+        out = "        |" + "".join(" %6d |" % c for c in range(n)) + "\n" + rule
+        for c in range(n):
+            out += " %6d |" % c + "".join(" %5.2f%% |" % (result[c][cc] * 100) for cc in range(n)) + "\n" + rule
+        return out
+
+    def print(self, result):
+        print(self.format(result), end="")
+
+    def measureAndPrint(self, classifier, X, labels, layer=0):
+        self.print(self.measure(classifier, X, labels, layer))
+
+
+class CorrelationTool:
+    """libf::CorrelationTool (tools.cpp:192-263): per tree pair, 1 - the normalised Hamming distance of their votes."""
+
+    def measure(self, forest, X, layer=0):
+        X = np.atleast_2d(X)
+        return capi.forest_tools_correlation(forest.ctx.forest_measure(X, None, layer, want=("agree",))["agree"], X.shape[0])
+
+    def format(self, result):  # tools.cpp:233-263
+        n = len(result)
+        rule = "---------|" * (n + 1) + "\n"
+        out = "         |" + "".join(" %7d |" % c for c in range(n)) + "\n" + rule
+        for c in range(n):
+            out += " %7d |" % c + "".join(" %6.2f%% |" % (result[c][cc] * 100) for cc in range(n)) + "\n" + rule
+        return out
+
+    def print(self, result):
+        print(self.format(result), end="")
+
+    def measureAndPrint(self, forest, X, layer=0):
+        self.print(self.measure(forest, X, layer))
 
 
 class FeatureExtractor:
