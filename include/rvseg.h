@@ -302,6 +302,66 @@ rvseg_status rvseg_forest_refit(rvseg_ctx *ctx, const float *X, int32_t P, int32
                                 const int32_t *class_counts, float smoothing, void *forest_out, size_t out_cap,
                                 size_t *size_out, uint32_t *counts_out);
 
+/* ---- forest pruning: replaces RandomForestPrune::prune (libforest todos.txt:310-350) and the simulated-annealing driver
+ *      it is written against (mcmc.h:147-240, GeometricCoolingSchedule :272-346) for the loaded RandomForest.  A state is
+ *      a list of 1 .. RVSEG_PRUNE_MAX_STATE tree indices, duplicates allowed.  X, P, D and `layer` as for the forest
+ *      tools above.  The chain, in fp32 as written there: while (temperature > end) { iteration++; temperature *= alpha;
+ *      inner_loops proposals; one trace row }; improvement = new energy - current energy; accepted when improvement <= 0,
+ *      else when logf(u) <= -improvement / temperature; the best state is updated after every proposal and is the result.
+ *      Build-owned, where the reference draws from std::random_device: step s (counted over the whole run) draws
+ *      d_k = draw64(mix64(seed ^ mix64(0x7072756E)), 4 s + k) (train_host.h) for slot k = 0 move choice, 1 tree, 2
+ *      position, 3 acceptance; a uniform is (float)(d >> 40) * 2^-24, an index below n is d % n.  Moves are registered in
+ *      the order exchange, remove, add, those with probability > 0 only, and chosen by the probSum scan of mcmc.h:178-198
+ *      (no match: the last registered).  Exchange (todos.txt:134-166): state[d_2 % |state|] = d_1 % T.  Remove (:51-93):
+ *      drops entry d_2 % |state|; a one-tree state is copied.  Add (:103-129): appends d_1 % T; a state already at
+ *      RVSEG_PRUNE_MAX_STATE is copied, which is this build's own rule.
+ *      RVSEG_PRUNE_ERROR (PruneEnergy, todos.txt:186-226): per point the trees of the state vote in order, the label is
+ *      the first whose count exceeds the running maximum (label 0 with 0 votes to start), a point whose label differs --
+ *      any label outside [0, C) does -- is an error; energy = (float)min(errors, 2^24) / (float)P.  The layer may have at
+ *      most 16 classes.  The votes of every tree stay on the device for the whole call and every proposal is one kernel;
+ *      the host is not waited for until the last.  RVSEG_PRUNE_COVER (the second PruneEnergy, todos.txt:245-297):
+ *      dist[i][j] = P - agree[i][j] (rvseg_forest_measure), energy = (float)(sum over trees j of the least dist[i][j]
+ *      over the state's i) / (float)|state|; the chain then runs on the host over the T x T counts. */
+#define RVSEG_PRUNE_MAX_STATE 64
+typedef enum { RVSEG_PRUNE_ERROR = 0, RVSEG_PRUNE_COVER = 1 } rvseg_prune_energy;
+typedef struct rvseg_prune_params {
+    float start_temperature;          /* todos.txt:319 (100)                                                  */
+    float end_temperature;            /* todos.txt:320 (1e-5)                                                 */
+    float alpha;                      /* todos.txt:318 (0.95), in (0, 1)                                      */
+    int32_t inner_loops;              /* todos.txt:314 (250)                                                  */
+    float p_exchange, p_remove, p_add; /* todos.txt:324-325 (1, 0, 0): >= 0, not all zero                     */
+    int32_t energy;                   /* rvseg_prune_energy; default RVSEG_PRUNE_ERROR (todos.txt:328)        */
+    uint64_t seed;
+} rvseg_prune_params;
+typedef struct rvseg_prune_trace_row {   /* the arguments of PruneCallback::callback, todos.txt:34-44 */
+    int32_t iteration;
+    float temperature, energy, best_energy;
+    int32_t state_size;
+} rvseg_prune_trace_row;
+void rvseg_prune_params_default(rvseg_prune_params *pp);
+/* Host only: the temperature iterations of a schedule, counted by running its fp32 loop, and its proposals
+ * (iterations x inner_loops).  RVSEG_ERR_INVALID_ARG for what rvseg_forest_prune refuses in `pp`. */
+rvseg_status rvseg_prune_schedule(const rvseg_prune_params *pp, int32_t *iterations_out, int32_t *steps_out);
+/* state_inout (capacity RVSEG_PRUNE_MAX_STATE) / n_state_inout: the initial state in, the best state out.  trace_out
+ * (optional, trace_cap rows): one row per temperature iteration, the first trace_cap of them; n_trace_out (optional):
+ * the iterations run.  step_kind_out (optional, one byte per proposal): 0 rejected, 1 accepted with improvement <= 0,
+ * 2 accepted uphill.  Refused with RVSEG_ERR_INVALID_ARG, outputs untouched: a boosted model, an empty or over-long
+ * state or a tree index outside [0, T), alpha outside (0, 1), inner_loops < 1, a negative or all-zero move probability,
+ * a schedule of more than 2^22 proposals, a layer out of range or, for RVSEG_PRUNE_ERROR, of more than 16 classes.
+ * start_temperature <= end_temperature runs no iteration and returns the initial state with its energy. */
+rvseg_status rvseg_forest_prune(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t layer,
+                                const rvseg_prune_params *pp, int32_t *state_inout, int32_t *n_state_inout,
+                                float *best_energy_out, rvseg_prune_trace_row *trace_out, int32_t trace_cap,
+                                int32_t *n_trace_out, uint8_t *step_kind_out);
+/* The energy of one state.  labels may be NULL for RVSEG_PRUNE_COVER. */
+rvseg_status rvseg_forest_prune_energy(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels,
+                                       int32_t layer, int32_t energy, const int32_t *state, int32_t n_state,
+                                       float *energy_out);
+/* The context's model becomes the forest of trees state[0 .. n_state) of the loaded one, in that order, duplicates
+ * included (newForest->addTree, todos.txt:344-348); rvseg_forest_write then emits it.  At most 64 entries, the loader's
+ * limit.  A refused call keeps the model. */
+rvseg_status rvseg_forest_prune_apply(rvseg_ctx *ctx, const int32_t *state, int32_t n_state);
+
 /* ---- features: replaces Features::FeatureExtractor::extract, NO_LABEL branch
  *      (include/feature_extractor.h:41-291).  Host buffers, one frame.  feat_out: capacity
  *      (H/stride+1)*(W/stride+1) x D floats; x_v / y_v same capacity.  Exists for parity tests:

@@ -1537,5 +1537,43 @@ inline std::vector<uint8_t> refit(rvseg_ctx* forest, const float* X, int P, int 
     return out;
 }
 
+// libf::RandomForestPrune (todos.txt:12-18, 310-350) on the RandomForest a context has loaded: simulated annealing
+// (mcmc.h:147-240) over lists of its trees.  `params` holds the reference's settings (the 100 -> 1e-5 schedule at alpha
+// 0.95 with 250 inner loops, the exchange move, the error energy) until changed.
+class RandomForestPrune {
+public:
+    rvseg_prune_params params;
+    std::vector<rvseg_prune_trace_row> trace;   // the last run's rows: what PruneCallback printed (todos.txt:34-44)
+    RandomForestPrune() { rvseg_prune_params_default(&params); }
+    // the best state found from `state` (empty: trees 0 .. min(15, T) - 1, todos.txt:336-340); the model is left as it is
+    std::vector<int32_t> optimize(rvseg_ctx* forest, const float* X, int P, int D, const int32_t* labels, int layer = 0,
+                                  std::vector<int32_t> state = {}, float* best_energy = nullptr) {
+        int T = 0;
+        tools_detail::class_count(forest, layer, &T);
+        if (state.empty())
+            for (int i = 0; i < 15 && i < T; i++) state.push_back(i);
+        int32_t n = (int32_t)state.size(), iterations = 0, n_trace = 0;
+        if (n > RVSEG_PRUNE_MAX_STATE) throw std::runtime_error("state longer than 64 entries");
+        state.resize(RVSEG_PRUNE_MAX_STATE);
+        if (rvseg_prune_schedule(&params, &iterations, nullptr) != RVSEG_OK) iterations = 0;   // rvseg_forest_prune says why
+        trace.assign((size_t)iterations, rvseg_prune_trace_row());
+        tools_detail::check(forest, rvseg_forest_prune(forest, X, P, D, labels, layer, &params, state.data(), &n, best_energy, trace.data(), iterations,
+                                                       &n_trace, nullptr));
+        state.resize((size_t)n);
+        return state;
+    }
+    // RandomForestPrune::prune: optimize, then the context's model becomes the forest of the best state's trees
+    // (todos.txt:343-349).  Returns that state.
+    std::vector<int32_t> prune(rvseg_ctx* forest, const float* X, int P, int D, const int32_t* labels, int layer = 0, std::vector<int32_t> state = {}) {
+        const std::vector<int32_t> best = optimize(forest, X, P, D, labels, layer, std::move(state));
+        tools_detail::check(forest, rvseg_forest_prune_apply(forest, best.data(), (int32_t)best.size()));
+        return best;
+    }
+    void print() const {   // PruneCallback::callback per row
+        for (const rvseg_prune_trace_row& r : trace)
+            std::printf("iteration: %d energy: %g best: %g temp: %g state: %d\n", r.iteration, r.energy, r.best_energy, r.temperature, r.state_size);
+    }
+};
+
 }  // namespace rvseg
 #endif

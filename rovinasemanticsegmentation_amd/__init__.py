@@ -11,7 +11,7 @@ from .segmenter import (BoostedRandomForest, Context, DenseCRF, Evaluator, Featu
                         RgbLabelConversion, Segmenter, PottsCompatibility, DiagonalCompatibility, MatrixCompatibility,
                         CONST_KERNEL, DIAG_KERNEL, FULL_KERNEL, NO_NORMALIZATION, NORMALIZE_BEFORE, NORMALIZE_AFTER,
                         NORMALIZE_SYMMETRIC, LogLikelihood, Hamming, IntersectionOverUnion, CRFEnergy, CRFKernelEnergy,
-                        minimizeLBFGS, numericGradient, gradCheck, AccuracyTool, ConfusionMatrixTool, CorrelationTool)
+                        minimizeLBFGS, numericGradient, gradCheck, AccuracyTool, ConfusionMatrixTool, CorrelationTool, RandomForestPrune)
 from . import synthetic  # noqa: F401
 
 __all__ = ["capi", "BoostedRandomForest", "Context", "DenseCRF", "FeatureExtractor", "LocalMapStore", "RandomForest", "Segmenter", "synthetic",
@@ -19,4 +19,4 @@ __all__ = ["capi", "BoostedRandomForest", "Context", "DenseCRF", "FeatureExtract
            "CONST_KERNEL", "DIAG_KERNEL", "FULL_KERNEL", "NO_NORMALIZATION", "NORMALIZE_BEFORE", "NORMALIZE_AFTER",
            "NORMALIZE_SYMMETRIC", "projection_matrix", "LogLikelihood", "Hamming", "IntersectionOverUnion",
            "CRFEnergy", "CRFKernelEnergy", "minimizeLBFGS", "numericGradient", "gradCheck", "AccuracyTool", "ConfusionMatrixTool",
-           "CorrelationTool"]
+           "CorrelationTool", "RandomForestPrune"]

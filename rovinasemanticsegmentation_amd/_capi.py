@@ -68,7 +68,10 @@ SYMBOLS = [
     "rvseg_boosted_write_mem", "rvseg_boosted_weights", "rvseg_boosted_train", "rvseg_boosted_train_result", "rvseg_boosted_resample",
     "rvseg_forest_classify", "rvseg_forest_classify_trees", "rvseg_forest_measure", "rvseg_forest_tools_scores",
     "rvseg_forest_tools_correlation", "rvseg_forest_refit",
+    "rvseg_prune_params_default", "rvseg_prune_schedule", "rvseg_forest_prune", "rvseg_forest_prune_energy", "rvseg_forest_prune_apply",
 ]
+PRUNE_ERROR, PRUNE_COVER = 0, 1   # rvseg_prune_energy
+PRUNE_MAX_STATE = 64
 BOOSTED_WEIGHT_FIRST, BOOSTED_TREE_FIRST, BOOSTED_AS_LOADED = 0, 1, -1   # rvseg_boosted_order
 # rvseg_lbfgs_status
 LBFGS_CONVERGED, LBFGS_MAX_ITERATIONS, LBFGS_STOPPED, LBFGS_LINESEARCH_FAILED, LBFGS_NOT_FINITE, LBFGS_BAD_ARGUMENTS = 0, 1, 2, 3, -1, -2
@@ -98,6 +101,20 @@ class RvsegTrainParams(C.Structure):
         ("min_child_split_examples", C.c_int32), ("num_features", C.c_int32), ("use_bootstrap", C.c_int32),
         ("smoothing", C.c_float), ("seed", C.c_uint64),
     ]
+
+
+class RvsegPruneParams(C.Structure):
+    """rvseg_prune_params: the schedule, the move probabilities and the energy of rvseg_forest_prune."""
+    _fields_ = [
+        ("start_temperature", C.c_float), ("end_temperature", C.c_float), ("alpha", C.c_float), ("inner_loops", C.c_int32),
+        ("p_exchange", C.c_float), ("p_remove", C.c_float), ("p_add", C.c_float), ("energy", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
+class RvsegPruneTraceRow(C.Structure):
+    """rvseg_prune_trace_row: what the reference's callback sees after every temperature iteration."""
+    _fields_ = [("iteration", C.c_int32), ("temperature", C.c_float), ("energy", C.c_float), ("best_energy", C.c_float),
+                ("state_size", C.c_int32)]
 
 
 class RvsegSchedule(C.Structure):
@@ -321,6 +338,13 @@ def lib():
     L.rvseg_forest_tools_scores.argtypes = [vp, i32, C.POINTER(f32), vp]
     L.rvseg_forest_tools_correlation.argtypes = [vp, i32, C.c_uint64, vp]
     L.rvseg_forest_refit.argtypes = [vp, vp, i32, i32, vp, i32, vp, f32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.rvseg_prune_params_default.argtypes = [C.POINTER(RvsegPruneParams)]
+    L.rvseg_prune_params_default.restype = None
+    L.rvseg_prune_schedule.argtypes = [C.POINTER(RvsegPruneParams), C.POINTER(i32), C.POINTER(i32)]
+    L.rvseg_forest_prune.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(RvsegPruneParams), vp, C.POINTER(i32), C.POINTER(f32), vp, i32,
+                                     C.POINTER(i32), vp]
+    L.rvseg_forest_prune_energy.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, i32, C.POINTER(f32)]
+    L.rvseg_forest_prune_apply.argtypes = [vp, vp, i32]
     # debug entry point (not in include/rvseg.h, not in SYMBOLS): see debug_live_resources
     L.rvseg_debug_live_resources.argtypes = [C.POINTER(C.c_longlong)]
     L.rvseg_debug_live_resources.restype = None
@@ -341,6 +365,26 @@ def default_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def prune_params(**kw):
+    """rvseg_prune_params with the reference's defaults (todos.txt:313-329), fields overridden by keyword."""
+    p = RvsegPruneParams()
+    lib().rvseg_prune_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("rvseg_prune_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def prune_schedule(params):
+    """Host only: (temperature iterations, proposals) of a schedule; RvsegError where rvseg_forest_prune refuses it."""
+    it, steps = C.c_int32(), C.c_int32()
+    st = lib().rvseg_prune_schedule(C.byref(params), C.byref(it), C.byref(steps))
+    if st != OK:
+        raise RvsegError(st, "refused prune schedule")
+    return it.value, steps.value
 
 
 def check(ctx, status):

@@ -24,9 +24,6 @@
 #include "rvseg_kernels.h"
 
 namespace rvseg {
-namespace {
-
-struct LayerView { int off = 0, C = 0; };   // the layer's classes inside a leaf row of the active mode
 
 // what every tools call checks first; the order of the refusals is the header's
 rvseg_status check_points(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D) {
@@ -69,6 +66,8 @@ rvseg_status upload_vote_table(rvseg_ctx* ctx, int layer, hipStream_t s) {
     RV_HIP(ctx, hipStreamSynchronize(s));   // `table` goes out of scope
     return RVSEG_OK;
 }
+
+namespace {
 
 // what a pass over X produces; null = not wanted.  Host pointers.
 struct ToolsOut {

@@ -118,6 +118,13 @@ struct ToolsScratch {
     DevBuf leaf_cnt;                // [n_leaves][sum of the refit's classes]
 };
 
+// scratch of rvseg_forest_prune (rvseg_prune.hip), sized by the whole point set and the schedule; grow-only
+struct PruneScratch {
+    DevBuf votes, labels;           // [T][stride] votes and [stride] labels of all P points
+    DevBuf steps, control;          // [steps] PruneStep, one PruneControl
+    DevBuf step_kind, trace;        // [steps] bytes, [iterations] rows
+};
+
 struct Pipeline;    // state of the frame / CRF / fusion pipelines (rvseg_pipeline.h)
 struct EvalState;   // colour codings + confusion counters of the scoring calls (kernels_eval.hip)
 
@@ -142,6 +149,7 @@ struct rvseg_ctx {
     int comm_rank = 0, comm_world = 0;
     rvseg::EvalState* eval = nullptr;     // allocated by the first scoring call; discarded by rvseg_forest_load
     rvseg::ToolsScratch tools;            // rvseg_forest_classify / _measure / _refit
+    rvseg::PruneScratch prune;            // rvseg_forest_prune / _prune_energy
 };
 
 namespace rvseg {
@@ -171,6 +179,14 @@ rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 
 // the stream of a device entry point: the caller's, or the context's own when the caller passes none
 inline hipStream_t stream_of(const rvseg_ctx* ctx, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : ctx->stream; }
+
+// ---- rvseg_forest_tools.hip: what every call on a data set checks first, and the per-leaf vote labels of a layer
+// (ctx->tools.vote_table) that launch_tools_votes reads -- shared with rvseg_prune.hip -------------------------------
+struct LayerView { int off = 0, C = 0; };   // the layer's classes inside a leaf row of the active mode
+rvseg_status check_points(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D);
+rvseg_status layer_of(rvseg_ctx* ctx, int32_t layer, LayerView& v);
+rvseg_status upload_vote_table(rvseg_ctx* ctx, int layer, hipStream_t s);
+int count_blocks(rvseg_ctx* ctx);   // grids that loop: a few blocks per compute unit
 
 // ---- kernels_eval.hip: frees the scoring state (waits for its pending work first) -----------------------------
 void eval_destroy(rvseg_ctx* ctx);

@@ -65,6 +65,26 @@ void launch_tools_confusion(const int32_t* d_labels, const int32_t* d_pred, int 
 void launch_tools_refit_count(const int32_t* d_rows, const int32_t* d_labels, int n_trees, int n, int stride, const RefitLayers& lay,
                               int max_blocks, uint32_t* d_counts, int* d_flag, hipStream_t s);
 
+// ---- kernels_prune.hip -----------------------------------------------------------------------
+// The simulated-annealing chain of rvseg_forest_prune, one launch per proposal (rules: prune_host.h).  d_votes is
+// [T][stride] bytes and d_labels [stride], stride a multiple of 4 and the tails beyond P zero.  What the chain carries
+// from launch to launch lives in one PruneControl on the device; errors and ticket are zero between launches.
+struct PruneStep;   // prune_host.h
+struct PruneControl {
+    unsigned errors, ticket;                          // this launch's error count; blocks that have added theirs
+    int32_t n_state[2], n_best;
+    float cur_energy, best_energy;
+    int32_t pad;
+    int32_t state[2][RVSEG_PRUNE_MAX_STATE];          // step s reads state[s & 1] and writes state[(s + 1) & 1]
+    int32_t best[RVSEG_PRUNE_MAX_STATE];
+};
+int prune_grid(int P, int max_blocks);
+// state[0] / n_state[0] -> its energy as cur_energy and best_energy, itself as the best state
+void launch_prune_init(const uint8_t* d_votes, const int32_t* d_labels, int P, size_t stride, int grid, PruneControl* d_ctl, hipStream_t s);
+// steps first_step .. first_step + n_steps - 1, back to back; d_step_kind [all steps], d_trace [all iterations]
+void launch_prune_steps(const uint8_t* d_votes, const int32_t* d_labels, int P, size_t stride, int grid, const PruneStep* d_steps,
+                        int first_step, int n_steps, PruneControl* d_ctl, uint8_t* d_step_kind, rvseg_prune_trace_row* d_trace, hipStream_t s);
+
 // ---- kernels_rf.hip --------------------------------------------------------------------------
 // The frame path: per-point features computed on demand + forest traversal over the stride grid of n frames.
 //   d_low   : n x (lh*lw*S) low-resolution log-posteriors, layers concatenated per frame, each

@@ -288,6 +288,54 @@ class Context:
                                                      _ptr(counts)))
         return (buf.raw[:size.value], counts) if return_counts else buf.raw[:size.value]
 
+    # ---- forest pruning (libforest todos.txt: RandomForestPrune over mcmc.h's simulated annealing) ----
+    def _prune_state(self, state):
+        """state -> int32 array; None: trees 0 .. min(15, T) - 1, the reference's initial state (todos.txt:336-340)."""
+        if state is None:
+            state = range(min(15, self.forest_info()["n_trees"]))
+        return np.ascontiguousarray(np.asarray(list(state), np.int32).reshape(-1))
+
+    def forest_prune(self, X, labels=None, layer=0, state=None, params=None, **kw):
+        """rvseg_forest_prune: simulated annealing over lists of the loaded forest's trees.  params: a
+        capi.RvsegPruneParams, or its fields by keyword over the reference's defaults.  Returns dict(state int32 (the best
+        state), best_energy float32, trace (structured: iteration, temperature, energy, best_energy, state_size -- one row
+        per temperature iteration), step_kind uint8 (one per proposal: 0 rejected, 1 accepted, 2 accepted uphill))."""
+        X = np.ascontiguousarray(X, np.float32)
+        P, D = X.shape
+        pp = params if params is not None else capi.prune_params(**kw)
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        assert lab is None or lab.shape == (P,)
+        first = self._prune_state(state)
+        buf = np.zeros(capi.PRUNE_MAX_STATE, np.int32)
+        n = C.c_int32(min(first.size, capi.PRUNE_MAX_STATE + 1))
+        buf[:min(first.size, capi.PRUNE_MAX_STATE)] = first[:capi.PRUNE_MAX_STATE]
+        try:
+            iterations, steps = capi.prune_schedule(pp)
+        except capi.RvsegError:
+            iterations, steps = 0, 0          # the call below refuses it, with the library's message
+        trace = np.zeros(iterations, np.dtype([("iteration", np.int32), ("temperature", np.float32), ("energy", np.float32),
+                                               ("best_energy", np.float32), ("state_size", np.int32)]))
+        kinds = np.zeros(steps, np.uint8)
+        best, n_trace = C.c_float(), C.c_int32()
+        capi.check(self.h, self.L.rvseg_forest_prune(self.h, _ptr(X), P, D, _ptr(lab), layer, C.byref(pp), _ptr(buf), C.byref(n), C.byref(best),
+                                                     _ptr(trace), iterations, C.byref(n_trace), _ptr(kinds)))
+        return {"state": buf[:n.value].copy(), "best_energy": np.float32(best.value), "trace": trace[:n_trace.value], "step_kind": kinds}
+
+    def forest_prune_energy(self, X, labels, state, layer=0, energy=capi.PRUNE_ERROR):
+        """rvseg_forest_prune_energy: the energy of one state (a list of tree indices) -> float32."""
+        X = np.ascontiguousarray(X, np.float32)
+        P, D = X.shape
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        state = self._prune_state(state)
+        out = C.c_float()
+        capi.check(self.h, self.L.rvseg_forest_prune_energy(self.h, _ptr(X), P, D, _ptr(lab), layer, energy, _ptr(state), state.size, C.byref(out)))
+        return np.float32(out.value)
+
+    def forest_prune_apply(self, state):
+        """rvseg_forest_prune_apply: the context's model becomes the forest of those trees, in that order."""
+        state = self._prune_state(state)
+        capi.check(self.h, self.L.rvseg_forest_prune_apply(self.h, _ptr(state), state.size))
+
     # ---- features ----------------------------------------------------------------------------
     def extract_features(self, rgb, depth, calib):
         p = self.params
@@ -1062,6 +1110,30 @@ class CorrelationTool:
 
     def measureAndPrint(self, forest, X, layer=0):
         self.print(self.measure(forest, X, layer))
+
+
+class RandomForestPrune:
+    """libf::RandomForestPrune (todos.txt:12-18, 310-350): simulated annealing over the trees of a forest.  The settings
+    are rvseg_prune_params' (the reference's schedule, the exchange move and the error energy by default); `trace` holds
+    the rows of the last run, which format() prints the way PruneCallback does."""
+
+    def __init__(self, **params):
+        self.params = params
+        self.trace = None
+        self.state = None
+
+    def prune(self, forest, X, labels, layer=0, state=None):
+        """Prunes forest (a RandomForest wrapper) on (X, labels): its context's model becomes the forest of the best
+        state's trees (todos.txt:343-349), which forest.write() then emits.  Returns forest."""
+        run = forest.ctx.forest_prune(np.atleast_2d(X), labels, layer, state, **self.params)
+        self.trace, self.state = run["trace"], run["state"]
+        forest.ctx.forest_prune_apply(run["state"])
+        return forest
+
+    def format(self, trace=None):  # PruneCallback::callback, todos.txt:36-41
+        rows = self.trace if trace is None else trace
+        return "".join("iteration: %d energy: %g best: %g temp: %g state: %d\n" % (r["iteration"], r["energy"], r["best_energy"], r["temperature"],
+                                                                                r["state_size"]) for r in rows)
 
 
 class FeatureExtractor:
