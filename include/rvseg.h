@@ -254,6 +254,51 @@ rvseg_status rvseg_boosted_resample(rvseg_ctx *ctx, const float *weights, const 
                                     uint64_t key, float *error_out, float *weights_out, float *cumsum_out,
                                     int32_t *idx_out);
 
+/* ---- class-frequency-weighted split objective: DecisionTreeLearner::setUseClassFrequency (libforest learning.h:111,
+ *      default true; learning.cpp:708-717).  src/train.cpp:232 switches it off for the ROVINA forests, which is what
+ *      rvseg_forest_train and rvseg_boosted_train learn; every other user of the library, libforest's own example among
+ *      them (example/main.cpp:92-104), gets it on.  Single-layer learners only: the reference refuses the weighting in
+ *      its multi-layer learner (learning.cpp:498-501) and train.cpp does not use it, so the multi-layer and the frames
+ *      entry points are not extended.
+ *   Build-owned definitions:
+ *   1. Weights of a tree.  cnt_c = the sum of multiplicities of class c in the tree's data set: the set after the
+ *      bootstrap when use_bootstrap is on, else the set as given; for a boosting round the round's resample, with the
+ *      bootstrap on top if set.  Nb = the sum of cnt_c.  INVERSE_FREQUENCY: w_c = (float)Nb / (float)cnt_c, which is
+ *      getInvertedClassFrequency on the bootstrapped storage (data.h:346-357, learning.cpp:712).  A class with
+ *      cnt_c == 0 has no weight; it is never read (2).  GIVEN: w_c = weights[c], the same for every tree and round.
+ *   2. Objective of one side with integer class counts n_c:
+ *        M = 0.0f;        for c ascending with n_c > 0:  M += w_c * (float)n_c
+ *        E = -ENTROPY(M); for c ascending with n_c > 0:  E += ENTROPY(w_c * (float)n_c)
+ *      with ENTROPY and fastlog2 as in the unweighted objective, all fp32, every product rounded before it is added (no
+ *      FMA).  The cut's objective is E(left) + E(right).
+ *   3. Everything else is unchanged: the stop rules and min_child_split_examples read the UNWEIGHTED integer masses
+ *      (learning.cpp:773, 842-843); candidates, thresholds and their guard, tie rules, the random keys, leaf histograms,
+ *      node numbering and the stream are rvseg_forest_train's.  NONE runs the integer expression, not the weighted one
+ *      with ones ((float)(sum of n_c) and the sum of (float)n_c differ above 2^24), so it keeps the bytes of
+ *      rvseg_forest_train / rvseg_boosted_train for every input.
+ *   4. What this is not: the reference's running value.  Its right-hand histogram starts from initEntropies, which
+ *      reads the unweighted histogram (:279-293), and turns weighted only class by class as subOne touches them
+ *      (:235-256); its weighted counts are running float sums.  The definition above is what its left-hand histogram
+ *      tracks (reset, then addOne, :220-234), applied to both sides and without the drift.  The weighted objective is
+ *      therefore unpinned against the reference, by nature, like the learner's random stream. */
+typedef enum { RVSEG_PRIOR_NONE = 0, RVSEG_PRIOR_INVERSE_FREQUENCY = 1, RVSEG_PRIOR_GIVEN = 2 } rvseg_prior_mode;
+typedef struct rvseg_class_prior {
+    int32_t mode;        /* rvseg_prior_mode */
+    float weights[16];   /* GIVEN: one weight per class, the first C are read */
+} rvseg_class_prior;
+/* rvseg_forest_train for one layer of C classes (2..16; labels: P class indices) and rvseg_boosted_train, with the
+ * split objective of `prior`.  prior == NULL or mode NONE return exactly what those two return.  The trained model is
+ * kept on the context in the same way, so rvseg_forest_train_result / rvseg_boosted_train_result serve both.
+ * RVSEG_ERR_INVALID_ARG, with the previous model kept and rvseg_last_error naming the field: an unknown mode; GIVEN
+ * with a weight among the first C that is not finite or not > 0; C outside 2..16. */
+rvseg_status rvseg_forest_train_prior(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t C,
+                                      const rvseg_train_params *tp, const rvseg_class_prior *prior, void *forest_out,
+                                      size_t out_cap, size_t *size_out);
+rvseg_status rvseg_boosted_train_prior(rvseg_ctx *ctx, const float *X, int32_t P, int32_t D, const int32_t *labels, int32_t C,
+                                       const rvseg_train_params *tp, const rvseg_class_prior *prior, void *out,
+                                       size_t out_cap, size_t *size_out, float *errors_out, float *alphas_out,
+                                       int32_t *rounds_out);
+
 /* ---- forest tools: replaces libforest's tools.h (AccuracyTool, ConfusionMatrixTool, CorrelationTool; tools.cpp) and
  *      Classifier::classify on a data set, for the loaded model, and re-estimates a loaded forest's leaves.
  *      X: P x D host floats, D == rvseg_feature_length, P >= 1.  `layer` indexes the layers of the context's active

@@ -69,7 +69,9 @@ SYMBOLS = [
     "rvseg_forest_classify", "rvseg_forest_classify_trees", "rvseg_forest_measure", "rvseg_forest_tools_scores",
     "rvseg_forest_tools_correlation", "rvseg_forest_refit",
     "rvseg_prune_params_default", "rvseg_prune_schedule", "rvseg_forest_prune", "rvseg_forest_prune_energy", "rvseg_forest_prune_apply",
+    "rvseg_forest_train_prior", "rvseg_boosted_train_prior",
 ]
+PRIOR_NONE, PRIOR_INVERSE_FREQUENCY, PRIOR_GIVEN = range(3)   # rvseg_prior_mode
 PRUNE_ERROR, PRUNE_COVER = 0, 1   # rvseg_prune_energy
 PRUNE_MAX_STATE = 64
 BOOSTED_WEIGHT_FIRST, BOOSTED_TREE_FIRST, BOOSTED_AS_LOADED = 0, 1, -1   # rvseg_boosted_order
@@ -101,6 +103,11 @@ class RvsegTrainParams(C.Structure):
         ("min_child_split_examples", C.c_int32), ("num_features", C.c_int32), ("use_bootstrap", C.c_int32),
         ("smoothing", C.c_float), ("seed", C.c_uint64),
     ]
+
+
+class RvsegClassPrior(C.Structure):
+    """rvseg_class_prior: the split objective of rvseg_forest_train_prior / rvseg_boosted_train_prior."""
+    _fields_ = [("mode", C.c_int32), ("weights", C.c_float * 16)]
 
 
 class RvsegPruneParams(C.Structure):
@@ -241,6 +248,10 @@ def lib():
     L.rvseg_boosted_weights.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.rvseg_boosted_train.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(RvsegTrainParams), vp, C.c_size_t, C.POINTER(C.c_size_t),
                                       vp, vp, C.POINTER(i32)]
+    L.rvseg_forest_train_prior.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(RvsegTrainParams), C.POINTER(RvsegClassPrior), vp, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]
+    L.rvseg_boosted_train_prior.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(RvsegTrainParams), C.POINTER(RvsegClassPrior), vp, C.c_size_t,
+                                            C.POINTER(C.c_size_t), vp, vp, C.POINTER(i32)]
     L.rvseg_boosted_train_result.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rvseg_boosted_resample.argtypes = [vp, vp, vp, i32, f32, C.c_uint64, C.POINTER(f32), vp, vp, vp]
     L.rvseg_host_register.argtypes = [vp, C.c_size_t]

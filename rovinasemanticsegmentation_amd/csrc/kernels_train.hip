@@ -11,7 +11,8 @@
 // per draw, the misclassification flags, and the three fp32 sums the reference accumulates in example order -- error, the
 // weights' total, their running sum -- each by one wave that adds a tile of 256 values at once where that is exact
 // (ordered_tile) and one after the other where it is not, so the result is the serial chain's bit for bit.
-// The objective is the oracle's definition 2 (oracle/rvseg_oracle_train.c), in its operation order.
+// The objective is the oracle's definition 2 (oracle/rvseg_oracle_train.c), in its operation order, or -- in the weighted
+// instantiation of the two cut kernels -- definition 2 of rvseg_class_prior (include/rvseg.h).
 #include <cstring>   // rocPRIM's headers call memset without including it
 
 #include <rocprim/rocprim.hpp>
@@ -61,6 +62,30 @@ __device__ __forceinline__ float hist_entropy(const unsigned (&cnt)[TR_CMAX]) {
     }
     return total;
 }
+
+// The class-weighted objective of one side (include/rvseg.h, rvseg_class_prior, definition 2): the weighted mass and
+// the weighted counts are w_c * (float)n_c, each product rounded before it is added, over the classes with n_c > 0 in
+// ascending order.  The weight of a class the side does not hold is never read.
+__device__ __forceinline__ float hist_entropy_weighted(const unsigned (&cnt)[TR_CMAX], const ClassWeights& cw) {
+    float mass = 0.0f;
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) {
+        if (cnt[c] == 0) continue;
+        mass += cw.w[c] * (float)cnt[c];
+    }
+    float total = -entropy_term(mass);
+#pragma unroll
+    for (int c = 0; c < TR_CMAX; c++) {
+        if (cnt[c] == 0) continue;
+        total += entropy_term(cw.w[c] * (float)cnt[c]);
+    }
+    return total;
+}
+
+// The two cut kernels end in a parameter pack `cw`: empty, they are the kernels of the integer objective as they always
+// were; holding a ClassWeights, they are the weighted instantiation.
+__device__ __forceinline__ float side_entropy(const unsigned (&cnt)[TR_CMAX]) { return hist_entropy(cnt); }
+__device__ __forceinline__ float side_entropy(const unsigned (&cnt)[TR_CMAX], const ClassWeights& cw) { return hist_entropy_weighted(cnt, cw); }
 
 // ---- the rules every kernel shares ----------------------------------------------------------------------------
 // a feature's value lives in Xb when it is byte-valued, else in its row of Xf
@@ -184,8 +209,9 @@ train_hist_kernel(TrainSetView v, LevelSlots sl, unsigned* __restrict__ hist) {
 }
 
 // byte features: one block per (slot, feature), one thread per value
+template <class... WEIGHTS>
 __global__ void __launch_bounds__(TR_BINS)
-train_best_cut_kernel(TrainSetView ts, LevelSlots sl, const unsigned* __restrict__ hist, CutResult* __restrict__ out) {
+train_best_cut_kernel(TrainSetView ts, LevelSlots sl, const unsigned* __restrict__ hist, CutResult* __restrict__ out, WEIGHTS... cw) {
     __shared__ unsigned h[TR_CMAX][TR_BINS + 1];   // inclusive prefix over the values, per class
     __shared__ unsigned occ[TR_BINS];
     __shared__ float best_obj[TR_BINS];
@@ -215,7 +241,7 @@ train_best_cut_kernel(TrainSetView ts, LevelSlots sl, const unsigned* __restrict
         unsigned l[TR_CMAX], r[TR_CMAX];
 #pragma unroll
         for (int c = 0; c < TR_CMAX; c++) { l[c] = h[c][b]; r[c] = h[c][TR_BINS - 1] - l[c]; lm += l[c]; rm += r[c]; }
-        const float el = hist_entropy(l), er = hist_entropy(r);
+        const float el = side_entropy(l, cw...), er = side_entropy(r, cw...);
         obj = el + er;
     }
     best_obj[b] = obj;
@@ -265,9 +291,10 @@ train_nb_emit_kernel(TrainSetView v, LevelSlots sl, unsigned long long* __restri
 
 // one wave per (slot, feature) segment of the sorted triples: ascending values, running class counts, every cut between
 // two values at least 1e-6 apart (learning.cpp:560-604)
+template <class... WEIGHTS>
 __global__ void __launch_bounds__(64)
 train_nb_scan_kernel(TrainSetView ts, LevelSlots sl, unsigned n_items, const unsigned long long* __restrict__ keys,
-                     const unsigned* __restrict__ vals, const unsigned* __restrict__ totals, CutResult* __restrict__ out) {
+                     const unsigned* __restrict__ vals, const unsigned* __restrict__ totals, CutResult* __restrict__ out, WEIGHTS... cw) {
     const unsigned seg = blockIdx.x;
     if (ts.nb_index[sl.slot_feat[seg]] < 0) return;   // a byte feature: the histogram path writes this record
     const int lane = threadIdx.x;
@@ -322,7 +349,7 @@ train_nb_scan_kernel(TrainSetView ts, LevelSlots sl, unsigned n_items, const uns
             unsigned right[TR_CMAX];
 #pragma unroll
             for (int c = 0; c < TR_CMAX; c++) right[c] = tot[c] - left[c];
-            const float el = hist_entropy(left), er = hist_entropy(right);
+            const float el = side_entropy(left, cw...), er = side_entropy(right, cw...);
             obj = el + er;
         }
         // the chunk's minimum, lowest position first; strict '<' against the running best
@@ -549,6 +576,10 @@ train_boost_sum_kernel(float* __restrict__ w, const uint8_t* __restrict__ miss, 
 
 inline dim3 blocks_of(long long threads) { return dim3((unsigned)((threads + 255) / 256)); }
 
+// Which objective a cut launch uses, stated once: no weights (RVSEG_PRIOR_NONE) is the integer expression of today's
+// kernels, never the weighted one run with ones -- (float)(sum of n_c) and the sum of (float)n_c differ above 2^24.
+inline bool use_weighted_objective(const ClassWeights* cw) { return cw != nullptr; }
+
 }  // namespace
 
 void launch_train_feature_stats(const float* X, int P, int D, int* not_byte, int* not_finite, hipStream_t s) {
@@ -592,14 +623,19 @@ void launch_train_bootstrap(int P, uint64_t kt, const int* positions, unsigned* 
     RV_LAUNCHED("train_bootstrap_kernel");
 }
 
-void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, unsigned* totals, unsigned* hist, CutResult* cuts,
-                               hipStream_t s) {
+void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, const ClassWeights* cw, unsigned* totals, unsigned* hist,
+                               CutResult* cuts, hipStream_t s) {
     train_slot_totals_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, sl, totals);
     RV_LAUNCHED("train_slot_totals_kernel");
     train_hist_kernel<<<blocks_of(v.P), dim3(256), 0, s>>>(v, sl, hist);
     RV_LAUNCHED("train_hist_kernel");
-    train_best_cut_kernel<<<dim3((unsigned)(S * sl.K)), dim3(TR_BINS), 0, s>>>(v, sl, hist, cuts);
-    RV_LAUNCHED("train_best_cut_kernel");
+    if (use_weighted_objective(cw)) {
+        train_best_cut_kernel<<<dim3((unsigned)(S * sl.K)), dim3(TR_BINS), 0, s>>>(v, sl, hist, cuts, *cw);
+        RV_LAUNCHED("train_best_cut_kernel<weighted>");
+    } else {
+        train_best_cut_kernel<<<dim3((unsigned)(S * sl.K)), dim3(TR_BINS), 0, s>>>(v, sl, hist, cuts);
+        RV_LAUNCHED("train_best_cut_kernel");
+    }
 }
 
 void launch_train_emit(const TrainSetView& v, const LevelSlots& sl, unsigned long long* keys, unsigned* vals, unsigned* counter,
@@ -620,10 +656,15 @@ hipError_t launch_train_sort(void* temp, size_t temp_bytes, unsigned long long* 
     return rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, s);
 }
 
-void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, unsigned n_items, const unsigned long long* keys, const unsigned* vals,
-                       const unsigned* totals, CutResult* cuts, hipStream_t s) {
-    train_nb_scan_kernel<<<dim3((unsigned)(S * sl.K)), dim3(64), 0, s>>>(v, sl, n_items, keys, vals, totals, cuts);
-    RV_LAUNCHED("train_nb_scan_kernel");
+void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, const ClassWeights* cw, unsigned n_items, const unsigned long long* keys,
+                       const unsigned* vals, const unsigned* totals, CutResult* cuts, hipStream_t s) {
+    if (use_weighted_objective(cw)) {
+        train_nb_scan_kernel<<<dim3((unsigned)(S * sl.K)), dim3(64), 0, s>>>(v, sl, n_items, keys, vals, totals, cuts, *cw);
+        RV_LAUNCHED("train_nb_scan_kernel<weighted>");
+    } else {
+        train_nb_scan_kernel<<<dim3((unsigned)(S * sl.K)), dim3(64), 0, s>>>(v, sl, n_items, keys, vals, totals, cuts);
+        RV_LAUNCHED("train_nb_scan_kernel");
+    }
 }
 
 void launch_train_route(const TrainSetView& v, int* node_of, const int* split_feat, const float* split_thr, const int* split_left,

@@ -44,6 +44,12 @@
 //   5. A loader stores a tree weight as w + 0.0f (forest_model.cpp), so -0.0 votes like the reference's 0 + (-0.0).
 // alpha and exp(alpha) come from the host's libm (train_host.h: boost_round).
 //
+// The class-frequency-weighted objective (DecisionTreeLearner::setUseClassFrequency, learning.cpp:708-717;
+// rvseg_forest_train_prior / rvseg_boosted_train_prior, single-layer): a Learner carries a rvseg_class_prior; unless its
+// mode is NONE, grow_tree forms the tree's class weights after start_tree (tree_weights: the class counts of the
+// bootstrapped set, class_prior_weights in train_host.h) and search_batch hands them to the two cut launches.  The
+// definitions are in include/rvseg.h; everything but the objective of a cut is the learner above.
+//
 // Oracle: oracle/rvseg_oracle_train.c restates the reference learner depth-first with sorts; tests compare forest.dat
 // byte for byte.  Both sides implement the same build-owned definitions, written down in that file's header: random
 // choices from a counter-based generator keyed by (seed, tree, node path); the objective evaluated from the class counts
@@ -124,6 +130,10 @@ struct Learner {
     // a boosting round's data set (null: every example once): multiplicities [P] and the example at each position [P]
     const unsigned* mult = nullptr;
     const int* positions = nullptr;
+    // the split objective (rvseg_class_prior; mode NONE: the integer one) and, when it is weighted, the current tree's weights
+    rvseg_class_prior prior{};
+    ClassWeights cw{};
+    const ClassWeights* objective_weights() const { return prior.mode == RVSEG_PRIOR_NONE ? nullptr : &cw; }
 };
 
 rvseg_status reserve_scratch(Learner& R) {
@@ -190,6 +200,20 @@ rvseg_status start_tree(Learner& R, uint64_t kt) {
     return RVSEG_OK;
 }
 
+// the tree's class weights (rvseg_class_prior, definition 1) from the class counts of its examples: start_tree's
+// multiplicities, i.e. the data set after the bootstrap
+rvseg_status tree_weights(Learner& R) {
+    rvseg_ctx* ctx = R.ctx;
+    unsigned cnt[TR_CMAX];
+    RV_HIP(ctx, hipMemsetAsync(R.sc.class_cnt.p, 0, sizeof(cnt), R.s));
+    launch_train_class_count(R.T.view(), R.sc.weights.as<unsigned>(), R.sc.class_cnt.as<unsigned>(), R.s);
+    RV_HIP(ctx, hipMemcpyAsync(cnt, R.sc.class_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, R.s));
+    RV_HIP(ctx, hipStreamSynchronize(R.s));
+    RV_LAUNCH_OK(ctx);
+    class_prior_weights(R.prior, cnt, R.T.class_counts[0], R.cw.w);
+    return RVSEG_OK;
+}
+
 // the host's random choices for the nodes of one batch, in the oracle's draw order (definition 1)
 struct SlotDraw {
     std::vector<int> layer, feat;   // [S], [S][K]
@@ -234,7 +258,7 @@ rvseg_status search_floats(Learner& R, const TrainSetView& v, const LevelSlots& 
         keys = &sc.keysB;
         vals = &sc.valsB;
     }
-    launch_train_scan(v, sl, S, n_items, keys->as<unsigned long long>(), vals->as<unsigned>(), sc.totals.as<unsigned>(), sc.cuts.as<CutResult>(), R.s);
+    launch_train_scan(v, sl, S, R.objective_weights(), n_items, keys->as<unsigned long long>(), vals->as<unsigned>(), sc.totals.as<unsigned>(), sc.cuts.as<CutResult>(), R.s);
     return RVSEG_OK;
 }
 
@@ -251,7 +275,7 @@ rvseg_status search_batch(Learner& R, const std::vector<int>& slot_of, const Slo
     RV_HIP(ctx, hipMemsetAsync(sc.totals.p, 0, S * TR_CMAX * 4, R.s));
     const TrainSetView v = R.T.view();
     const LevelSlots sl{R.K, sc.node_of.as<int>(), sc.slot_of.as<int>(), sc.weights.as<unsigned>(), sc.slot_layer.as<int>(), sc.slot_feat.as<int>()};
-    launch_train_search_bytes(v, sl, (int)S, sc.totals.as<unsigned>(), sc.hist.as<unsigned>(), sc.cuts.as<CutResult>(), R.s);
+    launch_train_search_bytes(v, sl, (int)S, R.objective_weights(), sc.totals.as<unsigned>(), sc.hist.as<unsigned>(), sc.cuts.as<CutResult>(), R.s);
     if (d.any_float) {
         const rvseg_status st = search_floats(R, v, sl, (int)S);
         if (st != RVSEG_OK) return st;
@@ -341,6 +365,7 @@ rvseg_status fill_leaves(Learner& R, GrowingTree& tree) {
 rvseg_status grow_tree(Learner& R, uint64_t kt, GrowingTree& tree) {
     rvseg_status st;
     if ((st = start_tree(R, kt)) != RVSEG_OK) return st;
+    if (R.objective_weights() && (st = tree_weights(R)) != RVSEG_OK) return st;
     std::vector<int> frontier(1, 0);
     while (!frontier.empty())
         if ((st = grow_level(R, tree, frontier)) != RVSEG_OK) return st;
@@ -351,8 +376,10 @@ rvseg_status grow_tree(Learner& R, uint64_t kt, GrowingTree& tree) {
 int features_per_node(int D, const rvseg_train_params& tp) { return std::min(D, tp.num_features > 0 ? tp.num_features : (int)std::ceil(std::sqrt((double)D))); }
 
 // ---- the learner over a device-resident training set ---------------------------------------------------------------
-rvseg_status train_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, std::vector<uint8_t>& bytes_out) {
+rvseg_status train_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, const rvseg_class_prior& prior,
+                        std::vector<uint8_t>& bytes_out) {
     Learner R{ctx, T, tp, features_per_node(T.D, tp), ctx->stream};
+    R.prior = prior;
     rvseg_status st;
     if ((st = reserve_scratch(R)) != RVSEG_OK || (st = class_frequencies(R)) != RVSEG_OK) return st;
     ForestModel model;
@@ -418,10 +445,11 @@ rvseg_status vote_flags(Learner& R, BoostScratch& b, const GrowingTree& tree) {
 }
 
 // the rounds; `model` receives the kept trees and their weights, errors / alphas (num_trees each, or null) the rounds'
-rvseg_status boosted_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, int C, ForestModel& model, float* errors,
-                          float* alphas) {
+rvseg_status boosted_core(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, const rvseg_class_prior& prior, int C,
+                          ForestModel& model, float* errors, float* alphas) {
     const int N = T.P;
     Learner R{ctx, T, tp, features_per_node(T.D, tp), ctx->stream};
+    R.prior = prior;
     BoostScratch b;
     rvseg_status st;
     if ((st = reserve_scratch(R)) != RVSEG_OK || (st = reserve_boost(ctx, b, (size_t)N)) != RVSEG_OK) return st;
@@ -506,9 +534,20 @@ rvseg_status hand_out(rvseg_ctx* ctx, void* forest_out, size_t out_cap, size_t* 
     return RVSEG_OK;
 }
 
+// the integer objective: what the multi-layer and the frames entry points always run
+const rvseg_class_prior kNoPrior{};   // mode RVSEG_PRIOR_NONE
+
+// a prior as the learner takes it: null is NONE; a refused one leaves the context's models as they are
+rvseg_status resolve_prior(rvseg_ctx* ctx, const rvseg_class_prior* prior_in, int C, rvseg_class_prior& prior) {
+    if (const char* what = class_prior_error(prior_in, C)) { ctx->err = what; return RVSEG_ERR_INVALID_ARG; }
+    prior = prior_in ? *prior_in : kNoPrior;
+    return RVSEG_OK;
+}
+
 // trains on the complete set; only a successful training replaces the context's model
-rvseg_status finish_training(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, void* forest_out, size_t out_cap, size_t* size_out) {
-    const rvseg_status st = train_core(ctx, T, tp, ctx->trained_model);
+rvseg_status finish_training(rvseg_ctx* ctx, const TrainSet& T, const rvseg_train_params& tp, const rvseg_class_prior& prior, void* forest_out,
+                             size_t out_cap, size_t* size_out) {
+    const rvseg_status st = train_core(ctx, T, tp, prior, ctx->trained_model);
     if (st != RVSEG_OK) return st;
     return hand_out(ctx, forest_out, out_cap, size_out);
 }
@@ -613,6 +652,52 @@ rvseg_status check_device_labels(rvseg_ctx* ctx, const TrainSet& T) {
     return RVSEG_OK;
 }
 
+// rvseg_forest_train and rvseg_forest_train_prior: the host matrix, packed and learnt with the objective of `prior`
+rvseg_status train_matrix(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t n_layers,
+                          const int32_t* class_counts, const rvseg_train_params* tp_in, const rvseg_class_prior& prior, void* forest_out,
+                          size_t out_cap, size_t* size_out) {
+    const rvseg_train_params tp = resolve_params(tp_in);
+    if (!X || !labels || !size_out || P < 1 || D < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    rvseg_status st = check_train_args(ctx, n_layers, class_counts, tp, D);
+    if (st != RVSEG_OK) return st;
+    for (int l = 0; l < n_layers; l++)
+        if ((st = labels_in_range(ctx, labels + l, (size_t)P, (size_t)n_layers, class_counts[l])) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    TrainSet T;
+    if ((st = pack_matrix(ctx, X, P, D, labels, n_layers, class_counts, T)) != RVSEG_OK) return st;
+    return finish_training(ctx, T, tp, prior, forest_out, out_cap, size_out);
+}
+
+// rvseg_boosted_train and rvseg_boosted_train_prior: the boosting rounds with the trees' objective of `prior`
+rvseg_status boosted_matrix(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t C,
+                            const rvseg_train_params* tp_in, const rvseg_class_prior& prior, void* out, size_t out_cap, size_t* size_out,
+                            float* errors_out, float* alphas_out, int32_t* rounds_out) {
+    const rvseg_train_params tp = resolve_params(tp_in);
+    if (!X || !labels || !size_out || P < 1 || D < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    rvseg_status st = check_train_args(ctx, 1, &C, tp, D);
+    if (st != RVSEG_OK) return st;
+    if (C < 2) { ctx->err = "boosting needs at least 2 classes (alpha takes log(C - 1))"; return RVSEG_ERR_INVALID_ARG; }
+    if ((st = labels_in_range(ctx, labels, (size_t)P, 1, C)) != RVSEG_OK) return st;
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    TrainSet T;
+    if ((st = pack_matrix(ctx, X, P, D, labels, 1, &C, T)) != RVSEG_OK) return st;
+    const float nan = std::nanf("");
+    for (int r = 0; r < tp.num_trees; r++) {
+        if (errors_out) errors_out[r] = nan;
+        if (alphas_out) alphas_out[r] = nan;
+    }
+    ForestModel model;
+    if ((st = boosted_core(ctx, T, tp, prior, C, model, errors_out, alphas_out)) != RVSEG_OK) return st;
+    if (rounds_out) *rounds_out = model.n_trees;
+    const std::vector<uint8_t> bytes = serialize_boosted(model, RVSEG_BOOSTED_WEIGHT_FIRST);
+    ctx->trained_boosted = std::move(model);   // only a successful training replaces the kept model
+    *size_out = bytes.size();
+    if (!out) return RVSEG_OK;
+    if (out_cap < bytes.size()) { ctx->err = "output buffer too small (the model is kept: rvseg_boosted_train_result)"; return RVSEG_ERR_INVALID_ARG; }
+    std::memcpy(out, bytes.data(), bytes.size());
+    return RVSEG_OK;
+}
+
 }  // namespace
 }  // namespace rvseg
 
@@ -643,16 +728,17 @@ rvseg_status rvseg_forest_train(rvseg_ctx* ctx, const float* X, int32_t P, int32
                                 const int32_t* class_counts, const rvseg_train_params* tp_in, void* forest_out, size_t out_cap,
                                 size_t* size_out) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    const rvseg_train_params tp = resolve_params(tp_in);
-    if (!X || !labels || !size_out || P < 1 || D < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    rvseg_status st = check_train_args(ctx, n_layers, class_counts, tp, D);
+    return train_matrix(ctx, X, P, D, labels, n_layers, class_counts, tp_in, kNoPrior, forest_out, out_cap, size_out);
+}
+
+rvseg_status rvseg_forest_train_prior(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t C,
+                                      const rvseg_train_params* tp_in, const rvseg_class_prior* prior_in, void* forest_out, size_t out_cap,
+                                      size_t* size_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    rvseg_class_prior prior;
+    const rvseg_status st = resolve_prior(ctx, prior_in, C, prior);
     if (st != RVSEG_OK) return st;
-    for (int l = 0; l < n_layers; l++)
-        if ((st = labels_in_range(ctx, labels + l, (size_t)P, (size_t)n_layers, class_counts[l])) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    TrainSet T;
-    if ((st = pack_matrix(ctx, X, P, D, labels, n_layers, class_counts, T)) != RVSEG_OK) return st;
-    return finish_training(ctx, T, tp, forest_out, out_cap, size_out);
+    return train_matrix(ctx, X, P, D, labels, 1, &C, tp_in, prior, forest_out, out_cap, size_out);
 }
 
 rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const uint8_t* rgb, const uint16_t* depth_mm, const float* calib,
@@ -701,37 +787,24 @@ rvseg_status rvseg_forest_train_frames(rvseg_ctx* ctx, int32_t n_frames, const u
     if (base == 0) { ctx->err = "no labelled point with valid depth in the training frames"; return RVSEG_ERR_INVALID_ARG; }
     T.P = (int)base;
     if ((st = check_device_labels(ctx, T)) != RVSEG_OK) return st;
-    return finish_training(ctx, T, tp, forest_out, out_cap, size_out);
+    return finish_training(ctx, T, tp, kNoPrior, forest_out, out_cap, size_out);
 }
 
 rvseg_status rvseg_boosted_train(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t C,
                                  const rvseg_train_params* tp_in, void* out, size_t out_cap, size_t* size_out, float* errors_out,
                                  float* alphas_out, int32_t* rounds_out) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    const rvseg_train_params tp = resolve_params(tp_in);
-    if (!X || !labels || !size_out || P < 1 || D < 1) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    rvseg_status st = check_train_args(ctx, 1, &C, tp, D);
+    return boosted_matrix(ctx, X, P, D, labels, C, tp_in, kNoPrior, out, out_cap, size_out, errors_out, alphas_out, rounds_out);
+}
+
+rvseg_status rvseg_boosted_train_prior(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, const int32_t* labels, int32_t C,
+                                       const rvseg_train_params* tp_in, const rvseg_class_prior* prior_in, void* out, size_t out_cap,
+                                       size_t* size_out, float* errors_out, float* alphas_out, int32_t* rounds_out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    rvseg_class_prior prior;
+    const rvseg_status st = resolve_prior(ctx, prior_in, C, prior);
     if (st != RVSEG_OK) return st;
-    if (C < 2) { ctx->err = "boosting needs at least 2 classes (alpha takes log(C - 1))"; return RVSEG_ERR_INVALID_ARG; }
-    if ((st = labels_in_range(ctx, labels, (size_t)P, 1, C)) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    TrainSet T;
-    if ((st = pack_matrix(ctx, X, P, D, labels, 1, &C, T)) != RVSEG_OK) return st;
-    const float nan = std::nanf("");
-    for (int r = 0; r < tp.num_trees; r++) {
-        if (errors_out) errors_out[r] = nan;
-        if (alphas_out) alphas_out[r] = nan;
-    }
-    ForestModel model;
-    if ((st = boosted_core(ctx, T, tp, C, model, errors_out, alphas_out)) != RVSEG_OK) return st;
-    if (rounds_out) *rounds_out = model.n_trees;
-    const std::vector<uint8_t> bytes = serialize_boosted(model, RVSEG_BOOSTED_WEIGHT_FIRST);
-    ctx->trained_boosted = std::move(model);   // only a successful training replaces the kept model
-    *size_out = bytes.size();
-    if (!out) return RVSEG_OK;
-    if (out_cap < bytes.size()) { ctx->err = "output buffer too small (the model is kept: rvseg_boosted_train_result)"; return RVSEG_ERR_INVALID_ARG; }
-    std::memcpy(out, bytes.data(), bytes.size());
-    return RVSEG_OK;
+    return boosted_matrix(ctx, X, P, D, labels, C, tp_in, prior, out, out_cap, size_out, errors_out, alphas_out, rounds_out);
 }
 
 rvseg_status rvseg_boosted_resample(rvseg_ctx* ctx, const float* weights, const uint8_t* miss, int32_t N, float exp_alpha, uint64_t key,

@@ -32,6 +32,13 @@ struct LevelSlots {
     const int* slot_feat;   // [slots][K] features the node drew, in sampled order
 };
 
+// The class weights of one tree's split objective (rvseg_class_prior), passed to the cut kernels by value: 16 floats,
+// uniform across the launch, so they sit in scalar registers.  A class the tree's data set does not hold has 0 here;
+// the kernels never read it.
+struct ClassWeights {
+    float w[TR_CMAX];
+};
+
 // ---- data set construction ------------------------------------------------------------------------------------
 // per feature of the row-major P x D matrix X: not_byte[f] = 1 unless every value is an integer in [0, 255];
 // not_finite[0] = 1 when a value is NaN or infinite
@@ -51,9 +58,11 @@ void launch_train_class_count(const TrainSetView& v, const unsigned* mult, unsig
 // w += P draws with replacement from the P positions of the data set; positions (null: position n is example n): the
 // example at each position of a resample
 void launch_train_bootstrap(int P, uint64_t kt, const int* positions, unsigned* w, hipStream_t s);
+// The two cut searches take the tree's class weights `cw`: null runs the integer objective (oracle definition 2), else
+// the class-weighted one (rvseg_class_prior, definition 2).
 // byte features of S slots: class totals, (feature, value, class) histograms, the best cut of every (slot, feature)
-void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, unsigned* totals, unsigned* hist, CutResult* cuts,
-                               hipStream_t s);
+void launch_train_search_bytes(const TrainSetView& v, const LevelSlots& sl, int S, const ClassWeights* cw, unsigned* totals, unsigned* hist,
+                               CutResult* cuts, hipStream_t s);
 // float features: one (segment << 32 | ordered value, example) pair per (bootstrap example, sampled float feature)
 void launch_train_emit(const TrainSetView& v, const LevelSlots& sl, unsigned long long* keys, unsigned* vals, unsigned* counter,
                        unsigned capacity, hipStream_t s);
@@ -61,8 +70,8 @@ size_t train_sort_temp_bytes(size_t n);
 hipError_t launch_train_sort(void* temp, size_t temp_bytes, unsigned long long* keys_in, unsigned long long* keys_out, unsigned* vals_in,
                              unsigned* vals_out, size_t n, unsigned end_bit, hipStream_t s);
 // the best cut of every float (slot, feature) segment of the sorted pairs (needs the slots' totals)
-void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, unsigned n_items, const unsigned long long* keys, const unsigned* vals,
-                       const unsigned* totals, CutResult* cuts, hipStream_t s);
+void launch_train_scan(const TrainSetView& v, const LevelSlots& sl, int S, const ClassWeights* cw, unsigned n_items, const unsigned long long* keys,
+                       const unsigned* vals, const unsigned* totals, CutResult* cuts, hipStream_t s);
 // every example of a freshly split node moves to a child
 void launch_train_route(const TrainSetView& v, int* node_of, const int* split_feat, const float* split_thr, const int* split_left,
                         hipStream_t s);

@@ -5,6 +5,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -86,6 +87,67 @@ inline Split decide_split(const unsigned* totals, const CutResult* cuts, const i
 inline float inverted_frequency(int P, unsigned count) {
     const float n = count <= 16777216u ? (float)count : 16777216.f;
     return P / n;
+}
+
+// ---- the class-weighted split objective (include/rvseg.h: rvseg_class_prior, definitions 1 and 2) -------------------
+// What is wrong with a prior for C classes, naming the field, or null.  A null prior is RVSEG_PRIOR_NONE.
+inline const char* class_prior_error(const rvseg_class_prior* prior, int C) {
+    if (C < 2 || C > TR_CMAX) return "C: the class-weighted objective takes 2..16 classes";
+    if (!prior) return nullptr;
+    if (prior->mode != RVSEG_PRIOR_NONE && prior->mode != RVSEG_PRIOR_INVERSE_FREQUENCY && prior->mode != RVSEG_PRIOR_GIVEN)
+        return "prior->mode: not a rvseg_prior_mode";
+    if (prior->mode == RVSEG_PRIOR_GIVEN)
+        for (int c = 0; c < C; c++)
+            if (!(prior->weights[c] > 0.0f) || !(prior->weights[c] <= 3.4028234663852886e38f))
+                return "prior->weights: every weight of the first C must be finite and > 0";
+    return nullptr;
+}
+
+// definition 1: the weights of one tree from the class counts cnt[TR_CMAX] of its data set (after the bootstrap).
+// INVERSE_FREQUENCY: (float)Nb / (float)cnt_c (getInvertedClassFrequency on the bootstrapped storage, data.h:346-357,
+// :712); GIVEN: the caller's.  A class the set does not hold gets 0: no side holds it either, so it is never read.
+inline void class_prior_weights(const rvseg_class_prior& prior, const unsigned* cnt, int C, float* w) {
+    unsigned nb = 0;
+    for (int c = 0; c < TR_CMAX; c++) nb += cnt[c];
+    for (int c = 0; c < TR_CMAX; c++) {
+        w[c] = 0.0f;
+        if (c >= C || cnt[c] == 0) continue;
+        w[c] = prior.mode == RVSEG_PRIOR_GIVEN ? prior.weights[c] : inverted_frequency((int)nb, cnt[c]);
+    }
+}
+
+// fastlog2 (fastlog.h:47-58) and ENTROPY (:13) on the host, in the operation order of the kernels
+inline float fastlog2_host(float x) {
+    uint32_t vi, mi;
+    std::memcpy(&vi, &x, 4);
+    mi = (vi & 0x007FFFFFu) | 0x3f000000u;
+    float mx;
+    std::memcpy(&mx, &mi, 4);
+    float y = (float)vi;
+    y = y * 1.1920928955078125e-7f;
+    const float a = 1.498030302f * mx;
+    const float den = 0.3520887068f + mx;
+    const float b = 1.72587999f / den;
+    float r = y - 124.22551499f;
+    r = r - a;
+    r = r - b;
+    return r;
+}
+inline float entropy_term_host(float p) { return (-p) * fastlog2_host(p); }
+
+// definition 2: the objective of one side with integer class counts cnt[TR_CMAX] under the weights w[TR_CMAX]
+inline float weighted_hist_entropy(const unsigned* cnt, const float* w) {
+    float mass = 0.0f;
+    for (int c = 0; c < TR_CMAX; c++) {
+        if (cnt[c] == 0) continue;
+        mass += w[c] * (float)cnt[c];
+    }
+    float total = -entropy_term_host(mass);
+    for (int c = 0; c < TR_CMAX; c++) {
+        if (cnt[c] == 0) continue;
+        total += entropy_term_host(w[c] * (float)cnt[c]);
+    }
+    return total;
 }
 
 // One leaf's log histograms (updateMultiHistograms, :960-1012) from its integer counts cnt[layer][TR_CMAX] over ALL

@@ -101,20 +101,46 @@ class Context:
         capi.check(self.h, self.L.rvseg_forest_write_mem(self.h, buf, size.value, C.byref(size)))
         return buf.raw[:size.value]
 
-    def forest_train(self, X, labels, class_counts, **train_params):
+    def forest_train(self, X, labels, class_counts, class_prior=None, **train_params):
         """rvseg_forest_train: X (P, D) float32, labels (P, L) int32 class indices.  Returns the forest.dat bytes.
-        train_params: fields of rvseg_train_params (num_trees, max_depth, min_split_examples, ...)."""
+        train_params: fields of rvseg_train_params (num_trees, max_depth, min_split_examples, ...).
+        class_prior: None (the unweighted split objective), "inverse_frequency" (libforest's useClassFrequency) or one
+        weight per class -- rvseg_forest_train_prior, one layer only."""
         X = np.ascontiguousarray(X, np.float32)
         labels = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(X.shape[0], -1))
         P, D = X.shape
         L = labels.shape[1]
         assert len(class_counts) == L
+        if class_prior is not None and L != 1:
+            raise ValueError("class_prior: the class-weighted objective trains single-layer forests only")
         tp = self._train_params(train_params)
         cc = (C.c_int32 * L)(*class_counts)
         size = C.c_size_t()
         # trains once (the model stays on the context), then fetches it into a buffer of the right size
-        capi.check(self.h, self.L.rvseg_forest_train(self.h, _ptr(X), P, D, _ptr(labels), L, cc, C.byref(tp), None, 0, C.byref(size)))
+        if class_prior is None:
+            capi.check(self.h, self.L.rvseg_forest_train(self.h, _ptr(X), P, D, _ptr(labels), L, cc, C.byref(tp), None, 0, C.byref(size)))
+        else:
+            prior = self._class_prior(class_prior, class_counts[0])
+            capi.check(self.h, self.L.rvseg_forest_train_prior(self.h, _ptr(X), P, D, _ptr(labels), class_counts[0], C.byref(tp),
+                                                               C.byref(prior), None, 0, C.byref(size)))
         return self._trained_model(size.value)
+
+    @staticmethod
+    def _class_prior(class_prior, n_classes):
+        """rvseg_class_prior from "inverse_frequency" or a sequence of n_classes weights."""
+        prior = capi.RvsegClassPrior()
+        if isinstance(class_prior, str):
+            if class_prior != "inverse_frequency":
+                raise ValueError("class_prior: None, 'inverse_frequency' or one weight per class, not %r" % class_prior)
+            prior.mode = capi.PRIOR_INVERSE_FREQUENCY
+            return prior
+        w = np.asarray(class_prior, np.float32).reshape(-1)
+        if w.shape[0] != n_classes or n_classes > 16:
+            raise ValueError("class_prior: %d weights for %d classes (at most 16)" % (w.shape[0], n_classes))
+        prior.mode = capi.PRIOR_GIVEN
+        for c in range(n_classes):
+            prior.weights[c] = w[c]
+        return prior
 
     def _train_params(self, train_params):
         tp = capi.RvsegTrainParams()
@@ -162,10 +188,11 @@ class Context:
         capi.check(self.h, self.L.rvseg_boosted_weights(self.h, _ptr(out), n.value, C.byref(n), None))
         return out
 
-    def boosted_train(self, X, labels, n_classes, **train_params):
+    def boosted_train(self, X, labels, n_classes, class_prior=None, **train_params):
         """rvseg_boosted_train: X (P, D) float32, labels (P,) int32 class indices of n_classes classes; num_trees is the
         number of boosting rounds.  Returns dict(model = the BOOSTED_WEIGHT_FIRST stream, rounds = trees kept, errors,
-        alphas = float32 (num_trees,), NaN where a round did not run or kept no tree)."""
+        alphas = float32 (num_trees,), NaN where a round did not run or kept no tree).  class_prior: as forest_train's
+        (rvseg_boosted_train_prior)."""
         X = np.ascontiguousarray(X, np.float32)
         labels = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
         P, D = X.shape
@@ -174,8 +201,13 @@ class Context:
         errors = np.empty(max(tp.num_trees, 1), np.float32)
         alphas = np.empty(max(tp.num_trees, 1), np.float32)
         size, rounds = C.c_size_t(), C.c_int32()
-        capi.check(self.h, self.L.rvseg_boosted_train(self.h, _ptr(X), P, D, _ptr(labels), n_classes, C.byref(tp), None, 0, C.byref(size),
-                                                      _ptr(errors), _ptr(alphas), C.byref(rounds)))
+        if class_prior is None:
+            capi.check(self.h, self.L.rvseg_boosted_train(self.h, _ptr(X), P, D, _ptr(labels), n_classes, C.byref(tp), None, 0, C.byref(size),
+                                                          _ptr(errors), _ptr(alphas), C.byref(rounds)))
+        else:
+            prior = self._class_prior(class_prior, n_classes)
+            capi.check(self.h, self.L.rvseg_boosted_train_prior(self.h, _ptr(X), P, D, _ptr(labels), n_classes, C.byref(tp), C.byref(prior),
+                                                                None, 0, C.byref(size), _ptr(errors), _ptr(alphas), C.byref(rounds)))
         # trained once (the model stays on the context, apart from a loaded one), then fetched into a buffer of the right size
         buf = C.create_string_buffer(size.value)
         capi.check(self.h, self.L.rvseg_boosted_train_result(self.h, capi.BOOSTED_WEIGHT_FIRST, buf, size.value, C.byref(size)))
