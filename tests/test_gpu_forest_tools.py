@@ -11,6 +11,7 @@ import pytest
 import boost_restate as br
 import tools_cases as tc
 import train_cases as trc
+from tools_cases import _leaves_from_counts, _walk_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -205,44 +206,6 @@ CTX_D6 = dict(multi_layer=1, patch_size_reduce=1)                               
 
 def _structure(tree):
     return tree["feat"].tobytes() + tree["thr"].tobytes() + tree["left"].tobytes()
-
-
-def _walk_counts(blob, X, labels, cc):
-    """[node over all trees][sumC]: the examples per leaf and (layer, class), zeros at inner nodes."""
-    offs = np.concatenate([[0], np.cumsum(cc)])
-    rows = []
-    for tree in trc.parse(blob):
-        cnt = np.zeros((len(tree["left"]), offs[-1]), np.uint32)
-        node = trc.route(tree, X)
-        for l in range(len(cc)):
-            np.add.at(cnt, (node, offs[l] + labels[:, l]), 1)
-        rows.append(cnt)
-    return np.concatenate(rows)
-
-
-def _leaves_from_counts(cnt, labels, cc, smoothing):
-    """updateMultiHistograms from integer counts, as tests/test_gpu_train.py recomputes the trainer's leaves: n additions of
-    the inverted class frequency, then log((h + s) / (total + C s)), all fp32."""
-    offs = np.concatenate([[0], np.cumsum(cc)])
-    P = labels.shape[0]
-    out = []
-    for l, Cn in enumerate(cc):
-        class_cnt = np.bincount(labels[:, l], minlength=Cn)
-        with np.errstate(divide="ignore"):
-            freq = (F32(P) / class_cnt.astype(F32)).astype(F32)
-        h = np.zeros(Cn, F32)
-        for c in range(Cn):
-            acc = F32(0)
-            for _ in range(int(cnt[offs[l] + c])):
-                acc = F32(acc + freq[c])
-            h[c] = acc
-        total = F32(0)
-        for c in range(Cn):
-            total = F32(total + h[c])
-        s = F32(smoothing)
-        arg = ((h + s) / F32(total + F32(Cn) * s)).astype(F32)
-        out.append(np.array([br._libm.logf(C.c_float(float(a))) for a in arg], F32))   # the host's own logf
-    return out
 
 
 @pytest.mark.parametrize("which", ["three_layers", "one_layer"])

@@ -3,12 +3,14 @@ restatement of libforest's tools.h (AccuracyTool, ConfusionMatrixTool, Correlati
 those lines, independently of the HIP code: trees vote through the CPU oracle's evaluator on one-tree files and the
 first-strict-maximum rule of boost_restate, the counts are numpy sums and the three score formulas are np.float32
 expressions.  What each case claims -- scores that are not trivial -- is pinned in tests/test_tools_cases_cpu.py."""
+import ctypes as C
 import os
 import struct
 
 import numpy as np
 
 import boost_restate as br
+import train_cases as trc
 from oracle import oracle as O
 
 F32 = np.float32
@@ -85,24 +87,27 @@ def _layer_slice(f, multi, layer):
     return slice(off, off + cc[layer])
 
 
-def restate(name, P, layer=0):
-    """dict(pred (P,), votes (T, P) uint8, C): Classifier::classify on the forest posterior and on every tree's own."""
-    key = ("restate", name, P, layer)
-    if key in _cache:
-        return _cache[key]
-    fo = forest(name)
-    multi = bool(fo["ctx"]["multi_layer"])
-    X = points(fo["D"], P)
-    whole = O.Forest(fo["blob"])
+def restate_blob(blob, X, multi, layer=0):
+    """dict(pred (P,), votes (T, P) uint8, C) of any forest.dat image on the points X: Classifier::classify on the forest
+    posterior and on every tree's own, through the CPU oracle on the whole forest and on one-tree files."""
+    whole = O.Forest(blob)
     sl = _layer_slice(whole, multi, layer)
     with np.errstate(invalid="ignore"):
         pred = br.first_strict_max(whole.eval(X, multi)[:, sl])
         by_tree, votes = {}, []
-        for tree in br.split_trees(fo["blob"]):
+        for tree in br.split_trees(blob):
             if tree not in by_tree:
                 by_tree[tree] = br.first_strict_max(O.Forest(br.one_tree_forest(tree)).eval(X, multi)[:, sl]).astype(np.uint8)
             votes.append(by_tree[tree])
-    _cache[key] = dict(pred=pred, votes=np.stack(votes), C=sl.stop - sl.start)
+    return dict(pred=pred, votes=np.stack(votes), C=sl.stop - sl.start)
+
+
+def restate(name, P, layer=0):
+    """restate_blob of a named forest of this module on its own points, computed once."""
+    key = ("restate", name, P, layer)
+    if key not in _cache:
+        fo = forest(name)
+        _cache[key] = restate_blob(fo["blob"], points(fo["D"], P), bool(fo["ctx"]["multi_layer"]), layer)
     return _cache[key]
 
 
@@ -150,3 +155,42 @@ def correlation(agree, P):
     """tools.cpp:226-228 -- 1 - hammingDist / (float)size per pair."""
     dist = (np.int64(P) - np.asarray(agree, np.uint64).astype(np.int64)).astype(F32)
     return (1 - (dist / F32(P)).astype(F32)).astype(F32)
+
+
+# ---- the refit: leaf counts and leaves, recomputed ---------------------------------------------------------------------
+def _walk_counts(blob, X, labels, cc):
+    """[node over all trees][sumC]: the examples per leaf and (layer, class), zeros at inner nodes."""
+    offs = np.concatenate([[0], np.cumsum(cc)])
+    rows = []
+    for tree in trc.parse(blob):
+        cnt = np.zeros((len(tree["left"]), offs[-1]), np.uint32)
+        node = trc.route(tree, X)
+        for l in range(len(cc)):
+            np.add.at(cnt, (node, offs[l] + labels[:, l]), 1)
+        rows.append(cnt)
+    return np.concatenate(rows)
+
+
+def _leaves_from_counts(cnt, labels, cc, smoothing):
+    """updateMultiHistograms from integer counts, as tests/test_gpu_train.py recomputes the trainer's leaves: n additions of
+    the inverted class frequency, then log((h + s) / (total + C s)), all fp32."""
+    offs = np.concatenate([[0], np.cumsum(cc)])
+    P = labels.shape[0]
+    out = []
+    for l, Cn in enumerate(cc):
+        class_cnt = np.bincount(labels[:, l], minlength=Cn)
+        with np.errstate(divide="ignore"):
+            freq = (F32(P) / class_cnt.astype(F32)).astype(F32)
+        h = np.zeros(Cn, F32)
+        for c in range(Cn):
+            acc = F32(0)
+            for _ in range(int(cnt[offs[l] + c])):
+                acc = F32(acc + freq[c])
+            h[c] = acc
+        total = F32(0)
+        for c in range(Cn):
+            total = F32(total + h[c])
+        s = F32(smoothing)
+        arg = ((h + s) / F32(total + F32(Cn) * s)).astype(F32)
+        out.append(np.array([br._libm.logf(C.c_float(float(a))) for a in arg], F32))   # the host's own logf
+    return out
