@@ -15,6 +15,10 @@ namespace rvseg {
 
 constexpr int TOOLS_CHUNK = 65536;   // points of X on the device at a time: scratch is bounded by this, not by P
 
+// The grid of a kernel whose blocks loop over their work: the `want` blocks that would each take one share, capped at
+// max_blocks -- a few blocks per compute unit (count_blocks) -- and at least one.
+inline int looping_grid(long want, int max_blocks) { return (int)(want < max_blocks ? want : (max_blocks > 0 ? max_blocks : 1)); }
+
 // AccuracyTool::measure (tools.cpp:61-78): 1.0f - error / (float)size, `error` an int -- the off-diagonal total
 inline float tools_accuracy(const uint64_t* confusion, int C) {
     uint64_t size = 0, errors = 0;

@@ -18,6 +18,7 @@
 // The walk keeps a point's (at most 16) class counters of (at most 64) votes as bytes in four registers and updates
 // them with selects: a dynamically indexed array would live in scratch.
 #include "device_math.h"
+#include "forest_tools_host.h"
 #include "prune_host.h"
 #include "rvseg_internal.h"
 #include "rvseg_kernels.h"
@@ -140,7 +141,7 @@ prune_step_kernel(const uint8_t* __restrict__ votes, const int32_t* __restrict__
 
 int prune_grid(int P, int max_blocks) {
     const long want = ((long)P + PRUNE_BLOCK * PRUNE_POINTS_PER_LANE - 1) / (PRUNE_BLOCK * PRUNE_POINTS_PER_LANE);
-    return (int)(want < max_blocks ? want : (max_blocks > 0 ? max_blocks : 1));
+    return looping_grid(want, max_blocks);
 }
 
 void launch_prune_init(const uint8_t* d_votes, const int32_t* d_labels, int P, size_t stride, int grid, PruneControl* d_ctl, hipStream_t s) {

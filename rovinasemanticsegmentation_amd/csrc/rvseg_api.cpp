@@ -580,26 +580,6 @@ rvseg_status rvseg_forest_info(const rvseg_ctx* ctx, int32_t* n_trees, int32_t* 
     return RVSEG_OK;
 }
 
-rvseg_status rvseg_forest_eval(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, float* out) {
-    if (!ctx) return RVSEG_ERR_INVALID_ARG;
-    if (!ctx->forest_loaded) { ctx->err = "no forest loaded"; return RVSEG_ERR_NO_FOREST; }
-    if (P < 0 || !out || (!X && P > 0)) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
-    if (D != ctx->feature_length) { ctx->err = "D does not match the configured feature length"; return RVSEG_ERR_INVALID_ARG; }
-    if (P == 0) return RVSEG_OK;
-    RV_HIP(ctx, hipSetDevice(ctx->params.device));
-    DevBuf dX, dO;   // freed on every return (hipFree waits for the device)
-    rvseg_status st;
-    const size_t S = (size_t)ctx->forest.sum_classes;
-    if ((st = dev_alloc(ctx, dX, (size_t)P * D * sizeof(float))) != RVSEG_OK) return st;
-    if ((st = dev_alloc(ctx, dO, (size_t)P * S * sizeof(float))) != RVSEG_OK) return st;
-    RV_HIP(ctx, hipMemcpyAsync(dX.p, X, (size_t)P * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    launch_forest_eval(ctx->forest, dX.as<float>(), P, D, dO.as<float>(), ctx->stream);
-    RV_LAUNCH_OK(ctx);
-    RV_HIP(ctx, hipMemcpyAsync(out, dO.p, (size_t)P * S * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    RV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RVSEG_OK;
-}
-
 // DenseCRF2D::addPairwiseGaussian / addPairwiseBilateral (densecrf.cpp:61-81): the feature matrices they
 // build, point-major (N x d == the column-major d x N Eigen matrix).  int / float and uchar / float
 // divisions in fp32, exactly the reference's expressions.

@@ -1,14 +1,15 @@
-// Forest tools on the GPU: libforest's tools.h and the leaf re-estimation of its learner, for the loaded model.
+// The loaded forest on a host matrix of points: its posterior sums, libforest's tools.h and its learner's leaf re-estimation.
+//   classLogPosterior / multiClassLogPosterior  classifier.cpp:166-208          rvseg_forest_eval
 //   Classifier::classify(DataStorage)           classifier.cpp:29-51, 53-62     rvseg_forest_classify
 //   DecisionTree::classify per tree             tools.cpp:214-218               rvseg_forest_classify_trees
 //   AccuracyTool / ConfusionMatrixTool /
 //   CorrelationTool ::measure                   tools.cpp:61-78, 95-138, 192-231 rvseg_forest_measure + rvseg_forest_tools_*
 //   updateHistograms / updateMultiHistograms    learning.cpp:918-1012           rvseg_forest_refit
 //
-// X is processed in chunks of TOOLS_CHUNK points (forest_tools_host.h): a chunk is uploaded, walked once
-// (tools_votes_kernel: leaf rows, per-tree votes, forest labels) and counted (agreement, confusion, leaf counts); the
-// integer counters stay on the device over all chunks and are read back once.  The float arithmetic on the counts is the
-// reference's own and runs on the host (forest_tools_host.h).
+// X is processed in chunks of TOOLS_CHUNK points (forest_tools_host.h, for_each_chunk): a chunk is uploaded, walked once
+// (forest_eval_kernel: the sums; tools_votes_kernel: leaf rows, per-tree votes, forest labels) and counted (agreement,
+// confusion, leaf counts); the integer counters stay on the device over all chunks and are read back once.  The float
+// arithmetic on the counts is the reference's own and runs on the host (forest_tools_host.h).
 //
 // Pinned to the reference: the label rule (vote_label, forest_model.h) and with it every tree's vote and the forest's
 // label; the three score formulas.  Build-owned: the chunking, the layout of counts_out, the `layer` argument on a
@@ -46,6 +47,21 @@ int count_blocks(rvseg_ctx* ctx) {   // grids that loop: a few blocks per comput
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->params.device) != hipSuccess || cus < 1) cus = 64;
     return cus * 4;
+}
+
+rvseg_status for_each_chunk(rvseg_ctx* ctx, const float* X, int P, int D, const std::function<rvseg_status(int base, int n)>& body) {
+    hipStream_t s = ctx->stream;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, ctx->tools.X, (size_t)std::min(P, TOOLS_CHUNK) * D * sizeof(float))) != RVSEG_OK) return st;
+    for (int base = 0; base < P; base += TOOLS_CHUNK) {
+        const int n = std::min(TOOLS_CHUNK, P - base);
+        RV_HIP(ctx, hipMemcpyAsync(ctx->tools.X.p, X + (size_t)base * D, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((st = body(base, n)) != RVSEG_OK) return st;
+        // the chunk's scratch is written again by the next chunk's upload, which a host-staged copy may start early
+        RV_HIP(ctx, hipStreamSynchronize(s));
+        RV_LAUNCH_OK(ctx);
+    }
+    return RVSEG_OK;
 }
 
 // DecisionTree::classLogPosterior + classify per leaf, from the model's own histograms as the stream holds them (for a
@@ -89,7 +105,7 @@ rvseg_status tools_pass(rvseg_ctx* ctx, const float* X, int P, int D, int layer,
     const int chunk = std::min(P, TOOLS_CHUNK), stride = (chunk + 3) & ~3;
     const int blocks = count_blocks(ctx);
     rvseg_status st;
-    if ((st = dev_reserve(ctx, sc.X, (size_t)chunk * D * sizeof(float))) != RVSEG_OK || (st = dev_reserve(ctx, sc.flag, 16)) != RVSEG_OK) return st;
+    if ((st = dev_reserve(ctx, sc.flag, 16)) != RVSEG_OK) return st;
     if (want_votes && ((st = dev_reserve(ctx, sc.votes, (size_t)T * stride)) != RVSEG_OK || (st = upload_vote_table(ctx, layer, s)) != RVSEG_OK)) return st;
     if (want_pred && (st = dev_reserve(ctx, sc.pred, (size_t)chunk * 4)) != RVSEG_OK) return st;
     if (out.agree && (st = dev_reserve(ctx, sc.agree, (size_t)T * T * 8)) != RVSEG_OK) return st;
@@ -101,9 +117,7 @@ rvseg_status tools_pass(rvseg_ctx* ctx, const float* X, int P, int D, int layer,
     std::vector<int32_t> pred_kept;
     int32_t* pred_host = out.pred;
     if (want_conf && out.pred) { pred_kept.resize((size_t)P); pred_host = pred_kept.data(); }
-    for (int base = 0; base < P; base += TOOLS_CHUNK) {
-        const int n = std::min(TOOLS_CHUNK, P - base);
-        RV_HIP(ctx, hipMemcpyAsync(sc.X.p, X + (size_t)base * D, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, s));
+    if ((st = for_each_chunk(ctx, X, P, D, [&](int base, int n) -> rvseg_status {
         launch_tools_votes(f, sc.vote_table.as<uint8_t>(), lv.off, C, sc.X.as<float>(), n, D, stride, nullptr,
                            want_votes ? sc.votes.as<uint8_t>() : nullptr, want_pred ? sc.pred.as<int32_t>() : nullptr, s);
         if (out.agree) launch_tools_agree(sc.votes.as<uint8_t>(), T, n, stride, blocks, sc.agree.as<unsigned long long>(), s);
@@ -113,10 +127,8 @@ rvseg_status tools_pass(rvseg_ctx* ctx, const float* X, int P, int D, int layer,
         }
         if (out.votes) RV_HIP(ctx, hipMemcpy2DAsync(out.votes + base, (size_t)P, sc.votes.p, (size_t)stride, (size_t)n, (size_t)T, hipMemcpyDeviceToHost, s));
         if (pred_host) RV_HIP(ctx, hipMemcpyAsync(pred_host + base, sc.pred.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        // the chunk's scratch is written again by the next chunk's upload, which a host-staged copy may start early
-        RV_HIP(ctx, hipStreamSynchronize(s));
-        RV_LAUNCH_OK(ctx);
-    }
+        return RVSEG_OK;
+    })) != RVSEG_OK) return st;
     int flag = 0;
     std::vector<uint64_t> conf((size_t)(want_conf ? C * C : 0));
     RV_HIP(ctx, hipMemcpyAsync(&flag, sc.flag.p, 4, hipMemcpyDeviceToHost, s));
@@ -143,21 +155,17 @@ rvseg_status refit_counts(rvseg_ctx* ctx, const float* X, int P, int D, const in
     const int blocks = count_blocks(ctx);
     counts.assign((size_t)f.n_leaves * lay.sum_classes, 0u);
     rvseg_status st;
-    if ((st = dev_reserve(ctx, sc.X, (size_t)chunk * D * sizeof(float))) != RVSEG_OK || (st = dev_reserve(ctx, sc.flag, 16)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, sc.rows, (size_t)T * stride * 4)) != RVSEG_OK || (st = dev_reserve(ctx, sc.labels, (size_t)chunk * L * 4)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, sc.leaf_cnt, counts.size() * 4)) != RVSEG_OK)
+    if ((st = dev_reserve(ctx, sc.flag, 16)) != RVSEG_OK || (st = dev_reserve(ctx, sc.rows, (size_t)T * stride * 4)) != RVSEG_OK ||
+        (st = dev_reserve(ctx, sc.labels, (size_t)chunk * L * 4)) != RVSEG_OK || (st = dev_reserve(ctx, sc.leaf_cnt, counts.size() * 4)) != RVSEG_OK)
         return st;
     RV_HIP(ctx, hipMemsetAsync(sc.flag.p, 0, 16, s));
     RV_HIP(ctx, hipMemsetAsync(sc.leaf_cnt.p, 0, counts.size() * 4, s));
-    for (int base = 0; base < P; base += TOOLS_CHUNK) {
-        const int n = std::min(TOOLS_CHUNK, P - base);
-        RV_HIP(ctx, hipMemcpyAsync(sc.X.p, X + (size_t)base * D, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, s));
+    if ((st = for_each_chunk(ctx, X, P, D, [&](int base, int n) -> rvseg_status {
         RV_HIP(ctx, hipMemcpyAsync(sc.labels.p, labels + (size_t)base * L, (size_t)n * L * 4, hipMemcpyHostToDevice, s));
         launch_tools_votes(f, nullptr, 0, 0, sc.X.as<float>(), n, D, stride, sc.rows.as<int32_t>(), nullptr, nullptr, s);
         launch_tools_refit_count(sc.rows.as<int32_t>(), sc.labels.as<int32_t>(), T, n, stride, lay, blocks, sc.leaf_cnt.as<uint32_t>(), sc.flag.as<int>(), s);
-        RV_HIP(ctx, hipStreamSynchronize(s));
-        RV_LAUNCH_OK(ctx);
-    }
+        return RVSEG_OK;
+    })) != RVSEG_OK) return st;
     int flag = 0;
     RV_HIP(ctx, hipMemcpyAsync(&flag, sc.flag.p, 4, hipMemcpyDeviceToHost, s));
     RV_HIP(ctx, hipMemcpyAsync(counts.data(), sc.leaf_cnt.p, counts.size() * 4, hipMemcpyDeviceToHost, s));
@@ -172,6 +180,24 @@ rvseg_status refit_counts(rvseg_ctx* ctx, const float* X, int P, int D, const in
 using namespace rvseg;
 
 extern "C" {
+
+rvseg_status rvseg_forest_eval(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, float* out) {
+    if (!ctx) return RVSEG_ERR_INVALID_ARG;
+    if (!ctx->forest_loaded) { ctx->err = "no forest loaded"; return RVSEG_ERR_NO_FOREST; }
+    if (P < 0 || !out || (!X && P > 0)) { ctx->err = "bad arguments"; return RVSEG_ERR_INVALID_ARG; }
+    if (D != ctx->feature_length) { ctx->err = "D does not match the configured feature length"; return RVSEG_ERR_INVALID_ARG; }
+    if (P == 0) return RVSEG_OK;
+    RV_HIP(ctx, hipSetDevice(ctx->params.device));
+    DevBuf& sums = ctx->tools.sums;
+    const size_t S = (size_t)ctx->forest.sum_classes;
+    rvseg_status st;
+    if ((st = dev_reserve(ctx, sums, (size_t)std::min(P, TOOLS_CHUNK) * S * sizeof(float))) != RVSEG_OK) return st;
+    return for_each_chunk(ctx, X, P, D, [&](int base, int n) -> rvseg_status {
+        launch_forest_eval(ctx->forest, ctx->tools.X.as<float>(), n, D, sums.as<float>(), ctx->stream);
+        RV_HIP(ctx, hipMemcpyAsync(out + (size_t)base * S, sums.p, (size_t)n * S * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        return RVSEG_OK;
+    });
+}
 
 rvseg_status rvseg_forest_classify(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D, int32_t layer, int32_t* labels_out) {
     if (!ctx) return RVSEG_ERR_INVALID_ARG;

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -112,6 +113,7 @@ struct StageTimer {
 // scratch of the forest tools (rvseg_forest_tools.hip), sized by a chunk of points and the loaded model; grow-only
 struct ToolsScratch {
     DevBuf X, labels;               // one chunk of points and of their labels
+    DevBuf sums;                    // [chunk][S] posterior sums (rvseg_forest_eval)
     DevBuf rows, votes, pred;       // [T][chunk] leaf rows and votes, [chunk] forest labels
     DevBuf vote_table;              // [n_leaves] vote label per leaf row
     DevBuf agree, confusion, flag;  // [T][T] and [C][C] 64-bit counters, the bad-label flag word
@@ -180,20 +182,18 @@ rvseg_status dev_reserve(rvseg_ctx* ctx, DevBuf& b, size_t bytes);
 // the stream of a device entry point: the caller's, or the context's own when the caller passes none
 inline hipStream_t stream_of(const rvseg_ctx* ctx, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : ctx->stream; }
 
-// ---- rvseg_forest_tools.hip: what every call on a data set checks first, and the per-leaf vote labels of a layer
-// (ctx->tools.vote_table) that launch_tools_votes reads -- shared with rvseg_prune.hip -------------------------------
+// ---- rvseg_forest_tools.hip: what every call on a data set checks first, the per-leaf vote labels of a layer
+// (ctx->tools.vote_table) that launch_tools_votes reads, and the loop over X -- shared with rvseg_prune.hip ----------
 struct LayerView { int off = 0, C = 0; };   // the layer's classes inside a leaf row of the active mode
 rvseg_status check_points(rvseg_ctx* ctx, const float* X, int32_t P, int32_t D);
 rvseg_status layer_of(rvseg_ctx* ctx, int32_t layer, LayerView& v);
 rvseg_status upload_vote_table(rvseg_ctx* ctx, int layer, hipStream_t s);
 int count_blocks(rvseg_ctx* ctx);   // grids that loop: a few blocks per compute unit
+// X [P][D] through ctx->tools.X in chunks of TOOLS_CHUNK points, on ctx->stream: body(base, n) enqueues what its caller
+// does with points base .. base + n - 1, which are on the device; the chunk's work is complete before the next begins
+rvseg_status for_each_chunk(rvseg_ctx* ctx, const float* X, int P, int D, const std::function<rvseg_status(int base, int n)>& body);
 
 // ---- kernels_eval.hip: frees the scoring state (waits for its pending work first) -----------------------------
 void eval_destroy(rvseg_ctx* ctx);
-
-// ---- kernels_rf.hip --------------------------------------------------------------------------
-// P points with materialised D-dimensional features -> P x S log-posteriors
-void launch_forest_eval(const DeviceForest& f, const float* d_X, int P, int D, float* d_out,
-                        hipStream_t s);
 
 }  // namespace rvseg

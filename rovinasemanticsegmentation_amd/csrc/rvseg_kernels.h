@@ -50,13 +50,15 @@ void launch_normal_feature(const FrameGeom& g, const float4* d_cloud, const uint
                            int n, hipStream_t s);
 
 // ---- kernels_forest_tools.hip ----------------------------------------------------------------
-// The forest tools on one chunk of n points (rvseg_forest_tools.hip).  Per-tree tables are [T][stride], stride a multiple
-// of 4 and >= n; every output of launch_tools_votes is optional.
+// The loaded forest on one chunk of n points with materialised D-dimensional features (rvseg_forest_tools.hip).
+// Per-tree tables are [T][stride], stride a multiple of 4 and >= n; every output of launch_tools_votes is optional.
+//   d_out        : [n][S] the forest's posterior sums
 //   d_vote_table : per leaf row, the label rule on the leaf's own histogram of the layer
 //   d_pred       : [n] the forest's label of the layer's classes [layer_off, layer_off + C) of a leaf row
 struct RefitLayers { int n_layers, sum_classes, class_counts[RVSEG_MAX_LAYERS], offset[RVSEG_MAX_LAYERS]; };
+void launch_forest_eval(const DeviceForest& f, const float* d_X, int n, int D, float* d_out, hipStream_t s);
 void launch_tools_votes(const DeviceForest& f, const uint8_t* d_vote_table, int layer_off, int C, const float* d_X, int n, int D,
-                        int stride, int32_t* d_rows, uint8_t* d_votes, int32_t* d_pred, hipStream_t s);
+                        size_t stride, int32_t* d_rows, uint8_t* d_votes, int32_t* d_pred, hipStream_t s);
 // d_agree [T][T] += the points of the chunk on which two trees vote alike; d_confusion [C][C] += [label][pred];
 // d_counts [leaf row][sum_classes] += the chunk's examples per (layer, class).  d_flag: a label was out of range.
 void launch_tools_agree(const uint8_t* d_votes, int n_trees, int n, int stride, int max_blocks, unsigned long long* d_agree, hipStream_t s);

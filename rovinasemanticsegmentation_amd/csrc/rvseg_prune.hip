@@ -45,23 +45,17 @@ rvseg_status votes_resident(rvseg_ctx* ctx, const float* X, int P, int D, const 
     ToolsScratch& sc = ctx->tools;
     PruneScratch& pr = ctx->prune;
     const DeviceForest& f = ctx->forest;
-    const int chunk = std::min(P, TOOLS_CHUNK);
     rvseg_status st;
-    if ((st = dev_reserve(ctx, sc.X, (size_t)chunk * D * sizeof(float))) != RVSEG_OK || (st = upload_vote_table(ctx, layer, s)) != RVSEG_OK ||
-        (st = dev_reserve(ctx, pr.votes, (size_t)f.n_trees * stride)) != RVSEG_OK || (st = dev_reserve(ctx, pr.labels, stride * 4)) != RVSEG_OK)
+    if ((st = upload_vote_table(ctx, layer, s)) != RVSEG_OK || (st = dev_reserve(ctx, pr.votes, (size_t)f.n_trees * stride)) != RVSEG_OK ||
+        (st = dev_reserve(ctx, pr.labels, stride * 4)) != RVSEG_OK)
         return st;
     RV_HIP(ctx, hipMemsetAsync(pr.votes.p, 0, (size_t)f.n_trees * stride, s));   // the rows' tails beyond P are read, four bytes at a time
     RV_HIP(ctx, hipMemsetAsync(pr.labels.p, 0, stride * 4, s));
     RV_HIP(ctx, hipMemcpyAsync(pr.labels.p, labels, (size_t)P * 4, hipMemcpyHostToDevice, s));
-    for (int base = 0; base < P; base += TOOLS_CHUNK) {   // (TOOLS_CHUNK is a multiple of 4: every chunk's rows stay word-aligned)
-        const int n = std::min(TOOLS_CHUNK, P - base);
-        RV_HIP(ctx, hipMemcpyAsync(sc.X.p, X + (size_t)base * D, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, s));
-        // (launch_tools_votes takes the row stride as an int; a table past 2^31 columns is refused by the caller)
-        launch_tools_votes(f, sc.vote_table.as<uint8_t>(), lv.off, lv.C, sc.X.as<float>(), n, D, (int)stride, nullptr, pr.votes.as<uint8_t>() + base, nullptr, s);
-        RV_HIP(ctx, hipStreamSynchronize(s));   // the chunk's X is written again by the next upload
-        RV_LAUNCH_OK(ctx);
-    }
-    return RVSEG_OK;
+    return for_each_chunk(ctx, X, P, D, [&](int base, int n) -> rvseg_status {   // (TOOLS_CHUNK is a multiple of 4: every chunk's rows stay word-aligned)
+        launch_tools_votes(f, sc.vote_table.as<uint8_t>(), lv.off, lv.C, sc.X.as<float>(), n, D, stride, nullptr, pr.votes.as<uint8_t>() + base, nullptr, s);
+        return RVSEG_OK;
+    });
 }
 
 // puts `state` into PruneControl::state[0] and runs the init launch: its energy becomes the current and the best one

@@ -40,6 +40,12 @@ static ForestModel parsed(const std::vector<RawTree>& trees) {
 }
 
 int main() {
+    // ---- the grid of a looping kernel: what it wants, capped, at least one block ----
+    {
+        CHECK(looping_grid(1, 1024) == 1 && looping_grid(1023, 1024) == 1023);
+        CHECK(looping_grid(1024, 1024) == 1024 && looping_grid(1025, 1024) == 1024 && looping_grid(1L << 40, 1024) == 1024);
+        CHECK(looping_grid(5, 0) == 1 && looping_grid(5, -3) == 1 && looping_grid(1L << 40, 0) == 1);
+    }
     // ---- scores ----
     {
         const uint64_t big = (1ull << 24) + 3;

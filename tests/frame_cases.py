@@ -1,5 +1,6 @@
-"""Data recipes for the limits of the forest walk (csrc/kernels_rf.hip, rvseg_api.cpp: upload_forest) and of the feature
-kernels (csrc/kernels_features.hip) -- a plain helper module like train_cases.py and fusion_cases.py: the CPU pins
+"""Data recipes for the limits of the forest walk (csrc/kernels_rf.hip, forest_eval_kernel of
+csrc/kernels_forest_tools.hip, rvseg_api.cpp: upload_forest) and of the feature kernels
+(csrc/kernels_features.hip) -- a plain helper module like train_cases.py and fusion_cases.py: the CPU pins
 (test_frame_cases_cpu.py: numpy and the oracle alone show that a recipe lies on the side of the edge it claims) and the
 GPU comparisons (test_gpu_forest_limits.py, test_gpu_feature_limits.py: GPU == oracle, float32 bit patterns) draw the
 same bytes from here.

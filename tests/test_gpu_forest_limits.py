@@ -1,6 +1,6 @@
-"""The forest walk (csrc/kernels_rf.hip, rvseg_api.cpp: upload_forest) at every limit of its code: tree counts and shapes
-at the lane arithmetic, degenerate trees, the strict '<' at special values on all three walkers (forest_eval_kernel,
-the 8-byte and the 16-byte lazy walk), the node formats on both sides of 2^20 nodes, the `wave_inside` fast path at its
+"""The forest walk (csrc/kernels_rf.hip, forest_eval_kernel of csrc/kernels_forest_tools.hip, rvseg_api.cpp: upload_forest) at
+every limit of its code: tree counts and shapes at the lane arithmetic, rvseg_forest_eval's chunks of points, degenerate
+trees, the strict '<' at special values on all three walkers (forest_eval_kernel, the 8-byte and the 16-byte lazy walk), the node formats on both sides of 2^20 nodes, the `wave_inside` fast path at its
 own boundary, the resize table in LDS and through L1, patch_size_reduce 1 and 16.  The recipes come from frame_cases.py
 and are pinned to their edges by test_frame_cases_cpu.py.  Every comparison is of float32 bit patterns of the whole
 output against the CPU oracle (which the CPU pins hold against the plain walker of frame_cases)."""
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import frame_cases as fc
+import tools_cases as tc
 from rovinasemanticsegmentation_amd import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +92,20 @@ def test_forest_eval_class_sums_and_point_counts(eval_ctx, oracle, S, T):
     assert eval_ctx.forest_info()["class_counts"] == [S]
     for P in fc.POINT_COUNTS:      # a block holds 64 or 16 points; the inactive lanes take part in the shuffles
         same(eval_ctx.forest_eval(X[:P]), want[:P], "P=%d" % P)
+
+
+@pytest.mark.parametrize("T", [3, 5])
+def test_forest_eval_across_the_chunk_boundary(eval_ctx, oracle, T):
+    """rvseg_forest_eval takes X through the context's scratch 65536 points at a time: exactly one chunk, a second chunk
+    of one point, a ragged second chunk -- and then 257 points on the same context, whose scratch the large call's last
+    chunk has left filled."""
+    trees, blob = fc.small_forest(700 + T, T, 3, fc.EVAL_D)
+    X = fc.eval_points(70 + T, tc.CHUNK_TAIL)
+    want = oracle.Forest(blob).eval(X, multi=True)
+    eval_ctx.forest_load(blob)
+    for P in (65536, 65537, tc.CHUNK_TAIL):
+        same(eval_ctx.forest_eval(X[:P]), want[:P], "P=%d" % P)
+    same(eval_ctx.forest_eval(X[:257]), want[:257], "P=257 after P=%d" % tc.CHUNK_TAIL)
 
 
 @pytest.mark.parametrize("T", [3, 5])
