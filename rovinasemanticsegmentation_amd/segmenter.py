@@ -995,7 +995,8 @@ class Context:
 
     def eval_confusion(self, layer):
         """(C x C uint64 counts, out-of-range count) of one layer; waits for the pending accumulates."""
-        Cn = self.forest_info()["class_counts"][layer]
+        cc = self.forest_info()["class_counts"]
+        Cn = cc[layer] if 0 <= layer < len(cc) else 1   # a layer the model does not have: the library refuses it
         counts = np.empty((Cn, Cn), np.uint64)
         oor = C.c_uint64()
         capi.check(self.h, self.L.rvseg_eval_confusion(self.h, layer, _ptr(counts), C.byref(oor)))
