@@ -1,5 +1,6 @@
-// The CRF state of a context and the mean-field pieces that rvseg_crf.hip (lattices, mean field, frame and cloud paths) and
-// rvseg_crf_model.hip (the kept DenseCRF model) share.  Private to those two files; the functions are defined in rvseg_crf.hip.
+// The CRF state of a context and what rvseg_lattice.hip (the lattice's host side), rvseg_crf.hip (mean field, frame and
+// cloud paths) and rvseg_crf_model.hip (the kept DenseCRF model) share.  Private to those three files; the functions are
+// defined in rvseg_lattice.hip and rvseg_crf.hip.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -11,7 +12,8 @@
 namespace rvseg {
 
 struct LatticeBufs {
-    DevBuf state, tkeys, slot_to_id, counters, vkeys, offsets, bary, nb1, nb2, csr_pw, csr_nrm, vstart, vend, norm;
+    DevBuf state, tkeys, slot_to_id, vkeys, offsets, bary, nb1, nb2, csr_pw, csr_nrm, norm;
+    DevBuf vstart;   // vstart | vend | counters (lattice_reserve)
     DevBuf keys_in, keys_out, vals_in, vals_out, sort_temp, scan_temp, fstart, vorder, block_hist;
     DevBuf r_desc, r_vl, r_info, r_small, r_verts, r_jb, r_trace;   // resident band schedule of the splat
     SplatResidentDev resident{};
@@ -122,17 +124,48 @@ struct MfRun {
 // needs anyway.  partials: [2 + n_terms][KL_MAX_BLOCKS] doubles.
 struct KlTap { double* partials; };
 
+// One pairwise term's lattice input: N x d features in host or device memory, the kernel parameters that transform them
+// (pairwise.cpp:140-152; none for CONST_KERNEL or a null pointer) and the normaliser the term needs (rvseg_norm_kind)
+// keep (a kept model's term only): where the point ranks and, for a DIAG or FULL kernel, a copy of the features go
+// in_place (term_rebuild): the features ARE keep->feat, and the model the term belongs to stays live
+struct TermInput {
+    int d; const float* features; bool on_host; int kernel_type; const float* kernel_params; int norm; TermKeep* keep = nullptr;
+    bool in_place = false;
+};
+
+// the input of a Potts term (the Segmenter's, the clouds', rvseg_crf_infer[_multi|_device], rvseg_lattice_build)
+static inline TermInput potts_input(int d, const float* features, bool on_host) {
+    return TermInput{d, features, on_host, RVSEG_CONST_KERNEL, nullptr, RVSEG_NORMALIZE_SYMMETRIC, nullptr};
+}
+
+// ---- rvseg_lattice.hip (each is described where it is defined); not exported by the library ----
+#pragma GCC visibility push(hidden)
+LatticeBufs& lattice_at(CrfState* cs, int k);
+rvseg_status lattice_raise_capacity(rvseg_ctx* ctx, Pipeline* im, int N);
+rvseg_status lattice_prepare(rvseg_ctx* ctx, LatticeBufs& b, int d, int N, int n_frames, bool safe, int vertices_per_frame_seen = 0,
+                             bool frame_ids = false);
+rvseg_status values_reserve(rvseg_ctx* ctx, CrfState* cs, long long m_bound, int C, int slot = 0);
+rvseg_status second_stream(rvseg_ctx* ctx, CrfState* cs);
+rvseg_status lattice_clear(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s);
+void model_replaced(CrfState* cs);
+rvseg_status lattice_build(rvseg_ctx* ctx, CrfState* cs, LatticeBufs& b, const FeatureSource& fs, hipStream_t s,
+                           int norm_kind = RVSEG_NORMALIZE_SYMMETRIC, bool ends_model = true);
+rvseg_status counters_readback(rvseg_ctx* ctx, CrfState* cs, const LatticeBufs& b, int slot, hipStream_t s);
+void counters_to_info(CrfState* cs, const int* h);
+rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s);
+rvseg_status build_lattices(rvseg_ctx* ctx, CrfState* cs, int N, int n, const TermInput* terms, hipStream_t s, int first = 0,
+                            int* vertices = nullptr);
+#pragma GCC visibility pop
+
 // ---- rvseg_crf.hip (each is described where it is defined); not exported by the library ----
 #pragma GCC visibility push(hidden)
 rvseg_status crf_enter(rvseg_ctx* ctx, CrfState** cs_out, const char* entry);
-void model_replaced(CrfState* cs);
 rvseg_status terms_prepare(rvseg_ctx* ctx, CrfState* cs, int N, int C, int n_terms, const rvseg_crf_term* terms, bool on_host,
                            std::vector<TermPlan>& plan, hipStream_t s, TermKeep* keep = nullptr);
 rvseg_status term_rebuild(rvseg_ctx* ctx, CrfState* cs, int k, const float* kernel_params, hipStream_t s);
 void plan_compat(int C, int compat, const float* params, TermPlan& tp, float* hc /* C, or C x C for a Matrix */);
 bool term_pre(const TermPlan& t);
 bool term_post(const TermPlan& t);
-rvseg_status ensure_csr_nrm(rvseg_ctx* ctx, LatticeBufs& b, hipStream_t s);
 rvseg_status mf_scratch(rvseg_ctx* ctx, CrfState* cs, const MfRun& r);
 rvseg_status mf_entry_norms(rvseg_ctx* ctx, CrfState* cs, const MfRun& r);
 void mf_start(rvseg_ctx* ctx, CrfState* cs, const MfRun& r, const ValueView& Q);

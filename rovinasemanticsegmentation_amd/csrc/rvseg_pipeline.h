@@ -5,7 +5,7 @@
 
 namespace rvseg {
 
-struct CrfState;     // rvseg_crf_state.h (rvseg_crf.hip, rvseg_crf_model.hip)
+struct CrfState;     // rvseg_crf_state.h (rvseg_lattice.hip, rvseg_crf.hip, rvseg_crf_model.hip)
 
 // buffers of the fusion and of the projector that feeds it, owned by the context (no allocation per call once they have
 // grown); created by fusion_state, deleted by fusion_state_free (rvseg_fusion.hip)

@@ -4,7 +4,7 @@ RCCL label gather" -- as far as ONE GPU can exercise it: the per-rank shard of t
 Rank 3 of 8 owns frames [96, 128) of the 256-frame map (`shard_frames`).  Its chunk of 32 synthetic 640x480 key
 frames (holes on, bench forest) goes through rvseg_segment_frames_device with max_batch = 32 -- 9.8 M points -- under
 BOTH splat schedules: the library's own choice for this shape (the resident bands, by the measured rule of
-rvseg_crf.hip: resident_pays) and the list-major walk, which neither the 64-frame nor the single-frame tests run at
+rvseg_lattice.hip: resident_pays) and the list-major walk, which neither the 64-frame nor the single-frame tests run at
 this size -- and then through the C-ABI RCCL gather (rvseg_comm_init / rvseg_gather_frames, world size 1 on this box:
 the 8-GPU run is the driver's).
 

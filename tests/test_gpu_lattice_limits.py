@@ -85,7 +85,7 @@ def _ceil_log2(v):
 
 
 def _capacity_after_overflows(max_vertices, N, base=12):
-    """rvseg_crf.hip: crf_frames_status raises the per-frame capacity (x8 per overflow, stopping at 2^13 on the way up,
+    """rvseg_lattice.hip: lattice_raise_capacity raises the per-frame capacity (x8 per overflow, stopping at 2^13 on the way up,
     never past the worst case 2 N (d+1)) until a frame's region holds its vertices at load factor 1/2."""
     safe = _ceil_log2(2 * ((N + 3) // 4 * 4) * (FRAME_D + 1))
     cur = min(base, safe)
@@ -95,7 +95,7 @@ def _capacity_after_overflows(max_vertices, N, base=12):
 
 
 def _resident_pays(n_frames, N, vertices_per_frame_seen):
-    """rvseg_crf.hip: resident_pays."""
+    """rvseg_lattice.hip: resident_pays."""
     vpf = vertices_per_frame_seen if vertices_per_frame_seen > 0 else 360
     return n_frames >= 2 and n_frames * N >= 6900000 + 4900 * vpf
 
